@@ -5,11 +5,15 @@ Step = one pass of the hot path over one batch of synthetic input already reside
 a batched forward NTT (the reference's cfft::evaluate_poly, natural order in and out) over the columns of a
 2^22-row trace (94 columns = the width of OlaVM's CPU table), BASELINE.json configs[1].
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One rank per GPU; columns are independent, so ranks shard them with no data-path collective (weak scaling: every
 rank transforms its own `--cols` columns).  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything else bench.py measures
+(per-pass launch times, the coset LDE roofline, the end-to-end proofs and cold processes, the CPU baseline, the N > 1
+collective and sharded extras); `--dump-outputs DIR` writes what the last timed step computed (see dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -655,6 +659,8 @@ def single_process_multi(args):
                 t_end[r] = time.perf_counter()
                 dev_ms[r] = e0.elapsed_time(e1)
                 bar.wait()
+                if r == 0 and args.dump_outputs:
+                    dump_outputs(args.dump_outputs, out, args.log_n, cols)
                 be.close()
         except Exception as e:          # noqa: BLE001
             errors.append(repr(e))
@@ -691,11 +697,12 @@ def single_process_multi(args):
         floor_ms = valu_floor_ms(ipe, cols * n)
         res["roofline"].update({"valu_insts_per_element": round(ipe, 1), "valu_floor_ms": round(floor_ms, 3),
                                 "frac_of_floor": round(floor_ms / (launch_ms * passes), 3)})
-    try:
-        res["collective"] = collective_report(Backend, devices, aliased, args.log_n, cols)
-    except Exception as e:              # noqa: BLE001 -- an extra: never at the price of the headline line
-        res["collective"] = {"error": repr(e)[:300]}
-    if not args.no_prove:
+    if args.full:
+        try:
+            res["collective"] = collective_report(Backend, devices, aliased, args.log_n, cols)
+        except Exception as e:              # noqa: BLE001 -- an extra: never at the price of the headline line
+            res["collective"] = {"error": repr(e)[:300]}
+    if args.full and not args.no_prove:
         carrier = os.environ.get("OLA_COLLECTIVE", "peer")
         try:
             res["prove_sharded"] = multi_context_prove(Backend, devices, args.log_n, real=False, aliased=aliased, collective=carrier)
@@ -871,6 +878,33 @@ def compact_line(res):
     return out
 
 
+DUMP_SAMPLES = 1 << 20
+DUMP_SEED = 0xD0A7
+
+
+def dump_outputs(path, out, log_n, cols):
+    """`--dump-outputs DIR`: what the last timed step handed its caller -- the `cols` x 2^log_n transformed columns -- as exact
+    float64 arrays of field elements in canonical form (a word >= p is its value minus p), so that two builds can be compared
+    output for output: a fixed, seeded sample of DUMP_SAMPLES elements (flat row-major index, low and high 32-bit halves) and,
+    over the whole output, every column's sums of its four 16-bit limbs.  About 24 MB in all."""
+    import torch
+    if out.is_cuda:
+        torch.cuda.synchronize(out.device)
+    os.makedirs(path, exist_ok=True)
+    flat = out.reshape(-1)
+    # as signed 64-bit words the non-canonical ones are [p, 2^64) = [-(2^32 - 1), -1]; subtracting p adds 2^32 - 1
+    canon = torch.where((flat < 0) & (flat >= -0xFFFFFFFF), flat + 0xFFFFFFFF, flat)
+    sums = torch.stack([((canon >> (16 * k)) & 0xFFFF).view(cols, 1 << log_n).sum(dim=1) for k in range(4)], dim=1)
+    total = cols << log_n
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=min(DUMP_SAMPLES, total), replace=False))
+    sample = canon[torch.from_numpy(idx).to(canon.device)].cpu().numpy().view(np.uint64)
+    arrays = {"ntt_out_sample_index": idx, "ntt_out_sample_lo": sample & np.uint64(0xFFFFFFFF), "ntt_out_sample_hi": sample >> np.uint64(32),
+              "ntt_out_column_limb_sums": sums.cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
+    del canon, sums
+
+
 def emit(res):
     """Details to the side file, then the compact line: the LAST thing on stdout, one line, under LINE_LIMIT bytes."""
     try:
@@ -902,6 +936,10 @@ def main():
     ap.add_argument("--no-prove", action="store_true", help="skip the end-to-end prove_with_traces timing")
     ap.add_argument("--no-config4", action="store_true", help="skip the Poseidon-heavy proof (BASELINE config 4) and its Merkle / FRI block")
     ap.add_argument("--no-2p24", action="store_true", help="skip the 2^24-row single-GPU proof (BASELINE config 5's N = 1 point)")
+    ap.add_argument("--full", action="store_true", help="after the headline, measure everything else: per-pass launch times, the coset LDE "
+                    "roofline, end-to-end proofs and cold processes, the CPU baseline, N > 1 collective and sharded extras (the --no-* "
+                    "options above trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     # N > 1 without a launcher: this process drives the N GPUs itself.  Under torch.distributed.run (WORLD_SIZE set) the ranks
@@ -944,7 +982,7 @@ def main():
     # VRAM that a still-living process has freed is handed out dirty and is scrubbed inside the next owner's hipMalloc (about 30 ms
     # per GB), which would be charged to whichever child runs first (docs/EXPERIMENTS.md, cold start).
     cold = cold_b3 = None
-    if world == 1 and rank == 0 and not args.no_prove:
+    if args.full and world == 1 and rank == 0 and not args.no_prove:
         # The very first GPU-heavy process on a box also pays for what the PREVIOUS tenant left behind (dirty VRAM is scrubbed inside
         # the new owner's hipMalloc): reported under its own name, so that the figures after it describe this library and not the
         # box's history.  Measured: 1.9x / 3.7x for whichever child ran first, 1.16 - 1.18x for the ones after it, either order.
@@ -986,22 +1024,25 @@ def main():
     dev_ms = ev0.elapsed_time(ev1)
     from olavm_amd import sharding
     elapsed, dev_ms = sharding.max_over_ranks([elapsed, dev_ms], device=coll_dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, args.log_n, cols)
     # `steps` more transforms with the library's events around every pass launch (ola_gpu_ntt_pass_times): which pass is the
     # dominant kernel and how long one launch of it takes -- outside the timed region, which runs without the extra records
     pass_times, pass_times_error = None, None
-    try:
-        be.ntt_pass_times(enable=True)
-        for _ in range(args.steps):
-            step()
-        pass_times = be.ntt_pass_times(enable=False)
-    except Exception as e:              # noqa: BLE001 -- keep the headline
-        pass_times_error = {"error": repr(e)[:200]}
+    if args.full:
+        try:
+            be.ntt_pass_times(enable=True)
+            for _ in range(args.steps):
+                step()
+            pass_times = be.ntt_pass_times(enable=False)
+        except Exception as e:              # noqa: BLE001 -- keep the headline
+            pass_times_error = {"error": repr(e)[:200]}
 
     # N > 1 extras (coset-partitioned commitment and proof).  They run in a helper thread under a wall-clock guard: whatever
     # happens there -- an exception or a collective that never returns -- the headline line below is still printed.
     sharded = sharded_prove = sharded_prove_real = None
     extras_hung = False
-    if world > 1 and world in (2, 4, 8) and os.environ.get("OLA_BENCH_SHARDED", "1") != "0":
+    if args.full and world > 1 and world in (2, 4, 8) and os.environ.get("OLA_BENCH_SHARDED", "1") != "0":
         import threading
         del data, out, scratch
         torch.cuda.empty_cache()
@@ -1067,7 +1108,8 @@ def main():
                          "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
                          "traffic_unit": "bytes per launch", "traffic_source": traffic_src,
                          "algorithmic_bytes_per_launch": bytes_per_step / passes,
-                         "kernel": dom_name + " (the slowest of the transform's passes)", "kernel_short": dom_name, "launches_per_step": passes,
+                         "kernel": dom_name + (" (the slowest of the transform's passes)" if pass_times else " (mean over the transform's passes; --full times each)"),
+                         "kernel_short": dom_name, "launches_per_step": passes,
                          "avg_launch_ms": round(dom_ms, 4), "mean_launch_ms_over_the_passes": round(launch_ms, 4), "per_pass_avg_ms": per_pass,
                          "dominant": {"whole_transform_ms": round(step_ms, 4), "whole_transform_frac": round(bytes_per_step / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)},
                          "valu_insts_per_element": round(ipe, 1) if ipe else None,
@@ -1086,14 +1128,14 @@ def main():
             res["prove_sharded"] = sharded_prove
         if sharded_prove_real is not None:
             res["prove_real_execution_sharded"] = sharded_prove_real
-        if world == 1:
+        if args.full and world == 1:
             del data, out, scratch
             torch.cuda.empty_cache()
             try:        # the transform the prover runs: leaf-order coset LDE x8, on the record next to the natural-order NTT
                 res["roofline_lde"] = lde_roofline(be, torch, stream, args.log_n, cols)
             except Exception as e:      # noqa: BLE001 -- an extra: never at the price of the headline line
                 res["roofline_lde"] = {"error": repr(e)[:200]}
-        if world == 1 and not args.no_prove:
+        if args.full and world == 1 and not args.no_prove:
             try:
                 be_b3 = Backend(device=local_rank, stream=stream.cuda_stream, hasher="blake3")
             except Exception:
@@ -1132,7 +1174,7 @@ def main():
                     res["prove_2p24_rows"] = prove_time_2p24(be)
                 except Exception as e:      # an extra: never at the price of the headline line
                     res["prove_2p24_rows"] = {"error": repr(e)[:200]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(args.log_n)
             if not args.no_prove:
                 for leg, ln in (("prove", args.cpu_prove_log_n), ("prove_small", 14)):

@@ -91,3 +91,34 @@ def test_valu_floor_is_the_stated_product():
     # 305 instructions per element x 94 x 2^22 elements / 64 lanes x 4.0 cycles / (256 x 4 x 2.4e9 SIMD-cycles/s)
     ms = bench.valu_floor_ms(305.0, 94 * (1 << 22))
     assert abs(ms - 305.0 * 94 * (1 << 22) / 64 * 4.0 / (256 * 4 * 2.4e9) * 1e3) < 1e-9 and 3.0 < ms < 3.1
+
+
+def test_dump_outputs_are_exact_canonical_and_small(tmp_path):
+    """--dump-outputs: float64 arrays that hold the output's field elements exactly, words >= p reduced, the same sample every run"""
+    import numpy as np
+    import torch
+    P = 0xFFFFFFFF00000001
+    cols, log_n = 3, 10
+    w = np.random.default_rng(3).integers(0, 2**64, size=(cols, 1 << log_n), dtype=np.uint64)
+    w[0, :5] = [P, P + 1, 2**64 - 1, P - 1, 0]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.from_numpy(w.view(np.int64).copy()), log_n, cols)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and all(n.endswith(".npy") for n in names)
+    a = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert a[n[:-4]].dtype == np.float64 and np.array_equal(a[n[:-4]], np.load(tmp_path / "b" / n))
+    canon = [int(x) % P for x in w.reshape(-1)]
+    idx = a["ntt_out_sample_index"].astype(np.int64)
+    got = a["ntt_out_sample_lo"].astype(np.uint64) | (a["ntt_out_sample_hi"].astype(np.uint64) << np.uint64(32))
+    assert len(idx) == cols << log_n and [int(g) for g in got] == [canon[i] for i in idx]
+    sums = [[sum((x >> (16 * k)) & 0xFFFF for x in canon[c << log_n:(c + 1) << log_n]) for k in range(4)] for c in range(cols)]
+    assert np.array_equal(a["ntt_out_column_limb_sums"], np.array(sums, dtype=np.float64))
+    # the headline shape stays within the 64 MB the dump may take: 3 arrays of DUMP_SAMPLES words plus 94 x 4 sums
+    assert 3 * 8 * bench.DUMP_SAMPLES + 8 * 94 * 4 < 64 << 20
+
+
+def test_plain_run_and_full_run_are_both_offered():
+    import subprocess
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs" in out.stdout

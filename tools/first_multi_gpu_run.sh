@@ -52,10 +52,10 @@ done
 [ "${OLA_KIT_DRY:-0}" = 1 ] && { echo "dry run: steps 2 and 4 skipped"; exit 0; }
 echo "=== 4. bench.py as the driver launches it (one process per GPU, RCCL under torch.distributed), then single-process under both carriers"
 for g in $GS; do
-  timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node $g --master-addr 127.0.0.1 --master-port $((29600 + g)) bench.py --gpus $g --steps 10 --warmup 2 \
+  timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node $g --master-addr 127.0.0.1 --master-port $((29600 + g)) bench.py --full --gpus $g --steps 10 --warmup 2 \
       > $O/04_bench_torchrun_$g.json 2> $O/04_bench_torchrun_$g.err; tail -c 600 $O/04_bench_torchrun_$g.json; echo
   for c in peer rccl; do
-    OLA_COLLECTIVE=$c timeout 1200 python bench.py --gpus $g --steps 10 --warmup 2 --no-cpu-baseline --no-config4 --no-2p24 > $O/04_bench_single_process_${g}_$c.json 2> $O/04_bench_single_process_${g}_$c.err
+    OLA_COLLECTIVE=$c timeout 1200 python bench.py --full --gpus $g --steps 10 --warmup 2 --no-cpu-baseline --no-config4 --no-2p24 > $O/04_bench_single_process_${g}_$c.json 2> $O/04_bench_single_process_${g}_$c.err
     tail -c 400 $O/04_bench_single_process_${g}_$c.json; echo
   done
 done

@@ -43,8 +43,8 @@ print('ola_gpu_warmup call %.2f ms, thread %.1f ms, ola_gpu_init after it %.1f m
 " 2>&1 | grep -v amdgpu | tee -a $O/init_split.txt ;;
     suite)       timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -15 | tee $O/pytest.log ;;
     smoke)       timeout 600 python -c 'import __graft_entry__ as g; g.smoke()' 2>&1 | tail -5 | tee $O/smoke.log ;;
-    bench)       timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; tail -c 2500 $O/bench.json; cp bench_details.json $O/ 2>/dev/null ;;
-    bench2)      timeout 900 python bench.py --gpus 2 --steps 10 --warmup 2 > $O/bench.json 2> $O/bench.err; tail -c 1500 $O/bench.json; tail -3 $O/bench.err ;;
+    bench)       timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; tail -c 2500 $O/bench.json; cp bench_details.json $O/ 2>/dev/null ;;
+    bench2)      timeout 900 python bench.py --full --gpus 2 --steps 10 --warmup 2 > $O/bench.json 2> $O/bench.err; tail -c 1500 $O/bench.json; tail -3 $O/bench.err ;;
     pool)        OLA_TIMING=0 timeout 600 python -m pytest tests/test_gpu_pool.py tests/test_gpu_host_api.py -x -q 2>&1 | tail -8 | tee $O/pytest.log
                  timeout 600 python - <<'PY' 2>&1 | grep -v amdgpu | tee $O/handover.txt
 import sys, time
@@ -66,7 +66,7 @@ for share in ("1", "0"):
 PY
                  ;;
     torchrun2)   # the launcher path of `bench.py --gpus N` (what the driver's scaling run uses), dry: two ranks share the one GPU, gloo carries the collectives
-                 OLA_BENCH_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 2 > $O/bench.json 2> $O/bench.err
+                 OLA_BENCH_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 10 --warmup 2 > $O/bench.json 2> $O/bench.err
                  tail -c 2500 $O/bench.json; tail -3 $O/bench.err ;;
     stats)       timeout 600 python tools/proof_stats.py --out $O/proof_stats.json 2>&1 | tail -8 ;;
     stats_real)  timeout 600 python tools/proof_stats.py --real --out $O/proof_stats_real.json 2>&1 | tail -8 ;;
@@ -185,7 +185,7 @@ be = Backend(device=0); print('$v library: ola_gpu_selftest(2^31) mismatches =',
     ntt_group)   # Infinity-Cache blocking of the transforms: working-set target in MB (0 = whole batch per launch)
                  for mb in 0 32 64 96 128 192; do
                    echo "-- OLA_NTT2_GROUP_MB=$mb"
-                   OLA_NTT2_GROUP_MB=$mb timeout 300 python bench.py --steps 20 --warmup 3 --no-prove --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('  ntt ms', d['ms_per_step'], 'frac', d['roofline']['frac'])"
+                   OLA_NTT2_GROUP_MB=$mb timeout 300 python bench.py --full --steps 20 --warmup 3 --no-prove --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('  ntt ms', d['ms_per_step'], 'frac', d['roofline']['frac'])"
                    OLA_NTT2_GROUP_MB=$mb timeout 300 python tools/bench_ntt_matrix.py --log-n 22 --cols 94 --reps 3 --out $O/m_$mb.json 2>&1 | grep -E "lde|intt|ntt" | cut -c1-120
                  done 2>&1 | tee $O/sweep.txt ;;
     canon_passes) # the canonical-arithmetic passes (OLA_NTT2_TFORM=0: the A/B control, and the path of transforms beyond 2^28) against the oracle
@@ -193,7 +193,7 @@ be = Backend(device=0); print('$v library: ola_gpu_selftest(2^31) mismatches =',
     tform_ab)    # T-form passes against the canonical-arithmetic passes, same box, alternating (OLA_NTT2_TFORM=0/1)
                  timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fullsize.py -x -q -k "ntt or lde or NTT or coset" 2>&1 | tail -8 | tee $O/pytest.log
                  for v in 0 1 0 1; do echo "-- OLA_NTT2_TFORM=$v"
-                   OLA_NTT2_TFORM=$v timeout 300 python bench.py --steps 30 --warmup 3 --no-prove --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('  ntt ms', d['ms_per_step'], 'frac', d['roofline']['frac'])"
+                   OLA_NTT2_TFORM=$v timeout 300 python bench.py --full --steps 30 --warmup 3 --no-prove --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('  ntt ms', d['ms_per_step'], 'frac', d['roofline']['frac'])"
                    OLA_NTT2_TFORM=$v timeout 300 python tools/bench_ntt_matrix.py --log-n 22 --cols 94 --reps 5 --out $O/m_$v.json 2>&1 | grep -E '"op"' | cut -c1-110
                  done 2>&1 | tee $O/ab.txt ;;
     tform_prof)  # per-kernel durations of the two pass families (NTT, iNTT and LDE of 94 x 2^22)
@@ -203,7 +203,7 @@ be = Backend(device=0); print('$v library: ola_gpu_selftest(2^31) mismatches =',
     lib_ab)      # same-box A/B of two builds of the library: ab_tmp/libola_<name>.so, alternating (take ab_tmp/ out of .gpurunignore for the call)
                  cp olavm_amd/lib/libola_gpu.so ab_tmp/libola_cur.so
                  for v in ${AB_VARIANTS:-old new old new}; do cp ab_tmp/libola_$v.so olavm_amd/lib/libola_gpu.so; echo "-- $v"
-                   timeout 300 python bench.py --steps 30 --warmup 3 --no-prove --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('  ntt ms', d['ms_per_step'], 'frac', d['roofline']['frac'])"
+                   timeout 300 python bench.py --full --steps 30 --warmup 3 --no-prove --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('  ntt ms', d['ms_per_step'], 'frac', d['roofline']['frac'])"
                    timeout 300 python tools/bench_ntt_matrix.py --log-n 22 --cols 94 --reps 5 --out $O/m_$v.json 2>&1 | grep -E '"op"' | cut -c1-110
                  done 2>&1 | tee $O/ab.txt; cp ab_tmp/libola_cur.so olavm_amd/lib/libola_gpu.so ;;
     pmc)         bash tools/pmc_ntt.sh r05 2>&1 | tail -30 ;;
@@ -248,7 +248,7 @@ PY
     prof_b3)     cd /tmp; OLA_HASHER=blake3 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o p -- python $R/tools/bench_prove.py 22 5 > $R/$O/run.log 2> $R/$O/err.txt; cd $R
                  f=$(find $O/prof -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp "$f" $O/kernel_stats.csv && head -16 $O/kernel_stats.csv | cut -c1-150; tail -3 $O/run.log ;;
     matrix)      timeout 1200 python tools/bench_ntt_matrix.py --out $O/ntt_matrix.json 2>&1 | tail -40 ;;
-    prof_bench)  cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o p -- python $R/bench.py --steps 20 --warmup 5 > $R/$O/bench.json 2> $R/$O/err.txt; cd $R
+    prof_bench)  cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o p -- python $R/bench.py --full --steps 20 --warmup 5 > $R/$O/bench.json 2> $R/$O/err.txt; cd $R
                  f=$(find $O/prof -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp "$f" $O/kernel_stats.csv && head -25 $O/kernel_stats.csv | cut -c1-160 ;;
     *)           echo "unknown step $step" ;;
   esac
