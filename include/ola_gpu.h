@@ -41,7 +41,9 @@ extern "C" {
  * ola_gpu_scope_times (the `timed!` scopes with device times, for the caller's TimingTree), ola_gpu_upload_stats; no struct of
  * revision 4 changed.
  * 6: ola_gpu_warmup / ola_gpu_warmup_wait (start-up work ahead of the first context, where the reference calls init_gpu()),
- * ola_gpu_ntt_pass_times (the transform passes one by one, for the dominant kernel's roofline); no struct changed. */
+ * ola_gpu_ntt_pass_times (the transform passes one by one, for the dominant kernel's roofline); no struct changed.
+ * 7 (number unchanged by the later additions, which change no struct and no existing behaviour): the hashers OLA_HASH_POSEIDON2 and
+ * OLA_HASH_POSEIDON2_POW_POSEIDON and the entry point ola_poseidon2_permute were added to revision 7. */
 #define OLA_GPU_ABI_VERSION 7
 #define OLA_OK 0
 #define OLA_E_INVALID_ARG (-1)
@@ -69,10 +71,16 @@ typedef struct OlaGpuConfig {
     uint32_t hasher;            /* GenericConfig::Hasher of the Merkle trees and the challenger (plonk/config.rs:112-161):
                                  * OLA_HASH_POSEIDON = PoseidonGoldilocksConfig (0, the default),
                                  * OLA_HASH_BLAKE3 = Blake3GoldilocksConfig.  InnerHasher (proof of work) is Poseidon in both.
+                                 * OLA_HASH_POSEIDON2 = Poseidon2GoldilocksConfig (plonk/config.rs:125): Merkle trees, challenger
+                                 * and proof of work all Poseidon2 (hash/poseidon2.rs:50); OLA_HASH_POSEIDON2_POW_POSEIDON =
+                                 * Poseidon2GoldilocksConfig2 (plonk/config.rs:135): Poseidon2 trees and challenger, Poseidon
+                                 * proof of work.
                                  * The field takes the place of the struct's tail padding: sizeof is unchanged.             */
 } OlaGpuConfig;
 #define OLA_HASH_POSEIDON 0u
 #define OLA_HASH_BLAKE3 1u
+#define OLA_HASH_POSEIDON2 2u
+#define OLA_HASH_POSEIDON2_POW_POSEIDON 3u
 
 /* ---- lifetime (replaces gpu_init / gpu_free, cfft/ntt/mod.rs:89-121 and core/src/storage/db.rs:248) ---- */
 int32_t ola_gpu_init(const OlaGpuConfig* cfg, OlaCtx** out_ctx);
@@ -280,11 +288,14 @@ int32_t ola_ntt_batch_dev(OlaCtx* ctx, int32_t op, const uint64_t* in_dev, uint6
                           uint32_t log_n, uint32_t batch, uint64_t shift, uint32_t blowup_log);
 
 /* ---- Poseidon / Merkle: replaces hash/poseidon.rs:593-603, hashing.rs:84-111, merkle_tree/mod.rs:180-337 --
- * ola_hash_rows, ola_merkle_cap and every commitment hash with the context's Hasher: the Poseidon sponge, or under
+ * ola_hash_rows, ola_merkle_cap and every commitment hash with the context's Hasher: the Poseidon sponge, the Poseidon2 sponge
+ * under OLA_HASH_POSEIDON2 / OLA_HASH_POSEIDON2_POW_POSEIDON (the same sponge and tree, hash/poseidon2.rs:500-512), or under
  * OLA_HASH_BLAKE3 Blake3_256 (hash/blake3.rs:203-233) of the canonical little-endian words; a digest is 4 words (32 bytes)
  * either way, and a Blake3 digest is bytes -- its words may be >= p and are never reduced. */
 /* n states of 12 elements each, permuted in place (host memory). */
 int32_t ola_poseidon_permute(OlaCtx* ctx, uint64_t* states, size_t n);
+/* The same with the Poseidon2 permutation, `poseidon2` (hash/poseidon2.rs:50-82), under any hasher of the context. */
+int32_t ola_poseidon2_permute(OlaCtx* ctx, uint64_t* states, size_t n);
 /* hash_no_pad over each row of a row-major num_rows x row_len host matrix -> digests (num_rows x 4). */
 int32_t ola_hash_rows(OlaCtx* ctx, const uint64_t* rows, size_t num_rows, size_t row_len, uint64_t* digests);
 /* MerkleTree::new_v2 over row-major host leaves: writes the cap (2^cap_height x 4). */
@@ -333,7 +344,7 @@ typedef struct OlaChallenger {
     uint64_t output_buffer[8];
     uint32_t input_len;
     uint32_t output_len;
-    uint32_t hasher;            /* OLA_HASH_*: the permutation (Poseidon, or Blake3Permutation, hash/blake3.rs:166-201) and  */
+    uint32_t hasher;            /* OLA_HASH_*: the permutation (Poseidon, Poseidon2, or Blake3Permutation, hash/blake3.rs:166-201) and */
     uint32_t reserved;          /* how a digest is observed; set by the init calls, do not change afterwards                 */
 } OlaChallenger;
 
@@ -359,7 +370,8 @@ int32_t ola_open_and_prove(OlaCtx* ctx, const OlaBatch* trace, const OlaBatch* z
                            size_t* out_len, size_t* openings_len);
 
 /* FRI proof of work (fri/prover.rs:126-148): the MINIMAL witness i such that
- * Poseidon.hash_no_pad([h0..h3, i])[0] has >= bits leading zeros. */
+ * InnerHasher.hash_no_pad([h0..h3, i])[0] has >= bits leading zeros; InnerHasher is Poseidon2 under OLA_HASH_POSEIDON2 and
+ * Poseidon under every other hasher. */
 int32_t ola_pow(OlaCtx* ctx, const uint64_t h[4], uint32_t bits, uint64_t* witness);
 
 /* ---- the same, one step per call (ABI revision 7): for a host that keeps the reference's own loops and its own Challenger and

@@ -58,6 +58,7 @@ struct StarkConfig {
     uint32_t rate_bits = 3, cap_height = 4, proof_of_work_bits = 16, fri_arity_bits = 4, fri_final_poly_bits = 5, num_query_rounds = 28,
              num_challenges = 2;
     // GenericConfig::Hasher (plonk/config.rs:112-161): OLA_HASH_POSEIDON = PoseidonGoldilocksConfig, OLA_HASH_BLAKE3 = Blake3GoldilocksConfig
+    // OLA_HASH_POSEIDON2 = Poseidon2GoldilocksConfig, OLA_HASH_POSEIDON2_POW_POSEIDON = Poseidon2GoldilocksConfig2
     uint32_t hasher = OLA_HASH_POSEIDON;
     static StarkConfig standard_fast_config() { return StarkConfig{}; }
 };

@@ -78,7 +78,7 @@ struct CtxKey {
 /// that many devices and the partition and its exchanges happen inside the library (`OLA_COLLECTIVE` = peer | rccl selects who
 /// moves the bytes).  The guard is held for the whole proof.
 fn with_ctx<R>(hasher: u32, config: &StarkConfig, body: impl FnOnce(*mut OlaCtx) -> Result<R>) -> Result<R> {
-    static CTX: [OnceLock<Mutex<Option<(SendPtr, CtxKey)>>>; 2] = [OnceLock::new(), OnceLock::new()];
+    static CTX: [OnceLock<Mutex<Option<(SendPtr, CtxKey)>>>; 4] = [OnceLock::new(), OnceLock::new(), OnceLock::new(), OnceLock::new()];
     let mut slot = CTX[hasher as usize].get_or_init(|| Mutex::new(None)).lock().unwrap_or_else(|e| e.into_inner());
     let fri = &config.fri_config;
     // the library folds with one arity; StarkConfig::standard_fast_config is ConstantArityBits(4, 5) (config.rs:18-30)
@@ -154,10 +154,20 @@ fn replay_scopes(c: *mut OlaCtx, timing: &mut TimingTree, t0: Instant) -> Result
 }
 
 /// `C::Hasher` -> OLA_HASH_*: the two configurations the reference instantiates the prover with
-/// (client/src/main.rs:21,31: PoseidonGoldilocksConfig; circuits/benches/fibo_loop.rs:26: Blake3GoldilocksConfig).
+/// (client/src/main.rs:21,31: PoseidonGoldilocksConfig; circuits/benches/fibo_loop.rs:26: Blake3GoldilocksConfig), and the
+/// fork's two Poseidon2 configurations, told apart by `C::InnerHasher` (plonk/config.rs:123-141: the proof-of-work hash).
 fn hasher_of<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, const D: usize>() -> Result<u32> {
     let name = type_name::<C::Hasher>();
-    if name.contains("PoseidonHash") {
+    if name.contains("Poseidon2Hash") {
+        let inner = type_name::<C::InnerHasher>();
+        if inner.contains("Poseidon2Hash") {
+            Ok(OLA_HASH_POSEIDON2)
+        } else if inner.contains("PoseidonHash") {
+            Ok(OLA_HASH_POSEIDON2_POW_POSEIDON)
+        } else {
+            Err(anyhow::anyhow!("the hip backend has no proof-of-work hash for {inner}"))
+        }
+    } else if name.contains("PoseidonHash") {
         Ok(OLA_HASH_POSEIDON)
     } else if name.contains("Blake3") {
         Ok(OLA_HASH_BLAKE3)

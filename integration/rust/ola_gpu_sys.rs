@@ -26,6 +26,10 @@ pub const OLA_E_INTERNAL: i32 = -7;
 pub const OLA_HASH_POSEIDON: u32 = 0;
 /// Blake3GoldilocksConfig (plonk/config.rs:153-161)
 pub const OLA_HASH_BLAKE3: u32 = 1;
+/// Poseidon2GoldilocksConfig (plonk/config.rs:123-131): Poseidon2 trees, transcript and proof of work
+pub const OLA_HASH_POSEIDON2: u32 = 2;
+/// Poseidon2GoldilocksConfig2 (plonk/config.rs:133-141): Poseidon2 trees and transcript, Poseidon proof of work
+pub const OLA_HASH_POSEIDON2_POW_POSEIDON: u32 = 3;
 pub const OLA_NTT_EVALUATE: i32 = 0;
 pub const OLA_NTT_INTERPOLATE: i32 = 1;
 pub const OLA_NTT_COSET_LDE: i32 = 2;
@@ -143,6 +147,7 @@ extern "C" {
     pub fn ola_ntt_batch_dev(ctx: *mut OlaCtx, op: i32, in_dev: *const u64, out_dev: *mut u64, scratch_dev: *mut u64,
         log_n: u32, batch: u32, shift: u64, blowup_log: u32) -> i32;
     pub fn ola_poseidon_permute(ctx: *mut OlaCtx, states: *mut u64, n: usize) -> i32;
+    pub fn ola_poseidon2_permute(ctx: *mut OlaCtx, states: *mut u64, n: usize) -> i32;
     pub fn ola_hash_rows(ctx: *mut OlaCtx, rows: *const u64, num_rows: usize, row_len: usize, digests: *mut u64) -> i32;
     pub fn ola_merkle_cap(ctx: *mut OlaCtx, leaves: *const u64, num_leaves: usize, leaf_len: usize, cap_height: u32,
         cap_out: *mut u64) -> i32;

@@ -42,9 +42,12 @@ class OlaChallenger(C.Structure):
                 ("input_len", C.c_uint32), ("output_len", C.c_uint32), ("hasher", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-# GenericConfig::Hasher (plonk/config.rs:112-161): PoseidonGoldilocksConfig / Blake3GoldilocksConfig
-OLA_HASH_POSEIDON, OLA_HASH_BLAKE3 = 0, 1
-HASHERS = {"poseidon": OLA_HASH_POSEIDON, "blake3": OLA_HASH_BLAKE3, OLA_HASH_POSEIDON: OLA_HASH_POSEIDON, OLA_HASH_BLAKE3: OLA_HASH_BLAKE3}
+# GenericConfig::Hasher (plonk/config.rs:112-161): PoseidonGoldilocksConfig / Blake3GoldilocksConfig / Poseidon2GoldilocksConfig /
+# Poseidon2GoldilocksConfig2 (Poseidon2 trees and transcript, Poseidon proof of work)
+OLA_HASH_POSEIDON, OLA_HASH_BLAKE3, OLA_HASH_POSEIDON2, OLA_HASH_POSEIDON2_POW_POSEIDON = 0, 1, 2, 3
+HASHERS = {"poseidon": OLA_HASH_POSEIDON, "blake3": OLA_HASH_BLAKE3, "poseidon2": OLA_HASH_POSEIDON2,
+           "poseidon2_pow_poseidon": OLA_HASH_POSEIDON2_POW_POSEIDON, OLA_HASH_POSEIDON: OLA_HASH_POSEIDON, OLA_HASH_BLAKE3: OLA_HASH_BLAKE3,
+           OLA_HASH_POSEIDON2: OLA_HASH_POSEIDON2, OLA_HASH_POSEIDON2_POW_POSEIDON: OLA_HASH_POSEIDON2_POW_POSEIDON}
 
 
 def lib_path():
@@ -88,6 +91,7 @@ def load_library():
     L.ola_ntt_batch_dev.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                     C.c_uint64, C.c_uint32]
     L.ola_poseidon_permute.argtypes = [C.c_void_p, U64P, C.c_size_t]
+    L.ola_poseidon2_permute.argtypes = [C.c_void_p, U64P, C.c_size_t]
     L.ola_hash_rows.argtypes = [C.c_void_p, U64P, C.c_size_t, C.c_size_t, U64P]
     L.ola_merkle_cap.argtypes = [C.c_void_p, U64P, C.c_size_t, C.c_size_t, C.c_uint32, U64P]
     L.ola_pow.argtypes = [C.c_void_p, U64P, C.c_uint32, U64P]
@@ -145,7 +149,7 @@ def load_library():
 
 EXPORTS = [
     "ola_gpu_init", "ola_gpu_free", "ola_gpu_last_error", "ola_gpu_sync", "ola_ntt_batch", "ola_ntt_batch_dev",
-    "ola_poseidon_permute", "ola_hash_rows", "ola_merkle_cap", "ola_commit_values", "ola_commit_coeffs",
+    "ola_poseidon_permute", "ola_poseidon2_permute", "ola_hash_rows", "ola_merkle_cap", "ola_commit_values", "ola_commit_coeffs",
     "ola_commit_values_dev", "ola_commit_coeffs_dev", "ola_batch_free", "ola_batch_shape", "ola_batch_get_coeffs",
     "ola_batch_get_leaf", "ola_batch_get_lde_row", "ola_challenger_init", "ola_challenger_observe",
     "ola_challenger_get", "ola_challenger_compact", "ola_challenger_init_hasher", "ola_challenger_observe_cap", "ola_blake3_hash_elements", "ola_open_and_prove", "ola_pow", "ola_prove_with_traces",
@@ -452,6 +456,12 @@ class Backend:
     def poseidon(self, states):
         s = np.array(states, dtype=np.uint64).reshape(-1, 12)
         self._chk(self.lib.ola_poseidon_permute(self.ctx, _p(s), s.shape[0]))
+        return s
+
+    def poseidon2(self, states):
+        """Poseidon2::poseidon2 (hash/poseidon2.rs:50) of each 12-element state, on the device, under any hasher of the context"""
+        s = np.array(states, dtype=np.uint64).reshape(-1, 12)
+        self._chk(self.lib.ola_poseidon2_permute(self.ctx, _p(s), s.shape[0]))
         return s
 
     def hash_rows(self, rows):

@@ -26,6 +26,7 @@
 #include "device_ctx.h"
 #include "gl.cuh"
 #include "poseidon_host.h"
+#include "poseidon2_host.h"
 #include "blake3.cuh"
 
 namespace ola {
@@ -36,8 +37,13 @@ static void challenger_duplex(OlaChallenger& ch) {
     ch.input_len = 0;
     u64 s[12];
     for (int i = 0; i < 12; i++) s[i] = ch.sponge_state[i];
-    if (ch.hasher == OLA_HASH_BLAKE3) b3_permutation_host(s);   // H::Permutation of Challenger<F, H> (challenger.rs:134-153)
-    else poseidon_permute_host(s);
+    switch (ch.hasher) {                                         // H::Permutation of Challenger<F, H> (challenger.rs:134-153)
+        case OLA_HASH_POSEIDON: poseidon_permute_host(s); break;
+        case OLA_HASH_BLAKE3: b3_permutation_host(s); break;
+        case OLA_HASH_POSEIDON2:
+        case OLA_HASH_POSEIDON2_POW_POSEIDON: poseidon2_permute_host(s); break;
+        default: throw OlaError(OLA_E_INTERNAL, "challenger of an unknown hasher");
+    }
     for (int i = 0; i < 12; i++) ch.sponge_state[i] = s[i];
     for (int i = 0; i < 8; i++) ch.output_buffer[i] = s[i];
     ch.output_len = 8;
@@ -51,6 +57,7 @@ void challenger_observe(OlaChallenger& ch, const u64* e, size_t n) {
 }
 // observe_cap (challenger.rs:75-84): GenericHashOut::to_vec of every digest
 void challenger_observe_cap(OlaChallenger& ch, const u64* digests, size_t n) {
+    // HashOut (Poseidon, Poseidon2): its four elements; Blake3's 32 bytes: five elements of 7 bytes (b3_digest_elements)
     if (ch.hasher != OLA_HASH_BLAKE3) { challenger_observe(ch, digests, 4 * n); return; }
     for (size_t i = 0; i < n; i++) {
         u64 e[5];
@@ -807,7 +814,7 @@ static bool pow_enqueue(DeviceCtx* ctx, PowDefer* d, const u64 h[4], u32 bits, s
     *j.h_best = ~0ull;
     j.d_best = ctx->side_words + d->jobs.size();
     HIP_CHECK(hipMemsetAsync(j.d_best, 0xFF, 8, side));
-    hipLaunchKernelGGL(pow_kernel, dim3((unsigned)(pow_batch(bits) / 256)), dim3(256), 0, side, h[0], h[1], h[2], h[3], (u64)0, bits, j.d_best);
+    launch_pow_batch(ctx, side, h, 0, pow_batch(bits), bits, j.d_best);
     HIP_CHECK(hipMemcpyAsync(j.h_best, j.d_best, 8, hipMemcpyDeviceToHost, side));
     d->jobs.push_back(j);
     return true;

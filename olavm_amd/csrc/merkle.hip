@@ -1,4 +1,6 @@
 // Poseidon-Goldilocks sponge + Merkle tree kernels for gfx950 (and the Blake3 leaves / nodes of Blake3GoldilocksConfig, blake3.cuh).
+// The sponge kernels are templates over the permutation: Poseidon (poseidon.cuh) or Poseidon2 (poseidon2.cuh, the Hasher of
+// Poseidon2GoldilocksConfig / Poseidon2GoldilocksConfig2 -- the same sponge and tree, hash/poseidon2.rs:500-512).
 //
 // Replaces (reference, relative to plonky2/plonky2/src/hash):
 //   hashing.rs:84-107            hash_n_to_m_no_pad  -- overwrite-mode sponge, rate 8, 4-element digest
@@ -12,10 +14,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
+#include "../../include/ola_gpu.h"
 #include "device_ctx.h"
 #include "gl.cuh"
 #include "poseidon.cuh"
+#include "poseidon2.cuh"
 #include "blake3.cuh"
 
 namespace ola {
@@ -23,7 +28,21 @@ namespace ola {
 // batches up to this many states / nodes / leaves use the quad-cooperative (latency-oriented) kernels
 static const size_t QUAD_MAX = 8192;
 
+// the algebraic permutation of a sponge kernel
+enum : int { PERM_POSEIDON = 0, PERM_POSEIDON2 = 1 };
+template <int PERM>
+__device__ __forceinline__ void permute12(u64 (&s)[12]) {
+    if constexpr (PERM == PERM_POSEIDON2) poseidon2_permute(s);
+    else poseidon_permute(s);
+}
+template <int PERM>
+__device__ __forceinline__ void permute_quad(u64 (&x)[3], int q) {
+    if constexpr (PERM == PERM_POSEIDON2) poseidon2_permute_quad(x, q);
+    else poseidon_permute_quad(x, q);
+}
+
 // leaf j = (cols[0][j], cols[1][j], ...), column c at base + c*col_stride
+template <int PERM>
 __global__ __launch_bounds__(256) void leaf_hash_colmajor_kernel(const u64* __restrict__ base, size_t col_stride,
                                                                   int ncols, size_t num_leaves, u64* __restrict__ out) {
     const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -36,7 +55,7 @@ __global__ __launch_bounds__(256) void leaf_hash_colmajor_kernel(const u64* __re
 #pragma unroll
         for (int i = 0; i < 8; i++)
             if (i < len) s[i] = gl_canon(base[(size_t)(c0 + i) * col_stride + j]);
-        poseidon_permute(s);
+        permute12<PERM>(s);
     }
     ulonglong2* o = reinterpret_cast<ulonglong2*>(out + j * 4);
     o[0] = make_ulonglong2(s[0], s[1]);
@@ -44,6 +63,7 @@ __global__ __launch_bounds__(256) void leaf_hash_colmajor_kernel(const u64* __re
 }
 
 // leaf j = row j of a row-major matrix (rows of row_len elements)
+template <int PERM>
 __global__ __launch_bounds__(256) void leaf_hash_rowmajor_kernel(const u64* __restrict__ rows, size_t row_len,
                                                                   size_t num_leaves, u64* __restrict__ out) {
     const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -57,7 +77,7 @@ __global__ __launch_bounds__(256) void leaf_hash_rowmajor_kernel(const u64* __re
 #pragma unroll
         for (int i = 0; i < 8; i++)
             if (i < len) s[i] = gl_canon(r[c0 + i]);
-        poseidon_permute(s);
+        permute12<PERM>(s);
     }
     ulonglong2* o = reinterpret_cast<ulonglong2*>(out + j * 4);
     o[0] = make_ulonglong2(s[0], s[1]);
@@ -66,6 +86,7 @@ __global__ __launch_bounds__(256) void leaf_hash_rowmajor_kernel(const u64* __re
 
 // FRI commit-phase leaves (fri/prover.rs:90-96): leaf j = flatten(16 consecutive bit-reversed extension values) =
 // (a[16j], b[16j], a[16j+1], b[16j+1], ...) with the extension field stored as two planes.
+template <int PERM>
 __global__ __launch_bounds__(256) void leaf_hash_ext_kernel(const u64* __restrict__ plane_a,
                                                             const u64* __restrict__ plane_b, int arity,
                                                             size_t num_leaves, u64* __restrict__ out) {
@@ -82,7 +103,7 @@ __global__ __launch_bounds__(256) void leaf_hash_ext_kernel(const u64* __restric
                 s[2 * k + 1] = plane_b[j * arity + k0 + k];
             }
         }
-        poseidon_permute(s);
+        permute12<PERM>(s);
     }
     ulonglong2* o = reinterpret_cast<ulonglong2*>(out + j * 4);
     o[0] = make_ulonglong2(s[0], s[1]);
@@ -103,6 +124,7 @@ __device__ __forceinline__ void quad_store_digest(u64* __restrict__ out4, const 
     if (q == 1) out4[3] = x[0];
 }
 
+template <int PERM>
 __global__ __launch_bounds__(256) void leaf_hash_colmajor_quad_kernel(const u64* __restrict__ base, size_t col_stride, int ncols,
                                                                        size_t num_leaves, u64* __restrict__ out) {
     QUAD_PROLOGUE(num_leaves)
@@ -113,11 +135,12 @@ __global__ __launch_bounds__(256) void leaf_hash_colmajor_quad_kernel(const u64*
             const int e = 3 * q + k;   // sponge lane
             if (e < 8 && c0 + e < ncols) x[k] = gl_canon(base[(size_t)(c0 + e) * col_stride + j]);
         }
-        poseidon_permute_quad(x, q);
+        permute_quad<PERM>(x, q);
     }
     quad_store_digest(out + j * 4, x, q, live);
 }
 
+template <int PERM>
 __global__ __launch_bounds__(256) void leaf_hash_rowmajor_quad_kernel(const u64* __restrict__ rows, size_t row_len, size_t num_leaves,
                                                                        u64* __restrict__ out) {
     QUAD_PROLOGUE(num_leaves)
@@ -129,11 +152,12 @@ __global__ __launch_bounds__(256) void leaf_hash_rowmajor_quad_kernel(const u64*
             const size_t e = 3 * q + k;
             if (e < 8 && c0 + e < row_len) x[k] = gl_canon(r[c0 + e]);
         }
-        poseidon_permute_quad(x, q);
+        permute_quad<PERM>(x, q);
     }
     quad_store_digest(out + j * 4, x, q, live);
 }
 
+template <int PERM>
 __global__ __launch_bounds__(256) void leaf_hash_ext_quad_kernel(const u64* __restrict__ plane_a, const u64* __restrict__ plane_b, int arity,
                                                                   size_t num_leaves, u64* __restrict__ out) {
     QUAD_PROLOGUE(num_leaves)
@@ -144,12 +168,13 @@ __global__ __launch_bounds__(256) void leaf_hash_ext_quad_kernel(const u64* __re
             const int e = 3 * q + k;
             if (e < 8 && k0 + e / 2 < arity) x[k] = ((e & 1) ? plane_b : plane_a)[j * arity + k0 + e / 2];
         }
-        poseidon_permute_quad(x, q);
+        permute_quad<PERM>(x, q);
     }
     quad_store_digest(out + j * 4, x, q, live);
 }
 
 // node i = H(heap[2i] || heap[2i+1]) for i in [first, first + count)
+template <int PERM>
 __device__ __forceinline__ void quad_hash_node(u64* __restrict__ heap, size_t i, int q, bool live) {
     u64 x[3];
 #pragma unroll
@@ -157,15 +182,17 @@ __device__ __forceinline__ void quad_hash_node(u64* __restrict__ heap, size_t i,
         const int e = 3 * q + k;
         x[k] = e < 8 ? heap[8 * i + e] : 0;   // the two child digests are adjacent
     }
-    poseidon_permute_quad(x, q);
+    permute_quad<PERM>(x, q);
     quad_store_digest(heap + 4 * i, x, q, live);
 }
+template <int PERM>
 __global__ __launch_bounds__(256) void merkle_level_quad_kernel(u64* __restrict__ heap, size_t first, size_t count) {
     QUAD_PROLOGUE(count)
-    quad_hash_node(heap, first + j, q, live);
+    quad_hash_node<PERM>(heap, first + j, q, live);
 }
 
 // parents [first, first+count) of a heap-ordered digest array
+template <int PERM>
 __global__ __launch_bounds__(256) void merkle_level_kernel(u64* __restrict__ heap, size_t first, size_t count) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count) return;
@@ -173,7 +200,7 @@ __global__ __launch_bounds__(256) void merkle_level_kernel(u64* __restrict__ hea
     const ulonglong2* ch = reinterpret_cast<const ulonglong2*>(heap + 8 * i);  // children 2i, 2i+1 are adjacent
     const ulonglong2 c0 = ch[0], c1 = ch[1], c2 = ch[2], c3 = ch[3];
     u64 s[12] = {c0.x, c0.y, c1.x, c1.y, c2.x, c2.y, c3.x, c3.y, 0, 0, 0, 0};
-    poseidon_permute(s);
+    permute12<PERM>(s);
     ulonglong2* o = reinterpret_cast<ulonglong2*>(heap + 4 * i);
     o[0] = make_ulonglong2(s[0], s[1]);
     o[1] = make_ulonglong2(s[2], s[3]);
@@ -181,6 +208,7 @@ __global__ __launch_bounds__(256) void merkle_level_kernel(u64* __restrict__ hea
 
 // The top of a tree in one launch: levels of `first` nodes and fewer (4 * first <= blockDim.x), down to the level of `last`
 // nodes, one workgroup of quads, a barrier between levels.
+template <int PERM>
 __global__ __launch_bounds__(1024) void merkle_top_kernel(u64* __restrict__ heap, size_t first, size_t last) {
     const size_t t = threadIdx.x >> 2;
     const int q = threadIdx.x & 3;
@@ -188,7 +216,7 @@ __global__ __launch_bounds__(1024) void merkle_top_kernel(u64* __restrict__ heap
     for (size_t level = first; level >= last && level >= 1; level >>= 1) {
         if (wave_first < level) {   // wavefronts without a node of this level only wait at the barrier
             const bool live = t < level;
-            quad_hash_node(heap, level + (live ? t : level - 1), q, live);
+            quad_hash_node<PERM>(heap, level + (live ? t : level - 1), q, live);
         }
         __threadfence_block();
         __syncthreads();
@@ -238,6 +266,7 @@ void launch_poseidon_trace(DeviceCtx* ctx, const u64* inputs, const u64* filters
 }
 
 // quad-cooperative permutation of whole states (4 threads per state); used for small n
+template <int PERM>
 __global__ __launch_bounds__(256) void poseidon_states_quad_kernel(u64* __restrict__ states, size_t n) {
     const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t t = g >> 2;
@@ -246,31 +275,33 @@ __global__ __launch_bounds__(256) void poseidon_states_quad_kernel(u64* __restri
     u64 x[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) x[k] = gl_canon(states[tt * 12 + 3 * q + k]);
-    poseidon_permute_quad(x, q);
+    permute_quad<PERM>(x, q);
     if (t < n) {
 #pragma unroll
         for (int k = 0; k < 3; k++) states[t * 12 + 3 * q + k] = x[k];
     }
 }
 
+template <int PERM>
 __global__ __launch_bounds__(256) void poseidon_states_kernel(u64* __restrict__ states, size_t n) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
     u64 s[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = gl_canon(states[t * 12 + i]);
-    poseidon_permute(s);
+    permute12<PERM>(s);
 #pragma unroll
     for (int i = 0; i < 12; i++) states[t * 12 + i] = s[i];
 }
 
 // FRI proof of work (fri/prover.rs:126-148): each thread tries nonce = start + global id; the minimum satisfying
 // nonce of the batch is kept with an atomicMin.
+template <int PERM>
 __global__ __launch_bounds__(256) void pow_kernel(u64 h0, u64 h1, u64 h2, u64 h3, u64 start, u32 bits,
                                                   unsigned long long* __restrict__ best) {
     const u64 nonce = start + (u64)blockIdx.x * blockDim.x + threadIdx.x;
     u64 s[12] = {h0, h1, h2, h3, nonce, 0, 0, 0, 0, 0, 0, 0};
-    poseidon_permute(s);
+    permute12<PERM>(s);
     if ((s[0] >> (64 - bits)) == 0) atomicMin(best, (unsigned long long)nonce);
 }
 
@@ -380,18 +411,36 @@ __global__ __launch_bounds__(256) void merkle_top_b3_kernel(u64* __restrict__ he
         __syncthreads();
     }
 }
-static inline bool is_b3(const DeviceCtx* ctx) { return ctx->hasher == 1; }
+static inline bool is_b3(const DeviceCtx* ctx) { return ctx->hasher == (int)OLA_HASH_BLAKE3; }
+// f(std::integral_constant<int, PERM>) with the sponge permutation of `hasher`: the context's Hasher (trees) or InnerHasher (proof of
+// work).  Every hasher the context accepts is named here: a new one is an error until it is, never a silent Poseidon.
+template <class F>
+static void with_perm(uint32_t hasher, F&& f) {
+    switch (hasher) {
+        case OLA_HASH_POSEIDON: f(std::integral_constant<int, PERM_POSEIDON>()); return;
+        case OLA_HASH_POSEIDON2:
+        case OLA_HASH_POSEIDON2_POW_POSEIDON: f(std::integral_constant<int, PERM_POSEIDON2>()); return;
+        default: throw OlaError(OLA_E_INTERNAL, "no sponge permutation for this hasher");
+    }
+}
+// plonk/config.rs:117-161: InnerHasher is Poseidon2 in Poseidon2GoldilocksConfig only, Poseidon in every other configuration
+static inline uint32_t inner_hasher(const DeviceCtx* ctx) {
+    return ctx->hasher == (int)OLA_HASH_POSEIDON2 ? OLA_HASH_POSEIDON2 : OLA_HASH_POSEIDON;
+}
 static void require_leaf_width(size_t words) {
     if (words == 0 || words > 4096) throw OlaError(-1, "Blake3 leaves hold 1..4096 field elements");
 }
 
 // ---- host launchers ----
-void poseidon_init(DeviceCtx*) { poseidon_upload_constants(); }
+void poseidon_init(DeviceCtx*) {   // both permutations' constants on the calling thread's device, whatever the hasher
+    poseidon_upload_constants();
+    poseidon2_upload_constants();
+}
 
 // hash invocations per leaf of `words` field elements: sponge permutations (rate 8), or Blake3 compressions (64-byte blocks,
 // plus the parent compressions of a multi-chunk leaf)
 static double leaf_hash_calls(const DeviceCtx* ctx, size_t words) {
-    if (ctx->hasher == 1) { const size_t blocks = (words * 8 + 63) / 64, chunks = (words * 8 + 1023) / 1024; return (double)(blocks + chunks - 1); }
+    if (is_b3(ctx)) { const size_t blocks = (words * 8 + 63) / 64, chunks = (words * 8 + 1023) / 1024; return (double)(blocks + chunks - 1); }
     return (double)((words + 7) / 8);
 }
 void launch_leaf_hash_colmajor(DeviceCtx* ctx, const u64* base, size_t col_stride, int ncols, size_t num_leaves,
@@ -406,14 +455,17 @@ void launch_leaf_hash_colmajor(DeviceCtx* ctx, const u64* base, size_t col_strid
         }
         return;
     }
-    if (num_leaves <= QUAD_MAX) {
-        hipLaunchKernelGGL(leaf_hash_colmajor_quad_kernel, dim3((unsigned)((4 * num_leaves + 255) / 256)), dim3(256), 0, ctx->stream, base,
-                           col_stride, ncols, num_leaves, out);
-        return;
-    }
-    const unsigned blocks = (unsigned)((num_leaves + 255) / 256);
-    hipLaunchKernelGGL(leaf_hash_colmajor_kernel, dim3(blocks), dim3(256), 0, ctx->stream, base, col_stride, ncols,
-                       num_leaves, out);
+    with_perm((uint32_t)ctx->hasher, [&](auto perm) {
+        constexpr int PERM = decltype(perm)::value;
+        if (num_leaves <= QUAD_MAX) {
+            hipLaunchKernelGGL(leaf_hash_colmajor_quad_kernel<PERM>, dim3((unsigned)((4 * num_leaves + 255) / 256)), dim3(256), 0, ctx->stream, base,
+                               col_stride, ncols, num_leaves, out);
+            return;
+        }
+        const unsigned blocks = (unsigned)((num_leaves + 255) / 256);
+        hipLaunchKernelGGL(leaf_hash_colmajor_kernel<PERM>, dim3(blocks), dim3(256), 0, ctx->stream, base, col_stride, ncols,
+                           num_leaves, out);
+    });
 }
 void launch_leaf_hash_rowmajor(DeviceCtx* ctx, const u64* rows, size_t row_len, size_t num_leaves, u64* out) {
     if (is_b3(ctx)) {
@@ -425,13 +477,16 @@ void launch_leaf_hash_rowmajor(DeviceCtx* ctx, const u64* rows, size_t row_len, 
         }
         return;
     }
-    if (num_leaves <= QUAD_MAX) {
-        hipLaunchKernelGGL(leaf_hash_rowmajor_quad_kernel, dim3((unsigned)((4 * num_leaves + 255) / 256)), dim3(256), 0, ctx->stream, rows,
-                           row_len, num_leaves, out);
-        return;
-    }
-    const unsigned blocks = (unsigned)((num_leaves + 255) / 256);
-    hipLaunchKernelGGL(leaf_hash_rowmajor_kernel, dim3(blocks), dim3(256), 0, ctx->stream, rows, row_len, num_leaves, out);
+    with_perm((uint32_t)ctx->hasher, [&](auto perm) {
+        constexpr int PERM = decltype(perm)::value;
+        if (num_leaves <= QUAD_MAX) {
+            hipLaunchKernelGGL(leaf_hash_rowmajor_quad_kernel<PERM>, dim3((unsigned)((4 * num_leaves + 255) / 256)), dim3(256), 0, ctx->stream, rows,
+                               row_len, num_leaves, out);
+            return;
+        }
+        const unsigned blocks = (unsigned)((num_leaves + 255) / 256);
+        hipLaunchKernelGGL(leaf_hash_rowmajor_kernel<PERM>, dim3(blocks), dim3(256), 0, ctx->stream, rows, row_len, num_leaves, out);
+    });
 }
 void launch_leaf_hash_ext(DeviceCtx* ctx, const u64* pa, const u64* pb, int arity, size_t num_leaves, u64* out) {
     PhaseScope ph(ctx, PH_LEAF_HASH, (double)num_leaves * leaf_hash_calls(ctx, (size_t)(2 * arity)), (double)num_leaves * ((size_t)arity * 16 + 32));
@@ -450,13 +505,16 @@ void launch_leaf_hash_ext(DeviceCtx* ctx, const u64* pa, const u64* pb, int arit
         }
         return;
     }
-    if (num_leaves <= QUAD_MAX) {
-        hipLaunchKernelGGL(leaf_hash_ext_quad_kernel, dim3((unsigned)((4 * num_leaves + 255) / 256)), dim3(256), 0, ctx->stream, pa, pb, arity,
-                           num_leaves, out);
-        return;
-    }
-    const unsigned blocks = (unsigned)((num_leaves + 255) / 256);
-    hipLaunchKernelGGL(leaf_hash_ext_kernel, dim3(blocks), dim3(256), 0, ctx->stream, pa, pb, arity, num_leaves, out);
+    with_perm((uint32_t)ctx->hasher, [&](auto perm) {
+        constexpr int PERM = decltype(perm)::value;
+        if (num_leaves <= QUAD_MAX) {
+            hipLaunchKernelGGL(leaf_hash_ext_quad_kernel<PERM>, dim3((unsigned)((4 * num_leaves + 255) / 256)), dim3(256), 0, ctx->stream, pa, pb, arity,
+                               num_leaves, out);
+            return;
+        }
+        const unsigned blocks = (unsigned)((num_leaves + 255) / 256);
+        hipLaunchKernelGGL(leaf_hash_ext_kernel<PERM>, dim3(blocks), dim3(256), 0, ctx->stream, pa, pb, arity, num_leaves, out);
+    });
 }
 // heap[N..2N) must hold the leaf digests; fills heap[2^cap_height .. N): like the reference (merkle_tree/mod.rs:228-233)
 // nothing above the cap is ever hashed
@@ -479,23 +537,37 @@ void launch_merkle_build(DeviceCtx* ctx, u64* heap, size_t num_leaves, uint32_t 
         if (level >= last && level >= 1) hipLaunchKernelGGL(merkle_top_b3_kernel, dim3(1), dim3(256), 0, ctx->stream, heap, level, last);
         return;
     }
-    for (; level >= last && level > top; level /= 2) {
-        if (level <= QUAD_MAX) {
-            hipLaunchKernelGGL(merkle_level_quad_kernel, dim3((unsigned)((4 * level + 255) / 256)), dim3(256), 0, ctx->stream, heap, level, level);
-        } else {
-            hipLaunchKernelGGL(merkle_level_kernel, dim3((unsigned)((level + 255) / 256)), dim3(256), 0, ctx->stream, heap, level, level);
+    with_perm((uint32_t)ctx->hasher, [&](auto perm) {
+        constexpr int PERM = decltype(perm)::value;
+        for (; level >= last && level > top; level /= 2) {
+            if (level <= QUAD_MAX) {
+                hipLaunchKernelGGL(merkle_level_quad_kernel<PERM>, dim3((unsigned)((4 * level + 255) / 256)), dim3(256), 0, ctx->stream, heap, level, level);
+            } else {
+                hipLaunchKernelGGL(merkle_level_kernel<PERM>, dim3((unsigned)((level + 255) / 256)), dim3(256), 0, ctx->stream, heap, level, level);
+            }
         }
-    }
-    if (level >= last && level >= 1) hipLaunchKernelGGL(merkle_top_kernel, dim3(1), dim3(1024), 0, ctx->stream, heap, level, last);
+        if (level >= last && level >= 1) hipLaunchKernelGGL(merkle_top_kernel<PERM>, dim3(1), dim3(1024), 0, ctx->stream, heap, level, last);
+    });
 }
-void launch_poseidon_states(DeviceCtx* ctx, u64* states, size_t n) {
+// `hasher` names the permutation (OLA_HASH_POSEIDON or OLA_HASH_POSEIDON2), not the context's configuration
+void launch_poseidon_states(DeviceCtx* ctx, u64* states, size_t n, uint32_t hasher = OLA_HASH_POSEIDON) {
     if (n == 0) return;
-    if (n <= QUAD_MAX) {
-        hipLaunchKernelGGL(poseidon_states_quad_kernel, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, ctx->stream, states, n);
-        return;
-    }
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(poseidon_states_kernel, dim3(blocks), dim3(256), 0, ctx->stream, states, n);
+    with_perm(hasher, [&](auto perm) {
+        constexpr int PERM = decltype(perm)::value;
+        if (n <= QUAD_MAX) {
+            hipLaunchKernelGGL(poseidon_states_quad_kernel<PERM>, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, ctx->stream, states, n);
+            return;
+        }
+        const unsigned blocks = (unsigned)((n + 255) / 256);
+        hipLaunchKernelGGL(poseidon_states_kernel<PERM>, dim3(blocks), dim3(256), 0, ctx->stream, states, n);
+    });
+}
+// one batch of the proof-of-work search with the context's InnerHasher (fri/prover.rs:133 C::InnerHasher::hash_no_pad)
+static void launch_pow_batch(DeviceCtx* ctx, hipStream_t stream, const u64 h[4], u64 start, u64 count, u32 bits, unsigned long long* best) {
+    with_perm(inner_hasher(ctx), [&](auto perm) {
+        constexpr int PERM = decltype(perm)::value;
+        hipLaunchKernelGGL(pow_kernel<PERM>, dim3((unsigned)(count / 256)), dim3(256), 0, stream, h[0], h[1], h[2], h[3], start, bits, best);
+    });
 }
 // minimal nonce with `bits` leading zeros; scans batches of 2^20 nonces in increasing order
 u64 run_pow(DeviceCtx* ctx, const u64 h[4], u32 bits) {
@@ -506,8 +578,7 @@ u64 run_pow(DeviceCtx* ctx, const u64 h[4], u32 bits) {
     const u64 batch = std::max<u64>((u64)1 << 14, (u64)4 << bits);
     for (u64 start = 0; best == none; start += batch) {
         HIP_CHECK(hipMemcpyAsync(d_best, &none, 8, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(pow_kernel, dim3((unsigned)(batch / 256)), dim3(256), 0, ctx->stream, h[0], h[1], h[2], h[3],
-                           start, bits, d_best);
+        launch_pow_batch(ctx, ctx->stream, h, start, batch, bits, d_best);
         HIP_CHECK(hipMemcpyAsync(&best, d_best, 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }

@@ -92,6 +92,10 @@ static void clear_stale_errors() {
 static void require(bool ok, const char* what) {
     if (!ok) throw OlaError(OLA_E_INVALID_ARG, std::string("invalid argument: ") + what);
 }
+// the GenericConfig<2> types the library proves under (include/ola_gpu.h OLA_HASH_*)
+static bool known_hasher(uint32_t h) {
+    return h == OLA_HASH_POSEIDON || h == OLA_HASH_BLAKE3 || h == OLA_HASH_POSEIDON2 || h == OLA_HASH_POSEIDON2_POW_POSEIDON;
+}
 
 // The HIP current device is a property of the calling host thread: every entry point that works on a context makes the
 // context's device current for its duration (and puts the caller's back), so that hipMalloc and constant uploads land on the
@@ -136,7 +140,7 @@ static OlaGpuConfig resolve_config(const OlaGpuConfig* cfg) {
     require(c.fri_final_poly_bits <= 16, "fri_final_poly_bits must be at most 16");
     require(c.num_query_rounds >= 1 && c.num_query_rounds <= 1024, "num_query_rounds must be in 1..1024");
     require(c.num_challenges == 2, "num_challenges must be 2 (circuits/src/stark/config.rs)");
-    require(c.hasher == OLA_HASH_POSEIDON || c.hasher == OLA_HASH_BLAKE3, "hasher must be OLA_HASH_POSEIDON or OLA_HASH_BLAKE3");
+    require(known_hasher(c.hasher), "hasher must be OLA_HASH_POSEIDON, OLA_HASH_BLAKE3, OLA_HASH_POSEIDON2 or OLA_HASH_POSEIDON2_POW_POSEIDON");
     return c;
 }
 
@@ -693,6 +697,19 @@ int32_t ola_poseidon_permute(OlaCtx* ctx, uint64_t* states, size_t n) {
     HIP_CHECK(hipStreamSynchronize(ctx->dev.stream));
     OLA_CATCH
 }
+int32_t ola_poseidon2_permute(OlaCtx* ctx, uint64_t* states, size_t n) {
+    OLA_TRY
+    OLA_ON_DEVICE(ctx);
+    require(ctx && (states || n == 0), "null pointer");
+    if (n == 0) return OLA_OK;
+    DevBuf mem(&ctx->dev);
+    u64* d = (u64*)mem.alloc_bytes(n * 96);
+    HIP_CHECK(hipMemcpyAsync(d, states, n * 96, hipMemcpyHostToDevice, ctx->dev.stream));
+    launch_poseidon_states(&ctx->dev, d, n, OLA_HASH_POSEIDON2);
+    HIP_CHECK(hipMemcpyAsync(states, d, n * 96, hipMemcpyDeviceToHost, ctx->dev.stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->dev.stream));
+    OLA_CATCH
+}
 
 int32_t ola_hash_rows(OlaCtx* ctx, const uint64_t* rows, size_t num_rows, size_t row_len, uint64_t* digests) {
     OLA_TRY
@@ -832,7 +849,7 @@ int32_t ola_challenger_init(OlaChallenger* ch) {
 int32_t ola_challenger_init_hasher(OlaChallenger* ch, uint32_t hasher) {
     OLA_TRY
     require(ch, "challenger");
-    require(hasher == OLA_HASH_POSEIDON || hasher == OLA_HASH_BLAKE3, "hasher must be OLA_HASH_POSEIDON or OLA_HASH_BLAKE3");
+    require(known_hasher(hasher), "hasher must be OLA_HASH_POSEIDON, OLA_HASH_BLAKE3, OLA_HASH_POSEIDON2 or OLA_HASH_POSEIDON2_POW_POSEIDON");
     challenger_init(*ch, hasher);
     OLA_CATCH
 }

@@ -10,6 +10,9 @@ everything else on the VALU (64-bit adds, carries, multiplies, multiply-adds, le
 selects: 4.2 - 4.8 cycles).  `cycles` = 2.6 * fast + 4.6 * slow is the issue-time model used in DESIGN.md.
 
     python tools/isa_count.py olavm_amd/csrc/ola_gpu.hip --filter ntt2_pass_kernel [--per N] [-D NAME=VAL ...]
+
+--trips 4,22,4 gives the loops of a kernel trip counts (in the order of their back edges) and prints the VALU instructions one pass
+through the kernel executes: how the per-permutation counts of the hash kernels (rounds in `#pragma unroll 1` loops) are taken.
 """
 import argparse
 import os
@@ -89,6 +92,40 @@ def parse(path):
     return kernels, meta
 
 
+def weighted_valu(path, kernel, trips):
+    """VALU instructions executed by one pass through `kernel` when its loops (back edges in order) run trips[i] times"""
+    lines, labels, inside = [], {}, False
+    for line in open(path):
+        s = line.strip()
+        if re.match(r"^%s:\s*(;.*)?$" % re.escape(kernel), s):
+            inside = True
+            continue
+        if not inside:
+            continue
+        if s.startswith(".Lfunc_end") or s.startswith("s_endpgm"):
+            break
+        if re.match(r"^\.L\w+:", s):
+            labels[s.split(":")[0]] = len(lines)
+        elif s and not s.startswith((".", ";", "//")):
+            lines.append(s)
+    loops = []
+    for i, s in enumerate(lines):
+        m = re.match(r"^s_(?:cbranch_\w+|branch)\s+(\.L\w+)", s)
+        if m and m.group(1) in labels and labels[m.group(1)] <= i:
+            loops.append((labels[m.group(1)], i))
+    if len(loops) != len(trips):
+        raise SystemExit(f"{kernel}: {len(loops)} loops, {len(trips)} trip counts given")
+    total = 0
+    for i, s in enumerate(lines):
+        if s.startswith("v_"):
+            w = 1
+            for (a, b), t in zip(loops, trips):
+                if a <= i <= b:
+                    w *= t
+            total += w
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("src")
@@ -97,6 +134,7 @@ def main():
     ap.add_argument("-D", action="append", default=[])
     ap.add_argument("--top", type=int, default=0, help="print the N most frequent VALU opcodes")
     ap.add_argument("--asm", default="", help="read this assembly file instead of compiling")
+    ap.add_argument("--trips", default="", help="comma-separated trip counts of the kernel's loops: print the executed VALU count")
     ap.add_argument("extra", nargs="*")
     a = ap.parse_args()
     path = a.asm or compile_asm(a.src, a.D, a.extra)
@@ -116,6 +154,8 @@ def main():
         line += f"\n   vgpr {m.get('vgpr')} (arch {m.get('accum_offset')})  lds {m.get('lds')} B  scratch {m.get('scratch')} B"
         if a.per:
             line += f"\n   per element (/{a.per:g}): VALU {valu / a.per:.1f}  fast {k['fast'] / a.per:.1f}  slow {k['slow'] / a.per:.1f}  model cycles {cyc / a.per:.1f}"
+        if a.trips:
+            line += f"\n   executed VALU with loop trips {a.trips}: {weighted_valu(path, name, [int(t) for t in a.trips.split(',')])}"
         print(line)
         if a.top:
             for op, n in sorted(k["ops"].items(), key=lambda t: -t[1])[:a.top]:

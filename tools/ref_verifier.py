@@ -65,8 +65,8 @@ def decode_all_proof(raw, hasher="poseidon"):
 
     def digest():
         nonlocal off
-        h = hash_out(raw, off) if hasher == "poseidon" else bytes_hash(raw[off:off + 32])
-        if hasher == "poseidon" and any(x.v != w for x, w in zip(h["elements"], struct.unpack_from("<4Q", raw, off))):
+        h = bytes_hash(raw[off:off + 32]) if hasher == "blake3" else hash_out(raw, off)      # a HashOut under Poseidon and Poseidon2
+        if hasher != "blake3" and any(x.v != w for x, w in zip(h["elements"], struct.unpack_from("<4Q", raw, off))):
             raise ValueError(f"non-canonical digest word at byte {off}")
         off += 32
         return h
@@ -290,7 +290,7 @@ def verifier_interp(reference, fast_hash=True, hasher="poseidon"):
     if re.search(r"const W: Self = Self\((\d+)\);", open(os.path.join(reference, "plonky2", "field", "src", "goldilocks_extensions.rs")).read()).group(1) != str(Fe2.W):
         raise SystemExit("the quadratic extension's W is not 7")
     # Hasher::zero_hash (plonk/config.rs:72-78): HASH_SIZE zero bytes through Hash::from_bytes
-    it.assoc_hooks[("Hasher", "zero_hash")] = (lambda args: hash_out(bytes(32), 0)) if hasher == "poseidon" else (lambda args: bytes_hash(bytes(32)))
+    it.assoc_hooks[("Hasher", "zero_hash")] = (lambda args: bytes_hash(bytes(32))) if hasher == "blake3" else (lambda args: hash_out(bytes(32), 0))
     poseidon = it.permutation_hook
     if fast_hash:
         fp = FastPoseidon(circ, diag, rc)
@@ -306,9 +306,38 @@ def verifier_interp(reference, fast_hash=True, hasher="poseidon"):
                             "Hash": ["BytesHash"]})
         # `H::Permutation::permute` (the challenger's sponge) is the config hasher's; `P::permute` inside hashing.rs is PoseidonHash's own
         it.permutation_hook = lambda st, segs=None: onion(st) if (segs and "Permutation" in segs) else poseidon(st)
+    elif hasher in POSEIDON2_CONFIGS:
+        # Poseidon2GoldilocksConfig / Poseidon2GoldilocksConfig2 (plonk/config.rs:123-141): Hasher = Poseidon2Hash; InnerHasher (the proof of
+        # work) = Poseidon2Hash / PoseidonHash.  Every permutation the interpreter reaches is Poseidon2's -- the challenger's and the one
+        # inside hashing.rs behind Poseidon2Hash::hash_no_pad / two_to_one -- except, under Config2, PoseidonHash::hash_no_pad of the proof
+        # of work (fri/challenges.rs:52), hooked here as the same sponge over the Poseidon permutation; its inputs go to it.pow_inputs.
+        import poseidon2_ref as Q
+        fp2 = Q.FastPoseidon2(it)
+        fp2.check(it)
+        it.extra_files.append(os.path.join(base, "hash", "poseidon2.rs"))
+        inner = "Poseidon2Hash" if hasher == "poseidon2" else "PoseidonHash"
+        it.generics.update({"C": [POSEIDON2_CONFIGS[hasher]], "Hasher": ["Poseidon2Hash", "Hasher"], "H": ["Poseidon2Hash", "Hasher"],
+                            "OH": ["Poseidon2Hash", "Hasher"], "InnerHasher": [inner, "Hasher"]})
+        it.permutation_hook = lambda st, segs=None: fp2.permute(st)
+        if inner == "PoseidonHash":
+            it.pow_inputs = []
+
+            def poseidon_hash_no_pad(args):          # hashing.rs:84-107 over Poseidon: overwrite-mode sponge, rate 8
+                x = list(args[0])
+                it.pow_inputs.append([e.v for e in x])
+                st = [Fe(0)] * 12
+                for c0 in range(0, len(x), 8):
+                    blk = x[c0:c0 + 8]
+                    st[:len(blk)] = blk
+                    st = poseidon(st)
+                return Struct({"__name__": "HashOut", "elements": st[:4]})
+            it.assoc_hooks[("PoseidonHash", "hash_no_pad")] = poseidon_hash_no_pad
     elif hasher != "poseidon":
         raise ValueError(hasher)
     return it
+
+
+POSEIDON2_CONFIGS = {"poseidon2": "Poseidon2GoldilocksConfig", "poseidon2_pow_poseidon": "Poseidon2GoldilocksConfig2"}
 
 
 STARK_FIELDS = ["cpu_stark", "memory_stark", "bitwise_stark", "cmp_stark", "rangecheck_stark", "poseidon_stark", "poseidon_chunk_stark", "storage_access_stark",
@@ -386,7 +415,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("proof")
     ap.add_argument("--reference", default="/root/reference")
-    ap.add_argument("--hasher", default="poseidon", choices=("poseidon", "blake3"), help="PoseidonGoldilocksConfig or Blake3GoldilocksConfig")
+    ap.add_argument("--hasher", default="poseidon", choices=("poseidon", "blake3", "poseidon2", "poseidon2_pow_poseidon"),
+                    help="PoseidonGoldilocksConfig, Blake3GoldilocksConfig, Poseidon2GoldilocksConfig or Poseidon2GoldilocksConfig2")
     a = ap.parse_args()
     raw = open(a.proof, "rb").read()
     proof = decode_all_proof(raw, a.hasher)
