@@ -113,6 +113,17 @@ def load_library():
     L.ola_challenger_compact.argtypes = [C.POINTER(OlaChallenger)]
     L.ola_open_and_prove.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(OlaChallenger),
                                      C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    # the opening proof one step per call (FriSteps)
+    L.ola_open.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, U64P, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t),
+                           C.POINTER(C.c_void_p)]
+    L.ola_fri_plan.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.ola_fri_commit_begin.argtypes = [C.c_void_p, U64P]
+    L.ola_fri_commit_next_layer.argtypes = [C.c_void_p, U64P, U64P]
+    L.ola_fri_commit_finish.argtypes = [C.c_void_p, U64P, U64P, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.ola_fri_query.argtypes = [C.c_void_p, U64P, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.ola_fri_free.argtypes = [C.c_void_p]
+    for f in ("ola_open", "ola_fri_plan", "ola_fri_commit_begin", "ola_fri_commit_next_layer", "ola_fri_commit_finish", "ola_fri_query", "ola_fri_free"):
+        getattr(L, f).restype = C.c_int32
     L.ola_prove_with_traces.argtypes = [C.c_void_p, U64P, C.c_size_t, C.POINTER(U64P), C.POINTER(C.c_uint32), U64P, U64P,
                                         C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.ola_prove_with_traces_cols.argtypes = [C.c_void_p, U64P, C.c_size_t, C.POINTER(C.POINTER(U64P)), C.POINTER(C.c_uint32), U64P, U64P,

@@ -476,7 +476,7 @@ struct DevBuf {
     size_t pinned_mark;
     struct Pending { void* dst; const u64* src; size_t bytes; };
     std::vector<Pending> pending;      // read-backs that landed in pinned memory and still have to reach the caller's buffer
-    bool use_pinned = true;            // false: a scope that outlives its call (OlaFri) -- the arena is a stack and is left to the calls
+    const bool use_pinned;             // false: a scope that outlives its call (OlaFri) -- the arena is a stack and is left to the calls
     HostSpan host(size_t elems) {
         if (use_pinned)
             if (void* p = ctx->pinned_alloc(std::max<size_t>(1, elems) * 8)) return {(u64*)p, elems};
@@ -510,7 +510,7 @@ struct DevBuf {
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
         collect();
     }
-    explicit DevBuf(DeviceCtx* c) : ctx(c), pinned_mark(c->pinned_top) {}
+    explicit DevBuf(DeviceCtx* c, bool pinned = true) : ctx(c), pinned_mark(c->pinned_top), use_pinned(pinned) {}
     u64* alloc(size_t elems) { return (u64*)alloc_bytes(elems * 8); }
     void* alloc_bytes(size_t bytes) {
         void* p = ctx->alloc(bytes);
@@ -839,154 +839,370 @@ void pow_abandon(DeviceCtx* ctx, PowDefer& d) {
     d.jobs.clear();
 }
 
-// ------------------------------------------------------------------------------------------------ the pipeline
-void open_and_prove(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, const OlaBatch& trace, const OlaBatch& zs,
-                    const OlaBatch& quot, uint32_t nperm, OlaChallenger& ch, std::vector<uint8_t>& bytes, size_t& openings_len,
-                    PowDefer* pow_defer = nullptr) {
-    DevBuf mem(ctx);
-    const int degree_bits = (int)trace.log_n;
-    const size_t n = trace.n();
-    const int rate_bits = (int)cfg.rate_bits;
-    const size_t N = n << rate_bits;
-    const int W = (int)trace.ncols, Z = (int)zs.ncols, Q = (int)quot.ncols;
-    const size_t len_cap = (size_t)1 << cfg.cap_height;
-    std::vector<int> arities = fri_arities(cfg, degree_bits);
-    {
-        int tot = 0;
-        for (int a : arities) tot += a;
-        if (tot > degree_bits + rate_bits - (int)cfg.cap_height) throw OlaError(OLA_E_INVALID_ARG, "FRI total reduction arity is too large.");
-    }
+// ------------------------------------------------------------------------------------------------ the phases of an opening proof
+// Each takes the DevBuf that its device and staging memory comes from: open_and_prove passes its one call-long scope, the
+// stepped entry points pass OlaFri::mem for what lives between the steps and a short-lived scope for the rest.
 
-    // ---- zeta and the opening set (prover.rs:499-524) ----
-    const Ext2 zeta = challenger_get_ext(ch);
+// the three committed oracles of a table in the order of the FRI instance (stark.rs:87-146)
+struct FriOracles {
+    const OlaBatch *trace, *zs, *quot;
+    uint32_t nperm;
+    const OlaBatch& at(int o) const { return o == 0 ? *trace : (o == 1 ? *zs : *quot); }
+};
+
+static void fri_check_arities(const std::vector<int>& arities, const OlaGpuConfig& cfg, int degree_bits) {
+    int tot = 0;
+    for (int a : arities) tot += a;
+    if (tot > degree_bits + (int)cfg.rate_bits - (int)cfg.cap_height) throw OlaError(OLA_E_INVALID_ARG, "FRI total reduction arity is too large.");
+}
+
+// the opening points zeta, g zeta, g^-1 (prover.rs:499-503): power tables of the points (the first three with limbs) and of
+// their inverses
+struct OpenPoints { ExtPow zpow[3], zinv[3]; };
+static OpenPoints open_points(DevBuf& mem, Ext2 zeta, int degree_bits) {
     if (ext_eq(ext_pow(zeta, (u64)1 << degree_bits), ext_make(1, 0))) throw OlaError(OLA_E_ZETA_IN_SUBGROUP, "Opening point is in the subgroup.");
     const u64 g = gl_root_of_unity(degree_bits);
-    const Ext2 zeta_next = ext_scalar_mul(zeta, g);
-    const Ext2 g_inv = ext_make(gl_inv(g), 0);
-    const Ext2 zpts[3] = {zeta, zeta_next, g_inv};
-    ExtPow zpow[3], zinv[3];
-    {
-        const Ext2 six[6] = {zeta, zeta_next, g_inv, ext_inv(zeta), ext_inv(zeta_next), ext_inv(g_inv)};
-        ExtPow tabs[6];
-        make_ext_pows(mem, six, 6, degree_bits, tabs, 3);
-        for (int b = 0; b < 3; b++) { zpow[b] = tabs[b]; zinv[b] = tabs[3 + b]; }
-    }
-    const ExtPow pz = zpow[0], pzn = zpow[1], pgi = zpow[2];
-    std::vector<Ext2> local, next, zs_local, zs_next, q_local, zs_last_all, dummy;
-    {
-        EvalJob jobs[4];
-        const OlaBatch* jb[4] = {&trace, &zs, &quot, &zs};
-        const int jp[4] = {2, 2, 1, 1};
-        const bool sharded = trace.is_shard() && ctx->shard.world > 1;
-        if (!sharded) {
-            {
-                WorkScope ws(ctx, 3);      // the partition divides the columns among the ranks
-                PhaseScope ph(ctx, PH_OPEN_EVAL, (double)n * (2 * W + 3 * Z + Q), (double)n * (W + 2 * Z + Q) * 8);
-                eval_batch_launch(mem, trace, 2, pz, pzn, &local, &next, jobs[0]);
-                eval_batch_launch(mem, zs, 2, pz, pzn, &zs_local, &zs_next, jobs[1]);
-                eval_batch_launch(mem, quot, 1, pz, pz, &q_local, &dummy, jobs[2]);
-                eval_batch_launch(mem, zs, 1, pgi, pgi, &zs_last_all, &dummy, jobs[3]);
-            }
-            if (ctx->acct.shardable) acct_exchange(ctx, (size_t)(2 * W + 3 * Z + Q) * 16);
-            mem.sync_collect();
-            for (auto& j : jobs) eval_batch_collect(j);
-        } else {
-            const uint32_t world = ctx->shard.world;
-            size_t record = 0;
-            for (int i = 0; i < 4; i++) {
-                jobs[i].cpr = (jb[i]->ncols + world - 1) / world;
-                jobs[i].send_off = record;
-                record += (size_t)jp[i] * jobs[i].cpr * 2;
-            }
-            u64* d_send = mem.alloc(record);
-            u64* d_recv = mem.alloc(record * world);
-            eval_batch_launch(mem, trace, 2, pz, pzn, &local, &next, jobs[0], d_send);
-            eval_batch_launch(mem, zs, 2, pz, pzn, &zs_local, &zs_next, jobs[1], d_send);
-            eval_batch_launch(mem, quot, 1, pz, pz, &q_local, &dummy, jobs[2], d_send);
-            eval_batch_launch(mem, zs, 1, pgi, pgi, &zs_last_all, &dummy, jobs[3], d_send);
-            shard_all_gather(ctx, d_send, d_recv, record * 8);
-            std::vector<u64> recv(record * world);
-            HIP_CHECK(hipMemcpyAsync(recv.data(), d_recv, recv.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            for (auto& j : jobs) eval_batch_collect_sharded(j, recv.data(), record);
-        }
-    }
+    const Ext2 zeta_next = ext_scalar_mul(zeta, g), g_inv = ext_make(gl_inv(g), 0);
+    const Ext2 six[6] = {zeta, zeta_next, g_inv, ext_inv(zeta), ext_inv(zeta_next), ext_inv(g_inv)};
+    ExtPow tabs[6];
+    make_ext_pows(mem, six, 6, degree_bits, tabs, 3);
+    OpenPoints p;
+    for (int b = 0; b < 3; b++) { p.zpow[b] = tabs[b]; p.zinv[b] = tabs[3 + b]; }
+    return p;
+}
+
+// StarkOpeningSet::new (circuits/src/stark/proof.rs:198-233)
+struct OpeningSet {
+    std::vector<Ext2> local, next, zs_local, zs_next, q_local;
     std::vector<u64> ctl_last;
-    for (int i = (int)nperm; i < Z; i++) ctl_last.push_back(zs_last_all[i].a);
+    // serialization.rs write_stark_opening_set: local, next, permutation_ctl_zs, its next, ctl_zs_last, quotient_polys
+    void write(ByteWriter& w) const {
+        w.ext_vec(local); w.ext_vec(next); w.ext_vec(zs_local); w.ext_vec(zs_next);
+        w.field_vec(ctl_last.data(), ctl_last.size());
+        w.ext_vec(q_local);
+    }
+};
+static OpeningSet open_set(DevBuf& mem, const FriOracles& o, const OpenPoints& pts) {
+    DeviceCtx* ctx = mem.ctx;
+    OpeningSet s;
+    std::vector<Ext2> zs_last_all, dummy;
+    const ExtPow pz = pts.zpow[0], pzn = pts.zpow[1], pgi = pts.zpow[2];
+    const struct { const OlaBatch* b; int npoints; ExtPow p0, p1; std::vector<Ext2>*out0, *out1; } list[4] = {
+        {o.trace, 2, pz, pzn, &s.local, &s.next},
+        {o.zs, 2, pz, pzn, &s.zs_local, &s.zs_next},
+        {o.quot, 1, pz, pz, &s.q_local, &dummy},
+        {o.zs, 1, pgi, pgi, &zs_last_all, &dummy}};
+    EvalJob jobs[4];
+    if (!(o.trace->is_shard() && ctx->shard.world > 1)) {
+        const size_t n = o.trace->n(), W = o.trace->ncols, Z = o.zs->ncols, Q = o.quot->ncols;
+        {
+            WorkScope ws(ctx, 3);      // the partition divides the columns among the ranks
+            PhaseScope ph(ctx, PH_OPEN_EVAL, (double)n * (2 * W + 3 * Z + Q), (double)n * (W + 2 * Z + Q) * 8);
+            for (int i = 0; i < 4; i++) eval_batch_launch(mem, *list[i].b, list[i].npoints, list[i].p0, list[i].p1, list[i].out0, list[i].out1, jobs[i]);
+        }
+        if (ctx->acct.shardable) acct_exchange(ctx, (2 * W + 3 * Z + Q) * 16);
+        mem.sync_collect();
+        for (auto& j : jobs) eval_batch_collect(j);
+    } else {
+        const uint32_t world = ctx->shard.world;
+        size_t record = 0;
+        for (int i = 0; i < 4; i++) {
+            jobs[i].cpr = (list[i].b->ncols + world - 1) / world;
+            jobs[i].send_off = record;
+            record += (size_t)list[i].npoints * jobs[i].cpr * 2;
+        }
+        u64* d_send = mem.alloc(record);
+        u64* d_recv = mem.alloc(record * world);
+        for (int i = 0; i < 4; i++) eval_batch_launch(mem, *list[i].b, list[i].npoints, list[i].p0, list[i].p1, list[i].out0, list[i].out1, jobs[i], d_send);
+        shard_all_gather(ctx, d_send, d_recv, record * 8);
+        std::vector<u64> recv(record * world);
+        HIP_CHECK(hipMemcpyAsync(recv.data(), d_recv, recv.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        for (auto& j : jobs) eval_batch_collect_sharded(j, recv.data(), record);
+    }
+    for (size_t i = o.nperm; i < zs_last_all.size(); i++) s.ctl_last.push_back(zs_last_all[i].a);
+    return s;
+}
 
-    ByteWriter w{bytes, ctx->hasher == (int)OLA_HASH_BLAKE3};
-    w.ext_vec(local); w.ext_vec(next); w.ext_vec(zs_local); w.ext_vec(zs_next);
-    w.field_vec(ctl_last.data(), ctl_last.size());
-    w.ext_vec(q_local);
-    openings_len = bytes.size();
-
-    // observe_openings (fri/challenges.rs:16-23) in to_fri_openings order (proof.rs:235-265)
-    for (auto& e : local) challenger_observe_ext(ch, e);
-    for (auto& e : zs_local) challenger_observe_ext(ch, e);
-    for (auto& e : q_local) challenger_observe_ext(ch, e);
-    for (auto& e : next) challenger_observe_ext(ch, e);
-    for (auto& e : zs_next) challenger_observe_ext(ch, e);
-    for (u64 x : ctl_last) challenger_observe_ext(ch, ext_make(x, 0));
-
-    // ---- prove_openings: final polynomial (fri/oracle.rs:178-219) ----
-    const Ext2 alpha = challenger_get_ext(ch);
+// prove_openings up to the final polynomial (fri/oracle.rs:178-219): its coefficient planes [fa | fb] of length N = n << rate_bits
+// from `keep` (zero padded: PolynomialCoeffs::lde, polynomial/mod.rs:215-217), everything else from `tmp`
+static u64* final_poly_coeffs(DevBuf& keep, DevBuf& tmp, const FriOracles& o, const OpenPoints& pts, Ext2 alpha, int rate_bits) {
+    DeviceCtx* ctx = tmp.ctx;
+    const int W = (int)o.trace->ncols, Z = (int)o.zs->ncols, Q = (int)o.quot->ncols;
+    const size_t n = o.trace->n(), N = n << rate_bits;
     const int napow = W + Z + Q;
-    HostSpan h_apow = mem.host(2 * (size_t)napow);
+    HostSpan h_apow = tmp.host(2 * (size_t)napow);
     {
         Ext2 acc = ext_make(1, 0);
         for (int i = 0; i < napow; i++) { h_apow[i] = acc.a; h_apow[napow + i] = acc.b; acc = ext_mul(acc, alpha); }
     }
-    u64* d_apow = mem.alloc(h_apow.size());
+    u64* d_apow = tmp.alloc(h_apow.size());
     HIP_CHECK(hipMemcpyAsync(d_apow, h_apow.data(), h_apow.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    u64* S = mem.alloc(6 * n);
-    hipLaunchKernelGGL(compose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, trace.coeffs, W, zs.coeffs, Z,
-                       quot.coeffs, Q, (int)nperm, n, d_apow, napow, S);
-    const int l0 = W + Z + Q, l1 = W + Z, l2 = Z - (int)nperm;
-    (void)l0;
+    u64* S = tmp.alloc(6 * n);
+    hipLaunchKernelGGL(compose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, o.trace->coeffs, W, o.zs->coeffs, Z,
+                       o.quot->coeffs, Q, (int)o.nperm, n, d_apow, napow, S);
+    const int l1 = W + Z, l2 = Z - (int)o.nperm;
     const bool use2 = l2 > 0;
-    (void)zpts;
-    u64* tot = mem.alloc((n + SCAN_B - 1) / SCAN_B + 1);
+    u64* tot = tmp.alloc((n + SCAN_B - 1) / SCAN_B + 1);
     for (int b = 0; b < 3; b++) {
         if (b == 2 && !use2) continue;
         hipLaunchKernelGGL(weight_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, S + 2 * b * n, S + (2 * b + 1) * n,
-                           n, zpow[b]);
-        scan_plane(mem, S + 2 * b * n, n, tot);
-        scan_plane(mem, S + (2 * b + 1) * n, n, tot);
+                           n, pts.zpow[b]);
+        scan_plane(tmp, S + 2 * b * n, n, tot);
+        scan_plane(tmp, S + (2 * b + 1) * n, n, tot);
     }
     // weights: ((q0 * alpha^l1) + q1) * alpha^l2 + q2   (oracle.rs:212-213)
     const Ext2 w2 = ext_make(1, 0);
     const Ext2 w1 = use2 ? ext_pow(alpha, (u64)l2) : ext_make(1, 0);
     const Ext2 w0 = ext_mul(ext_pow(alpha, (u64)l1), w1);
-    // coefficient planes [fa | fb] of length N (zero padded: PolynomialCoeffs::lde, polynomial/mod.rs:215-217)
-    u64* coef = mem.alloc(2 * N);
-    hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, S, n, zinv[0], zinv[1], zinv[2], w0,
+    u64* coef = keep.alloc(2 * N);
+    hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, S, n, pts.zinv[0], pts.zinv[1], pts.zinv[2], w0,
                        w1, w2, use2 ? 1 : 0, coef, coef + N, N);
+    return coef;
+}
+
+// the commit phase as it stands between two layers (fri/prover.rs:72-121)
+struct FriCommit {
+    u64* coef;             // planes [a | b] of the current polynomial, each `len`
+    size_t len;
+    size_t nz;             // coefficients that can be non-zero (the planes are zero beyond them)
+    u64 shift = GL_GENERATOR;
+    std::vector<FriLayer> layers;
+    FriCommit(u64* coef_, size_t N, size_t n) : coef(coef_), len(N), nz(n) {}
+};
+
+// values = coset_fft(coeffs, shift), kept bit-reversed (reverse_index_bits_in_place, prover.rs:88), their tree and its cap, which
+// is complete after the caller's synchronisation + collect().  `timed`: the fused path's first layer, where the reference's
+// `timed!` scopes sit (fri/oracle.rs:221-225, fri/prover.rs:41-58) -- "perform final FFT" around the transform, "fold codewords"
+// from there until the caller closes it
+static FriLayer commit_layer(DevBuf& mem, NttTables& tables, const FriCommit& c, int ab, uint32_t cap_height, std::unique_ptr<PhaseTimer>* timed = nullptr) {
+    DeviceCtx* ctx = mem.ctx;
+    const size_t len = c.len, nleaves = len >> ab, len_cap = (size_t)1 << cap_height;
+    int cur_bits = 0;
+    while (((size_t)1 << cur_bits) < len) cur_bits++;
+    FriLayer L;
+    L.len = len; L.arity_bits = ab;
+    L.cap.resize(len_cap * 4);
+    L.va = mem.alloc(2 * len);
+    L.vb = L.va + len;
+    {
+        std::unique_ptr<PhaseTimer> t_fft(timed ? new PhaseTimer(ctx, "      perform final FFT " + std::to_string(len)) : nullptr);
+        ntt_coset_evaluate(tables, c.coef, L.va, nullptr, cur_bits, 2, c.shift, false);
+    }
+    if (timed) timed->reset(new PhaseTimer(ctx, "      fold codewords in the commitment phase"));
+    L.heap = mem.alloc(2 * nleaves * 4);
+    launch_leaf_hash_ext(ctx, L.va, L.vb, 1 << ab, nleaves, L.heap + 4 * nleaves);
+    launch_merkle_build(ctx, L.heap, nleaves, cap_height);
+    mem.readback(L.cap.data(), L.heap + 4 * len_cap, len_cap * 32);
+    return L;
+}
+
+// the fold in the coefficient domain by the layer's beta (fri/prover.rs:102-109)
+static void fri_fold(DevBuf& mem, FriCommit& c, int ab, Ext2 beta) {
+    DeviceCtx* ctx = mem.ctx;
+    const int arity = 1 << ab;
+    const size_t len = c.len, out_len = len >> ab;
+    u64* folded = mem.alloc(2 * out_len);
+    static const bool fold16_off = getenv("OLA_FOLD16") && !strcmp(getenv("OLA_FOLD16"), "0");
+    if (arity == 16 && !fold16_off && c.nz % 16 == 0 && c.nz >= 4096) {
+        const size_t nz_out = c.nz / 16;
+        PhaseScope ph(ctx, PH_FRI_FOLD, (double)(c.nz + nz_out) * 16, (double)c.nz);
+        if (nz_out < out_len) {
+            HIP_CHECK(hipMemsetAsync(folded + nz_out, 0, (out_len - nz_out) * 8, ctx->stream));
+            HIP_CHECK(hipMemsetAsync(folded + out_len + nz_out, 0, (out_len - nz_out) * 8, ctx->stream));
+        }
+        const Ext2 b2 = ext_mul(beta, beta), b4 = ext_mul(b2, b2), b8 = ext_mul(b4, b4);
+        hipLaunchKernelGGL(fold16_kernel, dim3((unsigned)((nz_out * 8 + 255) / 256)), dim3(256), 0, ctx->stream, c.coef, c.coef + len, nz_out, beta,
+                           b2, b4, b8, folded, folded + out_len);
+        c.nz = nz_out;
+    } else {
+        PhaseScope ph(ctx, PH_FRI_FOLD, (double)(len + out_len) * 16, (double)len);
+        hipLaunchKernelGGL(fold_kernel, dim3((unsigned)((out_len + 255) / 256)), dim3(256), 0, ctx->stream, c.coef, c.coef + len, out_len,
+                           arity, beta, folded, folded + out_len);
+        c.nz = std::min(out_len, (c.nz + arity - 1) / arity);
+    }
+    c.coef = folded;
+    c.len = out_len;
+    c.shift = gl_pow(c.shift, (u64)arity);
+}
+
+// final polynomial: what is left after the last fold, truncated to len / 2^rate_bits coefficients (prover.rs:114-119)
+static std::vector<Ext2> fri_final_poly(DevBuf& mem, const FriCommit& c, int rate_bits) {
+    std::vector<u64> h_final(2 * c.len);
+    mem.readback(h_final.data(), c.coef, 2 * c.len * 8);
+    mem.sync_collect();
+    std::vector<Ext2> final_poly(c.len >> rate_bits);
+    for (size_t i = 0; i < final_poly.size(); i++) final_poly[i] = ext_make(h_final[i], h_final[c.len + i]);
+    return final_poly;
+}
+
+// What the query rounds open (fri/prover.rs:150-204): rows and paths of the three oracles, and per FRI layer the leaf (arity
+// extension elements) and path at x >> (sum of the arity bits up to and including this layer's)
+struct LayerQuery {
+    int depth;
+    std::vector<u64> rows, paths;
+    std::vector<unsigned long long> idx;     // staging of the leaf indices: lives until the synchronisation
+    LayerQuery(const FriLayer& L, uint32_t cap_height, int nq) {
+        const size_t nleaves = L.len >> L.arity_bits;
+        int lb = 0;
+        while (((size_t)1 << lb) < nleaves) lb++;
+        depth = lb - (int)cap_height;
+        idx.resize(nq);
+        rows.resize(((size_t)nq << L.arity_bits) * 2);
+        if (depth > 0) paths.resize((size_t)nq * depth * 4);
+    }
+};
+struct FriQueries {
+    int nq, depth0;
+    std::vector<u64> rows[3], paths[3];
+    std::vector<LayerQuery> layers;
+};
+// enqueued only (resident batches): complete after the caller's synchronisation + collect()
+static void query_oracles(DevBuf& mem, NttTables& tables, const FriOracles& o, const std::vector<size_t>& xs, int depth0, FriQueries& q) {
+    q.nq = (int)xs.size();
+    q.depth0 = depth0;
+    for (int i = 0; i < 3; i++) {
+        q.rows[i].resize(xs.size() * o.at(i).ncols);
+        q.paths[i].resize(xs.size() * (size_t)std::max(depth0, 1) * 4);
+        query_leaves(mem, tables, o.at(i), xs.data(), q.nq, depth0, q.rows[i].data(), q.paths[i].data());
+    }
+}
+// the layers [from, layers.size()), none of them partitioned; enqueued only, like query_oracles
+static void query_layers(DevBuf& mem, const std::vector<FriLayer>& layers, size_t from, uint32_t cap_height, const std::vector<size_t>& xs, FriQueries& q) {
+    DeviceCtx* ctx = mem.ctx;
+    const int nq = (int)xs.size();
+    std::vector<size_t> cur = xs;
+    q.layers.reserve(layers.size());
+    for (size_t li = 0; li < layers.size(); li++) {
+        const FriLayer& L = layers[li];
+        for (int r = 0; r < nq; r++) cur[r] >>= L.arity_bits;
+        if (li < from) continue;
+        q.layers.emplace_back(L, cap_height, nq);
+        LayerQuery& lq = q.layers.back();
+        const int arity = 1 << L.arity_bits;
+        unsigned long long* d_idx = (unsigned long long*)mem.alloc(nq);
+        for (int r = 0; r < nq; r++) lq.idx[r] = cur[r];
+        if (li == 0 && ctx->acct.shardable && ctx->shard.world <= 1) acct_exchange(ctx, ((size_t)nq * arity * 2 + (size_t)nq * std::max(lq.depth, 0) * 4) * 8 * 8);
+        HIP_CHECK(hipMemcpyAsync(d_idx, lq.idx.data(), nq * 8, hipMemcpyHostToDevice, ctx->stream));
+        u64* d_rows = mem.alloc((size_t)nq * arity * 2);
+        hipLaunchKernelGGL(gather_ext_leaves_kernel, dim3((unsigned)nq), dim3(64), 0, ctx->stream, L.va, L.vb, arity, d_idx, d_rows);
+        mem.readback(lq.rows.data(), d_rows, lq.rows.size() * 8);
+        if (lq.depth > 0) {
+            u64* d_paths = mem.alloc((size_t)nq * lq.depth * 4);
+            hipLaunchKernelGGL(gather_paths_kernel, dim3((unsigned)nq), dim3(((lq.depth * 4 + 63) / 64) * 64), 0, ctx->stream, L.heap,
+                               L.len >> L.arity_bits, lq.depth, d_idx, d_paths);
+            mem.readback(lq.paths.data(), d_paths, lq.paths.size() * 8);
+        }
+    }
+}
+
+// The first layer on the partition: every rank gathers all queries at the local index (meaningful on the owner only) and the
+// records [rank][rows nq*arity*2 | paths nq*depth*4] are all-gathered; after the caller's synchronisation take() reads each
+// query from its owner's copy.
+struct ShardedLayerQuery {
+    std::vector<u64> recv;
+    size_t record = 0;
+    void enqueue(DevBuf& mem, const FriLayer& L, const std::vector<size_t>& xs, LayerQuery& lq) {
+        DeviceCtx* ctx = mem.ctx;
+        const int nq = (int)xs.size(), arity = 1 << L.arity_bits;
+        unsigned long long* d_idx = (unsigned long long*)mem.alloc(nq);
+        for (int r = 0; r < nq; r++) lq.idx[r] = (xs[r] >> L.arity_bits) % L.shard_leaves;
+        HIP_CHECK(hipMemcpyAsync(d_idx, lq.idx.data(), nq * 8, hipMemcpyHostToDevice, ctx->stream));
+        const size_t rows_w = (size_t)nq * arity * 2, paths_w = (size_t)nq * std::max(lq.depth, 0) * 4;
+        record = rows_w + paths_w;
+        u64* d_send = mem.alloc(record);
+        u64* d_recv = mem.alloc(record * ctx->shard.world);
+        hipLaunchKernelGGL(gather_ext_leaves_kernel, dim3((unsigned)nq), dim3(64), 0, ctx->stream, L.va, L.vb, arity, d_idx, d_send);
+        if (lq.depth > 0)
+            hipLaunchKernelGGL(gather_paths_kernel, dim3((unsigned)nq), dim3(((lq.depth * 4 + 63) / 64) * 64), 0, ctx->stream, L.heap,
+                               L.shard_leaves, lq.depth, d_idx, d_send + rows_w);
+        shard_all_gather(ctx, d_send, d_recv, record * 8);
+        recv.resize(record * ctx->shard.world);
+        HIP_CHECK(hipMemcpyAsync(recv.data(), d_recv, recv.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    void take(const FriLayer& L, const std::vector<size_t>& xs, LayerQuery& lq) const {
+        const size_t leaf_w = (size_t)2 << L.arity_bits, path_w = (size_t)std::max(lq.depth, 0) * 4, rows_w = xs.size() * leaf_w;
+        for (size_t r = 0; r < xs.size(); r++) {
+            const u64* rec = recv.data() + ((xs[r] >> L.arity_bits) / L.shard_leaves) * record;
+            std::copy(rec + r * leaf_w, rec + (r + 1) * leaf_w, lq.rows.begin() + r * leaf_w);
+            std::copy(rec + rows_w + r * path_w, rec + rows_w + (r + 1) * path_w, lq.paths.begin() + r * path_w);
+        }
+    }
+};
+
+// the query round proofs (serialization.rs:305-317, the part between the caps and the final polynomial): count, then per query
+// the three oracles' rows and paths and every layer's leaf and path
+static void write_query_rounds(ByteWriter& w, const FriOracles& o, const FriQueries& q) {
+    const int depth0 = std::max(q.depth0, 0);
+    w.u32((uint32_t)q.nq);
+    for (int r = 0; r < q.nq; r++) {
+        w.u32(3);
+        for (int i = 0; i < 3; i++) {
+            const size_t ncols = o.at(i).ncols;
+            w.field_vec(q.rows[i].data() + (size_t)r * ncols, ncols);
+            w.merkle_proof(q.paths[i].data() + (size_t)r * (size_t)depth0 * 4, depth0);
+        }
+        w.u32((uint32_t)q.layers.size());
+        for (const LayerQuery& lq : q.layers) {
+            const size_t leaf_w = lq.rows.size() / (size_t)q.nq;     // arity extension elements
+            w.u32((uint32_t)(leaf_w / 2));
+            for (size_t k = 0; k < leaf_w; k++) w.field(lq.rows[(size_t)r * leaf_w + k]);
+            w.merkle_proof(lq.depth > 0 ? lq.paths.data() + (size_t)r * lq.depth * 4 : nullptr, lq.depth > 0 ? lq.depth : 0);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ the pipeline
+// The tail of prove_single_table (prover.rs:499-553) with prove_openings (fri/oracle.rs:178-241) and fri_proof
+// (fri/prover.rs:20-204) on the library's own transcript: the challenger, the branches of the coset partition and the deferral
+// of the proof of work are here, the device work is in the phases above.
+void open_and_prove(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, const OlaBatch& trace, const OlaBatch& zs,
+                    const OlaBatch& quot, uint32_t nperm, OlaChallenger& ch, std::vector<uint8_t>& bytes, size_t& openings_len,
+                    PowDefer* pow_defer = nullptr) {
+    DevBuf mem(ctx);
+    const FriOracles oracles{&trace, &zs, &quot, nperm};
+    const int degree_bits = (int)trace.log_n;
+    const size_t n = trace.n();
+    const int rate_bits = (int)cfg.rate_bits;
+    const size_t N = n << rate_bits;
+    const size_t len_cap = (size_t)1 << cfg.cap_height;
+    const std::vector<int> arities = fri_arities(cfg, degree_bits);
+    fri_check_arities(arities, cfg, degree_bits);
+
+    // ---- zeta and the opening set (prover.rs:499-524) ----
+    const Ext2 zeta = challenger_get_ext(ch);
+    const OpenPoints pts = open_points(mem, zeta, degree_bits);
+    const OpeningSet set = open_set(mem, oracles, pts);
+    ByteWriter w{bytes, ctx->hasher == (int)OLA_HASH_BLAKE3};
+    set.write(w);
+    openings_len = bytes.size();
+
+    // observe_openings (fri/challenges.rs:16-23) in to_fri_openings order (proof.rs:235-265)
+    for (auto& e : set.local) challenger_observe_ext(ch, e);
+    for (auto& e : set.zs_local) challenger_observe_ext(ch, e);
+    for (auto& e : set.q_local) challenger_observe_ext(ch, e);
+    for (auto& e : set.next) challenger_observe_ext(ch, e);
+    for (auto& e : set.zs_next) challenger_observe_ext(ch, e);
+    for (u64 x : set.ctl_last) challenger_observe_ext(ch, ext_make(x, 0));
+
+    // ---- prove_openings: final polynomial (fri/oracle.rs:178-219) ----
+    const Ext2 alpha = challenger_get_ext(ch);
+    FriCommit c(final_poly_coeffs(mem, mem, oracles, pts, alpha, rate_bits), N, n);
 
     // ---- FRI commit phase (fri/prover.rs:72-121) ----
-    // (OLA_TIMING scopes carry the reference's `timed!` names: fri/oracle.rs:221-225, fri/prover.rs:41-58)
-    std::unique_ptr<PhaseTimer> t_fold;
-    std::vector<FriLayer> layers;
-    u64 shift = GL_GENERATOR;
-    size_t len = N;
-    u64* cur_coef = coef;  // planes [a | b] each `len`
-    size_t nz = n;         // coefficients that can be non-zero (the planes are zero beyond them)
     // Under the coset partition the FIRST layer -- 15/16 of the commit phase's values and leaves -- is divided like a commitment
     // (fri/prover.rs:72-121): its bit-reversed values are the leaf-order LDE of the n coefficients (the planes
     // are zero beyond n), a rank extends and hashes its cosets only (n/arity leaves per coset), builds their sub-trees and the
     // cap slices are all-gathered; the layers after the first fold (1/16 of the data, and shrinking) stay replicated.
+    std::unique_ptr<PhaseTimer> t_fold;
     const bool sharded = trace.is_shard() && ctx->shard.world > 1;
     for (size_t li = 0; li < arities.size(); li++) {
         const int ab = arities[li];
-        const int arity = 1 << ab;
-        int cur_bits = 0;
-        while (((size_t)1 << cur_bits) < len) cur_bits++;
-        // values = coset_fft(coeffs, shift), kept bit-reversed (reverse_index_bits_in_place, prover.rs:88)
+        const bool shardable = li == 0 && degree_bits >= ab;
         FriLayer L;
-        L.len = len; L.arity_bits = ab;
-        const size_t nleaves = len >> ab;
-        L.cap.resize(len_cap * 4);
-        const bool shard_layer = sharded && li == 0 && degree_bits >= ab;
-        if (shard_layer) {
+        if (sharded && shardable) {
+            L.len = c.len; L.arity_bits = ab;
+            L.cap.resize(len_cap * 4);
             const uint32_t lw = ctx->shard.log_world;
             const size_t coset_count = ((size_t)1 << rate_bits) >> lw, coset_first = (size_t)ctx->shard.rank * coset_count;
             const size_t len_loc = n * coset_count, nl_loc = len_loc >> ab, cap_loc = len_cap >> lw;
@@ -994,68 +1210,27 @@ void open_and_prove(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, 
             L.va = mem.alloc(2 * len_loc);
             L.vb = L.va + len_loc;
             {
-                std::unique_ptr<PhaseTimer> t_fft(new PhaseTimer(ctx, "      perform final FFT " + std::to_string(len) + " (this rank's cosets)"));
-                ntt_lde_leaf_order(tables, cur_coef, L.va, degree_bits, rate_bits, 2, coset_first, coset_count, len);
+                std::unique_ptr<PhaseTimer> t_fft(new PhaseTimer(ctx, "      perform final FFT " + std::to_string(c.len) + " (this rank's cosets)"));
+                ntt_lde_leaf_order(tables, c.coef, L.va, degree_bits, rate_bits, 2, coset_first, coset_count, c.len);
             }
             t_fold.reset(new PhaseTimer(ctx, "      fold codewords in the commitment phase"));
             L.heap = mem.alloc(2 * nl_loc * 4);
-            launch_leaf_hash_ext(ctx, L.va, L.vb, arity, nl_loc, L.heap + 4 * nl_loc);
+            launch_leaf_hash_ext(ctx, L.va, L.vb, 1 << ab, nl_loc, L.heap + 4 * nl_loc);
             launch_merkle_build(ctx, L.heap, nl_loc, cfg.cap_height - lw);
             u64* d_cap = mem.alloc(len_cap * 4);
             shard_all_gather(ctx, L.heap + 4 * cap_loc, d_cap, cap_loc * 32);
             HIP_CHECK(hipMemcpyAsync(L.cap.data(), d_cap, len_cap * 32, hipMemcpyDeviceToHost, ctx->stream));
         } else {
-            WorkScope ws(ctx, (li == 0 && degree_bits >= ab) ? 3 : 0);
-            if (li == 0 && degree_bits >= ab && ctx->acct.shardable) acct_exchange(ctx, len_cap * 32);
-            L.va = mem.alloc(2 * len);
-            L.vb = L.va + len;
-            {
-                std::unique_ptr<PhaseTimer> t_fft(li == 0 ? new PhaseTimer(ctx, "      perform final FFT " + std::to_string(len)) : nullptr);
-                ntt_coset_evaluate(tables, cur_coef, L.va, nullptr, cur_bits, 2, shift, false);
-            }
-            if (li == 0) t_fold.reset(new PhaseTimer(ctx, "      fold codewords in the commitment phase"));
-            L.heap = mem.alloc(2 * nleaves * 4);
-            launch_leaf_hash_ext(ctx, L.va, L.vb, arity, nleaves, L.heap + 4 * nleaves);
-            launch_merkle_build(ctx, L.heap, nleaves, cfg.cap_height);
-            mem.readback(L.cap.data(), L.heap + 4 * len_cap, len_cap * 32);
+            WorkScope ws(ctx, shardable ? 3 : 0);
+            if (shardable && ctx->acct.shardable) acct_exchange(ctx, len_cap * 32);
+            L = commit_layer(mem, tables, c, ab, cfg.cap_height, li == 0 ? &t_fold : nullptr);
         }
         mem.sync_collect();
         challenger_observe_cap(ch, L.cap.data(), L.cap.size() / 4);
-        const Ext2 beta = challenger_get_ext(ch);
-        const size_t out_len = len >> ab;
-        u64* folded = mem.alloc(2 * out_len);
-        {
-            static const bool fold16_off = getenv("OLA_FOLD16") && !strcmp(getenv("OLA_FOLD16"), "0");
-            if (arity == 16 && !fold16_off && nz % 16 == 0 && nz >= 4096) {
-                const size_t nz_out = nz / 16;
-                PhaseScope ph(ctx, PH_FRI_FOLD, (double)(nz + nz_out) * 16, (double)nz);
-                if (nz_out < out_len) {
-                    HIP_CHECK(hipMemsetAsync(folded + nz_out, 0, (out_len - nz_out) * 8, ctx->stream));
-                    HIP_CHECK(hipMemsetAsync(folded + out_len + nz_out, 0, (out_len - nz_out) * 8, ctx->stream));
-                }
-                const Ext2 b2 = ext_mul(beta, beta), b4 = ext_mul(b2, b2), b8 = ext_mul(b4, b4);
-                hipLaunchKernelGGL(fold16_kernel, dim3((unsigned)((nz_out * 8 + 255) / 256)), dim3(256), 0, ctx->stream, cur_coef, cur_coef + len, nz_out, beta,
-                                   b2, b4, b8, folded, folded + out_len);
-                nz = nz_out;
-            } else {
-                PhaseScope ph(ctx, PH_FRI_FOLD, (double)(len + out_len) * 16, (double)len);
-                hipLaunchKernelGGL(fold_kernel, dim3((unsigned)((out_len + 255) / 256)), dim3(256), 0, ctx->stream, cur_coef, cur_coef + len, out_len,
-                                   arity, beta, folded, folded + out_len);
-                nz = std::min(out_len, (nz + arity - 1) / arity);
-            }
-        }
-        cur_coef = folded;
-        len = out_len;
-        shift = gl_pow(shift, (u64)arity);
-        layers.push_back(L);
+        fri_fold(mem, c, ab, challenger_get_ext(ch));
+        c.layers.push_back(std::move(L));
     }
-    // final polynomial: truncate to len / 2^rate_bits (prover.rs:114-119)
-    const size_t final_len = len >> rate_bits;
-    std::vector<u64> h_final(2 * len);
-    mem.readback(h_final.data(), cur_coef, 2 * len * 8);
-    mem.sync_collect();
-    std::vector<Ext2> final_poly(final_len);
-    for (size_t i = 0; i < final_len; i++) final_poly[i] = ext_make(h_final[i], h_final[len + i]);
+    const std::vector<Ext2> final_poly = fri_final_poly(mem, c, rate_bits);
     for (auto& e : final_poly) challenger_observe_ext(ch, e);
 
     // ---- proof of work (prover.rs:126-148), minimal witness ----
@@ -1064,7 +1239,6 @@ void open_and_prove(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, 
     t_fold.reset();
     u64 pow_witness = 0;
     bool pow_deferred = false;
-    PowDefer::Job pow_job = {};
     {
         PhaseTimer t_pow(ctx, "      find proof-of-work witness");
         // inside a whole proof: on the side stream, the witness is patched in at the end (its place in the bytes is known below)
@@ -1072,104 +1246,25 @@ void open_and_prove(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, 
         if (!pow_deferred) pow_witness = run_pow(ctx, hsh, cfg.proof_of_work_bits);
     }
 
-    // ---- query rounds (prover.rs:150-204) ----
-    const int nq = (int)cfg.num_query_rounds;
-    std::vector<size_t> xs(nq);
-    for (int r = 0; r < nq; r++) xs[r] = (size_t)(challenger_get(ch) % (u64)N);
-    const OlaBatch* oracles[3] = {&trace, &zs, &quot};
-    const int depth0 = degree_bits + rate_bits - (int)cfg.cap_height;
-    std::vector<std::vector<u64>> rows(3), paths(3);
-    for (int o = 0; o < 3; o++) {
-        rows[o].resize((size_t)nq * oracles[o]->ncols);
-        paths[o].resize((size_t)nq * (size_t)std::max(depth0, 1) * 4);
-        query_leaves(mem, tables, *oracles[o], xs.data(), nq, depth0, rows[o].data(), paths[o].data());
+    // ---- query rounds (prover.rs:150-204): the three oracles and the layers share ONE synchronisation ----
+    std::vector<size_t> xs(cfg.num_query_rounds);
+    for (size_t& x : xs) x = (size_t)(challenger_get(ch) % (u64)N);
+    FriQueries q;
+    query_oracles(mem, tables, oracles, xs, degree_bits + rate_bits - (int)cfg.cap_height, q);
+    ShardedLayerQuery first;
+    const bool first_sharded = !c.layers.empty() && c.layers[0].shard_leaves;
+    if (first_sharded) {
+        q.layers.emplace_back(c.layers[0], cfg.cap_height, q.nq);
+        first.enqueue(mem, c.layers[0], xs, q.layers[0]);
     }
-    // per layer: leaves (arity ext) and paths at x >> (sum of arity bits so far + this)
-    std::vector<std::vector<u64>> lrows(layers.size()), lpaths(layers.size());
-    std::vector<int> ldepth(layers.size());
-    {
-        std::vector<size_t> cur = xs;
-        std::vector<std::vector<unsigned long long>> h_idx_all(layers.size());   // staging buffers live until the one sync below
-        std::vector<u64> shard_recv;          // first layer on the partition: every rank's records [rank][rows nq*arity*2 | paths nq*depth*4]
-        size_t shard_record = 0;
-        for (size_t li = 0; li < layers.size(); li++) {
-            unsigned long long* d_idx = (unsigned long long*)mem.alloc(nq);
-            FriLayer& L = layers[li];
-            const int arity = 1 << L.arity_bits;
-            const size_t nleaves = L.len >> L.arity_bits;
-            int lb = 0;
-            while (((size_t)1 << lb) < nleaves) lb++;
-            ldepth[li] = lb - (int)cfg.cap_height;
-            std::vector<unsigned long long>& h_idx = h_idx_all[li];
-            h_idx.resize(nq);
-            for (int r = 0; r < nq; r++) { cur[r] >>= L.arity_bits; h_idx[r] = cur[r]; }
-            lrows[li].resize((size_t)nq * arity * 2);
-            if (ldepth[li] > 0) lpaths[li].resize((size_t)nq * ldepth[li] * 4);
-            if (L.shard_leaves) {
-                // every rank gathers all queries at the local index (meaningful on the owner only); the records are all-gathered
-                // and each query is read from its owner's copy below
-                for (int r = 0; r < nq; r++) h_idx[r] = cur[r] % L.shard_leaves;
-                HIP_CHECK(hipMemcpyAsync(d_idx, h_idx.data(), nq * 8, hipMemcpyHostToDevice, ctx->stream));
-                const size_t rows_w = (size_t)nq * arity * 2, paths_w = (size_t)nq * std::max(ldepth[li], 0) * 4;
-                shard_record = rows_w + paths_w;
-                u64* d_send = mem.alloc(shard_record);
-                u64* d_recv = mem.alloc(shard_record * ctx->shard.world);
-                hipLaunchKernelGGL(gather_ext_leaves_kernel, dim3((unsigned)nq), dim3(64), 0, ctx->stream, L.va, L.vb, arity, d_idx, d_send);
-                if (ldepth[li] > 0)
-                    hipLaunchKernelGGL(gather_paths_kernel, dim3((unsigned)nq), dim3(((ldepth[li] * 4 + 63) / 64) * 64), 0, ctx->stream, L.heap,
-                                       L.shard_leaves, ldepth[li], d_idx, d_send + rows_w);
-                shard_all_gather(ctx, d_send, d_recv, shard_record * 8);
-                shard_recv.resize(shard_record * ctx->shard.world);
-                HIP_CHECK(hipMemcpyAsync(shard_recv.data(), d_recv, shard_recv.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-                continue;
-            }
-            if (li == 0 && ctx->acct.shardable && ctx->shard.world <= 1) acct_exchange(ctx, ((size_t)nq * arity * 2 + (size_t)nq * std::max(ldepth[li], 0) * 4) * 8 * 8);
-            HIP_CHECK(hipMemcpyAsync(d_idx, h_idx.data(), nq * 8, hipMemcpyHostToDevice, ctx->stream));
-            u64* d_rows = mem.alloc((size_t)nq * arity * 2);
-            hipLaunchKernelGGL(gather_ext_leaves_kernel, dim3((unsigned)nq), dim3(64), 0, ctx->stream, L.va, L.vb, arity, d_idx, d_rows);
-            mem.readback(lrows[li].data(), d_rows, lrows[li].size() * 8);
-            if (ldepth[li] > 0) {
-                u64* d_paths = mem.alloc((size_t)nq * ldepth[li] * 4);
-                hipLaunchKernelGGL(gather_paths_kernel, dim3((unsigned)nq), dim3(((ldepth[li] * 4 + 63) / 64) * 64), 0, ctx->stream, L.heap,
-                                   nleaves, ldepth[li], d_idx, d_paths);
-                mem.readback(lpaths[li].data(), d_paths, lpaths[li].size() * 8);
-            }
-        }
-        mem.sync_collect();
-        if (!shard_recv.empty()) {
-            const FriLayer& L = layers[0];
-            const int arity = 1 << L.arity_bits, dep = std::max(ldepth[0], 0);
-            const size_t rows_w = (size_t)nq * arity * 2;
-            for (int r = 0; r < nq; r++) {
-                const size_t leaf = xs[r] >> L.arity_bits, owner = leaf / L.shard_leaves;
-                const u64* rec = shard_recv.data() + owner * shard_record;
-                std::copy(rec + (size_t)r * arity * 2, rec + (size_t)(r + 1) * arity * 2, lrows[0].begin() + (size_t)r * arity * 2);
-                if (dep) std::copy(rec + rows_w + (size_t)r * dep * 4, rec + rows_w + (size_t)(r + 1) * dep * 4, lpaths[0].begin() + (size_t)r * dep * 4);
-            }
-        }
-    }
+    query_layers(mem, c.layers, first_sharded ? 1 : 0, cfg.cap_height, xs, q);
+    mem.sync_collect();
+    if (first_sharded) first.take(c.layers[0], xs, q.layers[0]);
 
     // ---- serialise the FRI proof (serialization.rs:305-317) ----
-    w.u32((uint32_t)layers.size());
-    for (auto& L : layers) w.cap(L.cap.data(), len_cap);
-    w.u32((uint32_t)nq);
-    for (int r = 0; r < nq; r++) {
-        w.u32(3);
-        for (int o = 0; o < 3; o++) {
-            w.field_vec(rows[o].data() + (size_t)r * oracles[o]->ncols, oracles[o]->ncols);
-            w.merkle_proof(paths[o].data() + (size_t)r * (size_t)std::max(depth0, 0) * 4, std::max(depth0, 0));
-        }
-        w.u32((uint32_t)layers.size());
-        for (size_t li = 0; li < layers.size(); li++) {
-            const int arity = 1 << layers[li].arity_bits;
-            w.u32((uint32_t)arity);
-            for (int k = 0; k < arity; k++) {
-                w.field(lrows[li][((size_t)r * arity + k) * 2]);
-                w.field(lrows[li][((size_t)r * arity + k) * 2 + 1]);
-            }
-            w.merkle_proof(ldepth[li] > 0 ? lpaths[li].data() + (size_t)r * ldepth[li] * 4 : nullptr, ldepth[li] > 0 ? ldepth[li] : 0);
-        }
-    }
+    w.u32((uint32_t)c.layers.size());
+    for (auto& L : c.layers) w.cap(L.cap.data(), len_cap);
+    write_query_rounds(w, oracles, q);
     w.ext_vec(final_poly);
     if (pow_deferred) pow_defer->jobs.back().at = bytes.size();
     w.field(pow_witness);
@@ -1179,249 +1274,93 @@ void open_and_prove(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, 
 // "ola_open; ola_fri_commit_begin / next_layer(beta, cap_out) / finish(final_poly_out) -- layer-stepped because each
 // beta depends on the previous cap through the host challenger (fri/prover.rs:98-101); ola_pow; ola_fri_query".  For a host that
 // keeps the reference's own loops (StarkOpeningSet::new, prove_openings, fri_committed_trees, fri_proof_of_work,
-// fri_prover_query_rounds) and its own Challenger, and hands only the device work over.  Same kernels and helpers as
-// open_and_prove above, whose bytes the steps reassemble to (tests/test_gpu_fri_steps.py); single-device contexts only.
+// fri_prover_query_rounds) and its own Challenger, and hands only the device work over.  Each step checks its stage and its
+// arguments and calls the phase of open_and_prove that it stands for, so the steps reassemble to its bytes by construction
+// (tests/test_gpu_fri_steps.py holds them to it); single-device contexts only.
 }  // namespace ola
 struct OlaFri {      // (global, like OlaBatch: the C header names it)
     ola::DeviceCtx* ctx;
     ola::NttTables* tables;
     OlaGpuConfig cfg;
-    const OlaBatch *trace, *zs, *quot;
-    uint32_t nperm;
-    ola::DevBuf mem;                  // everything that lives between the steps
+    ola::FriOracles oracles;
+    ola::DevBuf mem;                  // everything that lives between the steps: not from the pinned arena, a stack that is left to the calls
     int degree_bits, rate_bits, stage = 0;   // 0 opened, 1 polynomial built / layers being committed, 2 finished
-    size_t n, N, len, nz;
-    ola::Ext2 zeta;
-    ola::ExtPow zpow[3], zinv[3];
+    size_t N;
+    ola::OpenPoints pts;
     std::vector<int> arities;
-    std::vector<ola::FriLayer> layers;
-    ola::u64* cur_coef = nullptr;
-    ola::u64 shift = ola::GL_GENERATOR;
+    ola::FriCommit commit;
     void* owner = nullptr;            // the OlaCtx the batches belong to (the C wrappers make its device current)
     OlaFri(ola::DeviceCtx* c, ola::NttTables* t, const OlaGpuConfig& g, const OlaBatch* tr, const OlaBatch* z, const OlaBatch* q, uint32_t np)
-        : ctx(c), tables(t), cfg(g), trace(tr), zs(z), quot(q), nperm(np), mem(c) {
-        mem.use_pinned = false;
-        degree_bits = (int)tr->log_n; rate_bits = (int)g.rate_bits;
-        n = tr->n(); N = n << rate_bits; len = N; nz = n;
-        arities = ola::fri_arities(cfg, degree_bits);
-        int tot = 0;
-        for (int a : arities) tot += a;
-        if (tot > degree_bits + rate_bits - (int)cfg.cap_height) throw ola::OlaError(OLA_E_INVALID_ARG, "FRI total reduction arity is too large.");
+        : ctx(c), tables(t), cfg(g), oracles{tr, z, q, np}, mem(c, /*pinned=*/false), degree_bits((int)tr->log_n), rate_bits((int)g.rate_bits),
+          N(tr->n() << g.rate_bits), arities(ola::fri_arities(g, (int)tr->log_n)), commit(nullptr, N, tr->n()) {
+        ola::fri_check_arities(arities, cfg, degree_bits);
     }
 };
 namespace ola {
 
+static Ext2 ext_arg(const u64 v[2]) { return ext_make(gl_canon(v[0]), gl_canon(v[1])); }
+
 // StarkOpeningSet::new (circuits/src/stark/proof.rs:198-233) at the caller's zeta: the opening set in wire format
-// (serialization.rs write_stark_opening_set: local, next, permutation_ctl_zs, its next, ctl_zs_last, quotient_polys)
-void fri_steps_open(OlaFri& f, const u64 zeta_in[2], std::vector<uint8_t>& bytes) {
-    DeviceCtx* ctx = f.ctx;
-    const int degree_bits = f.degree_bits;
-    f.zeta = ext_make(gl_canon(zeta_in[0]), gl_canon(zeta_in[1]));
-    if (ext_eq(ext_pow(f.zeta, (u64)1 << degree_bits), ext_make(1, 0))) throw OlaError(OLA_E_ZETA_IN_SUBGROUP, "Opening point is in the subgroup.");
-    const u64 g = gl_root_of_unity(degree_bits);
-    const Ext2 zeta_next = ext_scalar_mul(f.zeta, g), g_inv = ext_make(gl_inv(g), 0);
-    {
-        const Ext2 six[6] = {f.zeta, zeta_next, g_inv, ext_inv(f.zeta), ext_inv(zeta_next), ext_inv(g_inv)};
-        ExtPow tabs[6];
-        make_ext_pows(f.mem, six, 6, degree_bits, tabs, 3);
-        for (int b = 0; b < 3; b++) { f.zpow[b] = tabs[b]; f.zinv[b] = tabs[3 + b]; }
-    }
-    std::vector<Ext2> local, next, zs_local, zs_next, q_local, zs_last_all, dummy;
-    {
-        DevBuf tmp(ctx);
-        EvalJob jobs[4];
-        eval_batch_launch(tmp, *f.trace, 2, f.zpow[0], f.zpow[1], &local, &next, jobs[0]);
-        eval_batch_launch(tmp, *f.zs, 2, f.zpow[0], f.zpow[1], &zs_local, &zs_next, jobs[1]);
-        eval_batch_launch(tmp, *f.quot, 1, f.zpow[0], f.zpow[0], &q_local, &dummy, jobs[2]);
-        eval_batch_launch(tmp, *f.zs, 1, f.zpow[2], f.zpow[2], &zs_last_all, &dummy, jobs[3]);
-        tmp.sync_collect();
-        for (auto& j : jobs) eval_batch_collect(j);
-    }
-    std::vector<u64> ctl_last;
-    for (int i = (int)f.nperm; i < (int)f.zs->ncols; i++) ctl_last.push_back(zs_last_all[i].a);
-    ByteWriter w{bytes, ctx->hasher == (int)OLA_HASH_BLAKE3};
-    w.ext_vec(local); w.ext_vec(next); w.ext_vec(zs_local); w.ext_vec(zs_next);
-    w.field_vec(ctl_last.data(), ctl_last.size());
-    w.ext_vec(q_local);
+void fri_steps_open(OlaFri& f, const u64 zeta[2], std::vector<uint8_t>& bytes) {
+    f.pts = open_points(f.mem, ext_arg(zeta), f.degree_bits);
+    DevBuf tmp(f.ctx);
+    ByteWriter w{bytes, f.ctx->hasher == (int)OLA_HASH_BLAKE3};
+    open_set(tmp, f.oracles, f.pts).write(w);
 }
 
 // prove_openings up to the final polynomial (fri/oracle.rs:178-219) with the caller's alpha
-void fri_steps_begin(OlaFri& f, const u64 alpha_in[2]) {
+void fri_steps_begin(OlaFri& f, const u64 alpha[2]) {
     if (f.stage != 0) throw OlaError(OLA_E_INVALID_ARG, "ola_fri_commit_begin: already begun");
-    DeviceCtx* ctx = f.ctx;
-    const OlaBatch &trace = *f.trace, &zs = *f.zs, &quot = *f.quot;
-    const int W = (int)trace.ncols, Z = (int)zs.ncols, Q = (int)quot.ncols;
-    const size_t n = f.n, N = f.N;
-    const Ext2 alpha = ext_make(gl_canon(alpha_in[0]), gl_canon(alpha_in[1]));
-    const int napow = W + Z + Q;
-    u64* coef = f.mem.alloc(2 * N);
-    {
-        DevBuf tmp(ctx);
-        HostSpan h_apow = tmp.host(2 * (size_t)napow);
-        Ext2 acc = ext_make(1, 0);
-        for (int i = 0; i < napow; i++) { h_apow[i] = acc.a; h_apow[napow + i] = acc.b; acc = ext_mul(acc, alpha); }
-        u64* d_apow = tmp.alloc(h_apow.size());
-        HIP_CHECK(hipMemcpyAsync(d_apow, h_apow.data(), h_apow.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-        u64* S = tmp.alloc(6 * n);
-        hipLaunchKernelGGL(compose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, trace.coeffs, W, zs.coeffs, Z, quot.coeffs, Q,
-                           (int)f.nperm, n, d_apow, napow, S);
-        const int l1 = W + Z, l2 = Z - (int)f.nperm;
-        const bool use2 = l2 > 0;
-        u64* tot = tmp.alloc((n + SCAN_B - 1) / SCAN_B + 1);
-        for (int b = 0; b < 3; b++) {
-            if (b == 2 && !use2) continue;
-            hipLaunchKernelGGL(weight_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, S + 2 * b * n, S + (2 * b + 1) * n, n, f.zpow[b]);
-            scan_plane(tmp, S + 2 * b * n, n, tot);
-            scan_plane(tmp, S + (2 * b + 1) * n, n, tot);
-        }
-        const Ext2 w2 = ext_make(1, 0);
-        const Ext2 w1 = use2 ? ext_pow(alpha, (u64)l2) : ext_make(1, 0);
-        const Ext2 w0 = ext_mul(ext_pow(alpha, (u64)l1), w1);
-        hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, S, n, f.zinv[0], f.zinv[1], f.zinv[2], w0, w1, w2,
-                           use2 ? 1 : 0, coef, coef + N, N);
-    }       // (the scope waits for the stream before its scratch goes back to the pool)
-    f.cur_coef = coef;
+    DevBuf tmp(f.ctx);       // (the scope waits for the stream before its scratch goes back to the pool)
+    f.commit.coef = final_poly_coeffs(f.mem, tmp, f.oracles, f.pts, ext_arg(alpha), f.rate_bits);
     f.stage = 1;
-}
-
-static void fri_steps_fold(OlaFri& f, const u64 beta_in[2]) {
-    DeviceCtx* ctx = f.ctx;
-    const int ab = f.layers.back().arity_bits, arity = 1 << ab;
-    const Ext2 beta = ext_make(gl_canon(beta_in[0]), gl_canon(beta_in[1]));
-    const size_t len = f.len, out_len = len >> ab;
-    u64* folded = f.mem.alloc(2 * out_len);
-    if (arity == 16 && f.nz % 16 == 0 && f.nz >= 4096) {
-        const size_t nz_out = f.nz / 16;
-        if (nz_out < out_len) {
-            HIP_CHECK(hipMemsetAsync(folded + nz_out, 0, (out_len - nz_out) * 8, ctx->stream));
-            HIP_CHECK(hipMemsetAsync(folded + out_len + nz_out, 0, (out_len - nz_out) * 8, ctx->stream));
-        }
-        const Ext2 b2 = ext_mul(beta, beta), b4 = ext_mul(b2, b2), b8 = ext_mul(b4, b4);
-        hipLaunchKernelGGL(fold16_kernel, dim3((unsigned)((nz_out * 8 + 255) / 256)), dim3(256), 0, ctx->stream, f.cur_coef, f.cur_coef + len, nz_out, beta, b2, b4, b8,
-                           folded, folded + out_len);
-        f.nz = nz_out;
-    } else {
-        hipLaunchKernelGGL(fold_kernel, dim3((unsigned)((out_len + 255) / 256)), dim3(256), 0, ctx->stream, f.cur_coef, f.cur_coef + len, out_len, arity, beta, folded,
-                           folded + out_len);
-        f.nz = std::min(out_len, (f.nz + arity - 1) / arity);
-    }
-    f.cur_coef = folded;
-    f.len = out_len;
-    f.shift = gl_pow(f.shift, (u64)arity);
 }
 
 // one turn of fri_committed_trees (fri/prover.rs:72-121): fold by the previous layer's beta (none before the first layer), then
 // commit the values of the current polynomial on its coset -> the layer's cap
 void fri_steps_next_layer(OlaFri& f, const u64* beta, u64* cap_out) {
+    FriCommit& c = f.commit;
     if (f.stage != 1) throw OlaError(OLA_E_INVALID_ARG, "ola_fri_commit_next_layer: call ola_fri_commit_begin first");
-    if (f.layers.size() >= f.arities.size()) throw OlaError(OLA_E_INVALID_ARG, "ola_fri_commit_next_layer: every layer of the reduction plan is committed");
-    if (f.layers.empty() != (beta == nullptr)) throw OlaError(OLA_E_INVALID_ARG, "ola_fri_commit_next_layer: beta is NULL for the first layer and only there");
-    DeviceCtx* ctx = f.ctx;
-    if (beta) fri_steps_fold(f, beta);
-    const int ab = f.arities[f.layers.size()], arity = 1 << ab;
-    const size_t len = f.len, len_cap = (size_t)1 << f.cfg.cap_height, nleaves = len >> ab;
-    int cur_bits = 0;
-    while (((size_t)1 << cur_bits) < len) cur_bits++;
-    FriLayer L;
-    L.len = len; L.arity_bits = ab;
-    L.cap.resize(len_cap * 4);
-    L.va = f.mem.alloc(2 * len);
-    L.vb = L.va + len;
-    ntt_coset_evaluate(*f.tables, f.cur_coef, L.va, nullptr, cur_bits, 2, f.shift, false);
-    L.heap = f.mem.alloc(2 * nleaves * 4);
-    launch_leaf_hash_ext(ctx, L.va, L.vb, arity, nleaves, L.heap + 4 * nleaves);
-    launch_merkle_build(ctx, L.heap, nleaves, f.cfg.cap_height);
-    HIP_CHECK(hipMemcpyAsync(L.cap.data(), L.heap + 4 * len_cap, len_cap * 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (c.layers.size() >= f.arities.size()) throw OlaError(OLA_E_INVALID_ARG, "ola_fri_commit_next_layer: every layer of the reduction plan is committed");
+    if (c.layers.empty() != (beta == nullptr)) throw OlaError(OLA_E_INVALID_ARG, "ola_fri_commit_next_layer: beta is NULL for the first layer and only there");
+    if (beta) fri_fold(f.mem, c, c.layers.back().arity_bits, ext_arg(beta));
+    FriLayer L = commit_layer(f.mem, *f.tables, c, f.arities[c.layers.size()], f.cfg.cap_height);
+    f.mem.sync_collect();
     std::copy(L.cap.begin(), L.cap.end(), cap_out);
-    f.layers.push_back(L);
+    c.layers.push_back(std::move(L));
 }
 
-// fold by the last beta and hand out the final polynomial, truncated to len / 2^rate_bits coefficients (prover.rs:114-119)
+// fold by the last beta and hand out the final polynomial
 size_t fri_steps_finish(OlaFri& f, const u64* beta, u64* final_poly_out, size_t cap_elems) {
-    if (f.stage != 1 || f.layers.size() != f.arities.size()) throw OlaError(OLA_E_INVALID_ARG, "ola_fri_commit_finish: layers of the reduction plan are missing");
-    if (f.layers.empty() != (beta == nullptr)) throw OlaError(OLA_E_INVALID_ARG, "ola_fri_commit_finish: beta is NULL exactly when the plan has no layer");
-    if (beta) fri_steps_fold(f, beta);
-    const size_t final_len = f.len >> f.rate_bits;
-    if (final_len > cap_elems || !final_poly_out) throw OlaError(OLA_E_INVALID_ARG, "ola_fri_commit_finish: output buffer too small");
-    std::vector<u64> h(2 * f.len);
-    HIP_CHECK(hipMemcpyAsync(h.data(), f.cur_coef, 2 * f.len * 8, hipMemcpyDeviceToHost, f.ctx->stream));
-    HIP_CHECK(hipStreamSynchronize(f.ctx->stream));
-    for (size_t i = 0; i < final_len; i++) { final_poly_out[2 * i] = h[i]; final_poly_out[2 * i + 1] = h[f.len + i]; }
+    FriCommit& c = f.commit;
+    if (f.stage != 1 || c.layers.size() != f.arities.size()) throw OlaError(OLA_E_INVALID_ARG, "ola_fri_commit_finish: layers of the reduction plan are missing");
+    if (c.layers.empty() != (beta == nullptr)) throw OlaError(OLA_E_INVALID_ARG, "ola_fri_commit_finish: beta is NULL exactly when the plan has no layer");
+    if (beta) fri_fold(f.mem, c, c.layers.back().arity_bits, ext_arg(beta));
+    if ((c.len >> f.rate_bits) > cap_elems || !final_poly_out) throw OlaError(OLA_E_INVALID_ARG, "ola_fri_commit_finish: output buffer too small");
+    DevBuf tmp(f.ctx);
+    const std::vector<Ext2> final_poly = fri_final_poly(tmp, c, f.rate_bits);
+    for (size_t i = 0; i < final_poly.size(); i++) { final_poly_out[2 * i] = final_poly[i].a; final_poly_out[2 * i + 1] = final_poly[i].b; }
     f.stage = 2;
-    return final_len;
+    return final_poly.size();
 }
 
 // fri_prover_query_rounds (fri/prover.rs:150-204) for the caller's indices: the query round proofs in wire format
-// (serialization.rs:305-317, the part between the caps and the final polynomial: count, then per query the three oracles' rows
-// and paths and every layer's leaf and path)
-void fri_steps_query(OlaFri& f, const u64* x_index, uint32_t nq_in, std::vector<uint8_t>& bytes) {
+void fri_steps_query(OlaFri& f, const u64* x_index, uint32_t nq, std::vector<uint8_t>& bytes) {
     if (f.stage != 2) throw OlaError(OLA_E_INVALID_ARG, "ola_fri_query: call ola_fri_commit_finish first");
-    DeviceCtx* ctx = f.ctx;
-    const int nq = (int)nq_in;
     std::vector<size_t> xs(nq);
-    for (int r = 0; r < nq; r++) {
+    for (uint32_t r = 0; r < nq; r++) {
         if (x_index[r] >= (u64)f.N) throw OlaError(OLA_E_INVALID_ARG, "ola_fri_query: index beyond the LDE");
         xs[r] = (size_t)x_index[r];
     }
-    const OlaBatch* oracles[3] = {f.trace, f.zs, f.quot};
-    const int depth0 = f.degree_bits + f.rate_bits - (int)f.cfg.cap_height;
-    std::vector<std::vector<u64>> rows(3), paths(3), lrows(f.layers.size()), lpaths(f.layers.size());
-    std::vector<int> ldepth(f.layers.size());
+    FriQueries q;
     {
-        DevBuf tmp(ctx);
-        for (int o = 0; o < 3; o++) {
-            rows[o].resize((size_t)nq * oracles[o]->ncols);
-            paths[o].resize((size_t)nq * (size_t)std::max(depth0, 1) * 4);
-            query_leaves(tmp, *f.tables, *oracles[o], xs.data(), nq, depth0, rows[o].data(), paths[o].data());
-        }
-        std::vector<size_t> cur = xs;
-        std::vector<std::vector<unsigned long long>> h_idx_all(f.layers.size());
-        for (size_t li = 0; li < f.layers.size(); li++) {
-            FriLayer& L = f.layers[li];
-            const int arity = 1 << L.arity_bits;
-            const size_t nleaves = L.len >> L.arity_bits;
-            int lb = 0;
-            while (((size_t)1 << lb) < nleaves) lb++;
-            ldepth[li] = lb - (int)f.cfg.cap_height;
-            std::vector<unsigned long long>& h_idx = h_idx_all[li];
-            h_idx.resize(nq);
-            for (int r = 0; r < nq; r++) { cur[r] >>= L.arity_bits; h_idx[r] = cur[r]; }
-            lrows[li].resize((size_t)nq * arity * 2);
-            if (ldepth[li] > 0) lpaths[li].resize((size_t)nq * ldepth[li] * 4);
-            unsigned long long* d_idx = (unsigned long long*)tmp.alloc(nq);
-            HIP_CHECK(hipMemcpyAsync(d_idx, h_idx.data(), nq * 8, hipMemcpyHostToDevice, ctx->stream));
-            u64* d_rows = tmp.alloc((size_t)nq * arity * 2);
-            hipLaunchKernelGGL(gather_ext_leaves_kernel, dim3((unsigned)nq), dim3(64), 0, ctx->stream, L.va, L.vb, arity, d_idx, d_rows);
-            tmp.readback(lrows[li].data(), d_rows, lrows[li].size() * 8);
-            if (ldepth[li] > 0) {
-                u64* d_paths = tmp.alloc((size_t)nq * ldepth[li] * 4);
-                hipLaunchKernelGGL(gather_paths_kernel, dim3((unsigned)nq), dim3(((ldepth[li] * 4 + 63) / 64) * 64), 0, ctx->stream, L.heap, nleaves, ldepth[li], d_idx,
-                                   d_paths);
-                tmp.readback(lpaths[li].data(), d_paths, lpaths[li].size() * 8);
-            }
-        }
+        DevBuf tmp(f.ctx);
+        query_oracles(tmp, *f.tables, f.oracles, xs, f.degree_bits + f.rate_bits - (int)f.cfg.cap_height, q);
+        query_layers(tmp, f.commit.layers, 0, f.cfg.cap_height, xs, q);
         tmp.sync_collect();
     }
-    ByteWriter w{bytes, ctx->hasher == (int)OLA_HASH_BLAKE3};
-    w.u32((uint32_t)nq);
-    for (int r = 0; r < nq; r++) {
-        w.u32(3);
-        for (int o = 0; o < 3; o++) {
-            w.field_vec(rows[o].data() + (size_t)r * oracles[o]->ncols, oracles[o]->ncols);
-            w.merkle_proof(paths[o].data() + (size_t)r * (size_t)std::max(depth0, 0) * 4, std::max(depth0, 0));
-        }
-        w.u32((uint32_t)f.layers.size());
-        for (size_t li = 0; li < f.layers.size(); li++) {
-            const int arity = 1 << f.layers[li].arity_bits;
-            w.u32((uint32_t)arity);
-            for (int k = 0; k < arity; k++) {
-                w.field(lrows[li][((size_t)r * arity + k) * 2]);
-                w.field(lrows[li][((size_t)r * arity + k) * 2 + 1]);
-            }
-            w.merkle_proof(ldepth[li] > 0 ? lpaths[li].data() + (size_t)r * ldepth[li] * 4 : nullptr, ldepth[li] > 0 ? ldepth[li] : 0);
-        }
-    }
+    ByteWriter w{bytes, f.ctx->hasher == (int)OLA_HASH_BLAKE3};
+    write_query_rounds(w, f.oracles, q);
 }
 
 }  // namespace ola

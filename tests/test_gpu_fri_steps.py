@@ -26,7 +26,7 @@ def field_vec(buf, at):
     return np.frombuffer(buf, dtype="<u8", count=k, offset=at + 4), at + 4 + 8 * k
 
 
-@pytest.mark.parametrize("hasher", ["poseidon", "blake3"])
+@pytest.mark.parametrize("hasher", ["poseidon", "blake3", "poseidon2"])
 @pytest.mark.parametrize("log_n,cols,nperm", [(3, (3, 2, 2), 0), (7, (5, 4, 4), 1), (12, (9, 5, 4), 2), (16, (7, 4, 2), 0), (18, (6, 3, 2), 1)])
 def test_steps_with_the_callers_transcript_reassemble_the_fused_proof(hasher, log_n, cols, nperm):
     from olavm_amd.backend import Backend, Challenger
