@@ -43,7 +43,8 @@ extern "C" {
  * 6: ola_gpu_warmup / ola_gpu_warmup_wait (start-up work ahead of the first context, where the reference calls init_gpu()),
  * ola_gpu_ntt_pass_times (the transform passes one by one, for the dominant kernel's roofline); no struct changed.
  * 7 (number unchanged by the later additions, which change no struct and no existing behaviour): the hashers OLA_HASH_POSEIDON2 and
- * OLA_HASH_POSEIDON2_POW_POSEIDON and the entry point ola_poseidon2_permute were added to revision 7. */
+ * OLA_HASH_POSEIDON2_POW_POSEIDON and the entry point ola_poseidon2_permute were added to revision 7; so were OlaConstraintFailure
+ * and the entry point ola_check_constraints (which constraint of which table fails at which row). */
 #define OLA_GPU_ABI_VERSION 7
 #define OLA_OK 0
 #define OLA_E_INVALID_ARG (-1)
@@ -434,6 +435,58 @@ int32_t ola_prove_with_traces(OlaCtx* ctx, const uint64_t* airset, size_t airset
 int32_t ola_prove_with_traces_cols(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, const uint64_t* const* const* cols,
                                    const uint32_t* log_n, const uint64_t* params, const uint64_t* compress_challenges,
                                    uint8_t* out, size_t cap, size_t* out_len);
+
+/* ---- why a trace does not prove: the constraint check on the trace domain -------------------------------------------------
+ * ola_prove_with_traces* answers a trace that breaks a constraint with OLA_E_QUOTIENT_DEGREE and nothing more.  This is the
+ * reference's debugging aid for that case on the device: `check_constraints` (circuits/src/stark/prover.rs:711-819), which
+ * evaluates a table's constraints on the trace domain H itself instead of the LDE, `verify_cross_table_lookups`
+ * (cross_table_lookup.rs:551-584), which compares the last values of the CTL Z columns, and the per-table recipe that strings
+ * them together (test_utils.rs:152-195).  Nothing is committed, extended or hashed.
+ * airset, cols, log_n, params: as for ola_prove_with_traces_cols (per-column pointers: host memory, staged through the pinned
+ *   ring, or a table whose first column is device memory is taken as resident); words may be >= p.  Only the tables of
+ *   table_mask (bit t = table t; a bit beyond the set is OLA_E_INVALID_ARG) are read, cols[t] of the others may be NULL.
+ * out[0 .. min(cap, *n_out)): the failures, sorted by (table, section, index, kind); *n_out is their TOTAL number also when it
+ *   exceeds cap (out may be NULL when cap is 0), so one call sizes the buffer.  A trace that satisfies everything gives
+ *   *n_out == 0; the return value is OLA_OK whether or not failures were found.
+ *   OLA_CHECK_AIR          one entry per failing emit of the table's constraint program: index = ordinal of the emit in program
+ *                          order, kind = OLA_CONSTRAINT_* (the ConstraintConsumer method, constraint_consumer.rs:57-78); the emit
+ *                          fails at row i iff its value there is non-zero and the kind applies: every row (ALL), every row but
+ *                          the last (TRANSITION), row 0 (FIRST_ROW), row n-1 (LAST_ROW) -- where z_last and the Lagrange
+ *                          selectors are non-zero on H (constraint_consumer.rs:34-78).  The next row of row n-1 is row 0.
+ *                          first_row = the smallest failing row, rows_failing = their number.
+ *   OLA_CHECK_PERMUTATION  one entry per permutation batch (index) whose running product does not close,
+ *                          Z[n-1] num(n-1) != den(n-1) Z[0] (permutation.rs:302-360): the two sides of a pair are not
+ *                          permutations of each other.  first_row = n-1, rows_failing = 1, kind = 0.
+ *   OLA_CHECK_LOOKUP       one entry per (cross-table lookup, challenge) for which the product of the looking tables' last CTL Z
+ *                          values differs from the looked table's: table = the looked table, index = the lookup's position in
+ *                          all_cross_table_lookups() order (the AIR set's), kind = the challenge, first_row = filter-selected
+ *                          rows on the looking side (all looking tables), rows_failing = filter-selected rows of the looked
+ *                          table.  A lookup is checked when all of its tables are in table_mask.  The per-row recurrences of
+ *                          the CTL Z columns hold by construction (the library computes the columns) and are not evaluated.
+ * ctl_challenges: [num_challenges][2] = (beta, gamma), or NULL.  The permutation challenges, and with NULL the CTL challenges
+ *   too, come from a fresh Challenger of the context's hasher that has observed nothing: first num_challenges (beta, gamma)
+ *   pairs for the lookups, then for every table of the set in order its permutation_batch_size x num_challenges pairs
+ *   (tables without permutation pairs draw nothing).  Deterministic; a random trace error escapes with probability ~ n / p.
+ * A multi-device context runs the check on its first device.  The proving state of the context is not touched.  Without a HIP
+ * device there is no context to pass: a call whose other arguments are valid then returns OLA_E_NO_DEVICE (no CPU fallback). */
+#define OLA_CHECK_AIR 0u
+#define OLA_CHECK_PERMUTATION 1u
+#define OLA_CHECK_LOOKUP 2u
+#define OLA_CONSTRAINT_ALL 0u
+#define OLA_CONSTRAINT_TRANSITION 1u
+#define OLA_CONSTRAINT_FIRST_ROW 2u
+#define OLA_CONSTRAINT_LAST_ROW 3u
+typedef struct OlaConstraintFailure {
+    uint32_t table;
+    uint32_t section;           /* OLA_CHECK_AIR | OLA_CHECK_PERMUTATION | OLA_CHECK_LOOKUP                                   */
+    uint32_t index;             /* AIR: emit ordinal; PERMUTATION: batch; LOOKUP: lookup index                                */
+    uint32_t kind;              /* AIR: OLA_CONSTRAINT_*; LOOKUP: challenge index                                             */
+    uint64_t first_row;         /* LOOKUP: selected rows on the looking side                                                  */
+    uint64_t rows_failing;      /* LOOKUP: selected rows on the looked side                                                   */
+} OlaConstraintFailure;
+int32_t ola_check_constraints(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, const uint64_t* const* const* cols,
+                              const uint32_t* log_n, const uint64_t* params, const uint64_t* ctl_challenges, uint32_t table_mask,
+                              OlaConstraintFailure* out, uint32_t cap, uint32_t* n_out);
 
 /* Copies out (and forgets) the proof a preceding ola_prove_with_traces could not return because its buffer was too small. */
 int32_t ola_take_pending_proof(OlaCtx* ctx, uint8_t* out, size_t cap, size_t* out_len);

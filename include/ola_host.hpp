@@ -344,6 +344,38 @@ inline std::vector<uint8_t> prove_with_traces(const Gpu& g, const std::vector<F>
     return out;
 }
 
+// ---- circuits/src/stark/prover.rs:711-819, cross_table_lookup.rs:551-584, test_utils.rs:152-195 ------------------------------------
+// Why a trace does not prove: the constraint programs, permutation arguments and cross-table lookups of the tables in `table_mask`
+// on the trace domain (ola_check_constraints).  traces / log_n / params as for prove_with_traces (a table outside the mask may be
+// empty); ctl_challenges: num_challenges x {beta, gamma}, or empty for the library's deterministic ones.  Returns the failures
+// sorted by (table, section, index); empty for a trace that satisfies everything.
+inline std::vector<OlaConstraintFailure> check_constraints(const Gpu& g, const std::vector<F>& airset, const std::vector<std::vector<F>>& traces,
+                                                           const std::vector<uint32_t>& log_n, const std::vector<F>& params = {},
+                                                           uint32_t table_mask = 0xFFFFFFFFu, const std::vector<std::array<F, 2>>& ctl_challenges = {}) {
+    if (traces.size() != log_n.size() || traces.size() > 32) throw Error(OLA_E_INVALID_ARG, "one height per trace, at most 32 tables");
+    if (traces.size() < 32) table_mask &= ((uint32_t)1 << traces.size()) - 1;
+    std::vector<std::vector<const F*>> cols(traces.size());
+    std::vector<const F* const*> tabs;
+    for (size_t t = 0; t < traces.size(); t++) {
+        const size_t n = (size_t)1 << log_n[t];
+        if (traces[t].size() % n) throw Error(OLA_E_INVALID_ARG, "a table is not a whole number of columns");
+        for (size_t c = 0; c * n < traces[t].size(); c++) cols[t].push_back(traces[t].data() + c * n);
+        tabs.push_back(cols[t].empty() ? nullptr : cols[t].data());
+    }
+    std::vector<F> ctl;
+    for (const auto& c : ctl_challenges) { ctl.push_back(c[0]); ctl.push_back(c[1]); }
+    std::vector<OlaConstraintFailure> out(64);
+    uint32_t n = 0;
+    auto call = [&]() {
+        return ola_check_constraints(g.ctx(), airset.data(), airset.size(), tabs.data(), log_n.data(), params.empty() ? nullptr : params.data(),
+                                     ctl.empty() ? nullptr : ctl.data(), table_mask, out.data(), (uint32_t)out.size(), &n);
+    };
+    check(call());
+    if (n > out.size()) { out.resize(n); check(call()); }
+    out.resize(n);
+    return out;
+}
+
 // prove_single_table (prover.rs:330-513) for callers that keep the reference's orchestration: `trace` = the table's columns,
 // `commitment` = PolynomialBatch::from_values of them, ctl_challenges = num_challenges x {beta, gamma}; the shared challenger
 // advances as in the reference.  Returns the table's StarkProof bytes (serialization.rs:349-358).

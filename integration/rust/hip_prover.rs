@@ -176,6 +176,33 @@ fn hasher_of<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, const D: 
     }
 }
 
+/// The report of `ola_check_constraints` over all tables as one line per entry.
+fn describe_failures(c: *mut OlaCtx, words: &[u64], tables: &[*const *const u64], log_n: &[u32], params: &[u64]) -> String {
+    const KINDS: [&str; 4] = ["constraint", "constraint_transition", "constraint_first_row", "constraint_last_row"];
+    let mut found = vec![OlaConstraintFailure::default(); 64];
+    let mut n = 0u32;
+    let mask = if tables.len() >= 32 { u32::MAX } else { (1u32 << tables.len()) - 1 };
+    let rc = unsafe {
+        ola_check_constraints(c, words.as_ptr(), words.len(), tables.as_ptr(), log_n.as_ptr(), params.as_ptr(), std::ptr::null(), mask,
+                              found.as_mut_ptr(), found.len() as u32, &mut n)
+    };
+    if rc != OLA_OK {
+        return format!("(the constraint check itself failed with code {rc})");
+    }
+    if n == 0 {
+        return "the constraint check on the trace domain finds nothing wrong".to_string();
+    }
+    let mut lines: Vec<String> = found.iter().take(n as usize).map(|f| match f.section {
+        OLA_CHECK_AIR => format!("table {}, constraint #{} ({}), first at row {}, {} rows", f.table, f.index, KINDS[(f.kind & 3) as usize], f.first_row, f.rows_failing),
+        OLA_CHECK_PERMUTATION => format!("table {}, permutation batch {}: the running product does not close", f.table, f.index),
+        _ => format!("table {}, cross-table lookup {} (challenge {}): {} looking rows, {} looked rows", f.table, f.index, f.kind, f.first_row, f.rows_failing),
+    }).collect();
+    if n as usize > found.len() {
+        lines.push(format!("... and {} more", n as usize - found.len()));
+    }
+    lines.join("; ")
+}
+
 pub fn prove_with_traces_hip<F, C, const D: usize>(
     ola_stark: &OlaStark<F, D>,
     config: &StarkConfig,
@@ -226,6 +253,12 @@ where
             // the proof is larger than the buffer: it was kept, fetch it without proving again
             out.resize(len, 0);
             check(unsafe { ola_take_pending_proof(c, out.as_mut_ptr(), out.len(), &mut len) })?;
+        } else if rc == OLA_E_QUOTIENT_DEGREE {
+            // "vanishing polynomial is not divisible by Z_H" names neither table nor constraint: ask the device which
+            // constraint fails at which row (the reference's check_constraints, prover.rs:711-819)
+            let err = check(rc).unwrap_err();
+            let why = describe_failures(c, words, &tables, &log_n, &params);
+            return Err(anyhow::anyhow!("{err}: {why}"));
         } else {
             check(rc)?;
         }

@@ -43,6 +43,15 @@ pub const OLA_COLLECTIVE_RCCL: u32 = 2;
 pub const OLA_PHASE_COUNT: u32 = 7;
 /// ola_gpu_warmup: also pin the trace upload's staging ring
 pub const OLA_WARMUP_PINNED_RING: u32 = 1;
+/// ola_check_constraints: `OlaConstraintFailure::section`
+pub const OLA_CHECK_AIR: u32 = 0;
+pub const OLA_CHECK_PERMUTATION: u32 = 1;
+pub const OLA_CHECK_LOOKUP: u32 = 2;
+/// ... and `kind` of an AIR entry: the ConstraintConsumer method of the emit
+pub const OLA_CONSTRAINT_ALL: u32 = 0;
+pub const OLA_CONSTRAINT_TRANSITION: u32 = 1;
+pub const OLA_CONSTRAINT_FIRST_ROW: u32 = 2;
+pub const OLA_CONSTRAINT_LAST_ROW: u32 = 3;
 
 #[repr(C)]
 pub struct OlaCtx {
@@ -107,6 +116,17 @@ pub struct OlaPassTime {
     pub reserved: u32,
     pub total_ms: f64,
     pub elements: f64,
+}
+/// One failing constraint, permutation batch or cross-table lookup (`ola_check_constraints`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct OlaConstraintFailure {
+    pub table: u32,
+    pub section: u32,
+    pub index: u32,
+    pub kind: u32,
+    pub first_row: u64,
+    pub rows_failing: u64,
 }
 /// `ola_all_gather_fn`: gather `bytes` bytes of device memory from every rank into `recv_dev` (rank order), 0 = done
 pub type OlaAllGatherFn = Option<unsafe extern "C" fn(user: *mut c_void, send_dev: *const c_void, recv_dev: *mut c_void, bytes: usize) -> i32>;
@@ -194,6 +214,9 @@ extern "C" {
     pub fn ola_prove_with_traces_cols(ctx: *mut OlaCtx, airset: *const u64, airset_words: usize, cols: *const *const *const u64,
         log_n: *const u32, params: *const u64, compress_challenges: *const u64, out: *mut u8, cap: usize,
         out_len: *mut usize) -> i32;
+    pub fn ola_check_constraints(ctx: *mut OlaCtx, airset: *const u64, airset_words: usize, cols: *const *const *const u64,
+        log_n: *const u32, params: *const u64, ctl_challenges: *const u64, table_mask: u32, out: *mut OlaConstraintFailure,
+        cap: u32, n_out: *mut u32) -> i32;
     pub fn ola_take_pending_proof(ctx: *mut OlaCtx, out: *mut u8, cap: usize, out_len: *mut usize) -> i32;
     pub fn ola_prove_single_table(ctx: *mut OlaCtx, airset: *const u64, airset_words: usize, table: u32,
         trace_cols: *const *const u64, trace_commitment: *const OlaBatch, trace_cap: *const u64,

@@ -37,6 +37,15 @@ class OlaPassTime(C.Structure):
     _fields_ = [("kernel", C.c_char * 48), ("launches", C.c_uint32), ("reserved", C.c_uint32), ("total_ms", C.c_double), ("elements", C.c_double)]
 
 
+class OlaConstraintFailure(C.Structure):
+    _fields_ = [("table", C.c_uint32), ("section", C.c_uint32), ("index", C.c_uint32), ("kind", C.c_uint32),
+                ("first_row", C.c_uint64), ("rows_failing", C.c_uint64)]
+
+
+CHECK_SECTIONS = ("AIR", "PERMUTATION", "LOOKUP")
+CONSTRAINT_KINDS = ("constraint", "constraint_transition", "constraint_first_row", "constraint_last_row")
+
+
 class OlaChallenger(C.Structure):
     _fields_ = [("sponge_state", C.c_uint64 * 12), ("input_buffer", C.c_uint64 * 8), ("output_buffer", C.c_uint64 * 8),
                 ("input_len", C.c_uint32), ("output_len", C.c_uint32), ("hasher", C.c_uint32), ("reserved", C.c_uint32)]
@@ -154,6 +163,9 @@ def load_library():
     L.ola_gpu_selftest.argtypes = [C.c_void_p, C.c_uint64, U64P]
     L.ola_gpu_reserve.argtypes = [C.c_void_p, U64P, C.c_size_t, C.POINTER(C.c_uint32)]
     L.ola_air_kernels_available.argtypes = [U64P, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t]
+    L.ola_check_constraints.argtypes = [C.c_void_p, U64P, C.c_size_t, C.POINTER(C.POINTER(U64P)), C.POINTER(C.c_uint32), U64P, U64P, C.c_uint32,
+                                        C.POINTER(OlaConstraintFailure), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.ola_check_constraints.restype = C.c_int32
     _lib = L
     return L
 
@@ -170,6 +182,7 @@ EXPORTS = [
     "ola_gpu_abi_version", "ola_gpu_init_multi", "ola_gpu_device_count", "ola_gpu_proof_stats", "ola_gpu_phase_stats",
     "ola_gpu_collective", "ola_gpu_all_gather_check", "ola_prove_with_traces_cols", "ola_gpu_scope_times", "ola_gpu_upload_stats",
     "ola_gpu_warmup", "ola_gpu_warmup_wait", "ola_gpu_ntt_pass_times",
+    "ola_check_constraints",
     "ola_open", "ola_fri_plan", "ola_fri_commit_begin", "ola_fri_commit_next_layer", "ola_fri_commit_finish", "ola_fri_query", "ola_fri_free",
 ]
 
@@ -705,6 +718,76 @@ class Backend:
             rc = self.lib.ola_take_pending_proof(self.ctx, buf, need.value, C.byref(need))
         self._chk(rc)
         return bytes(buf.raw[:need.value])
+
+    def check_constraints_raw(self, airset_blob, traces, params=None, tables=None, ctl_challenges=None, cap=256):
+        """ola_check_constraints as it is: -> (the first min(cap, total) entries as OlaConstraintFailure tuples
+        (table, section, index, kind, first_row, rows_failing), total number of entries)."""
+        blob = np.ascontiguousarray(airset_blob, dtype=np.uint64)
+        nt = len(traces)
+        mask = 0
+        for t in (range(nt) if tables is None else tables):
+            if int(t) < 0:
+                raise ValueError("negative table index")
+            mask |= 1 << int(t)
+        if mask >> 32:
+            raise OlaGpuError(-1, "invalid argument: table_mask names a table beyond the AIR set")
+        pr = None if params is None or len(params) == 0 else np.ascontiguousarray(params, dtype=np.uint64)
+        cc = None if ctl_challenges is None else np.ascontiguousarray(np.array(ctl_challenges, dtype=np.uint64).reshape(-1))
+        keep, tabs, logs = [], [], []
+        for i, t in enumerate(traces):
+            if t is None or not (mask >> i & 1):
+                tabs.append(None)
+                logs.append(0)
+                continue
+            if isinstance(t, (list, tuple)):
+                cols = [c if hasattr(c, "data_ptr") else np.ascontiguousarray(c, dtype=np.uint64).reshape(-1) for c in t]
+                n = int(cols[0].numel()) if hasattr(cols[0], "data_ptr") else cols[0].size
+                addrs = [c.data_ptr() if hasattr(c, "data_ptr") else c.ctypes.data for c in cols]
+            elif hasattr(t, "data_ptr"):
+                if not (t.is_contiguous() and t.element_size() == 8):
+                    raise ValueError("device-resident tables must be contiguous 64-bit tensors")
+                cols, n = t, int(t.shape[1])
+                addrs = [t.data_ptr() + 8 * n * c for c in range(int(t.shape[0]))]
+            else:
+                cols = np.ascontiguousarray(t, dtype=np.uint64)
+                n = cols.shape[1]
+                addrs = [cols.ctypes.data + 8 * n * c for c in range(cols.shape[0])]
+            arr = (U64P * len(addrs))(*[C.cast(C.c_void_p(a), U64P) for a in addrs])
+            keep.append((cols, arr))
+            tabs.append(arr)
+            logs.append(n.bit_length() - 1)
+        ptrs = (C.POINTER(U64P) * nt)(*[C.cast(a, C.POINTER(U64P)) if a is not None else C.POINTER(U64P)() for a in tabs])
+        logs = (C.c_uint32 * nt)(*logs)
+        n_out = C.c_uint32(0)
+        out = (OlaConstraintFailure * max(1, cap))()
+        self._chk(self.lib.ola_check_constraints(self.ctx, _p(blob), blob.size, ptrs, logs, None if pr is None else _p(pr),
+                                                 None if cc is None else _p(cc), mask, out, cap, C.byref(n_out)))
+        got = [(int(f.table), int(f.section), int(f.index), int(f.kind), int(f.first_row), int(f.rows_failing)) for f in out[:min(cap, n_out.value)]]
+        return got, int(n_out.value)
+
+    def check_constraints(self, airset, traces, params=None, tables=None, ctl_challenges=None):
+        """Why a trace does not prove (ola_check_constraints): the constraint programs, permutation arguments and cross-table
+        lookups of `tables` (indices; default all) evaluated on the trace domain.  airset: an olavm_amd.air.AirSet (its table
+        names go into the report) or a blob; traces: as for prove_with_traces, a table may also be a list of 1-d device tensors
+        (entries outside `tables` may be None).
+        -> list of dicts {table, table_name, section, index, kind, first_row, rows_failing}, sorted by (table, section, index):
+        section "AIR" (index = ordinal of the emit in AirTable.emits, kind = its ConstraintConsumer method), "PERMUTATION"
+        (index = batch) or "LOOKUP" (index = the lookup, kind = the challenge index, and first_row / rows_failing are also given
+        as looking_rows / looked_rows).  Empty for a trace that satisfies everything."""
+        names = [t.name for t in airset.tables] if hasattr(airset, "tables") else None
+        blob = airset.blob() if hasattr(airset, "blob") else airset
+        got, total = self.check_constraints_raw(blob, traces, params, tables, ctl_challenges)
+        if total > len(got):
+            got, total = self.check_constraints_raw(blob, traces, params, tables, ctl_challenges, cap=total)
+        report = []
+        for table, sec, index, kind, first_row, rows_failing in got:
+            section = CHECK_SECTIONS[sec]
+            d = {"table": table, "table_name": names[table] if names else None, "section": section, "index": index,
+                 "kind": CONSTRAINT_KINDS[kind] if section == "AIR" else kind, "first_row": first_row, "rows_failing": rows_failing}
+            if section == "LOOKUP":
+                d["looking_rows"], d["looked_rows"] = first_row, rows_failing
+            report.append(d)
+        return report
 
     def prove_single_table(self, airset_blob, table, trace, batch, ctl_challenges, params, challenger):
         """StarkProof bytes of one table (ola_prove_single_table): `batch` is the table's trace commitment, `challenger` the

@@ -28,6 +28,7 @@
 #include "batch.hip"
 #include "fri.hip"
 #include "stark.hip"
+#include "check.hip"
 #include "selftest.hip"
 
 using namespace ola;
@@ -1056,6 +1057,41 @@ int32_t ola_prove_with_traces_cols(OlaCtx* ctx, const uint64_t* airset, size_t a
         src[t].cols = (const u64* const*)cols[t];
     }
     prove_all(ctx, airset, airset_words, src, log_n, params, compress_challenges, out, cap, out_len);
+    OLA_CATCH
+}
+
+int32_t ola_check_constraints(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, const uint64_t* const* const* cols,
+                              const uint32_t* log_n, const uint64_t* params, const uint64_t* ctl_challenges, uint32_t table_mask,
+                              OlaConstraintFailure* out, uint32_t cap, uint32_t* n_out) {
+    OLA_TRY
+    require(airset && cols && log_n && n_out && (out || cap == 0), "null pointer");
+    const std::vector<size_t> widths = airset_widths((const u64*)airset, airset_words);
+    const size_t nt = widths.size();
+    require(nt <= 32 && (nt == 32 || (table_mask >> nt) == 0), "table_mask names a table beyond the AIR set");
+    std::vector<TraceSource> src(nt);
+    for (size_t t = 0; t < nt; t++) {
+        if (!(table_mask >> t & 1)) continue;
+        require(cols[t] != nullptr, "cols[t] is NULL");
+        for (size_t c = 0; c < widths[t]; c++) require(cols[t][c] != nullptr, "cols[t][c] is NULL");
+        src[t].cols = (const u64* const*)cols[t];
+    }
+    if (!ctx) {
+        // a context cannot exist without a device: say so rather than "null pointer" (there is no CPU fallback)
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+            (void)hipGetLastError();
+            throw OlaError(OLA_E_NO_DEVICE, "no HIP device visible (the backend has no CPU fallback)");
+        }
+        require(false, "ctx is NULL");
+    }
+    OLA_ON_DEVICE(ctx);
+    for (size_t t = 0; t < nt; t++)
+        if (table_mask >> t & 1) require(log_n[t] <= 30, "table size out of range");
+    std::vector<OlaConstraintFailure> found;
+    check_constraints(&ctx->dev, ctx->cfg, (const u64*)airset, airset_words, src.data(), log_n, (const u64*)params, (const u64*)ctl_challenges,
+                      table_mask, found);
+    *n_out = (uint32_t)found.size();
+    for (size_t i = 0; i < found.size() && i < cap; i++) out[i] = found[i];
     OLA_CATCH
 }
 
