@@ -44,7 +44,8 @@ extern "C" {
  * ola_gpu_ntt_pass_times (the transform passes one by one, for the dominant kernel's roofline); no struct changed.
  * 7 (number unchanged by the later additions, which change no struct and no existing behaviour): the hashers OLA_HASH_POSEIDON2 and
  * OLA_HASH_POSEIDON2_POW_POSEIDON and the entry point ola_poseidon2_permute were added to revision 7; so were OlaConstraintFailure
- * and the entry point ola_check_constraints (which constraint of which table fails at which row). */
+ * and the entry point ola_check_constraints (which constraint of which table fails at which row); so were ola_generate_rc_trace,
+ * ola_generate_bitwise_trace and ola_generate_prog_trace (the range-check, bitwise and program tables completed in HBM). */
 #define OLA_GPU_ABI_VERSION 7
 #define OLA_OK 0
 #define OLA_E_INVALID_ARG (-1)
@@ -522,6 +523,52 @@ int32_t ola_permuted_cols(OlaCtx* ctx, const uint64_t* inputs, const uint64_t* t
                           uint64_t* permuted_table);
 int32_t ola_permuted_cols_dev(OlaCtx* ctx, const uint64_t* inputs_dev, const uint64_t* table_dev, size_t n,
                               uint64_t* permuted_inputs_dev, uint64_t* permuted_table_dev);
+
+/* ---- whole derived tables from their primary columns --------------------------------------------------------
+ * The range-check, bitwise and program tables are mostly columns that are a function of a few primary ones: limbs, the fixed
+ * sub-tables, compress columns and the permuted pairs of their in-table lookups (one sequential merge loop per pair on the host,
+ * lookup.rs:68-132).  The host keeps what is cheap and policy-laden -- row order, filler rows, the filters -- and these calls
+ * write everything else on the device, the permuted pairs of a table as ONE batch (a table column that several pairs look into is
+ * sorted once).
+ * out: the table, column-major ncols x 2^log_n -- the layout ola_prove_with_traces takes -- in host memory or in memory of the
+ *   context's GPU (the library looks at the pointer); a table written into HBM can be passed to ola_prove_with_traces as a
+ *   resident table and never crosses the link.  Inputs may be host or device memory as well and may hold words >= p; every
+ *   word written is canonical.  Device buffers, inputs and `out` alike, must be memory of the context's GPU (memory of
+ *   another GPU is OLA_E_INVALID_ARG) and complete when the call is made: the work runs on the context's stream, which does
+ *   not wait for copies or fills the caller enqueued on another stream.  Every column of `out` is written; rows beyond the
+ *   live inputs are zero in the primary columns.  The calls return when the table is complete.
+ * out == NULL (ola_generate_rc_trace, ola_generate_bitwise_trace): *log_n_out receives the height and nothing else happens; this
+ *   sizing call takes ctx == NULL as well.
+ * ctx == NULL in a call that would do work: OLA_E_NO_DEVICE when the machine has no HIP device (there is no CPU fallback),
+ *   OLA_E_INVALID_ARG otherwise; the other arguments are validated first.
+ *
+ * ola_generate_rc_trace: the 12-column range-check table of generate_rc_trace (generation/builtin.rs:249-316).
+ *   vals[n_rows]; filters: 4 x n_rows column-major (CPU, MEMORY_SORT, MEMORY_REGION, CMP filter) or NULL for zeros.
+ *   n = next_pow2(max(n_rows, 2^range_bits)), at least 2 (range_bits = 16 in the reference, smaller for miniature tables).
+ *   LIMB_LO = val mod 2^range_bits, LIMB_HI = val >> range_bits of the canonical value -- a value >= 2^(2 range_bits) is not
+ *   refused: it gives a table the AIR rejects, as the reference's would; FIX_RANGE_CHECK_U16 = 0 .. 2^range_bits - 1, then the
+ *   last value repeated; the two permuted pairs.
+ * ola_generate_bitwise_trace: the 59-column bitwise table of generate_bitwise_trace (generation/builtin.rs:35-206).
+ *   ops: 5 x n_ops column-major -- filter, tag, op0, op1, res, copied as given (res is not recomputed).
+ *   n = next_pow2(max(2^limb_bits, 3 * 4^limb_bits, n_ops)) (limb_bits = 8 in the reference).  Written: the twelve limb columns
+ *   (limb l = bits [l limb_bits, (l + 1) limb_bits) of the canonical operand), the fixed AND / OR / XOR table in the reference's
+ *   row order with FIX_TAG, FIX_RANGE_CHECK_U8 = 0 .. 2^limb_bits - 1 then zeros, the four COMPRESS_LIMBS columns and
+ *   FIX_COMPRESS = tag + a beta + b beta^2 + c beta^3, and the sixteen permuted pairs (twelve against FIX_RANGE_CHECK_U8, four
+ *   against FIX_COMPRESS).  beta is the caller's: the reference draws it from a transcript over the twelve limb columns
+ *   (generation/builtin.rs:120-131), a sequential sponge that stays on the host (ola_challenger_*).
+ *   flags: OLA_TABLEGEN_REFERENCE_QUIRKS leaves the three limb-3 columns zero, as the reference's generator does
+ *   (generation/builtin.rs:65,70,75 write them to the exclusive end of their range; include/ola_tracegen.h describes the defect).
+ * ola_generate_prog_trace: the 18-column program table of generate_prog_trace (generation/prog.rs:18-156).
+ *   exec, prog: each 7 x 2^log_n column-major -- four code-address words, pc, inst, filter -- the executed side and the listing
+ *   side at full height, filler rows as the caller lays them out (the reference's zero rows, or a listed word repeated with
+ *   filter 0).  The fourteen columns are copied, COL_PROG_EXEC_COMP_PROG and COL_PROG_COMP_PROG =
+ *   a0 + a1 beta + a2 beta^2 + a3 beta^3 + pc beta^4 + inst beta^5 (generation/prog.rs:149-156), and the permuted pair. */
+#define OLA_TABLEGEN_REFERENCE_QUIRKS 1u
+int32_t ola_generate_rc_trace(OlaCtx* ctx, const uint64_t* vals, const uint64_t* filters, size_t n_rows, uint32_t range_bits,
+                              uint64_t* out, uint32_t* log_n_out);
+int32_t ola_generate_bitwise_trace(OlaCtx* ctx, const uint64_t* ops, size_t n_ops, uint32_t limb_bits, uint64_t beta, uint32_t flags,
+                                   uint64_t* out, uint32_t* log_n_out);
+int32_t ola_generate_prog_trace(OlaCtx* ctx, const uint64_t* exec, const uint64_t* prog, uint32_t log_n, uint64_t beta, uint64_t* out);
 
 /* ---- coset-partitioned proving over several GPUs ---------------------------------------------------------
  * One process per GPU; every process calls ola_prove_with_traces with the SAME traces.  Because the transcript is a

@@ -43,6 +43,8 @@ pub const OLA_COLLECTIVE_RCCL: u32 = 2;
 pub const OLA_PHASE_COUNT: u32 = 7;
 /// ola_gpu_warmup: also pin the trace upload's staging ring
 pub const OLA_WARMUP_PINNED_RING: u32 = 1;
+/// `flags` of `ola_generate_bitwise_trace`: leave the three limb-3 columns zero, as the reference's generator does.
+pub const OLA_TABLEGEN_REFERENCE_QUIRKS: u32 = 1;
 /// ola_check_constraints: `OlaConstraintFailure::section`
 pub const OLA_CHECK_AIR: u32 = 0;
 pub const OLA_CHECK_PERMUTATION: u32 = 1;
@@ -227,6 +229,11 @@ extern "C" {
         permuted_table: *mut u64) -> i32;
     pub fn ola_permuted_cols_dev(ctx: *mut OlaCtx, inputs_dev: *const u64, table_dev: *const u64, n: usize,
         permuted_inputs_dev: *mut u64, permuted_table_dev: *mut u64) -> i32;
+    pub fn ola_generate_rc_trace(ctx: *mut OlaCtx, vals: *const u64, filters: *const u64, n_rows: usize, range_bits: u32,
+        out: *mut u64, log_n_out: *mut u32) -> i32;
+    pub fn ola_generate_bitwise_trace(ctx: *mut OlaCtx, ops: *const u64, n_ops: usize, limb_bits: u32, beta: u64, flags: u32,
+        out: *mut u64, log_n_out: *mut u32) -> i32;
+    pub fn ola_generate_prog_trace(ctx: *mut OlaCtx, exec: *const u64, prog: *const u64, log_n: u32, beta: u64, out: *mut u64) -> i32;
     pub fn ola_set_shard(ctx: *mut OlaCtx, rank: u32, world: u32, all_gather: OlaAllGatherFn, user: *mut c_void) -> i32;
     pub fn ola_set_shard_options(ctx: *mut OlaCtx, flags: u32) -> i32;
     pub fn ola_gpu_get_stream(ctx: *mut OlaCtx, stream_out: *mut *mut c_void) -> i32;

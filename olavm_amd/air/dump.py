@@ -35,3 +35,30 @@ def columns_header():
         out.append("constexpr uint32_t OP_%s = %d;" % (op, sh))
     out.append("}  // namespace olacols")
     return "\n".join(out) + "\n"
+
+
+TABLEGEN_COLUMNS_H = "olavm_amd/csrc/tablegen_columns.h"
+
+
+def tablegen_columns_header():
+    """The checked header olavm_amd/csrc/tablegen_columns.h: column indices of the range-check, bitwise and program tables and the three
+    bitwise opcode masks, for the device-side table generators in olavm_amd/csrc/lookup.hip.  The file is committed (lookup.hip is compiled
+    before anything is generated); tests/test_tablegen_abi.py compares it with this text.  Regenerate:
+        python -c "from olavm_amd.air import dump; print(dump.tablegen_columns_header(), end='')" > olavm_amd/csrc/tablegen_columns.h"""
+    from . import ola_tables as T
+    out = ["// generated from olavm_amd/air/ola_tables.py by olavm_amd.air.dump.tablegen_columns_header() -- do not edit",
+           "#pragma once", "#include <cstdint>", "namespace olatg {"]
+    wanted = lambda n: n.startswith(("RC_", "BW_")) or n in ("COL_NUM_RC", "COL_NUM_BITWISE", "NUM_PROG_COLS") or (
+        n.startswith("COL_PROG_") and not n.startswith("COL_PROG_CHUNK_"))
+    for name in sorted(n for n in dir(T) if n.isupper() and wanted(n)):
+        v = getattr(T, name)
+        if isinstance(v, bool):
+            continue
+        if isinstance(v, int):
+            out.append("constexpr uint32_t %s = %du;" % (name, v))
+        elif isinstance(v, range):
+            out.append("constexpr uint32_t %s_START = %du, %s_END = %du;" % (name, v.start, name, v.stop))
+    for op in ("AND", "OR", "XOR"):
+        out.append("constexpr uint64_t OP_MASK_%s = %dull;" % (op, T.op_mask(op)))
+    out.append("}  // namespace olatg")
+    return "\n".join(out) + "\n"

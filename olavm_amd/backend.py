@@ -152,6 +152,11 @@ def load_library():
     L.ola_take_pending_proof.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.ola_permuted_cols.argtypes = [C.c_void_p, U64P, U64P, C.c_size_t, U64P, U64P]
     L.ola_permuted_cols_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.ola_generate_rc_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.ola_generate_bitwise_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.ola_generate_prog_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
+    for f in ("ola_generate_rc_trace", "ola_generate_bitwise_trace", "ola_generate_prog_trace"):
+        getattr(L, f).restype = C.c_int32
     L.ola_set_shard.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, ALL_GATHER_FN, C.c_void_p]
     L.ola_set_shard_options.argtypes = [C.c_void_p, C.c_uint32]
     L.ola_gpu_get_stream.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -182,12 +187,13 @@ EXPORTS = [
     "ola_gpu_abi_version", "ola_gpu_init_multi", "ola_gpu_device_count", "ola_gpu_proof_stats", "ola_gpu_phase_stats",
     "ola_gpu_collective", "ola_gpu_all_gather_check", "ola_prove_with_traces_cols", "ola_gpu_scope_times", "ola_gpu_upload_stats",
     "ola_gpu_warmup", "ola_gpu_warmup_wait", "ola_gpu_ntt_pass_times",
-    "ola_check_constraints",
+    "ola_check_constraints", "ola_generate_rc_trace", "ola_generate_bitwise_trace", "ola_generate_prog_trace",
     "ola_open", "ola_fri_plan", "ola_fri_commit_begin", "ola_fri_commit_next_layer", "ola_fri_commit_finish", "ola_fri_query", "ola_fri_free",
 ]
 
 
 OLA_WARMUP_PINNED_RING = 1
+OLA_TABLEGEN_REFERENCE_QUIRKS = 1
 
 
 def warmup(device=-1, pinned_ring=True, airset=None):
@@ -219,6 +225,44 @@ ALL_GATHER_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_s
 
 def _p(a):
     return a.ctypes.data_as(U64P)
+
+
+def _words(a, rows=None):
+    """An input of the table generators -> (address, keep-alive, shape): a numpy array (made contiguous uint64), a 64-bit torch
+    tensor on the GPU, or an integer device address (its shape is then the caller's to give)."""
+    if a is None:
+        return None, None, None
+    if isinstance(a, int):
+        if rows is None:
+            raise ValueError("a device address needs its size (n_rows / n_ops / log_n)")
+        return C.c_void_p(a), None, rows
+    if hasattr(a, "data_ptr"):
+        if not (a.is_contiguous() and a.element_size() == 8):
+            raise ValueError("device-resident inputs must be contiguous 64-bit tensors")
+        return C.c_void_p(a.data_ptr()), a, tuple(int(x) for x in a.shape)
+    h = np.ascontiguousarray(a, dtype=np.uint64)
+    return C.c_void_p(h.ctypes.data), h, h.shape
+
+
+def bitwise_beta(ops, limb_bits=8, reference_quirks=False):
+    """The compress challenge of the bitwise table as generation/builtin.rs:120-131 derives it: a fresh Poseidon Challenger observes
+    the twelve limb columns at full height (op0, op1, res limbs 0..3) and draws one challenge -- on the host, through the library's
+    host challenger (a sequential sponge: it stays off the device).  ops: (5, n_ops) words -- filter, tag, op0, op1, res."""
+    ops = np.ascontiguousarray(ops, dtype=np.uint64).reshape(5, -1)
+    n_ops = ops.shape[1]
+    size = 1 << limb_bits
+    n = 2
+    while n < max(size, 3 * size * size, n_ops):
+        n *= 2
+    p = np.uint64(0xFFFFFFFF00000001)
+    ch = Challenger()
+    col = np.zeros(n, dtype=np.uint64)
+    for k in (2, 3, 4):
+        v = np.where(ops[k] >= p, ops[k] - p, ops[k])
+        for i in range(4):
+            col[:n_ops] = 0 if (reference_quirks and i == 3) else (v >> np.uint64(limb_bits * i)) & np.uint64(size - 1)
+            ch.observe(col)
+    return ch.get()
 
 
 class _DeviceBytes:
@@ -561,6 +605,79 @@ class Backend:
 
     def permuted_cols_dev(self, in_ptr, table_ptr, n, out_in_ptr, out_table_ptr):
         self._chk(self.lib.ola_permuted_cols_dev(self.ctx, in_ptr, table_ptr, n, out_in_ptr, out_table_ptr))
+
+    # ---- whole derived tables from their primary columns (ola_generate_*_trace) ----
+    # Inputs: numpy arrays, 64-bit torch tensors on this GPU, or integer device addresses.  out: None -> a new numpy array is
+    # returned; a torch tensor on this GPU or an integer device address -> written in place (the table never crosses the link) and
+    # log_n is returned.  Device buffers must be complete when the call is made (torch.cuda.synchronize() after copies and fills
+    # on torch's stream): the library works on the context's stream.
+    def _table_out(self, out, ncols, log_n):
+        if out is None:
+            t = np.empty((ncols, 1 << log_n), dtype=np.uint64)
+            return C.c_void_p(t.ctypes.data), t
+        if isinstance(out, int):
+            return C.c_void_p(out), log_n
+        if hasattr(out, "data_ptr"):
+            if not (out.is_contiguous() and out.element_size() == 8 and out.numel() >= ncols << log_n):
+                raise ValueError("out must be a contiguous 64-bit tensor of at least ncols * 2^log_n words")
+            return C.c_void_p(out.data_ptr()), log_n
+        t = np.ascontiguousarray(out)
+        if t is not out or t.dtype != np.uint64 or t.size < ncols << log_n:
+            raise ValueError("out must be a contiguous uint64 array of at least ncols * 2^log_n words")
+        return C.c_void_p(t.ctypes.data), log_n
+
+    def rc_trace_log_n(self, n_rows, range_bits=16):
+        log_n = C.c_uint32()
+        self._chk(self.lib.ola_generate_rc_trace(self.ctx, None, None, n_rows, range_bits, None, C.byref(log_n)))
+        return log_n.value
+
+    def bitwise_trace_log_n(self, n_ops, limb_bits=8):
+        log_n = C.c_uint32()
+        self._chk(self.lib.ola_generate_bitwise_trace(self.ctx, None, n_ops, limb_bits, 0, 0, None, C.byref(log_n)))
+        return log_n.value
+
+    def generate_rc_trace(self, vals, filters=None, range_bits=16, out=None, n_rows=None):
+        """ola_generate_rc_trace: the range-check table (12 x n) from vals (n_rows) and filters (4 x n_rows, or None for zeros).
+        n_rows must be given when vals is a device address."""
+        pv, kv, shape = _words(vals, None if n_rows is None else (n_rows,))
+        n_rows = int(np.prod(shape)) if shape is not None else 0
+        pf, kf, fshape = _words(filters, (4, n_rows))
+        if fshape is not None and int(np.prod(fshape)) != 4 * n_rows:
+            raise ValueError("filters must be 4 x n_rows")
+        log_n = self.rc_trace_log_n(n_rows, range_bits)
+        po, ret = self._table_out(out, 12, log_n)
+        got = C.c_uint32()
+        self._chk(self.lib.ola_generate_rc_trace(self.ctx, pv if n_rows else None, pf, n_rows, range_bits, po, C.byref(got)))
+        return ret
+
+    def generate_bitwise_trace(self, ops, beta, limb_bits=8, reference_quirks=False, out=None, n_ops=None):
+        """ola_generate_bitwise_trace: the bitwise table (59 x n) from ops (5 x n_ops: filter, tag, op0, op1, res) and the compress
+        challenge beta (bitwise_beta derives the reference's).  n_ops must be given when ops is a device address."""
+        po_, ko, shape = _words(ops, None if n_ops is None else (5, n_ops))
+        if shape is None:
+            n_ops = 0
+        else:
+            if int(np.prod(shape)) % 5:
+                raise ValueError("ops must be 5 x n_ops")
+            n_ops = int(np.prod(shape)) // 5
+        log_n = self.bitwise_trace_log_n(n_ops, limb_bits)
+        po, ret = self._table_out(out, 59, log_n)
+        got = C.c_uint32()
+        self._chk(self.lib.ola_generate_bitwise_trace(self.ctx, po_ if n_ops else None, n_ops, limb_bits, int(beta) % (1 << 64),
+                                                      OLA_TABLEGEN_REFERENCE_QUIRKS if reference_quirks else 0, po, C.byref(got)))
+        return ret
+
+    def generate_prog_trace(self, exec_side, prog_side, beta, out=None, log_n=None):
+        """ola_generate_prog_trace: the program table (18 x n) from the executed side and the listing side, each 7 x n (four
+        code-address words, pc, inst, filter) at full height.  log_n must be given when the sides are device addresses."""
+        pe, ke, es = _words(exec_side, None if log_n is None else (7, 1 << log_n))
+        pp, kp, ps = _words(prog_side, None if log_n is None else (7, 1 << log_n))
+        if es is None or ps is None or tuple(es) != tuple(ps) or len(es) != 2 or es[0] != 7 or es[1] & (es[1] - 1) or es[1] < 2:
+            raise ValueError("exec_side and prog_side must both be 7 x 2^log_n")
+        log_n = int(es[1]).bit_length() - 1
+        po, ret = self._table_out(out, 18, log_n)
+        self._chk(self.lib.ola_generate_prog_trace(self.ctx, pe, pp, log_n, int(beta) % (1 << 64), po))
+        return ret
 
     def trim(self):
         """Return the context's cached device buffers to the driver (ola_gpu_trim)."""

@@ -164,6 +164,14 @@ struct UploadStats {
     uint32_t threads = 0;
 };
 
+// Is `p` device (or managed) memory?  *device (may be NULL) receives the GPU it lives on.
+inline bool is_device_pointer(const void* p, int* device = nullptr) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // plain malloc memory: "invalid value"
+    if (device) *device = a.device;
+    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
+}
+
 struct DeviceCtx;
 // The contexts of this process, for the hand-over of cached blocks between the ones that share a GPU (DeviceCtx::adopt).
 struct PoolRegistry {

@@ -12,4 +12,25 @@ namespace ola {
 // hold non-canonical words.  permuted_inputs = the inputs sorted (canonical), permuted_table as the reference builds it.
 void permuted_cols_dev(DeviceCtx* ctx, const u64* inputs, const u64* table, size_t n, u64* permuted_inputs, u64* permuted_table);
 
+// The same for a batch of pairs of one height n: tables[0 .. n_tables) are the table columns, pair p looks into
+// tables[pairs[p].table].  A table column that several pairs share (the same pointer) is canonicalised and sorted once; the
+// classification, scans, bracket matching and fill run over all pairs together, one launch each.  permuted_cols_dev is the
+// batch of one.
+struct PermutedPair {
+    const u64* inputs;
+    u32 table;
+    u64* permuted_inputs;
+    u64* permuted_table;
+};
+void permuted_cols_batch_dev(DeviceCtx* ctx, size_t n, const u64* const* tables, size_t n_tables, const PermutedPair* pairs, size_t n_pairs);
+
+// Whole tables from their primary columns (ola_generate_rc_trace / _bitwise_trace / _prog_trace of include/ola_gpu.h): all
+// pointers are device memory, `out` is column-major ncols x 2^log_n with log_n as the *_log_n functions give it (the
+// program table: as passed).  Every column of `out` is written; complete when the call returns.
+u32 rc_trace_log_n(u64 n_rows, u32 range_bits);
+u32 bitwise_trace_log_n(u64 n_ops, u32 limb_bits);
+void generate_rc_trace_dev(DeviceCtx* ctx, const u64* vals, const u64* filters, size_t n_rows, u32 range_bits, u64* out);
+void generate_bitwise_trace_dev(DeviceCtx* ctx, const u64* ops, size_t n_ops, u32 limb_bits, u64 beta, bool reference_quirks, u64* out);
+void generate_prog_trace_dev(DeviceCtx* ctx, const u64* exec, const u64* prog, u32 log_n, u64 beta, u64* out);
+
 }  // namespace ola

@@ -20,6 +20,7 @@
 //      height they push to / pop from puts every pop right behind the push it takes;
 //   4. pushes nobody took (in event order) fill the slots of the unmatched pops (in event order) followed by the tail
 //      slots (in index order).
+#include <algorithm>
 #include <cstring>
 
 #include <hip/hip_runtime.h>
@@ -28,12 +29,24 @@
 #include "device_ctx.h"
 #include "gl.cuh"
 #include "lookup.h"
+#include "tablegen_columns.h"
 
 namespace ola {
 
 namespace {
 
-enum : u32 { K_MATCHED = 0, K_EVENT = 1, K_TAIL = 2 };
+// A batch of pairs that share their height runs steps 2 - 4 together: every kernel below has the pair index in grid.y, the
+// scans run once over the concatenation of the pairs' flag arrays (a pair's own prefix is the difference to the value at its
+// first entry), the events of all pairs sit back to back (pair p at ev_base[p]) with the pair index as the key of the two
+// segmented scans and as the high bits of the level key, so that one stable sort orders every pair's events.  The table
+// generators further down fill a whole table and hand its lookup pairs to one such batch.
+constexpr u32 kMaxBatch = 16;
+
+struct PairArgs {                  // kernel argument (by value): pair p of the batch
+    const u64* si[kMaxBatch];      // its inputs, canonical and sorted = permuted_inputs
+    const u64* st[kMaxBatch];      // its table, canonical and sorted
+    u64* pt[kMaxBatch];            // permuted_table
+};
 
 struct Scratch {
     DeviceCtx* ctx;
@@ -51,9 +64,11 @@ struct Scratch {
     }
 };
 
-__global__ __launch_bounds__(256) void canon_kernel(const u64* __restrict__ in, u64* __restrict__ out, u32 n) {
+// column y of a batch of columns: src[y] -> dst + y * n
+struct CanonArgs { const u64* src[kMaxBatch]; };
+__global__ __launch_bounds__(256) void canon_kernel(CanonArgs a, u64* __restrict__ dst, u32 n) {
     const u32 i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = gl_canon(in[i]);
+    if (i < n) dst[(size_t)blockIdx.y * n + i] = gl_canon(a.src[blockIdx.y][i]);
 }
 
 __device__ __forceinline__ u32 lower_bound_u64(const u64* __restrict__ a, u32 n, u64 v) {
@@ -73,56 +88,74 @@ __device__ __forceinline__ u32 upper_bound_u64(const u64* __restrict__ a, u32 n,
     return lo;
 }
 
+// Flags of a batch: three classes (FL_POP: input that pops, FL_PUSH: table entry that pushes, FL_TAIL: input reached after the
+// table ran out) x pairs x (n + 1) entries, entry n of every run is 0 -- the exclusive scan over all of it then holds, at a run's
+// entry n, the run's total on top of what came before.
+enum : u32 { FL_POP = 0, FL_PUSH = 1, FL_TAIL = 2, FL_CLASSES = 3 };
+__device__ __forceinline__ size_t flag_at(u32 cls, u32 pairs, u32 n, u32 p, u32 i) { return ((size_t)cls * pairs + p) * (n + 1) + i; }
+__device__ __forceinline__ u32 before(const u32* __restrict__ sc, u32 cls, u32 pairs, u32 n, u32 p, u32 i) {
+    const size_t b = flag_at(cls, pairs, n, p, 0);
+    return sc[b + i] - sc[b];
+}
+
 // step 2: thread t < n classifies input t, thread n + t classifies table entry t.  other[t] = first position of the
 // opposite column whose value is not below this one (where events of smaller values end).
-__global__ __launch_bounds__(256) void classify_kernel(const u64* __restrict__ si, const u64* __restrict__ st, u32 n,
-                                                       u32* __restrict__ kind_in, u32* __restrict__ kind_tab,
-                                                       u32* __restrict__ other_in, u32* __restrict__ other_tab,
-                                                       u64* __restrict__ permuted_table) {
-    const u32 t = blockIdx.x * 256 + threadIdx.x;
+__global__ __launch_bounds__(256) void classify_kernel(PairArgs a, u32 pairs, u32 n, u32* __restrict__ flags, u32* __restrict__ other_in,
+                                                       u32* __restrict__ other_tab) {
+    const u32 t = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y;
+    const u64* __restrict__ si = a.si[p];
+    const u64* __restrict__ st = a.st[p];
     if (t < n) {
-        const u64 a = si[t];
-        const u32 rank = t - lower_bound_u64(si, n, a);
-        const u32 lb = lower_bound_u64(st, n, a), ub = upper_bound_u64(st, n, a);
-        other_in[t] = lb;
-        if (rank < ub - lb) {
-            kind_in[t] = K_MATCHED;
-            permuted_table[t] = a;
-        } else {
-            kind_in[t] = ub < n ? K_EVENT : K_TAIL;
-        }
+        const u64 v = si[t];
+        const u32 rank = t - lower_bound_u64(si, n, v);
+        const u32 lb = lower_bound_u64(st, n, v), ub = upper_bound_u64(st, n, v);
+        other_in[(size_t)p * n + t] = lb;
+        const bool matched = rank < ub - lb;
+        if (matched) a.pt[p][t] = v;
+        flags[flag_at(FL_POP, pairs, n, p, t)] = (!matched && ub < n) ? 1u : 0u;
+        flags[flag_at(FL_TAIL, pairs, n, p, t)] = (!matched && ub >= n) ? 1u : 0u;
+        if (t == 0)
+            for (u32 c = 0; c < FL_CLASSES; c++) flags[flag_at(c, pairs, n, p, n)] = 0;
     } else if (t < 2 * n) {
         const u32 j = t - n;
         const u64 b = st[j];
         const u32 rank = j - lower_bound_u64(st, n, b);
         const u32 lb = lower_bound_u64(si, n, b), ub = upper_bound_u64(si, n, b);
-        other_tab[j] = lb;
-        kind_tab[j] = rank < ub - lb ? K_MATCHED : K_EVENT;
+        other_tab[(size_t)p * n + j] = lb;
+        flags[flag_at(FL_PUSH, pairs, n, p, j)] = rank < ub - lb ? 0u : 1u;
     }
 }
 
-__global__ __launch_bounds__(256) void flag_kernel(const u32* __restrict__ kind, u32 n, u32 which, u32* __restrict__ flag) {
-    const u32 i = blockIdx.x * 256 + threadIdx.x;
-    if (i <= n) flag[i] = (i < n && kind[i] == which) ? 1u : 0u;      // n + 1 entries: the scan's last one is the total
+// ev_base[p] = where pair p's events start in the concatenated event list, ev_base[pairs] = their number
+__global__ void event_base_kernel(const u32* __restrict__ sc, u32 pairs, u32 n, u32* __restrict__ ev_base) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    u32 acc = 0;
+    for (u32 p = 0; p < pairs; p++) {
+        ev_base[p] = acc;
+        acc += before(sc, FL_POP, pairs, n, p, n) + before(sc, FL_PUSH, pairs, n, p, n);
+    }
+    ev_base[pairs] = acc;
 }
 
-// events in loop order: delta[e] = +1 (push) / -1 (pop), src[e] = table index / input index
-__global__ __launch_bounds__(256) void place_events_kernel(u32 n, const u32* __restrict__ kind_in, const u32* __restrict__ kind_tab,
+// events in loop order: delta[e] = +1 (push) / -1 (pop), src[e] = table index / input index, ev_pair[e] = the pair
+__global__ __launch_bounds__(256) void place_events_kernel(u32 pairs, u32 n, const u32* __restrict__ flags, const u32* __restrict__ sc,
                                                            const u32* __restrict__ other_in, const u32* __restrict__ other_tab,
-                                                           const u32* __restrict__ pop_before, const u32* __restrict__ push_before,
-                                                           int* __restrict__ delta, u32* __restrict__ src) {
-    const u32 t = blockIdx.x * 256 + threadIdx.x;
+                                                           const u32* __restrict__ ev_base, int* __restrict__ delta, u32* __restrict__ src,
+                                                           u32* __restrict__ ev_pair) {
+    const u32 t = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y;
     if (t < n) {
-        if (kind_in[t] != K_EVENT) return;
-        const u32 e = pop_before[t] + push_before[other_in[t]];
+        if (!flags[flag_at(FL_POP, pairs, n, p, t)]) return;
+        const u32 e = ev_base[p] + before(sc, FL_POP, pairs, n, p, t) + before(sc, FL_PUSH, pairs, n, p, other_in[(size_t)p * n + t]);
         delta[e] = -1;
         src[e] = t;
+        ev_pair[e] = p;
     } else if (t < 2 * n) {
         const u32 j = t - n;
-        if (kind_tab[j] != K_EVENT) return;
-        const u32 e = push_before[j] + pop_before[other_tab[j]];
+        if (!flags[flag_at(FL_PUSH, pairs, n, p, j)]) return;
+        const u32 e = ev_base[p] + before(sc, FL_PUSH, pairs, n, p, j) + before(sc, FL_POP, pairs, n, p, other_tab[(size_t)p * n + j]);
         delta[e] = 1;
         src[e] = j;
+        ev_pair[e] = p;
     }
 }
 
@@ -131,25 +164,29 @@ __global__ __launch_bounds__(256) void clamp_min_kernel(const int* __restrict__ 
     if (e < count) m[e] = s[e] < 0 ? s[e] : 0;
 }
 
+// Flags of the events: two runs of count + 1 entries (empty pops, then free pushes), entry `count` of each is 0.
 // level key of every event: pushes sort under the height they create, matched pops under the height they remove;
-// pops that found the stack empty get key 0 and an `empty_pop` flag.
+// pops that found the stack empty get level 0 and an `empty_pop` flag.  The pair index sits above the level.
 __global__ __launch_bounds__(256) void level_kernel(const int* __restrict__ delta, const int* __restrict__ s, const int* __restrict__ runmin,
-                                                    u32 count, u32* __restrict__ key, u32* __restrict__ ident, u32* __restrict__ empty_pop) {
+                                                    const u32* __restrict__ ev_pair, const u32* __restrict__ ev_base, u32 count, u32 level_bits,
+                                                    u32* __restrict__ key, u32* __restrict__ ident, u32* __restrict__ empty_pop) {
     const u32 e = blockIdx.x * 256 + threadIdx.x;
     if (e > count) return;
     if (e == count) { empty_pop[e] = 0; return; }
-    const int m = runmin[e], m_prev = e ? runmin[e - 1] : 0;
+    const u32 p = ev_pair[e];
+    const int m = runmin[e], m_prev = e != ev_base[p] ? runmin[e - 1] : 0;
     const int height = s[e] - m;                      // stack height after the event
     const bool unmatched = delta[e] < 0 && s[e] < m_prev;
     ident[e] = e;
     empty_pop[e] = unmatched ? 1u : 0u;
-    key[e] = delta[e] > 0 ? (u32)height : (unmatched ? 0u : (u32)height + 1u);
+    const u32 level = delta[e] > 0 ? (u32)height : (unmatched ? 0u : (u32)height + 1u);
+    key[e] = (p << level_bits) | level;
 }
 
-// after the stable sort by level a matched pop sits right behind its push
-__global__ __launch_bounds__(256) void pair_kernel(const u32* __restrict__ key_sorted, const u32* __restrict__ ev_sorted, u32 count,
-                                                   const int* __restrict__ delta, const u32* __restrict__ src, const u64* __restrict__ st,
-                                                   u64* __restrict__ permuted_table, u32* __restrict__ free_push) {
+// after the stable sort by (pair, level) a matched pop sits right behind its push
+__global__ __launch_bounds__(256) void pair_kernel(PairArgs a, const u32* __restrict__ key_sorted, const u32* __restrict__ ev_sorted, u32 count,
+                                                   u32 level_bits, const int* __restrict__ delta, const u32* __restrict__ src,
+                                                   u32* __restrict__ free_push) {
     const u32 q = blockIdx.x * 256 + threadIdx.x;
     if (q > count) return;
     if (q == count) { free_push[count] = 0; return; }
@@ -159,38 +196,55 @@ __global__ __launch_bounds__(256) void pair_kernel(const u32* __restrict__ key_s
         free_push[e] = taken ? 0u : 1u;
     } else {
         free_push[e] = 0;
-        if (key_sorted[q] != 0) permuted_table[src[e]] = st[src[ev_sorted[q - 1]]];
+        const u32 p = key_sorted[q] >> level_bits;
+        if ((key_sorted[q] & ((1u << level_bits) - 1u)) != 0 && q > 0) a.pt[p][src[e]] = a.st[p][src[ev_sorted[q - 1]]];
     }
 }
 
-// step 4: slot list (unmatched pops, then tail inputs) and value list (free pushes), then the fill
-__global__ __launch_bounds__(256) void gather_lists_kernel(u32 n, u32 count, const int* __restrict__ delta, const u32* __restrict__ src,
-                                                           const u32* __restrict__ empty_pop, const u32* __restrict__ empty_before,
-                                                           const u32* __restrict__ free_push, const u32* __restrict__ free_before,
-                                                           const u32* __restrict__ kind_in, const u32* __restrict__ tail_before,
-                                                           const u64* __restrict__ st, u32* __restrict__ slots, u64* __restrict__ values) {
-    const u32 t = blockIdx.x * 256 + threadIdx.x;
-    if (t < count) {
-        if (empty_pop[t]) slots[empty_before[t]] = src[t];
-        if (free_push[t]) values[free_before[t]] = st[src[t]];
+// step 4: slot list (unmatched pops, then tail inputs) and value list (free pushes) of every pair, then the fill.
+// ev_sc: exclusive scan of the events' flags (empty pops at [0, count], free pushes at [count + 1, 2 count + 1]).
+__global__ __launch_bounds__(256) void gather_lists_kernel(PairArgs a, u32 pairs, u32 n, u32 count, const u32* __restrict__ ev_base,
+                                                           const u32* __restrict__ src, const u32* __restrict__ ev_flags,
+                                                           const u32* __restrict__ ev_sc, const u32* __restrict__ flags,
+                                                           const u32* __restrict__ sc, u32* __restrict__ slots, u64* __restrict__ values) {
+    const u32 t = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y;
+    const u32 base = ev_base[p], mine = ev_base[p + 1] - base;
+    const u32* __restrict__ free_flags = ev_flags + count + 1;
+    const u32* __restrict__ free_sc = ev_sc + count + 1;
+    if (t < mine) {
+        const u32 g = base + t;
+        if (ev_flags[g]) { const u32 k = ev_sc[g] - ev_sc[base]; if (k < n) slots[(size_t)p * n + k] = src[g]; }
+        if (free_flags[g]) { const u32 k = free_sc[g] - free_sc[base]; if (k < n) values[(size_t)p * n + k] = a.st[p][src[g]]; }
     }
-    if (t < n && kind_in[t] == K_TAIL) slots[empty_before[count] + tail_before[t]] = t;
+    if (t < n && flags[flag_at(FL_TAIL, pairs, n, p, t)]) {
+        const u32 k = (ev_sc[base + mine] - ev_sc[base]) + before(sc, FL_TAIL, pairs, n, p, t);
+        if (k < n) slots[(size_t)p * n + k] = t;
+    }
 }
 
-__global__ __launch_bounds__(256) void fill_kernel(const u32* __restrict__ slots, const u64* __restrict__ values,
-                                                   const u32* __restrict__ free_total, u64* __restrict__ permuted_table) {
-    const u32 k = blockIdx.x * 256 + threadIdx.x;
-    if (k < *free_total) permuted_table[slots[k]] = values[k];
+__global__ __launch_bounds__(256) void fill_kernel(PairArgs a, u32 n, u32 count, const u32* __restrict__ ev_base, const u32* __restrict__ ev_sc,
+                                                   const u32* __restrict__ slots, const u64* __restrict__ values) {
+    const u32 k = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y;
+    const u32* __restrict__ free_sc = ev_sc + count + 1;
+    const u32 free_total = free_sc[ev_base[p + 1]] - free_sc[ev_base[p]];
+    if (k < n && k < free_total) {
+        const u32 slot = slots[(size_t)p * n + k];
+        if (slot < n) a.pt[p][slot] = values[(size_t)p * n + k];
+    }
 }
 
 inline unsigned blocks(size_t n) { return (unsigned)((n + 255) / 256); }
 
-void sort_u64(Scratch& mem, hipStream_t stream, const u64* in, u64* out, size_t n) {
-    size_t bytes = 0;
-    HIP_CHECK(rocprim::radix_sort_keys(nullptr, bytes, in, out, n, 0, 64, stream));
-    void* tmp = mem.alloc<unsigned char>(bytes);
-    HIP_CHECK(rocprim::radix_sort_keys(tmp, bytes, in, out, n, 0, 64, stream));
-}
+// radix sorts of one length share their temporary storage (everything runs on one stream)
+struct SortU64 {
+    size_t n, bytes = 0;
+    void* tmp = nullptr;
+    SortU64(Scratch& mem, hipStream_t stream, size_t n_) : n(n_) {
+        HIP_CHECK(rocprim::radix_sort_keys(nullptr, bytes, (const u64*)nullptr, (u64*)nullptr, n, 0, 64, stream));
+        tmp = mem.alloc<unsigned char>(bytes);
+    }
+    void run(hipStream_t stream, const u64* in, u64* out) { HIP_CHECK(rocprim::radix_sort_keys(tmp, bytes, in, out, n, 0, 64, stream)); }
+};
 
 template <typename T, typename Op>
 void scan_exclusive(Scratch& mem, hipStream_t stream, const T* in, T* out, T init, size_t n, Op op) {
@@ -199,92 +253,276 @@ void scan_exclusive(Scratch& mem, hipStream_t stream, const T* in, T* out, T ini
     void* tmp = mem.alloc<unsigned char>(bytes);
     HIP_CHECK(rocprim::exclusive_scan(tmp, bytes, in, out, init, n, op, stream));
 }
+// inclusive scan that starts again wherever the key changes
 template <typename T, typename Op>
-void scan_inclusive(Scratch& mem, hipStream_t stream, const T* in, T* out, size_t n, Op op) {
+void scan_inclusive_by_key(Scratch& mem, hipStream_t stream, const u32* keys, const T* in, T* out, size_t n, Op op) {
     size_t bytes = 0;
-    HIP_CHECK(rocprim::inclusive_scan(nullptr, bytes, in, out, n, op, stream));
+    HIP_CHECK(rocprim::inclusive_scan_by_key(nullptr, bytes, keys, in, out, n, op, rocprim::equal_to<u32>(), stream));
     void* tmp = mem.alloc<unsigned char>(bytes);
-    HIP_CHECK(rocprim::inclusive_scan(tmp, bytes, in, out, n, op, stream));
+    HIP_CHECK(rocprim::inclusive_scan_by_key(tmp, bytes, keys, in, out, n, op, rocprim::equal_to<u32>(), stream));
+}
+
+u32 bit_length(u64 v) { u32 b = 0; while (v) { b++; v >>= 1; } return b; }
+
+// One batch of at most kMaxBatch pairs of n rows.  tables[k]: the distinct table columns (any words), sorted once each;
+// table_of[p]: which of them pair p looks into.  Enqueued on the context's stream; `mem` is released by the caller.
+void permuted_batch(DeviceCtx* ctx, Scratch& mem, u32 n, const u64* const* tables, u32 n_tables, const PermutedPair* pairs_in,
+                    const u32* table_of, u32 pairs) {
+    hipStream_t stream = ctx->stream;
+    // ---- 1. canonical, sorted: every distinct table once, every pair's inputs into its permuted_inputs
+    u64* canon = mem.alloc<u64>((size_t)std::max(pairs, n_tables) * n);
+    u64* st = mem.alloc<u64>((size_t)n_tables * n);
+    SortU64 sort(mem, stream, n);
+    CanonArgs ca = {};
+    for (u32 k = 0; k < n_tables; k++) ca.src[k] = tables[k];
+    hipLaunchKernelGGL(canon_kernel, dim3(blocks(n), n_tables), dim3(256), 0, stream, ca, canon, n);
+    for (u32 k = 0; k < n_tables; k++) sort.run(stream, canon + (size_t)k * n, st + (size_t)k * n);
+    PairArgs a = {};
+    for (u32 p = 0; p < pairs; p++) {
+        ca.src[p] = pairs_in[p].inputs;
+        a.si[p] = pairs_in[p].permuted_inputs;
+        a.st[p] = st + (size_t)table_of[p] * n;
+        a.pt[p] = pairs_in[p].permuted_table;
+    }
+    hipLaunchKernelGGL(canon_kernel, dim3(blocks(n), pairs), dim3(256), 0, stream, ca, canon, n);
+    for (u32 p = 0; p < pairs; p++) sort.run(stream, canon + (size_t)p * n, pairs_in[p].permuted_inputs);
+    // ---- 2. classify, order the events
+    const size_t n_flags = (size_t)FL_CLASSES * pairs * (n + 1);
+    u32* flags = mem.alloc<u32>(n_flags);
+    u32* sc = mem.alloc<u32>(n_flags);
+    u32* other_in = mem.alloc<u32>((size_t)pairs * n);
+    u32* other_tab = mem.alloc<u32>((size_t)pairs * n);
+    u32* ev_base = mem.alloc<u32>(kMaxBatch + 1);
+    hipLaunchKernelGGL(classify_kernel, dim3(blocks(2 * (size_t)n), pairs), dim3(256), 0, stream, a, pairs, n, flags, other_in, other_tab);
+    scan_exclusive(mem, stream, flags, sc, 0u, n_flags, rocprim::plus<u32>());
+    hipLaunchKernelGGL(event_base_kernel, dim3(1), dim3(64), 0, stream, sc, pairs, n, ev_base);
+    u32 base_host[kMaxBatch + 1];
+    HIP_CHECK(hipMemcpyAsync(base_host, ev_base, (pairs + 1) * sizeof(u32), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    const u32 count = base_host[pairs];
+    if (count == 0) return;        // every input found its table entry: no push, hence nothing left to place
+    u32 most = 0;
+    for (u32 p = 0; p < pairs; p++) most = std::max(most, base_host[p + 1] - base_host[p]);
+    // ---- 3. the stack, as bracket matching
+    const u32 level_bits = bit_length(2 * (u64)n), pair_bits = bit_length(pairs - 1);
+    int* delta = mem.alloc<int>(count);
+    u32* src = mem.alloc<u32>(count);
+    u32* ev_pair = mem.alloc<u32>(count);
+    int* s = mem.alloc<int>(count);
+    int* runmin = mem.alloc<int>(count);
+    int* clamped = mem.alloc<int>(count);
+    u32* key = mem.alloc<u32>(count);
+    u32* ident = mem.alloc<u32>(count);
+    u32* key_sorted = mem.alloc<u32>(count);
+    u32* ev_sorted = mem.alloc<u32>(count);
+    u32* ev_flags = mem.alloc<u32>(2 * ((size_t)count + 1));
+    u32* ev_sc = mem.alloc<u32>(2 * ((size_t)count + 1));
+    hipLaunchKernelGGL(place_events_kernel, dim3(blocks(2 * (size_t)n), pairs), dim3(256), 0, stream, pairs, n, flags, sc, other_in, other_tab,
+                       ev_base, delta, src, ev_pair);
+    scan_inclusive_by_key(mem, stream, ev_pair, delta, s, count, rocprim::plus<int>());
+    hipLaunchKernelGGL(clamp_min_kernel, dim3(blocks(count)), dim3(256), 0, stream, s, count, clamped);
+    scan_inclusive_by_key(mem, stream, ev_pair, clamped, runmin, count, rocprim::minimum<int>());
+    hipLaunchKernelGGL(level_kernel, dim3(blocks((size_t)count + 1)), dim3(256), 0, stream, delta, s, runmin, ev_pair, ev_base, count, level_bits,
+                       key, ident, ev_flags);
+    {
+        size_t bytes = 0;
+        HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, key, key_sorted, ident, ev_sorted, count, 0, level_bits + pair_bits, stream));
+        void* tmp = mem.alloc<unsigned char>(bytes);
+        HIP_CHECK(rocprim::radix_sort_pairs(tmp, bytes, key, key_sorted, ident, ev_sorted, count, 0, level_bits + pair_bits, stream));
+    }
+    hipLaunchKernelGGL(pair_kernel, dim3(blocks((size_t)count + 1)), dim3(256), 0, stream, a, key_sorted, ev_sorted, count, level_bits, delta, src,
+                       ev_flags + count + 1);
+    scan_exclusive(mem, stream, ev_flags, ev_sc, 0u, 2 * ((size_t)count + 1), rocprim::plus<u32>());
+    // ---- 4. leftovers
+    u32* slots = mem.alloc<u32>((size_t)pairs * n);
+    u64* values = mem.alloc<u64>((size_t)pairs * n);
+    // both lists of a pair have free_total entries (two columns of one height: the loop ends with as many open slots as unused
+    // values); the kernels bound every index by n all the same, a compare per store
+    hipLaunchKernelGGL(gather_lists_kernel, dim3(blocks(std::max<size_t>(n, most)), pairs), dim3(256), 0, stream, a, pairs, n, count, ev_base, src,
+                       ev_flags, ev_sc, flags, sc, slots, values);
+    hipLaunchKernelGGL(fill_kernel, dim3(blocks(n), pairs), dim3(256), 0, stream, a, n, count, ev_base, ev_sc, slots, values);
 }
 
 }  // namespace
 
-void permuted_cols_dev(DeviceCtx* ctx, const u64* inputs, const u64* table, size_t n_, u64* permuted_inputs, u64* permuted_table) {
-    if (n_ == 0) return;
+void permuted_cols_batch_dev(DeviceCtx* ctx, size_t n_, const u64* const* tables, size_t n_tables, const PermutedPair* pairs, size_t n_pairs) {
+    if (n_ == 0 || n_pairs == 0) return;
     if (n_ >= ((size_t)1 << 30)) throw OlaError(-2, "permuted_cols: more than 2^30 rows");
     const u32 n = (u32)n_;
-    hipStream_t stream = ctx->stream;
-    Scratch mem(ctx);
-    // ---- 1. canonical, sorted
-    u64* canon = mem.alloc<u64>(n);
-    u64* st = mem.alloc<u64>(n);
-    u64* si = permuted_inputs;
-    hipLaunchKernelGGL(canon_kernel, dim3(blocks(n)), dim3(256), 0, stream, inputs, canon, n);
-    sort_u64(mem, stream, canon, si, n);
-    hipLaunchKernelGGL(canon_kernel, dim3(blocks(n)), dim3(256), 0, stream, table, canon, n);
-    sort_u64(mem, stream, canon, st, n);
-    // ---- 2. classify, order the events
-    u32* kind_in = mem.alloc<u32>(n);
-    u32* kind_tab = mem.alloc<u32>(n);
-    u32* other_in = mem.alloc<u32>(n);
-    u32* other_tab = mem.alloc<u32>(n);
-    hipLaunchKernelGGL(classify_kernel, dim3(blocks(2 * (size_t)n)), dim3(256), 0, stream, si, st, n, kind_in, kind_tab, other_in, other_tab,
-                       permuted_table);
-    u32* flag = mem.alloc<u32>(n + 1);
-    u32* pop_before = mem.alloc<u32>(n + 1);
-    u32* push_before = mem.alloc<u32>(n + 1);
-    u32* tail_before = mem.alloc<u32>(n + 1);
-    hipLaunchKernelGGL(flag_kernel, dim3(blocks(n + 1)), dim3(256), 0, stream, kind_in, n, (u32)K_EVENT, flag);
-    scan_exclusive(mem, stream, flag, pop_before, 0u, n + 1, rocprim::plus<u32>());
-    hipLaunchKernelGGL(flag_kernel, dim3(blocks(n + 1)), dim3(256), 0, stream, kind_tab, n, (u32)K_EVENT, flag);
-    scan_exclusive(mem, stream, flag, push_before, 0u, n + 1, rocprim::plus<u32>());
-    hipLaunchKernelGGL(flag_kernel, dim3(blocks(n + 1)), dim3(256), 0, stream, kind_in, n, (u32)K_TAIL, flag);
-    scan_exclusive(mem, stream, flag, tail_before, 0u, n + 1, rocprim::plus<u32>());
-    u32 totals[2];
-    HIP_CHECK(hipMemcpyAsync(&totals[0], pop_before + n, 4, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipMemcpyAsync(&totals[1], push_before + n, 4, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    const u32 count = totals[0] + totals[1];
-    // ---- 3. the stack, as bracket matching
-    int* delta = mem.alloc<int>(count + 1);
-    u32* src = mem.alloc<u32>(count + 1);
-    u32* empty_pop = mem.alloc<u32>(count + 1);
-    u32* empty_before = mem.alloc<u32>(count + 1);
-    u32* free_push = mem.alloc<u32>(count + 1);
-    u32* free_before = mem.alloc<u32>(count + 1);
-    if (count) {
-        int* s = mem.alloc<int>(count);
-        int* runmin = mem.alloc<int>(count);
-        int* clamped = mem.alloc<int>(count);
-        u32* key = mem.alloc<u32>(count);
-        u32* ident = mem.alloc<u32>(count);
-        u32* key_sorted = mem.alloc<u32>(count);
-        u32* ev_sorted = mem.alloc<u32>(count);
-        hipLaunchKernelGGL(place_events_kernel, dim3(blocks(2 * (size_t)n)), dim3(256), 0, stream, n, kind_in, kind_tab, other_in, other_tab,
-                           pop_before, push_before, delta, src);
-        scan_inclusive(mem, stream, delta, s, count, rocprim::plus<int>());
-        hipLaunchKernelGGL(clamp_min_kernel, dim3(blocks(count)), dim3(256), 0, stream, s, count, clamped);
-        scan_inclusive(mem, stream, clamped, runmin, count, rocprim::minimum<int>());
-        hipLaunchKernelGGL(level_kernel, dim3(blocks(count + 1)), dim3(256), 0, stream, delta, s, runmin, count, key, ident, empty_pop);
-        size_t bytes = 0;
-        HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, key, key_sorted, ident, ev_sorted, count, 0, 32, stream));
-        void* tmp = mem.alloc<unsigned char>(bytes);
-        HIP_CHECK(rocprim::radix_sort_pairs(tmp, bytes, key, key_sorted, ident, ev_sorted, count, 0, 32, stream));
-        hipLaunchKernelGGL(pair_kernel, dim3(blocks(count + 1)), dim3(256), 0, stream, key_sorted, ev_sorted, count, delta, src, st,
-                           permuted_table, free_push);
-    } else {
-        HIP_CHECK(hipMemsetAsync(empty_pop, 0, 4, stream));
-        HIP_CHECK(hipMemsetAsync(free_push, 0, 4, stream));
+    for (size_t p = 0; p < n_pairs; p++)
+        if (pairs[p].table >= n_tables) throw OlaError(-1, "permuted_cols: a pair names a table beyond the list");
+    // a group: as many pairs as the kernel argument holds, the level key has bits for and the 32-bit prefix sums can count
+    const u32 level_bits = bit_length(2 * (u64)n);
+    size_t group = kMaxBatch;
+    while (group > 1 && (bit_length(group - 1) + level_bits > 32 || (size_t)FL_CLASSES * group * ((size_t)n + 1) >= ((size_t)1 << 32))) group >>= 1;
+    for (size_t first = 0; first < n_pairs; first += group) {
+        const u32 count = (u32)std::min(group, n_pairs - first);
+        // the distinct tables of this group
+        const u64* tabs[kMaxBatch];
+        u32 table_of[kMaxBatch], n_tabs = 0;
+        for (u32 p = 0; p < count; p++) {
+            const u64* t = tables[pairs[first + p].table];
+            u32 k = 0;
+            while (k < n_tabs && tabs[k] != t) k++;
+            if (k == n_tabs) tabs[n_tabs++] = t;
+            table_of[p] = k;
+        }
+        Scratch mem(ctx);
+        permuted_batch(ctx, mem, n, tabs, n_tabs, pairs + first, table_of, count);
+        HIP_CHECK(hipGetLastError());
     }
-    scan_exclusive(mem, stream, empty_pop, empty_before, 0u, count + 1, rocprim::plus<u32>());
-    scan_exclusive(mem, stream, free_push, free_before, 0u, count + 1, rocprim::plus<u32>());
-    // ---- 4. leftovers
-    u32* slots = mem.alloc<u32>(n);
-    u64* values = mem.alloc<u64>(n);
-    hipLaunchKernelGGL(gather_lists_kernel, dim3(blocks(std::max<size_t>(n, count))), dim3(256), 0, stream, n, count, delta, src, empty_pop,
-                       empty_before, free_push, free_before, kind_in, tail_before, st, slots, values);
-    hipLaunchKernelGGL(fill_kernel, dim3(blocks(n)), dim3(256), 0, stream, slots, values, free_before + count, permuted_table);
-    HIP_CHECK(hipGetLastError());
+}
+
+void permuted_cols_dev(DeviceCtx* ctx, const u64* inputs, const u64* table, size_t n, u64* permuted_inputs, u64* permuted_table) {
+    const PermutedPair pair = {inputs, 0, permuted_inputs, permuted_table};
+    permuted_cols_batch_dev(ctx, n, &table, 1, &pair, 1);
+}
+
+// ------------------------------------------------------------------------------------------------ table generators
+// The range-check, bitwise and program tables from their primary columns (generation/builtin.rs:35-206, 249-316,
+// generation/prog.rs:18-156): one fill kernel per table writes every column that is not a permuted one -- thread = row, so
+// every column is stored along rows, and rows beyond the live inputs get their zeros in the same pass -- then the table's
+// lookup pairs go through one batch of permuted_cols, straight into their columns of `out`.
+namespace {
+
+namespace tg = olatg;
+
+__global__ __launch_bounds__(256) void rc_fill_kernel(const u64* __restrict__ vals, const u64* __restrict__ filters, u32 n_rows, u32 range_bits,
+                                                      u32 n, u64* __restrict__ out) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const bool live = i < n_rows;
+    const u64 v = live ? gl_canon(vals[i]) : 0;
+    const u32 filter_cols[4] = {tg::RC_CPU_FILTER, tg::RC_MEMORY_SORT_FILTER, tg::RC_MEMORY_REGION_FILTER, tg::RC_CMP_FILTER};
+#pragma unroll
+    for (u32 k = 0; k < 4; k++) out[(size_t)filter_cols[k] * n + i] = (live && filters) ? gl_canon(filters[(size_t)k * n_rows + i]) : 0;
+    const u64 top = ((u64)1 << range_bits) - 1;
+    out[(size_t)tg::RC_VAL * n + i] = v;
+    out[(size_t)tg::RC_LIMB_LO * n + i] = v & top;
+    out[(size_t)tg::RC_LIMB_HI * n + i] = v >> range_bits;
+    out[(size_t)tg::RC_FIX_RANGE_CHECK_U16 * n + i] = i < top ? i : top;
+}
+
+__device__ __forceinline__ u64 compress4(u64 tag, u64 a, u64 b, u64 c, u64 beta) {
+    return gl_add(gl_mul(gl_add(gl_mul(gl_add(gl_mul(c, beta), b), beta), a), beta), tag);     // tag + a B + b B^2 + c B^3
+}
+
+// ops: filter, tag, op0, op1, res (n_ops each).  skip_limb3: the reference's generator leaves the three limb-3 columns zero.
+__global__ __launch_bounds__(256) void bitwise_fill_kernel(const u64* __restrict__ ops, u32 n_ops, u32 limb_bits, u64 beta, u32 skip_limb3,
+                                                           u32 n, u64* __restrict__ out) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const bool live = i < n_ops;
+    const u64 mask = ((u64)1 << limb_bits) - 1;
+    u64 w[5];
+#pragma unroll
+    for (u32 k = 0; k < 5; k++) w[k] = live ? gl_canon(ops[(size_t)k * n_ops + i]) : 0;
+    out[(size_t)tg::BW_FILTER * n + i] = w[0];
+    out[(size_t)tg::BW_TAG * n + i] = w[1];
+    out[(size_t)tg::BW_OP0 * n + i] = w[2];
+    out[(size_t)tg::BW_OP1 * n + i] = w[3];
+    out[(size_t)tg::BW_RES * n + i] = w[4];
+#pragma unroll
+    for (u32 l = 0; l < 4; l++) {
+        const bool keep = !(skip_limb3 && l == 3);
+        const u64 a = keep ? (w[2] >> (limb_bits * l)) & mask : 0;
+        const u64 b = keep ? (w[3] >> (limb_bits * l)) & mask : 0;
+        const u64 c = keep ? (w[4] >> (limb_bits * l)) & mask : 0;
+        out[(size_t)(tg::BW_OP0_LIMBS_START + l) * n + i] = a;
+        out[(size_t)(tg::BW_OP1_LIMBS_START + l) * n + i] = b;
+        out[(size_t)(tg::BW_RES_LIMBS_START + l) * n + i] = c;
+        out[(size_t)(tg::BW_COMPRESS_LIMBS_START + l) * n + i] = compress4(w[1], a, b, c, beta);
+    }
+    // the fixed tables: 0 .. 2^limb_bits - 1 then zeros; AND, OR, XOR of every operand pair, one operation after the other
+    const u64 per = (u64)1 << (2 * limb_bits);
+    const u32 which = (u32)(i / per);
+    const u64 index = i % per;
+    const bool fixed = which < 3;
+    const u64 x = fixed ? index >> limb_bits : 0, y = fixed ? index & mask : 0;
+    const u64 z = !fixed ? 0 : which == 0 ? (x & y) : which == 1 ? (x | y) : (x ^ y);
+    const u64 tag = !fixed ? 0 : which == 0 ? tg::OP_MASK_AND : which == 1 ? tg::OP_MASK_OR : tg::OP_MASK_XOR;
+    out[(size_t)tg::BW_FIX_RANGE_CHECK_U8 * n + i] = i <= mask ? i : 0;
+    out[(size_t)tg::BW_FIX_TAG * n + i] = tag;
+    out[(size_t)tg::BW_FIX_BITWSIE_OP0 * n + i] = x;
+    out[(size_t)tg::BW_FIX_BITWSIE_OP1 * n + i] = y;
+    out[(size_t)tg::BW_FIX_BITWSIE_RES * n + i] = z;
+    out[(size_t)tg::BW_FIX_COMPRESS * n + i] = compress4(tag, x, y, z, beta);
+}
+
+// side: a0 .. a3, pc, inst, filter (n each) -> its six data columns, its compress column, its filter column
+__device__ __forceinline__ void prog_side(const u64* __restrict__ side, u32 i, u32 n, u64 beta, u32 addr_start, u32 pc_col, u32 inst_col,
+                                          u32 comp_col, u32 filter_col, u64* __restrict__ out) {
+    u64 w[7];
+#pragma unroll
+    for (u32 k = 0; k < 7; k++) w[k] = gl_canon(side[(size_t)k * n + i]);
+#pragma unroll
+    for (u32 k = 0; k < 4; k++) out[(size_t)(addr_start + k) * n + i] = w[k];
+    out[(size_t)pc_col * n + i] = w[4];
+    out[(size_t)inst_col * n + i] = w[5];
+    out[(size_t)filter_col * n + i] = w[6];
+    u64 acc = w[5];                                     // a0 + a1 B + a2 B^2 + a3 B^3 + pc B^4 + inst B^5
+#pragma unroll
+    for (int k = 4; k >= 0; k--) acc = gl_add(gl_mul(acc, beta), w[k]);
+    out[(size_t)comp_col * n + i] = acc;
+}
+__global__ __launch_bounds__(256) void prog_fill_kernel(const u64* __restrict__ exec, const u64* __restrict__ prog, u32 n, u64 beta,
+                                                        u64* __restrict__ out) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    prog_side(exec, i, n, beta, tg::COL_PROG_EXEC_CODE_ADDR_RANGE_START, tg::COL_PROG_EXEC_PC, tg::COL_PROG_EXEC_INST, tg::COL_PROG_EXEC_COMP_PROG,
+              tg::COL_PROG_FILTER_EXEC, out);
+    prog_side(prog, i, n, beta, tg::COL_PROG_CODE_ADDR_RANGE_START, tg::COL_PROG_PC, tg::COL_PROG_INST, tg::COL_PROG_COMP_PROG,
+              tg::COL_PROG_FILTER_PROG_CHUNK, out);
+}
+
+u32 log2_rows(u64 rows) {            // next power of two, at least 2 (the reference's ext_trace_len)
+    u32 log_n = 1;
+    while (((u64)1 << log_n) < rows) log_n++;
+    return log_n;
+}
+
+}  // namespace
+
+u32 rc_trace_log_n(u64 n_rows, u32 range_bits) { return log2_rows(std::max<u64>(n_rows, (u64)1 << range_bits)); }
+u32 bitwise_trace_log_n(u64 n_ops, u32 limb_bits) { return log2_rows(std::max<u64>(n_ops, std::max<u64>((u64)1 << limb_bits, (u64)3 << (2 * limb_bits)))); }
+
+void generate_rc_trace_dev(DeviceCtx* ctx, const u64* vals, const u64* filters, size_t n_rows, u32 range_bits, u64* out) {
+    const u32 n = 1u << rc_trace_log_n(n_rows, range_bits);
+    hipLaunchKernelGGL(rc_fill_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, vals, filters, (u32)n_rows, range_bits, n, out);
+    const u64* table = out + (size_t)tg::RC_FIX_RANGE_CHECK_U16 * n;
+    const PermutedPair pairs[2] = {
+        {out + (size_t)tg::RC_LIMB_LO * n, 0, out + (size_t)tg::RC_LIMB_LO_PERMUTED * n, out + (size_t)tg::RC_FIX_RANGE_CHECK_U16_PERMUTED_LO * n},
+        {out + (size_t)tg::RC_LIMB_HI * n, 0, out + (size_t)tg::RC_LIMB_HI_PERMUTED * n, out + (size_t)tg::RC_FIX_RANGE_CHECK_U16_PERMUTED_HI * n}};
+    permuted_cols_batch_dev(ctx, n, &table, 1, pairs, 2);
+}
+
+void generate_bitwise_trace_dev(DeviceCtx* ctx, const u64* ops, size_t n_ops, u32 limb_bits, u64 beta, bool reference_quirks, u64* out) {
+    const u32 n = 1u << bitwise_trace_log_n(n_ops, limb_bits);
+    hipLaunchKernelGGL(bitwise_fill_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, ops, (u32)n_ops, limb_bits, gl_canon(beta),
+                       reference_quirks ? 1u : 0u, n, out);
+    auto col = [&](u32 c) { return out + (size_t)c * n; };
+    const u64* tables[2] = {col(tg::BW_FIX_RANGE_CHECK_U8), col(tg::BW_FIX_COMPRESS)};
+    PermutedPair pairs[16];
+    // generation/builtin.rs:161-195: limb l of op0 / op1 / res against the range table (permuted table columns l, 4 + l, 8 + l), its
+    // compress column against the compressed operation table
+    const u32 limb_cols[3][2] = {{tg::BW_OP0_LIMBS_START, tg::BW_OP0_LIMBS_PERMUTED_START}, {tg::BW_OP1_LIMBS_START, tg::BW_OP1_LIMBS_PERMUTED_START},
+                                 {tg::BW_RES_LIMBS_START, tg::BW_RES_LIMBS_PERMUTED_START}};
+    u32 k = 0;
+    for (u32 g = 0; g < 3; g++)
+        for (u32 l = 0; l < 4; l++)
+            pairs[k++] = {col(limb_cols[g][0] + l), 0, col(limb_cols[g][1] + l), col(tg::BW_FIX_RANGE_CHECK_U8_PERMUTED_START + 4 * g + l)};
+    for (u32 l = 0; l < 4; l++)
+        pairs[k++] = {col(tg::BW_COMPRESS_LIMBS_START + l), 1, col(tg::BW_COMPRESS_PERMUTED_START + l), col(tg::BW_FIX_COMPRESS_PERMUTED_START + l)};
+    permuted_cols_batch_dev(ctx, n, tables, 2, pairs, 16);
+}
+
+void generate_prog_trace_dev(DeviceCtx* ctx, const u64* exec, const u64* prog, u32 log_n, u64 beta, u64* out) {
+    const u32 n = 1u << log_n;
+    hipLaunchKernelGGL(prog_fill_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, exec, prog, n, gl_canon(beta), out);
+    const u64* table = out + (size_t)tg::COL_PROG_COMP_PROG * n;
+    const PermutedPair pair = {out + (size_t)tg::COL_PROG_EXEC_COMP_PROG * n, 0, out + (size_t)tg::COL_PROG_EXEC_COMP_PROG_PERM * n,
+                               out + (size_t)tg::COL_PROG_COMP_PROG_PERM * n};
+    permuted_cols_batch_dev(ctx, n, &table, 1, &pair, 1);
 }
 
 }  // namespace ola

@@ -18,6 +18,7 @@
 #include "gl.cuh"
 #include "poseidon_host.h"
 #include "lookup.h"
+#include "tablegen_columns.h"
 #include "peer_group.h"
 #include "rccl_carrier.h"
 
@@ -1211,6 +1212,104 @@ int32_t ola_permuted_cols(OlaCtx* ctx, const uint64_t* inputs, const uint64_t* t
     HIP_CHECK(hipMemcpyAsync(permuted_inputs, d + 2 * n, n * 8, hipMemcpyDeviceToHost, ctx->dev.stream));
     HIP_CHECK(hipMemcpyAsync(permuted_table, d + 3 * n, n * 8, hipMemcpyDeviceToHost, ctx->dev.stream));
     HIP_CHECK(hipStreamSynchronize(ctx->dev.stream));
+    OLA_CATCH
+}
+
+// ---- whole tables from their primary columns (lookup.hip) ----
+// device memory must be the context's GPU's: the kernels run there
+static bool pointer_on_device(OlaCtx* ctx, const void* p) {
+    int device = -1;
+    if (!is_device_pointer(p, &device)) return false;
+    require(device == ctx->dev.device, "a device buffer is not memory of the context's GPU");
+    return true;
+}
+// a context cannot exist without a device: say so rather than "null pointer" (there is no CPU fallback)
+static void require_context(OlaCtx* ctx) {
+    if (ctx) return;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        (void)hipGetLastError();
+        throw OlaError(OLA_E_NO_DEVICE, "no HIP device visible (the backend has no CPU fallback)");
+    }
+    require(false, "ctx is NULL");
+}
+// input of `words` words wherever the caller has it -> device memory (a copy on the context's stream when it is host memory)
+static const u64* table_input(OlaCtx* ctx, DevBuf& mem, const uint64_t* src, size_t words) {
+    if (!src || words == 0 || pointer_on_device(ctx, src)) return (const u64*)src;
+    u64* d = mem.alloc(words);
+    HIP_CHECK(hipMemcpyAsync(d, src, words * 8, hipMemcpyHostToDevice, ctx->dev.stream));
+    return d;
+}
+// the generated table: in place when `out` is device memory, else through a device buffer
+struct TableOutput {
+    OlaCtx* ctx;
+    uint64_t* out;
+    u64* dev;
+    size_t words;
+    TableOutput(OlaCtx* c, DevBuf& mem, uint64_t* out_, size_t words_) : ctx(c), out(out_), words(words_) {
+        dev = pointer_on_device(ctx, out) ? (u64*)out : mem.alloc(words);
+    }
+    void finish() {
+        if (dev != (u64*)out) HIP_CHECK(hipMemcpyAsync(out, dev, words * 8, hipMemcpyDeviceToHost, ctx->dev.stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->dev.stream));
+    }
+};
+
+int32_t ola_generate_rc_trace(OlaCtx* ctx, const uint64_t* vals, const uint64_t* filters, size_t n_rows, uint32_t range_bits, uint64_t* out,
+                              uint32_t* log_n_out) {
+    OLA_TRY
+    require(log_n_out, "null pointer");
+    require(range_bits >= 1 && range_bits <= 24, "range_bits out of range (1 .. 24)");
+    require(n_rows <= ((size_t)1 << 28), "more than 2^28 rows");
+    *log_n_out = rc_trace_log_n(n_rows, range_bits);
+    if (!out) return OLA_OK;       // the sizing call
+    require(vals || n_rows == 0, "null pointer");
+    require_context(ctx);
+    OLA_ON_DEVICE(ctx);
+    const size_t n = (size_t)1 << *log_n_out;
+    DevBuf mem(&ctx->dev);
+    const u64* d_vals = table_input(ctx, mem, vals, n_rows);
+    const u64* d_filters = table_input(ctx, mem, filters, 4 * n_rows);
+    TableOutput t(ctx, mem, out, (size_t)olatg::COL_NUM_RC * n);
+    generate_rc_trace_dev(&ctx->dev, d_vals, d_filters, n_rows, range_bits, t.dev);
+    t.finish();
+    OLA_CATCH
+}
+
+int32_t ola_generate_bitwise_trace(OlaCtx* ctx, const uint64_t* ops, size_t n_ops, uint32_t limb_bits, uint64_t beta, uint32_t flags,
+                                   uint64_t* out, uint32_t* log_n_out) {
+    OLA_TRY
+    require(log_n_out, "null pointer");
+    require(limb_bits >= 1 && limb_bits <= 12, "limb_bits out of range (1 .. 12)");
+    require((flags & ~(uint32_t)OLA_TABLEGEN_REFERENCE_QUIRKS) == 0, "unknown flag");
+    require(n_ops <= ((size_t)1 << 26), "more than 2^26 operations");
+    *log_n_out = bitwise_trace_log_n(n_ops, limb_bits);
+    if (!out) return OLA_OK;       // the sizing call
+    require(ops || n_ops == 0, "null pointer");
+    require_context(ctx);
+    OLA_ON_DEVICE(ctx);
+    const size_t n = (size_t)1 << *log_n_out;
+    DevBuf mem(&ctx->dev);
+    const u64* d_ops = table_input(ctx, mem, ops, 5 * n_ops);
+    TableOutput t(ctx, mem, out, (size_t)olatg::COL_NUM_BITWISE * n);
+    generate_bitwise_trace_dev(&ctx->dev, d_ops, n_ops, limb_bits, beta, (flags & OLA_TABLEGEN_REFERENCE_QUIRKS) != 0, t.dev);
+    t.finish();
+    OLA_CATCH
+}
+
+int32_t ola_generate_prog_trace(OlaCtx* ctx, const uint64_t* exec, const uint64_t* prog, uint32_t log_n, uint64_t beta, uint64_t* out) {
+    OLA_TRY
+    require(exec && prog && out, "null pointer");
+    require(log_n >= 1 && log_n <= 26, "log_n out of range (1 .. 26)");
+    require_context(ctx);
+    OLA_ON_DEVICE(ctx);
+    const size_t n = (size_t)1 << log_n;
+    DevBuf mem(&ctx->dev);
+    const u64* d_exec = table_input(ctx, mem, exec, 7 * n);
+    const u64* d_prog = table_input(ctx, mem, prog, 7 * n);
+    TableOutput t(ctx, mem, out, (size_t)olatg::NUM_PROG_COLS * n);
+    generate_prog_trace_dev(&ctx->dev, d_exec, d_prog, log_n, beta, t.dev);
+    t.finish();
     OLA_CATCH
 }
 

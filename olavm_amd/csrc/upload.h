@@ -184,11 +184,6 @@ class TraceUploader {
         if (!e || !*e) return dflt;
         return std::max(lo, std::min(hi, atoi(e)));
     }
-    static bool is_device_pointer(const void* p) {
-        hipPointerAttribute_t a;
-        if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // plain malloc memory: "invalid value"
-        return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-    }
     void plan() {
         if (order_.size() != jobs_.size()) { order_.resize(jobs_.size()); for (size_t t = 0; t < jobs_.size(); t++) order_[t] = t; }
         for (size_t t : order_) {

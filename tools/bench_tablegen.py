@@ -1,0 +1,252 @@
+"""Times ola_generate_rc_trace / ola_generate_bitwise_trace / ola_generate_prog_trace with resident inputs and outputs, next to
+the same derived columns obtained without them: one ola_permuted_cols_dev call per pair (device) plus numpy for the other columns
+(host), and next to the oracle's sequential permuted_cols on one host core (as tools/bench_lookup.py measures it).
+
+    python tools/bench_tablegen.py [--runs 7] [--json out.json] [--skip-launches] [case ...]     # cases: bitwise:18 rc:16 rc:21 prog:20 prog:23
+
+Device times: two events on the context's stream around the whole call (the call synchronises inside), median of --runs after a
+warm-up.  Wall times: time.perf_counter around the same calls.  Launch counts: the kernel-trace rows of a child process that makes
+two calls minus those of one that makes one (rocprofv3 --kernel-trace; `--child` is that process)."""
+import argparse
+import csv
+import glob
+import json
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+
+from olavm_amd.air import ola_tables as T
+from olavm_amd.air.dsl import P
+
+CASES = ["bitwise:18", "rc:16", "rc:21", "prog:20", "prog:23"]
+FN = (lambda x, y: x & y, lambda x, y: x | y, lambda x, y: x ^ y)
+
+
+def inputs(kind, log_n, rng):
+    """-> (primary inputs as numpy arrays, keyword arguments) of a table that fills 2^log_n rows"""
+    n = 1 << log_n
+    if kind == "rc":
+        rows = n if log_n > 16 else n // 2
+        vals = rng.integers(0, 1 << 32, rows, dtype=np.uint64)
+        vals[: rows // 4] = rng.integers(0, 50, rows // 4)             # small values dominate, as with real range checks
+        return (vals, rng.integers(0, 2, (4, rows), dtype=np.uint64)), {"range_bits": 16}
+    if kind == "bitwise":
+        rows = n // 2
+        which = rng.integers(0, 3, rows)
+        x, y = rng.integers(0, 1 << 32, rows, dtype=np.uint64), rng.integers(0, 1 << 32, rows, dtype=np.uint64)
+        res = np.choose(which, [x & y, x | y, x ^ y])
+        tag = np.array([T.op_mask("AND"), T.op_mask("OR"), T.op_mask("XOR")], dtype=np.uint64)[which]
+        return (np.stack([np.ones(rows, dtype=np.uint64), tag, x, y, res]),), {"limb_bits": 8, "beta": 0x123456789ABCDEF}
+    listed = 3 * n // 4
+    pr = np.zeros((7, n), dtype=np.uint64)
+    pr[:4, :listed] = rng.integers(0, P, (4, 1), dtype=np.uint64)
+    pr[4, :listed] = np.arange(listed, dtype=np.uint64)
+    pr[5, :listed] = rng.integers(0, P, listed, dtype=np.uint64)
+    pr[6, :listed] = 1
+    ex = np.ascontiguousarray(pr[:, rng.integers(0, listed // 2, n)])
+    return (ex, pr), {"beta": 0x123456789ABCDEF}
+
+
+def to_dev(a):
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
+    torch.cuda.synchronize()           # complete before the library's stream reads it
+    return t
+
+
+def call(be, kind, dev, kw, out):
+    if kind == "rc":
+        return be.generate_rc_trace(dev[0], dev[1], range_bits=kw["range_bits"], out=out)
+    if kind == "bitwise":
+        return be.generate_bitwise_trace(dev[0], kw["beta"], limb_bits=kw["limb_bits"], out=out)
+    return be.generate_prog_trace(dev[0], dev[1], kw["beta"], out=out)
+
+
+NCOLS = {"rc": T.COL_NUM_RC, "bitwise": T.COL_NUM_BITWISE, "prog": T.NUM_PROG_COLS}
+
+
+def pairs_of(kind):
+    """(input column, table column, permuted input column, permuted table column) of every lookup pair of the table"""
+    if kind == "rc":
+        return [(T.RC_LIMB_LO, T.RC_FIX_RANGE_CHECK_U16, T.RC_LIMB_LO_PERMUTED, T.RC_FIX_RANGE_CHECK_U16_PERMUTED_LO),
+                (T.RC_LIMB_HI, T.RC_FIX_RANGE_CHECK_U16, T.RC_LIMB_HI_PERMUTED, T.RC_FIX_RANGE_CHECK_U16_PERMUTED_HI)]
+    if kind == "prog":
+        return [(T.COL_PROG_EXEC_COMP_PROG, T.COL_PROG_COMP_PROG, T.COL_PROG_EXEC_COMP_PROG_PERM, T.COL_PROG_COMP_PROG_PERM)]
+    out = []
+    for g, (src, perm) in enumerate(((T.BW_OP0_LIMBS, T.BW_OP0_LIMBS_PERMUTED), (T.BW_OP1_LIMBS, T.BW_OP1_LIMBS_PERMUTED), (T.BW_RES_LIMBS, T.BW_RES_LIMBS_PERMUTED))):
+        out += [(src.start + i, T.BW_FIX_RANGE_CHECK_U8, perm.start + i, T.BW_FIX_RANGE_CHECK_U8_PERMUTED.start + 4 * g + i) for i in range(4)]
+    return out + [(T.BW_COMPRESS_LIMBS.start + i, T.BW_FIX_COMPRESS, T.BW_COMPRESS_PERMUTED.start + i, T.BW_FIX_COMPRESS_PERMUTED.start + i) for i in range(4)]
+
+
+def host_columns(kind, host, kw, n):
+    """the non-permuted derived columns with numpy, the way a host without the entry points fills them (wall seconds)"""
+    t0 = time.perf_counter()
+    if kind == "rc":
+        vals = host[0]
+        lo, hi = vals & np.uint64(0xFFFF), vals >> np.uint64(16)
+        fix = np.minimum(np.arange(n, dtype=np.uint64), np.uint64(0xFFFF))
+        keep = (lo, hi, fix)
+    else:
+        b = kw["beta"] % P
+        pw = [pow(b, k, P) for k in range(6)]
+        if kind == "prog":
+            keep = []
+            for side in host:
+                acc = np.zeros(n, dtype=object)
+                for k in range(6):
+                    acc = acc + side[k].astype(object) * pw[k]
+                keep.append((acc % P).astype(np.uint64))
+        else:
+            ops = host[0]
+            keep = []
+            for i in range(4):
+                limbs = [(ops[k] >> np.uint64(8 * i)) & np.uint64(255) for k in (2, 3, 4)]
+                acc = ops[1].astype(object) + limbs[0].astype(object) * pw[1] + limbs[1].astype(object) * pw[2] + limbs[2].astype(object) * pw[3]
+                keep += limbs + [(acc % P).astype(np.uint64)]
+            idx = np.arange(1 << 16, dtype=np.uint64)
+            x, y = idx >> np.uint64(8), idx & np.uint64(255)
+            for f, name in zip(FN, ("AND", "OR", "XOR")):
+                acc = T.op_mask(name) + x.astype(object) * pw[1] + y.astype(object) * pw[2] + f(x, y).astype(object) * pw[3]
+                keep.append((acc % P).astype(np.uint64))
+    return time.perf_counter() - t0, keep
+
+
+def measure(kind, log_n, runs):
+    import torch
+    import ctypes as C
+    from olavm_amd.backend import Backend
+    from tests import oracle_lib
+    rng = np.random.default_rng(log_n)
+    n = 1 << log_n
+    host, kw = inputs(kind, log_n, rng)
+    be = Backend(device=0)
+    sp = C.c_void_p()
+    be._chk(be.lib.ola_gpu_get_stream(be.ctx, C.byref(sp)))
+    stream = torch.cuda.ExternalStream(sp.value)
+    dev = [to_dev(a) for a in host]
+    out = torch.empty((NCOLS[kind], n), dtype=torch.int64, device="cuda")
+    assert call(be, kind, dev, kw, out) == log_n           # warm-up (pool blocks, code objects)
+
+    def timed(f):
+        dev_ms, wall_ms = [], []
+        for _ in range(runs):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            a.record(stream)
+            f()
+            b.record(stream)
+            b.synchronize()
+            wall_ms.append((time.perf_counter() - t0) * 1e3)
+            dev_ms.append(a.elapsed_time(b))
+        return statistics.median(dev_ms), statistics.median(wall_ms)
+
+    rec = {"table": kind, "log_n": log_n, "runs": runs}
+    rec["call_device_ms"], rec["call_wall_ms"] = timed(lambda: call(be, kind, dev, kw, out))
+    # the same permuted columns pair by pair, from the columns the call just wrote
+    pairs = pairs_of(kind)
+    tmp = torch.empty((2, n), dtype=torch.int64, device="cuda")
+
+    def pair_by_pair():
+        for ci, ct, _, _ in pairs:
+            be.permuted_cols_dev(out[ci].data_ptr(), out[ct].data_ptr(), n, tmp[0].data_ptr(), tmp[1].data_ptr())
+    pair_by_pair()
+    rec["pairs"] = len(pairs)
+    rec["pair_by_pair_device_ms"], rec["pair_by_pair_wall_ms"] = timed(pair_by_pair)
+    same = True
+    for ci, ct, pi, pt in pairs:
+        be.permuted_cols_dev(out[ci].data_ptr(), out[ct].data_ptr(), n, tmp[0].data_ptr(), tmp[1].data_ptr())
+        same &= bool(torch.equal(tmp[0], out[pi]) and torch.equal(tmp[1], out[pt]))
+    rec["pair_by_pair_identical"] = same
+    if kind != "prog" or log_n <= 20:
+        rec["numpy_other_columns_wall_ms"] = host_columns(kind, host, kw, n)[0] * 1e3
+    # the sequential loop on one host core, one pair
+    o = oracle_lib.load()
+    ci, ct = pairs[0][0], pairs[0][1]
+    a, b = out[ci].cpu().numpy().view(np.uint64), out[ct].cpu().numpy().view(np.uint64)
+    t0 = time.perf_counter()
+    o.permuted_cols(a, b)
+    rec["oracle_one_pair_wall_ms"] = (time.perf_counter() - t0) * 1e3
+    rec["oracle_all_pairs_wall_ms_projected"] = rec["oracle_one_pair_wall_ms"] * len(pairs)
+    rec["table_words"] = NCOLS[kind] * n
+    be.close()
+    return rec
+
+
+def child(kind, log_n, calls, pair_by_pair):
+    import torch
+    from olavm_amd.backend import Backend
+    host, kw = inputs(kind, log_n, np.random.default_rng(log_n))
+    n = 1 << log_n
+    be = Backend(device=0)
+    dev = [to_dev(a) for a in host]
+    out = torch.empty((NCOLS[kind], n), dtype=torch.int64, device="cuda")
+    tmp = torch.empty((2, n), dtype=torch.int64, device="cuda")
+    call(be, kind, dev, kw, out)
+    for _ in range(calls):
+        if pair_by_pair:
+            for ci, ct, _, _ in pairs_of(kind):
+                be.permuted_cols_dev(out[ci].data_ptr(), out[ct].data_ptr(), n, tmp[0].data_ptr(), tmp[1].data_ptr())
+        else:
+            call(be, kind, dev, kw, out)
+    be.close()
+
+
+def traced_kernels(kind, log_n, calls, pair_by_pair):
+    """kernel launches (by name) of a child that makes `calls` calls after its warm-up"""
+    d = tempfile.mkdtemp(prefix="tablegen_trace_")
+    # the child under a time limit of its own that also ends the traced process; 20 children at most (5 cases x 2 ways x 2 runs),
+    # a few seconds each
+    cmd = ["timeout", "-k", "10", "60", "rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "t", "--", sys.executable, os.path.abspath(__file__), "--child",
+           kind, str(log_n), str(calls), "1" if pair_by_pair else "0"]
+    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, cwd=tempfile.gettempdir())
+    names = {}
+    for f in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
+        for row in csv.DictReader(open(f)):
+            k = row.get("Kernel_Name", "?")
+            names[k] = names.get(k, 0) + 1
+    return names
+
+
+def launches(kind, log_n):
+    rec = {}
+    for label, pbp in (("call", False), ("pair_by_pair", True)):
+        one, two = traced_kernels(kind, log_n, 1, pbp), traced_kernels(kind, log_n, 2, pbp)
+        per = {k: two.get(k, 0) - one.get(k, 0) for k in two}
+        rec[label + "_launches"] = sum(per.values())
+        sorts = {k: v for k, v in per.items() if "radix" in k.lower() or "onesweep" in k.lower() or "sort" in k.lower()}
+        rec[label + "_sort_kernel_launches"] = sum(sorts.values())
+        rec[label + "_kernels"] = {k[:96]: v for k, v in sorted(per.items()) if v}
+    return rec
+
+
+def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--child":
+        return child(sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), sys.argv[5] == "1")
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--json")
+    ap.add_argument("--skip-launches", action="store_true")
+    ap.add_argument("cases", nargs="*")
+    a = ap.parse_args()
+    recs = []
+    for case in a.cases or CASES:
+        kind, log_n = case.split(":")
+        rec = measure(kind, int(log_n), a.runs)
+        if not a.skip_launches:
+            rec.update(launches(kind, int(log_n)))
+        recs.append(rec)
+        print(json.dumps({k: v for k, v in rec.items() if not k.endswith("_kernels")}), flush=True)
+        if a.json:
+            json.dump(recs, open(a.json, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
