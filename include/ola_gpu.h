@@ -45,7 +45,8 @@ extern "C" {
  * 7 (number unchanged by the later additions, which change no struct and no existing behaviour): the hashers OLA_HASH_POSEIDON2 and
  * OLA_HASH_POSEIDON2_POW_POSEIDON and the entry point ola_poseidon2_permute were added to revision 7; so were OlaConstraintFailure
  * and the entry point ola_check_constraints (which constraint of which table fails at which row); so were ola_generate_rc_trace,
- * ola_generate_bitwise_trace and ola_generate_prog_trace (the range-check, bitwise and program tables completed in HBM). */
+ * ola_generate_bitwise_trace and ola_generate_prog_trace (the range-check, bitwise and program tables completed in HBM); so were
+ * OlaLookupMismatch and the entry point ola_check_lookup (the tuples a failing cross-table lookup is missing). */
 #define OLA_GPU_ABI_VERSION 7
 #define OLA_OK 0
 #define OLA_E_INVALID_ARG (-1)
@@ -488,6 +489,45 @@ typedef struct OlaConstraintFailure {
 int32_t ola_check_constraints(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, const uint64_t* const* const* cols,
                               const uint32_t* log_n, const uint64_t* params, const uint64_t* ctl_challenges, uint32_t table_mask,
                               OlaConstraintFailure* out, uint32_t cap, uint32_t* n_out);
+
+/* ---- which rows a failing cross-table lookup is missing ---------------------------------------------------------------------
+ * An OLA_CHECK_LOOKUP entry says that lookup `index` fails and how many rows each side selects; the CTL Z products it compares
+ * have no memory of WHICH tuple is unmatched.  The reference answers that by hand: one file per lookup under
+ * circuits/src/generation/ctl_test/ (cpu_mem.rs, cpu_program.rs, poseidon_chunk_mem.rs, storage_access_poseidon.rs, ...)
+ * filters the looking and the looked rows, projects the lookup's data columns and prints both lists for a person to diff
+ * (generation/ctl_test/debug_trace_print.rs:64-88, :299-333).  This call computes the exact multiset difference of the two sides of ONE lookup on the
+ * device -- what verify_cross_table_lookups (stark/cross_table_lookup.rs:551-584) can only refuse as a whole.  No challenge is
+ * involved: the answer is exact, not probabilistic.
+ * airset, cols, log_n: as for ola_check_constraints (per-column pointers: host memory, staged through the pinned ring, or a
+ *   table whose first column is device memory is taken as resident; words may be >= p).  Only the tables the lookup names are
+ *   read, cols[t] of the others may be NULL.
+ * lookup: position in all_cross_table_lookups() order = OlaConstraintFailure.index of an OLA_CHECK_LOOKUP entry; out of range is
+ *   OLA_E_INVALID_ARG, and so is a lookup of more than OLA_LOOKUP_MAX_VALUES data columns (a foreign AIR set).
+ * A row of a side is selected when its filter column's canonical value is 1 (every row when the side has no filter), as the CTL Z
+ *   columns select it; its tuple is the canonical values of the side's `Column` linear combinations.
+ * out[0 .. min(cap, *n_out)): one entry per distinct tuple with looking_count != looked_count, sorted lexicographically by
+ *   values[0 .. *width) as unsigned canonical words; *n_out is their TOTAL number also beyond cap (out may be NULL when cap is 0).
+ *   The first carrier on the looking side is the minimum of (entry position in the lookup's looking list, row): looking_entry and
+ *   looking_table name it (one table may appear in several entries).
+ * totals: {selected looking rows (all entries), selected looked rows, distinct mismatching tuples, sum of |looking_count -
+ *   looked_count|}; *width: the lookup's number of data columns.  n_out, totals and width must not be NULL.
+ * The return value is OLA_OK whether or not anything mismatches.  The proving state of the context is not touched; a multi-device
+ * context works on its first device; without a HIP device a call whose other arguments are valid returns OLA_E_NO_DEVICE.
+ * OLA_LOOKUP_MAX_VALUES: the widest lookup of the 12-table OlaStark (olavm_amd/air/ola_tables.py), as `python -m olavm_amd.air.dump
+ * --lookup-max-values` prints it. */
+#define OLA_LOOKUP_MAX_VALUES 24
+typedef struct OlaLookupMismatch {
+    uint64_t looking_count;     /* filter-selected looking rows (all looking entries) that carry this tuple */
+    uint64_t looked_count;      /* filter-selected rows of the looked table that carry it                   */
+    uint32_t looking_entry;     /* position in the lookup's looking list of the first carrier, or UINT32_MAX */
+    uint32_t looking_table;     /* that entry's table, or UINT32_MAX                                         */
+    uint64_t looking_row;       /* smallest row of that entry carrying the tuple, or UINT64_MAX              */
+    uint64_t looked_row;        /* smallest looked row carrying it, or UINT64_MAX                            */
+    uint64_t values[OLA_LOOKUP_MAX_VALUES]; /* the tuple, canonical, the first `width` words; the rest zero  */
+} OlaLookupMismatch;
+int32_t ola_check_lookup(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, const uint64_t* const* const* cols,
+                         const uint32_t* log_n, uint32_t lookup, OlaLookupMismatch* out, uint32_t cap, uint32_t* n_out,
+                         uint64_t totals[4], uint32_t* width);
 
 /* Copies out (and forgets) the proof a preceding ola_prove_with_traces could not return because its buffer was too small. */
 int32_t ola_take_pending_proof(OlaCtx* ctx, uint8_t* out, size_t cap, size_t* out_len);

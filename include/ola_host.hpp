@@ -19,6 +19,7 @@
 // ola_host::Error carrying the C ABI's code (OLA_E_*) and message.  Field elements are plain uint64_t words
 // (GoldilocksField is #[repr(transparent)] u64); any representative is accepted on input, outputs are canonical.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <memory>
@@ -374,6 +375,59 @@ inline std::vector<OlaConstraintFailure> check_constraints(const Gpu& g, const s
     if (n > out.size()) { out.resize(n); check(call()); }
     out.resize(n);
     return out;
+}
+
+// ---- circuits/src/generation/ctl_test/*.rs, cross_table_lookup.rs:551-584 ---------------------------------------------------------
+// Which tuples cross-table lookup `lookup` (the `index` of an OLA_CHECK_LOOKUP failure) is missing: the exact multiset difference of its
+// two sides (ola_check_lookup).  traces / log_n as for check_constraints; tables the lookup does not name may be empty.  max_tuples:
+// report at most that many (0: all).
+struct LookupReport {
+    uint32_t lookup = 0, width = 0;
+    uint64_t totals[4] = {0, 0, 0, 0};          // selected looking rows, selected looked rows, mismatching tuples, unmatched rows
+    std::vector<OlaLookupMismatch> mismatches;  // sorted by values[0 .. width)
+    // one line per tuple, the text of olavm_amd.backend.format_lookup_report
+    std::string text() const {
+        auto num = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+        std::string s = "lookup " + num(lookup) + ": width " + num(width) + ", " + num(totals[0]) + " looking rows, " + num(totals[1]) +
+                        " looked rows, " + num(totals[2]) + " mismatching tuples, " + num(totals[3]) + " rows unmatched";
+        for (const OlaLookupMismatch& m : mismatches) {
+            s += "\n  (";
+            for (uint32_t k = 0; k < width && k < OLA_LOOKUP_MAX_VALUES; k++) s += (k ? ", " : "") + num(m.values[k]);
+            s += "): looking " + num(m.looking_count) + " (first: ";
+            s += m.looking_entry == UINT32_MAX ? std::string("-")
+                                               : "entry " + num(m.looking_entry) + " table " + num(m.looking_table) + " row " + num(m.looking_row);
+            s += "), looked " + num(m.looked_count) + " (first: ";
+            s += m.looked_row == UINT64_MAX ? std::string("-") : "row " + num(m.looked_row);
+            s += ")";
+        }
+        if (mismatches.size() < totals[2]) s += "\n  ... " + num(totals[2] - mismatches.size()) + " more";
+        return s;
+    }
+};
+inline LookupReport check_lookup(const Gpu& g, const std::vector<F>& airset, const std::vector<std::vector<F>>& traces,
+                                 const std::vector<uint32_t>& log_n, uint32_t lookup, uint32_t max_tuples = 0) {
+    if (traces.size() != log_n.size()) throw Error(OLA_E_INVALID_ARG, "one height per trace");
+    std::vector<std::vector<const F*>> cols(traces.size());
+    std::vector<const F* const*> tabs;
+    for (size_t t = 0; t < traces.size(); t++) {
+        if (log_n[t] > 30) throw Error(OLA_E_INVALID_ARG, "table size out of range");
+        const size_t n = (size_t)1 << log_n[t];
+        if (traces[t].size() % n) throw Error(OLA_E_INVALID_ARG, "a table is not a whole number of columns");
+        for (size_t c = 0; c * n < traces[t].size(); c++) cols[t].push_back(traces[t].data() + c * n);
+        tabs.push_back(cols[t].empty() ? nullptr : cols[t].data());
+    }
+    LookupReport rep;
+    rep.lookup = lookup;
+    rep.mismatches.resize(max_tuples ? max_tuples : 64);
+    uint32_t n = 0;
+    auto call = [&]() {
+        return ola_check_lookup(g.ctx(), airset.data(), airset.size(), tabs.data(), log_n.data(), lookup, rep.mismatches.data(),
+                                (uint32_t)rep.mismatches.size(), &n, rep.totals, &rep.width);
+    };
+    check(call());
+    if (!max_tuples && n > rep.mismatches.size()) { rep.mismatches.resize(n); check(call()); }
+    rep.mismatches.resize(std::min<size_t>(n, rep.mismatches.size()));
+    return rep;
 }
 
 // prove_single_table (prover.rs:330-513) for callers that keep the reference's orchestration: `trace` = the table's columns,

@@ -176,6 +176,26 @@ fn hasher_of<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, const D: 
     }
 }
 
+/// The first three tuples a failing cross-table lookup is missing (`ola_check_lookup`), for the line that names the lookup.
+fn describe_lookup(c: *mut OlaCtx, words: &[u64], tables: &[*const *const u64], log_n: &[u32], lookup: u32) -> String {
+    let mut found = [OlaLookupMismatch::default(); 3];
+    let (mut n, mut width, mut totals) = (0u32, 0u32, [0u64; 4]);
+    let rc = unsafe {
+        ola_check_lookup(c, words.as_ptr(), words.len(), tables.as_ptr(), log_n.as_ptr(), lookup, found.as_mut_ptr(), found.len() as u32, &mut n,
+                         totals.as_mut_ptr(), &mut width)
+    };
+    if rc != OLA_OK || n == 0 {
+        return String::new();
+    }
+    let tuples: Vec<String> = found.iter().take(n as usize).map(|m| {
+        let looking = if m.looking_entry == u32::MAX { "-".to_string() } else { format!("entry {} table {} row {}", m.looking_entry, m.looking_table, m.looking_row) };
+        let looked = if m.looked_row == u64::MAX { "-".to_string() } else { format!("row {}", m.looked_row) };
+        format!("{:?}: looking {} (first: {}), looked {} (first: {})", &m.values[..(width as usize).min(OLA_LOOKUP_MAX_VALUES)], m.looking_count, looking,
+                m.looked_count, looked)
+    }).collect();
+    format!(" -- {} tuples differ, {} rows unmatched: {}{}", totals[2], totals[3], tuples.join(", "), if n as usize > found.len() { ", ..." } else { "" })
+}
+
 /// The report of `ola_check_constraints` over all tables as one line per entry.
 fn describe_failures(c: *mut OlaCtx, words: &[u64], tables: &[*const *const u64], log_n: &[u32], params: &[u64]) -> String {
     const KINDS: [&str; 4] = ["constraint", "constraint_transition", "constraint_first_row", "constraint_last_row"];
@@ -193,6 +213,8 @@ fn describe_failures(c: *mut OlaCtx, words: &[u64], tables: &[*const *const u64]
         return "the constraint check on the trace domain finds nothing wrong".to_string();
     }
     let mut lines: Vec<String> = found.iter().take(n as usize).map(|f| match f.section {
+        OLA_CHECK_LOOKUP if f.kind == 0 => format!("table {}, cross-table lookup {} (challenge {}): {} looking rows, {} looked rows{}", f.table, f.index, f.kind,
+                                                   f.first_row, f.rows_failing, describe_lookup(c, words, tables, log_n, f.index)),
         OLA_CHECK_AIR => format!("table {}, constraint #{} ({}), first at row {}, {} rows", f.table, f.index, KINDS[(f.kind & 3) as usize], f.first_row, f.rows_failing),
         OLA_CHECK_PERMUTATION => format!("table {}, permutation batch {}: the running product does not close", f.table, f.index),
         _ => format!("table {}, cross-table lookup {} (challenge {}): {} looking rows, {} looked rows", f.table, f.index, f.kind, f.first_row, f.rows_failing),

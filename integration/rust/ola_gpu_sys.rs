@@ -130,6 +130,20 @@ pub struct OlaConstraintFailure {
     pub first_row: u64,
     pub rows_failing: u64,
 }
+/// `ola_check_lookup`: the widest lookup of the 12-table OlaStark (`OLA_LOOKUP_MAX_VALUES` of ola_gpu.h)
+pub const OLA_LOOKUP_MAX_VALUES: usize = 24;
+/// One tuple that the two sides of a cross-table lookup carry unequally often (`ola_check_lookup`); `u32::MAX` / `u64::MAX` = none.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct OlaLookupMismatch {
+    pub looking_count: u64,
+    pub looked_count: u64,
+    pub looking_entry: u32,
+    pub looking_table: u32,
+    pub looking_row: u64,
+    pub looked_row: u64,
+    pub values: [u64; OLA_LOOKUP_MAX_VALUES],
+}
 /// `ola_all_gather_fn`: gather `bytes` bytes of device memory from every rank into `recv_dev` (rank order), 0 = done
 pub type OlaAllGatherFn = Option<unsafe extern "C" fn(user: *mut c_void, send_dev: *const c_void, recv_dev: *mut c_void, bytes: usize) -> i32>;
 
@@ -219,6 +233,9 @@ extern "C" {
     pub fn ola_check_constraints(ctx: *mut OlaCtx, airset: *const u64, airset_words: usize, cols: *const *const *const u64,
         log_n: *const u32, params: *const u64, ctl_challenges: *const u64, table_mask: u32, out: *mut OlaConstraintFailure,
         cap: u32, n_out: *mut u32) -> i32;
+    pub fn ola_check_lookup(ctx: *mut OlaCtx, airset: *const u64, airset_words: usize, cols: *const *const *const u64,
+        log_n: *const u32, lookup: u32, out: *mut OlaLookupMismatch, cap: u32, n_out: *mut u32, totals: *mut u64,
+        width: *mut u32) -> i32;
     pub fn ola_take_pending_proof(ctx: *mut OlaCtx, out: *mut u8, cap: usize, out_len: *mut usize) -> i32;
     pub fn ola_prove_single_table(ctx: *mut OlaCtx, airset: *const u64, airset_words: usize, table: u32,
         trace_cols: *const *const u64, trace_commitment: *const OlaBatch, trace_cap: *const u64,

@@ -1,11 +1,20 @@
 """Writes the AIR-set blob of the reference's 12-table OlaStark (what `ola_prove_with_traces` takes as `airset`) to a file of
-little-endian u64 words, for a host binding that embeds it.  usage: python -m olavm_amd.air.dump out.bin"""
+little-endian u64 words, for a host binding that embeds it.  usage: python -m olavm_amd.air.dump out.bin
+python -m olavm_amd.air.dump --lookup-max-values prints the OLA_LOOKUP_MAX_VALUES line of include/ola_gpu.h."""
 import sys
 
 from . import ola_tables
 
 
+def lookup_max_values():
+    """the widest cross-table lookup of ola_stark(): data columns per side"""
+    return max(len(c.looked_table.columns) for c in ola_tables.ola_stark().ctls)
+
+
 def main(argv):
+    if len(argv) > 1 and argv[1] == "--lookup-max-values":
+        print("#define OLA_LOOKUP_MAX_VALUES %d" % lookup_max_values())
+        return
     path = argv[1] if len(argv) > 1 else "ola_airset.bin"
     blob = ola_tables.ola_stark().blob()
     blob.astype("<u8").tofile(path)

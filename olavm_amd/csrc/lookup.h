@@ -24,6 +24,15 @@ struct PermutedPair {
 };
 void permuted_cols_batch_dev(DeviceCtx* ctx, size_t n, const u64* const* tables, size_t n_tables, const PermutedPair* pairs, size_t n_pairs);
 
+// The radix sort and the prefix sum of this unit for a caller outside it (ola_check_lookup, check.hip): one stable sort pass of
+// (64-bit key, 32-bit payload) pairs over all 64 key bits, and the exclusive sum of n 32-bit words.  The caller owns the
+// temporary storage (*_tmp_bytes says how much; never 0); everything is enqueued on `stream`, nothing synchronises.  n >= 1.
+size_t sort_pairs_tmp_bytes(size_t n);
+void sort_pairs_dev(hipStream_t stream, void* tmp, size_t tmp_bytes, const u64* keys_in, u64* keys_out, const u32* payload_in,
+                    u32* payload_out, size_t n);
+size_t exclusive_sum_tmp_bytes(size_t n);
+void exclusive_sum_dev(hipStream_t stream, void* tmp, size_t tmp_bytes, const u32* in, u32* out, size_t n);
+
 // Whole tables from their primary columns (ola_generate_rc_trace / _bitwise_trace / _prog_trace of include/ola_gpu.h): all
 // pointers are device memory, `out` is column-major ncols x 2^log_n with log_n as the *_log_n functions give it (the
 // program table: as passed).  Every column of `out` is written; complete when the call returns.

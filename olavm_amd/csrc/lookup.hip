@@ -378,6 +378,26 @@ void permuted_cols_dev(DeviceCtx* ctx, const u64* inputs, const u64* table, size
     permuted_cols_batch_dev(ctx, n, &table, 1, &pair, 1);
 }
 
+// ------------------------------------------------------------------------------------------------ sort / scan for check.hip
+// the key + payload variant of SortU64 (rocPRIM's radix sort is stable: equal keys keep the order of their payloads)
+size_t sort_pairs_tmp_bytes(size_t n) {
+    size_t bytes = 0;
+    HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, (const u64*)nullptr, (u64*)nullptr, (const u32*)nullptr, (u32*)nullptr, n, 0, 64, (hipStream_t) nullptr));
+    return std::max<size_t>(bytes, 8);
+}
+void sort_pairs_dev(hipStream_t stream, void* tmp, size_t tmp_bytes, const u64* keys_in, u64* keys_out, const u32* payload_in, u32* payload_out,
+                    size_t n) {
+    HIP_CHECK(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys_in, keys_out, payload_in, payload_out, n, 0, 64, stream));
+}
+size_t exclusive_sum_tmp_bytes(size_t n) {
+    size_t bytes = 0;
+    HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, (const u32*)nullptr, (u32*)nullptr, 0u, n, rocprim::plus<u32>(), (hipStream_t) nullptr));
+    return std::max<size_t>(bytes, 8);
+}
+void exclusive_sum_dev(hipStream_t stream, void* tmp, size_t tmp_bytes, const u32* in, u32* out, size_t n) {
+    HIP_CHECK(rocprim::exclusive_scan(tmp, tmp_bytes, in, out, 0u, n, rocprim::plus<u32>(), stream));
+}
+
 // ------------------------------------------------------------------------------------------------ table generators
 // The range-check, bitwise and program tables from their primary columns (generation/builtin.rs:35-206, 249-316,
 // generation/prog.rs:18-156): one fill kernel per table writes every column that is not a permuted one -- thread = row, so

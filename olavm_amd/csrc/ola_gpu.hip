@@ -1096,6 +1096,39 @@ int32_t ola_check_constraints(OlaCtx* ctx, const uint64_t* airset, size_t airset
     OLA_CATCH
 }
 
+int32_t ola_check_lookup(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, const uint64_t* const* const* cols, const uint32_t* log_n,
+                         uint32_t lookup, OlaLookupMismatch* out, uint32_t cap, uint32_t* n_out, uint64_t totals[4], uint32_t* width) {
+    OLA_TRY
+    require(airset && cols && log_n && n_out && totals && width && (out || cap == 0), "null pointer");
+    const std::vector<size_t> widths = airset_widths((const u64*)airset, airset_words);
+    const size_t nt = widths.size();
+    const uint32_t mask = check_lookup_tables(parse_airset((const u64*)airset, airset_words), lookup);
+    std::vector<TraceSource> src(nt);
+    for (size_t t = 0; t < nt; t++) {
+        if (!(mask >> t & 1)) continue;
+        require(cols[t] != nullptr, "cols[t] is NULL");
+        for (size_t c = 0; c < widths[t]; c++) require(cols[t][c] != nullptr, "cols[t][c] is NULL");
+        require(log_n[t] <= 30, "table size out of range");
+        src[t].cols = (const u64* const*)cols[t];
+    }
+    if (!ctx) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+            (void)hipGetLastError();
+            throw OlaError(OLA_E_NO_DEVICE, "no HIP device visible (the backend has no CPU fallback)");
+        }
+        require(false, "ctx is NULL");
+    }
+    OLA_ON_DEVICE(ctx);
+    LookupReport rep;
+    check_lookup(&ctx->dev, (const u64*)airset, airset_words, src.data(), log_n, lookup, cap, rep);
+    *n_out = (uint32_t)rep.totals[2];
+    *width = rep.width;
+    for (int k = 0; k < 4; k++) totals[k] = rep.totals[k];
+    for (size_t i = 0; i < rep.entries.size() && i < cap; i++) out[i] = rep.entries[i];
+    OLA_CATCH
+}
+
 int32_t ola_take_pending_proof(OlaCtx* ctx, uint8_t* out, size_t cap, size_t* out_len) {
     OLA_TRY
     OLA_ON_DEVICE(ctx);

@@ -255,6 +255,10 @@ PY
                  ( set -o pipefail
                    timeout -k 10 900 python -m pytest tests/test_gpu_tablegen.py tests/test_gpu_lookup.py -x -q 2>&1 | tail -15 | tee $O/pytest.log && \
                    timeout -k 10 1500 python tools/bench_tablegen.py --json $O/tablegen.json 2>&1 | grep -v amdgpu | tee $O/tablegen.txt ) ;;
+    check_lookup) # ola_check_lookup: its tests, then the CPU -> memory and CPU -> program lookups of a 2^22-row executed instance, valid and with one looked row dropped
+                 ( set -o pipefail
+                   timeout -k 10 600 python -m pytest tests/test_gpu_check_lookup.py -x -q 2>&1 | tail -15 | tee $O/pytest.log && \
+                   timeout -k 10 900 python tools/bench_check_lookup.py --json $O/check_lookup.json 2>&1 | grep -v amdgpu | tee $O/check_lookup.txt ) ;;
     *)           echo "unknown step $step" ;;
   esac
 done
