@@ -46,7 +46,8 @@ extern "C" {
  * OLA_HASH_POSEIDON2_POW_POSEIDON and the entry point ola_poseidon2_permute were added to revision 7; so were OlaConstraintFailure
  * and the entry point ola_check_constraints (which constraint of which table fails at which row); so were ola_generate_rc_trace,
  * ola_generate_bitwise_trace and ola_generate_prog_trace (the range-check, bitwise and program tables completed in HBM); so were
- * OlaLookupMismatch and the entry point ola_check_lookup (the tuples a failing cross-table lookup is missing). */
+ * OlaLookupMismatch and the entry point ola_check_lookup (the tuples a failing cross-table lookup is missing); so were
+ * ola_generate_cpu_trace and ola_generate_prog_trace_steps (the CPU table and the program table from the executor's step records). */
 #define OLA_GPU_ABI_VERSION 7
 #define OLA_OK 0
 #define OLA_E_INVALID_ARG (-1)
@@ -609,6 +610,42 @@ int32_t ola_generate_rc_trace(OlaCtx* ctx, const uint64_t* vals, const uint64_t*
 int32_t ola_generate_bitwise_trace(OlaCtx* ctx, const uint64_t* ops, size_t n_ops, uint32_t limb_bits, uint64_t beta, uint32_t flags,
                                    uint64_t* out, uint32_t* log_n_out);
 int32_t ola_generate_prog_trace(OlaCtx* ctx, const uint64_t* exec, const uint64_t* prog, uint32_t log_n, uint64_t beta, uint64_t* out);
+
+/* ---- the CPU table and the program table's executed side from step records -------------------------------------------------
+ * Both tables are per-row functions of the executor's `Step`s (generation/cpu.rs:11-218 maps one Step to one row of 94 columns: 66
+ * copied words and 28 that follow from them -- 19 opcode selectors, 7 flags and filters, IS_PADDING and the constant TX_IDX; the
+ * executed side of generation/prog.rs:31-108 is a stream compaction of the same steps), so the host hands over the
+ * records and neither assembles, zero-fills nor uploads the widest table of the proof.  The contract is the one of the calls above:
+ * `steps`, `prog` and `out` may each be host memory or memory of the context's GPU, words may be >= p, every word written is
+ * canonical, every column of `out` is written (no memset of the table), the work runs on the context's stream and is complete on
+ * return, arguments are validated first, ctx == NULL answers OLA_E_NO_DEVICE on a machine without a HIP device, a multi-device
+ * context works on its first device, and `out` can go into ola_prove_with_traces* as a resident table.
+ *
+ * A step record is OLA_CPU_STEP_WORDS = 66 words per executed row, column-major 66 x n_steps:
+ *   words 0 .. 64 = CPU columns 1 .. 65 (COL_ENV_IDX .. COL_IDX_STORAGE, then the 30 register-selector columns, cpu/columns.rs) --
+ *     exactly the fields generation/cpu.rs:64-105 copies from a Step.  The selector columns travel as whole words because extension lines use
+ *     them as data carriers (executor/src/lib.rs:165 the tape address, :1298-1312 the storage slot's addresses, key, value and tree
+ *     key, :1937 the callee's context), which a bit mask cannot hold;
+ *   word 65 = filter_tape_looking (generation/cpu.rs:146).
+ *
+ * ola_generate_cpu_trace: out = 94 x 2^log_n; 2^log_n < n_steps is OLA_E_INVALID_ARG.  Live rows follow generation/cpu.rs:62-179: TX_IDX = 0,
+ *   the 65 copied columns, the opcode selector of generation/cpu.rs:20-60 (an opcode word that is none of the 25 masks sets none), IS_ENTRY_SC,
+ *   IS_NEXT_LINE_DIFF_INST (ext_length == ext_cnt; TLOAD's ext_length op0 * op1 + (1 - op0) is computed in the field, the reference's
+ *   u64 expression agrees wherever it does not overflow), IS_NEXT_LINE_SAME_TX, FILTER_TAPE_LOOKING, IS_SCCALL_EXT_LINE,
+ *   IS_STORAGE_EXT_LINE, FILTER_SCCALL_END, FILTER_LOOKING_PROG_IMM; every comparison is on canonical values.  Rows n_steps .. 2^log_n
+ *   are the padding rows of generation/cpu.rs:180-208 with INST and IDX_STORAGE of the last live row (2^20 and 0 when n_steps == 0).
+ * ola_generate_prog_trace_steps: out = 18 x 2^log_n.  prog: the listing side, 7 x 2^log_n, as ola_generate_prog_trace takes it.  The
+ *   executed side follows generation/prog.rs:31-44,59-108: a step with is_ext_line == 1 gives nothing, every other step the row (addr_code, pc,
+ *   inst, filter 1) and, when op1_imm == 1 or the opcode is MLOAD or MSTORE, a second row (addr_code, pc + 1, imm_val, filter 1).
+ *   *exec_rows_out receives the number of executed rows; more than 2^log_n is OLA_E_INVALID_ARG with the count still returned and
+ *   `out` untouched, so that one call sizes the table.  n_steps >= 2^31 is OLA_E_INVALID_ARG.  Rows beyond the executed ones repeat
+ *   executed row 0 with filter 0 (a listed word, so that the in-table lookup holds); with OLA_TABLEGEN_ZERO_FILLER, or when nothing
+ *   was executed, they are generation/prog.rs:57's zero rows.  The rest is ola_generate_prog_trace. */
+#define OLA_CPU_STEP_WORDS 66
+#define OLA_TABLEGEN_ZERO_FILLER 1u
+int32_t ola_generate_cpu_trace(OlaCtx* ctx, const uint64_t* steps, size_t n_steps, uint32_t log_n, uint64_t* out);
+int32_t ola_generate_prog_trace_steps(OlaCtx* ctx, const uint64_t* steps, size_t n_steps, const uint64_t* prog, uint32_t log_n,
+                                      uint64_t beta, uint32_t flags, uint64_t* out, uint64_t* exec_rows_out);
 
 /* ---- coset-partitioned proving over several GPUs ---------------------------------------------------------
  * One process per GPU; every process calls ola_prove_with_traces with the SAME traces.  Because the transcript is a

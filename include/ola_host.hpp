@@ -14,6 +14,8 @@
 //   circuits/src/stark/prover.rs:330             prove_single_table       ola_host::prove_single_table
 //   circuits/src/stark/lookup.rs:68              permuted_cols            ola_host::permuted_cols
 //   circuits/src/generation/poseidon.rs:5        generate_poseidon_trace  ola_host::generate_poseidon_trace
+//   circuits/src/generation/cpu.rs:11            generate_cpu_trace       ola_host::generate_cpu_trace
+//   circuits/src/generation/prog.rs:18           generate_prog_trace      ola_host::generate_prog_trace_steps
 //
 // Errors: the Rust code returns anyhow::Result / panics on contract violations; here every failing call throws
 // ola_host::Error carrying the C ABI's code (OLA_E_*) and message.  Field elements are plain uint64_t words
@@ -466,6 +468,26 @@ inline std::vector<F> generate_poseidon_trace(const Gpu& g, const std::vector<F>
     if (inputs.size() != 12 * n || (!filters.empty() && filters.size() != 4 * n)) throw Error(OLA_E_INVALID_ARG, "shape");
     std::vector<F> out(134 * n);
     check(ola_generate_poseidon_trace(g.ctx(), inputs.data(), filters.empty() ? nullptr : filters.data(), n, out.data()));
+    return out;
+}
+// step records (OLA_CPU_STEP_WORDS x n_steps column-major) -> the 94 x 2^log_n CPU table (generation/cpu.rs:11-218)
+inline std::vector<F> generate_cpu_trace(const Gpu& g, const std::vector<F>& steps, size_t n_steps, uint32_t log_n) {
+    if (steps.size() != OLA_CPU_STEP_WORDS * n_steps || log_n > 26) throw Error(OLA_E_INVALID_ARG, "shape");
+    std::vector<F> out((size_t)94 << log_n);
+    check(ola_generate_cpu_trace(g.ctx(), n_steps ? steps.data() : nullptr, n_steps, log_n, out.data()));
+    return out;
+}
+// step records and the listing side (7 x 2^log_n) -> the 18 x 2^log_n program table (generation/prog.rs:18-156); *exec_rows
+// receives the number of executed rows also when they do not fit (the call then throws OLA_E_INVALID_ARG)
+inline std::vector<F> generate_prog_trace_steps(const Gpu& g, const std::vector<F>& steps, size_t n_steps, const std::vector<F>& prog,
+                                                uint32_t log_n, F beta, uint64_t* exec_rows = nullptr, uint32_t flags = 0) {
+    if (steps.size() != OLA_CPU_STEP_WORDS * n_steps || log_n > 26 || prog.size() != (size_t)7 << log_n) throw Error(OLA_E_INVALID_ARG, "shape");
+    std::vector<F> out((size_t)18 << log_n);
+    uint64_t rows = 0;
+    const int32_t rc = ola_generate_prog_trace_steps(g.ctx(), n_steps ? steps.data() : nullptr, n_steps, prog.data(), log_n, beta, flags,
+                                                     out.data(), &rows);
+    if (exec_rows) *exec_rows = rows;
+    check(rc);
     return out;
 }
 

@@ -43,6 +43,10 @@ typedef struct OlaTraceSet OlaTraceSet;
  * (b) the memory table of a run without memory cells is generation/memory.rs:95-153's: every row a prophet-region row, row 0 without
  * its selector (default: one stack-region row first, so that memory_stark.rs:265-270 hold on the wrap-around). */
 #define OLA_TRACEGEN_REFERENCE_QUIRKS 4u
+/* flags: do not build the CPU table and the program table -- the two that are per-row functions of the executed steps and that the
+ * GPU generates from them (include/ola_gpu.h ola_generate_cpu_trace, ola_generate_prog_trace_steps).  ola_tracegen_table answers the
+ * two with their shape and data = NULL; ola_tracegen_cpu_steps and ola_tracegen_prog_listing return what the GPU calls take. */
+#define OLA_TRACEGEN_STEPS_ONLY 8u
 
 /* Executes the program (at most max_steps CPU rows) and builds the 12 tables of ola_stark(range_bits, limb_bits) in
  * `enum Table` order.  range_bits / limb_bits are 16 / 8 in the reference; smaller values give structurally identical
@@ -50,8 +54,12 @@ typedef struct OlaTraceSet OlaTraceSet;
 int32_t ola_tracegen_run(const OlaInstr* program, size_t n_instr, const uint64_t code_addr[4], const uint64_t storage_addr[4],
                          uint32_t range_bits, uint32_t limb_bits, uint64_t bitwise_beta, uint64_t program_beta, uint64_t max_steps,
                          uint32_t flags, OlaTraceSet** out);
-/* Table t: column-major ncols x 2^log_n words, owned by the set. */
+/* Table t: column-major ncols x 2^log_n words, owned by the set (data = NULL for a table OLA_TRACEGEN_STEPS_ONLY left out). */
 int32_t ola_tracegen_table(const OlaTraceSet* set, uint32_t table, uint32_t* ncols, uint32_t* log_n, const uint64_t** data);
+/* OLA_TRACEGEN_STEPS_ONLY sets only (-1 otherwise): the step records, OLA_CPU_STEP_WORDS x n_steps column-major, and the program
+ * table's listing side, 7 x 2^log_n column-major (four code-address words, pc, inst, filter); both owned by the set. */
+int32_t ola_tracegen_cpu_steps(const OlaTraceSet* set, uint64_t* n_steps, const uint64_t** data);
+int32_t ola_tracegen_prog_listing(const OlaTraceSet* set, uint32_t* log_n, const uint64_t** data);
 /* Number of executed CPU rows (before padding). */
 uint64_t ola_tracegen_cpu_rows(const OlaTraceSet* set);
 /* out[0] = the bitwise table's compress challenge, out[1] = the program table's. */

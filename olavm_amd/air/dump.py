@@ -71,3 +71,36 @@ def tablegen_columns_header():
         out.append("constexpr uint64_t OP_MASK_%s = %dull;" % (op, T.op_mask(op)))
     out.append("}  // namespace olatg")
     return "\n".join(out) + "\n"
+
+
+TABLEGEN_CPU_COLUMNS_H = "olavm_amd/csrc/tablegen_cpu_columns.h"
+CPU_STEP_WORDS = 66      # include/ola_gpu.h OLA_CPU_STEP_WORDS; olavm_amd/air/cpu_steps.py STEP_WORDS
+
+
+def tablegen_cpu_columns_header():
+    """The checked header olavm_amd/csrc/tablegen_cpu_columns.h: every column index of the CPU table, the bit position of every opcode
+    mask and the layout of a step record, for ola_generate_cpu_trace / ola_generate_prog_trace_steps in olavm_amd/csrc/lookup.hip (the
+    program table's indices are in tablegen_columns.h).  Committed like its sibling; tests/test_cpu_tablegen_abi.py compares it with
+    this text.  Regenerate:
+        python -c "from olavm_amd.air import dump; print(dump.tablegen_cpu_columns_header(), end='')" > olavm_amd/csrc/tablegen_cpu_columns.h"""
+    from . import ola_tables as T
+    out = ["// generated from olavm_amd/air/ola_tables.py by olavm_amd.air.dump.tablegen_cpu_columns_header() -- do not edit",
+           "#pragma once", "#include <cstdint>", "namespace olatgc {"]
+    # cpu/columns.rs: the COL_* names that carry no other table's prefix, and IS_SCCALL_EXT_LINE
+    others = ("COL_MEM_", "COL_CMP_", "COL_SCCALL_", "COL_TAPE_", "COL_PROG_", "COL_POSEIDON_", "COL_ST_", "COL_NUM_")
+    cpu = [n for n in dir(T) if n.isupper() and ((n.startswith("COL_") and not n.startswith(others)) or n == "IS_SCCALL_EXT_LINE")]
+    for name in sorted(cpu):
+        v = getattr(T, name)
+        if isinstance(v, range):
+            out.append("constexpr uint32_t %s_START = %du, %s_END = %du;" % (name, v.start, name, v.stop))
+        else:
+            out.append("constexpr uint32_t %s = %du;" % (name, v))
+    out.append("constexpr uint32_t NUM_CPU_COLS = %du;" % T.NUM_CPU_COLS)
+    for op, sh in sorted(T.OPCODE_SHIFT.items()):
+        out.append("constexpr uint32_t OP_SHIFT_%s = %du;" % (op, sh))
+    # a step record: the columns cpu.rs copies from a Step (COL_ENV_IDX .. the last register-selector column), then filter_tape_looking
+    out.append("constexpr uint32_t STEP_FIRST_COL = %du, STEP_COPIED_COLS = %du;" % (T.COL_ENV_IDX, T.COL_S_DST.stop - T.COL_ENV_IDX))
+    out.append("constexpr uint32_t STEP_FILTER_TAPE_LOOKING = %du;" % (T.COL_S_DST.stop - T.COL_ENV_IDX))
+    out.append("constexpr uint32_t STEP_WORDS = %du;" % CPU_STEP_WORDS)
+    out.append("}  // namespace olatgc")
+    return "\n".join(out) + "\n"

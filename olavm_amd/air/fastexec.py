@@ -5,7 +5,7 @@ import os
 
 import numpy as np
 
-from . import ola_tables as T
+from . import cpu_steps, ola_tables as T
 from .dsl import P
 
 _lib = None
@@ -15,8 +15,9 @@ class OlaInstr(C.Structure):
     _fields_ = [("op", C.c_uint32), ("dst", C.c_int32), ("op0", C.c_int32), ("op1", C.c_int32), ("op1_is_imm", C.c_uint32), ("imm", C.c_uint64)]
 
 
-EXPORTS = ["ola_tracegen_run", "ola_tracegen_table", "ola_tracegen_cpu_rows", "ola_tracegen_free", "ola_tracegen_last_error", "ola_tracegen_betas"]
-OLA_TRACEGEN_PROVE_PROGRAM_HASH, OLA_TRACEGEN_EXPLICIT_BETAS, OLA_TRACEGEN_REFERENCE_QUIRKS = 1, 2, 4
+EXPORTS = ["ola_tracegen_run", "ola_tracegen_table", "ola_tracegen_cpu_rows", "ola_tracegen_free", "ola_tracegen_last_error", "ola_tracegen_betas",
+           "ola_tracegen_cpu_steps", "ola_tracegen_prog_listing"]
+OLA_TRACEGEN_PROVE_PROGRAM_HASH, OLA_TRACEGEN_EXPLICIT_BETAS, OLA_TRACEGEN_REFERENCE_QUIRKS, OLA_TRACEGEN_STEPS_ONLY = 1, 2, 4, 8
 
 
 def lib_path():
@@ -37,6 +38,8 @@ def load_library():
         L.ola_tracegen_free.argtypes = [C.c_void_p]
         L.ola_tracegen_last_error.restype = C.c_char_p
         L.ola_tracegen_betas.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.ola_tracegen_cpu_steps.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64))]
+        L.ola_tracegen_prog_listing.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint64))]
         _lib = L
     return _lib
 
@@ -51,9 +54,14 @@ def encode(prog):
     return arr
 
 
-def instance(prog, range_bits=4, limb_bits=2, bitwise_beta=None, program_beta=None, prove_program_hash=False, max_steps=1 << 16, reference_quirks=False):
+def instance(prog, range_bits=4, limb_bits=2, bitwise_beta=None, program_beta=None, prove_program_hash=False, max_steps=1 << 16, reference_quirks=False,
+             steps_only=False, timings=None):
     """Same contract as miniexec.instance(prog, ...).  -> (traces, params, compress).  Betas left at None are derived by the
-    generator's own Fiat-Shamir transcript, as the reference does; explicit values (both or neither) are for tests."""
+    generator's own Fiat-Shamir transcript, as the reference does; explicit values (both or neither) are for tests.
+    steps_only: the CPU and the program table are not built -- traces[0] and traces[10] are None -- and a fourth value is returned,
+    dict(steps, cpu_log_n, listing, prog_log_n): what Backend.generate_cpu_trace / generate_prog_trace_steps make the two from.
+    timings: a dict that receives native_s (ola_tracegen_run alone) and copy_s (this binding's copies of the set into numpy arrays)."""
+    import time
     assert (bitwise_beta is None) == (program_beta is None), "give both compress challenges or neither"
     explicit = bitwise_beta is not None
     L = load_library()
@@ -62,21 +70,39 @@ def instance(prog, range_bits=4, limb_bits=2, bitwise_beta=None, program_beta=No
     stor = (C.c_uint64 * 4)(*prog.storage_addr)
     handle = C.c_void_p()
     flags = ((OLA_TRACEGEN_PROVE_PROGRAM_HASH if prove_program_hash else 0) | (OLA_TRACEGEN_EXPLICIT_BETAS if explicit else 0) |
-             (OLA_TRACEGEN_REFERENCE_QUIRKS if reference_quirks else 0))
+             (OLA_TRACEGEN_REFERENCE_QUIRKS if reference_quirks else 0) | (OLA_TRACEGEN_STEPS_ONLY if steps_only else 0))
+    t0 = time.perf_counter()
     rc = L.ola_tracegen_run(ins, len(prog.ins), code, stor, range_bits, limb_bits, bitwise_beta if explicit else 0, program_beta if explicit else 0,
                             max_steps, flags, C.byref(handle))
+    t1 = time.perf_counter()
     if rc != 0:
         raise RuntimeError("ola_tracegen_run: " + L.ola_tracegen_last_error().decode())
     try:
-        traces = []
+        traces, shapes = [], {}
         for t in range(12):
             ncols, log_n, data = C.c_uint32(), C.c_uint32(), C.POINTER(C.c_uint64)()
             assert L.ola_tracegen_table(handle, t, C.byref(ncols), C.byref(log_n), C.byref(data)) == 0
             n = 1 << log_n.value
+            if not data:
+                assert steps_only and t in (T.CPU, T.PROGRAM)
+                shapes[t] = log_n.value
+                traces.append(None)
+                continue
             traces.append(np.ctypeslib.as_array(data, shape=(ncols.value, n)).copy())
+        if steps_only:
+            n_steps, log_n, data = C.c_uint64(), C.c_uint32(), C.POINTER(C.c_uint64)()
+            assert L.ola_tracegen_cpu_steps(handle, C.byref(n_steps), C.byref(data)) == 0
+            steps = (np.ctypeslib.as_array(data, shape=(cpu_steps.STEP_WORDS, n_steps.value)).copy() if n_steps.value
+                     else np.zeros((cpu_steps.STEP_WORDS, 0), dtype=np.uint64))
+            assert L.ola_tracegen_prog_listing(handle, C.byref(log_n), C.byref(data)) == 0 and log_n.value == shapes[T.PROGRAM]
+            listing = np.ctypeslib.as_array(data, shape=(7, 1 << log_n.value)).copy()
+            extra = dict(steps=steps, cpu_log_n=shapes[T.CPU], listing=listing, prog_log_n=shapes[T.PROGRAM])
         betas = (C.c_uint64 * 2)()
         assert L.ola_tracegen_betas(handle, betas) == 0
         bitwise_beta, program_beta = int(betas[0]), int(betas[1])
     finally:
         L.ola_tracegen_free(handle)
-    return traces, [bitwise_beta, program_beta], [0, 0, bitwise_beta, 0, 0, 0, 0, 0, 0, 0, program_beta, 0]
+    if timings is not None:
+        timings["native_s"], timings["copy_s"] = t1 - t0, time.perf_counter() - t1
+    result = traces, [bitwise_beta, program_beta], [0, 0, bitwise_beta, 0, 0, 0, 0, 0, 0, 0, program_beta, 0]
+    return result + (extra,) if steps_only else result

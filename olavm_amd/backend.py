@@ -164,7 +164,11 @@ def load_library():
     L.ola_generate_rc_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
     L.ola_generate_bitwise_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
     L.ola_generate_prog_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
-    for f in ("ola_generate_rc_trace", "ola_generate_bitwise_trace", "ola_generate_prog_trace"):
+    L.ola_generate_cpu_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
+    L.ola_generate_prog_trace_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p,
+                                                C.POINTER(C.c_uint64)]
+    for f in ("ola_generate_rc_trace", "ola_generate_bitwise_trace", "ola_generate_prog_trace", "ola_generate_cpu_trace",
+              "ola_generate_prog_trace_steps"):
         getattr(L, f).restype = C.c_int32
     L.ola_set_shard.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, ALL_GATHER_FN, C.c_void_p]
     L.ola_set_shard_options.argtypes = [C.c_void_p, C.c_uint32]
@@ -200,6 +204,7 @@ EXPORTS = [
     "ola_gpu_collective", "ola_gpu_all_gather_check", "ola_prove_with_traces_cols", "ola_gpu_scope_times", "ola_gpu_upload_stats",
     "ola_gpu_warmup", "ola_gpu_warmup_wait", "ola_gpu_ntt_pass_times",
     "ola_check_constraints", "ola_check_lookup", "ola_generate_rc_trace", "ola_generate_bitwise_trace", "ola_generate_prog_trace",
+    "ola_generate_cpu_trace", "ola_generate_prog_trace_steps",
     "ola_open", "ola_fri_plan", "ola_fri_commit_begin", "ola_fri_commit_next_layer", "ola_fri_commit_finish", "ola_fri_query", "ola_fri_free",
 ]
 
@@ -230,6 +235,8 @@ def format_lookup_report(rep, max_tuples=None):
 
 OLA_WARMUP_PINNED_RING = 1
 OLA_TABLEGEN_REFERENCE_QUIRKS = 1
+OLA_TABLEGEN_ZERO_FILLER = 1
+OLA_CPU_STEP_WORDS = 66
 
 
 def warmup(device=-1, pinned_ring=True, airset=None):
@@ -714,6 +721,41 @@ class Backend:
         po, ret = self._table_out(out, 18, log_n)
         self._chk(self.lib.ola_generate_prog_trace(self.ctx, pe, pp, log_n, int(beta) % (1 << 64), po))
         return ret
+
+    def _steps(self, steps, n_steps):
+        ps, ks, shape = _words(steps, None if n_steps is None else (OLA_CPU_STEP_WORDS, n_steps))
+        if shape is None:
+            return None, None, 0
+        if len(shape) != 2 or shape[0] != OLA_CPU_STEP_WORDS:
+            raise ValueError("steps must be OLA_CPU_STEP_WORDS x n_steps")
+        return (ps if shape[1] else None), ks, int(shape[1])
+
+    def generate_cpu_trace(self, steps, log_n, out=None, n_steps=None):
+        """ola_generate_cpu_trace: the CPU table (94 x 2^log_n) from step records (OLA_CPU_STEP_WORDS x n_steps, column-major; None
+        or zero columns for a table of padding rows).  n_steps must be given when steps is a device address."""
+        ps, ks, n_steps = self._steps(steps, n_steps)
+        po, ret = self._table_out(out, 94, log_n)
+        self._chk(self.lib.ola_generate_cpu_trace(self.ctx, ps, n_steps, log_n, po))
+        return ret
+
+    def generate_prog_trace_steps(self, steps, prog_side, beta, zero_filler=False, out=None, n_steps=None, log_n=None):
+        """ola_generate_prog_trace_steps: the program table (18 x 2^log_n) from step records and the listing side (7 x 2^log_n).
+        -> (table or log_n, executed rows).  More executed rows than 2^log_n: OlaGpuError with the count in its `exec_rows`."""
+        ps, ks, n_steps = self._steps(steps, n_steps)
+        pp, kp, shape = _words(prog_side, None if log_n is None else (7, 1 << log_n))
+        if shape is None or len(shape) != 2 or shape[0] != 7 or shape[1] & (shape[1] - 1) or shape[1] < 2:
+            raise ValueError("prog_side must be 7 x 2^log_n")
+        log_n = int(shape[1]).bit_length() - 1
+        po, ret = self._table_out(out, 18, log_n)
+        rows = C.c_uint64()
+        rc = self.lib.ola_generate_prog_trace_steps(self.ctx, ps, n_steps, pp, log_n, int(beta) % (1 << 64),
+                                                    OLA_TABLEGEN_ZERO_FILLER if zero_filler else 0, po, C.byref(rows))
+        try:
+            self._chk(rc)
+        except OlaGpuError as e:
+            e.exec_rows = rows.value
+            raise
+        return ret, rows.value
 
     def trim(self):
         """Return the context's cached device buffers to the driver (ola_gpu_trim)."""

@@ -536,10 +536,47 @@ void cpu_table(const Run& R, Table& t) {                                        
     for (const auto& pv : pad_vals) std::fill(t.d.begin() + pv[0] * n + live, t.d.begin() + (pv[0] + 1) * n, pv[1]);
 }
 
-void program_table(const Run& R, const u64 code_addr[4], u64 beta, Table& t, std::vector<u64>& words) {
-    words = R.words;
+// OLA_TRACEGEN_STEPS_ONLY: the executed CPU rows as step records (include/ola_gpu.h OLA_CPU_STEP_WORDS: CPU columns
+// COL_ENV_IDX .. the last register selector, then FILTER_TAPE_LOOKING), column-major, instead of the padded 94-column table
+const size_t STEP_COPIED = COL_S_DST_END - COL_ENV_IDX, STEP_WORDS = STEP_COPIED + 1;
+void cpu_steps(const Run& R, Table& shape, std::vector<u64>& steps) {
+    const size_t live = R.nrows();
+    shape.ncols = NUM_CPU_COLS; shape.n = next_pow2(std::max<size_t>(live, 8));
+    steps.resize(STEP_WORDS * live);
+    const size_t B = 256;
+    for (size_t i0 = 0; i0 < live; i0 += B) {
+        const size_t i1 = std::min(live, i0 + B);
+        for (size_t c = 0; c < STEP_WORDS; c++) {
+            const size_t src = c < STEP_COPIED ? COL_ENV_IDX + c : COL_FILTER_TAPE_LOOKING;
+            u64* dst = &steps[c * live];
+            for (size_t i = i0; i < i1; i++) dst[i] = R.row(i)[src];
+        }
+    }
+}
+
+std::vector<u64> listing_words(const Run& R) {
+    std::vector<u64> words = R.words;
     while (words.size() % 8) words.push_back(0);                                   // prog_chunk hashes 8 words at a time
-    const size_t n = next_pow2(std::max<size_t>(std::max(words.size(), R.executed.size()), 8));
+    return words;
+}
+size_t program_table_rows(const Run& R, const std::vector<u64>& words) {
+    return next_pow2(std::max<size_t>(std::max(words.size(), R.executed.size()), 8));
+}
+// ... and the program table's listing side as ola_generate_prog_trace takes it: a0 .. a3, pc, inst, filter (n each)
+void program_listing(const Run& R, const u64 code_addr[4], Table& shape, std::vector<u64>& listing, std::vector<u64>& words) {
+    words = listing_words(R);
+    const size_t n = program_table_rows(R, words);
+    shape.ncols = NUM_PROG_COLS; shape.n = n;
+    listing.assign(7 * n, 0);
+    for (size_t pc = 0; pc < words.size(); pc++) {
+        for (int k = 0; k < 4; k++) listing[k * n + pc] = code_addr[k];
+        listing[4 * n + pc] = pc; listing[5 * n + pc] = words[pc]; listing[6 * n + pc] = 1;
+    }
+}
+
+void program_table(const Run& R, const u64 code_addr[4], u64 beta, Table& t, std::vector<u64>& words) {
+    words = listing_words(R);
+    const size_t n = program_table_rows(R, words);
     t.init(NUM_PROG_COLS, n);
     const u64 b = beta % P, b2 = mulm(b, b), b3 = mulm(b2, b), b4 = mulm(b3, b), b5 = mulm(b4, b);
     auto comp = [&](u64 pc, u64 w) {
@@ -907,6 +944,8 @@ struct OlaTraceSet {
     std::array<Table, 12> tables;
     uint64_t cpu_rows = 0;
     uint64_t bitwise_beta = 0, program_beta = 0;   // the compress challenges the tables were built with
+    bool steps_only = false;                       // OLA_TRACEGEN_STEPS_ONLY: tables CPU and PROGRAM have a shape and no data ...
+    std::vector<u64> steps, listing;               // ... these stand for them
 };
 
 extern "C" {
@@ -945,9 +984,15 @@ int32_t ola_tracegen_run(const OlaInstr* program, size_t n_instr, const uint64_t
         }
         set->program_beta = program_beta % P;
         auto& T = set->tables;
-        cpu_table(R, T[CPU]);
         std::vector<u64> words;
-        program_table(R, code_addr, program_beta, T[PROGRAM], words);
+        set->steps_only = flags & OLA_TRACEGEN_STEPS_ONLY;
+        if (set->steps_only) {
+            cpu_steps(R, T[CPU], set->steps);
+            program_listing(R, code_addr, T[PROGRAM], set->listing, words);
+        } else {
+            cpu_table(R, T[CPU]);
+            program_table(R, code_addr, program_beta, T[PROGRAM], words);
+        }
         std::vector<std::vector<u64>> builtin_rows;
         poseidon_chunk_table(R.psdn, T[POSEIDON_CHUNK], builtin_rows);
         std::vector<std::vector<StorageRow>> prog_reads;
@@ -985,7 +1030,23 @@ int32_t ola_tracegen_table(const OlaTraceSet* set, uint32_t table, uint32_t* nco
     const Table& t = set->tables[table];
     uint32_t l = 0;
     while (((size_t)1 << l) < t.n) l++;
-    *ncols = (uint32_t)t.ncols; *log_n = l; *data = t.d.data();
+    *ncols = (uint32_t)t.ncols; *log_n = l; *data = t.d.empty() ? nullptr : t.d.data();
+    return 0;
+}
+
+int32_t ola_tracegen_cpu_steps(const OlaTraceSet* set, uint64_t* n_steps, const uint64_t** data) {
+    if (!set || !n_steps || !data) { g_err = "invalid argument"; return -1; }
+    if (!set->steps_only) { g_err = "the set was not generated with OLA_TRACEGEN_STEPS_ONLY"; return -1; }
+    *n_steps = set->cpu_rows; *data = set->steps.data();
+    return 0;
+}
+
+int32_t ola_tracegen_prog_listing(const OlaTraceSet* set, uint32_t* log_n, const uint64_t** data) {
+    if (!set || !log_n || !data) { g_err = "invalid argument"; return -1; }
+    if (!set->steps_only) { g_err = "the set was not generated with OLA_TRACEGEN_STEPS_ONLY"; return -1; }
+    uint32_t l = 0;
+    while (((size_t)1 << l) < set->tables[PROGRAM].n) l++;
+    *log_n = l; *data = set->listing.data();
     return 0;
 }
 

@@ -42,4 +42,12 @@ void generate_rc_trace_dev(DeviceCtx* ctx, const u64* vals, const u64* filters, 
 void generate_bitwise_trace_dev(DeviceCtx* ctx, const u64* ops, size_t n_ops, u32 limb_bits, u64 beta, bool reference_quirks, u64* out);
 void generate_prog_trace_dev(DeviceCtx* ctx, const u64* exec, const u64* prog, u32 log_n, u64 beta, u64* out);
 
+// The CPU table (94 x 2^log_n) and the program table with its executed side built on the device, both from step records
+// (ola_generate_cpu_trace / ola_generate_prog_trace_steps): steps is device memory, OLA_CPU_STEP_WORDS x n_steps column-major,
+// n_steps <= 2^log_n and < 2^31.  generate_prog_trace_steps_dev returns false, with the count in *exec_rows and nothing written,
+// when the steps give more than 2^log_n executed rows; otherwise it ends in generate_prog_trace_dev.
+void generate_cpu_trace_dev(DeviceCtx* ctx, const u64* steps, size_t n_steps, u32 log_n, u64* out);
+bool generate_prog_trace_steps_dev(DeviceCtx* ctx, const u64* steps, size_t n_steps, const u64* prog, u32 log_n, u64 beta, bool zero_filler,
+                                   u64* out, u64* exec_rows);
+
 }  // namespace ola

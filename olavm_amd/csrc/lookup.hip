@@ -30,6 +30,7 @@
 #include "gl.cuh"
 #include "lookup.h"
 #include "tablegen_columns.h"
+#include "tablegen_cpu_columns.h"
 
 namespace ola {
 
@@ -406,6 +407,7 @@ void exclusive_sum_dev(hipStream_t stream, void* tmp, size_t tmp_bytes, const u3
 namespace {
 
 namespace tg = olatg;
+namespace tc = olatgc;
 
 __global__ __launch_bounds__(256) void rc_fill_kernel(const u64* __restrict__ vals, const u64* __restrict__ filters, u32 n_rows, u32 range_bits,
                                                       u32 n, u64* __restrict__ out) {
@@ -495,6 +497,126 @@ __global__ __launch_bounds__(256) void prog_fill_kernel(const u64* __restrict__ 
               tg::COL_PROG_FILTER_PROG_CHUNK, out);
 }
 
+// ---- the CPU table and the program table's executed side from step records (generation/cpu.rs:11-218, generation/prog.rs:31-108)
+// A step record is what cpu.rs copies from one `Step`: tc::STEP_COPIED_COLS words = CPU columns COL_ENV_IDX .. the last register
+// selector (cpu.rs:64-105), then filter_tape_looking; records are column-major tc::STEP_WORDS x n_steps.
+__device__ __forceinline__ u64 step_word(const u64* __restrict__ steps, u32 n_steps, u32 col, u32 i) {
+    return gl_canon(steps[(size_t)(col - tc::STEP_FIRST_COL) * n_steps + i]);
+}
+__device__ __forceinline__ bool is_op(u64 opcode, u32 shift) { return opcode == (u64)1 << shift; }
+
+// cpu.rs:20-60, the column of the opcode's selector; 0 (no selector column) for a word that is none of the 25 masks
+__device__ __forceinline__ u32 opcode_selector(u64 opcode) {
+    if (opcode == 0 || (opcode & (opcode - 1)) != 0 || (opcode >> 32) != 0) return 0;
+    switch ((u32)__ffsll((unsigned long long)opcode) - 1u) {
+        case tc::OP_SHIFT_ADD: case tc::OP_SHIFT_MUL: case tc::OP_SHIFT_EQ: case tc::OP_SHIFT_ASSERT: case tc::OP_SHIFT_NEQ:
+            return tc::COL_S_SIMPLE_ARITHMATIC_OP;
+        case tc::OP_SHIFT_MOV: return tc::COL_S_MOV;
+        case tc::OP_SHIFT_JMP: return tc::COL_S_JMP;
+        case tc::OP_SHIFT_CJMP: return tc::COL_S_CJMP;
+        case tc::OP_SHIFT_CALL: return tc::COL_S_CALL;
+        case tc::OP_SHIFT_RET: return tc::COL_S_RET;
+        case tc::OP_SHIFT_MLOAD: return tc::COL_S_MLOAD;
+        case tc::OP_SHIFT_MSTORE: return tc::COL_S_MSTORE;
+        case tc::OP_SHIFT_END: return tc::COL_S_END;
+        case tc::OP_SHIFT_RC: return tc::COL_S_RC;
+        case tc::OP_SHIFT_AND: case tc::OP_SHIFT_OR: case tc::OP_SHIFT_XOR: return tc::COL_S_BITWISE;
+        case tc::OP_SHIFT_NOT: return tc::COL_S_NOT;
+        case tc::OP_SHIFT_GTE: return tc::COL_S_GTE;
+        case tc::OP_SHIFT_POSEIDON: return tc::COL_S_PSDN;
+        case tc::OP_SHIFT_SLOAD: return tc::COL_S_SLOAD;
+        case tc::OP_SHIFT_SSTORE: return tc::COL_S_SSTORE;
+        case tc::OP_SHIFT_TLOAD: return tc::COL_S_TLOAD;
+        case tc::OP_SHIFT_TSTORE: return tc::COL_S_TSTORE;
+        case tc::OP_SHIFT_SCCALL: return tc::COL_S_CALL_SC;
+        default: return 0;
+    }
+}
+
+// thread = row: the record is loaded along rows, all 94 columns are stored along rows; rows n_steps .. n are cpu.rs:180-208's padding
+__global__ __launch_bounds__(256) void cpu_fill_kernel(const u64* __restrict__ steps, u32 n_steps, u32 n, u64* __restrict__ out) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const bool live = i < n_steps;
+    const u32 r = live ? i : n_steps - 1;                                     // padding carries INST and IDX_STORAGE of the last live row
+    const u64 end_mask = (u64)1 << tc::OP_SHIFT_END;
+    out[(size_t)tc::COL_TX_IDX * n + i] = 0;
+    u64 opcode = end_mask, env_idx = 0, is_ext = 0, ext_cnt = 0, op1_imm = 0, op0 = 0, op1 = 0;
+#pragma unroll
+    for (u32 c = tc::STEP_FIRST_COL; c < tc::STEP_FIRST_COL + tc::STEP_COPIED_COLS; c++) {
+        u64 v = 0;
+        if (live) v = step_word(steps, n_steps, c, i);
+        else if (c == tc::COL_OPCODE) v = end_mask;
+        else if (c == tc::COL_INST) v = n_steps ? step_word(steps, n_steps, c, r) : (u64)1048576;
+        else if (c == tc::COL_IDX_STORAGE) v = n_steps ? step_word(steps, n_steps, c, r) : 0;
+        out[(size_t)c * n + i] = v;
+        if (c == tc::COL_OPCODE) opcode = v;
+        if (c == tc::COL_ENV_IDX) env_idx = v;
+        if (c == tc::COL_IS_EXT_LINE) is_ext = v;
+        if (c == tc::COL_EXT_CNT) ext_cnt = v;
+        if (c == tc::COL_OP1_IMM) op1_imm = v;
+        if (c == tc::COL_OP0) op0 = v;
+        if (c == tc::COL_OP1) op1 = v;
+    }
+    const u32 sel = opcode_selector(opcode);
+#pragma unroll
+    for (u32 c = tc::COL_S_SIMPLE_ARITHMATIC_OP; c <= tc::COL_S_CALL_SC; c++) out[(size_t)c * n + i] = c == sel ? 1 : 0;
+    const bool entry = env_idx == 0;
+    const bool end = is_op(opcode, tc::OP_SHIFT_END), sload = is_op(opcode, tc::OP_SHIFT_SLOAD), sstore = is_op(opcode, tc::OP_SHIFT_SSTORE);
+    const bool sccall = is_op(opcode, tc::OP_SHIFT_SCCALL), mem = is_op(opcode, tc::OP_SHIFT_MLOAD) || is_op(opcode, tc::OP_SHIFT_MSTORE);
+    // cpu.rs:119-132 ext_length; TLOAD's op0 * op1 + (1 - op0) in the field
+    u64 ext_length = 0;
+    if (sload || sstore || sccall || (end && !entry)) ext_length = 1;
+    else if (is_op(opcode, tc::OP_SHIFT_TLOAD)) ext_length = gl_add(gl_mul(op0, op1), gl_sub(1, op0));
+    else if (is_op(opcode, tc::OP_SHIFT_TSTORE)) ext_length = op1;
+    out[(size_t)tc::COL_IS_ENTRY_SC * n + i] = entry ? 1 : 0;
+    out[(size_t)tc::COL_IS_NEXT_LINE_DIFF_INST * n + i] = (!live || ext_length == ext_cnt) ? 1 : 0;
+    out[(size_t)tc::COL_IS_NEXT_LINE_SAME_TX * n + i] = (!live || (entry && end)) ? 0 : 1;
+    out[(size_t)tc::COL_FILTER_TAPE_LOOKING * n + i] = live ? gl_canon(steps[(size_t)tc::STEP_FILTER_TAPE_LOOKING * n_steps + i]) : 0;
+    out[(size_t)tc::IS_SCCALL_EXT_LINE * n + i] = (live && sccall && ext_cnt == 1) ? 1 : 0;
+    out[(size_t)tc::COL_IS_STORAGE_EXT_LINE * n + i] = (live && (sload || sstore) && is_ext == 1) ? 1 : 0;
+    out[(size_t)tc::COL_FILTER_SCCALL_END * n + i] = (live && end && is_ext == 1) ? 1 : 0;
+    out[(size_t)tc::COL_FILTER_LOOKING_PROG_IMM * n + i] = (live && is_ext != 1 && (mem || op1_imm == 1)) ? 1 : 0;
+    out[(size_t)tc::COL_IS_PADDING * n + i] = live ? 0 : 1;
+}
+
+// prog.rs:31-44: rows a step gives to the executed side -- none for an extension line, two when an immediate word follows
+__device__ __forceinline__ u32 step_exec_rows(const u64* __restrict__ steps, u32 n_steps, u32 i) {
+    if (step_word(steps, n_steps, tc::COL_IS_EXT_LINE, i) == 1) return 0;
+    const u64 opcode = step_word(steps, n_steps, tc::COL_OPCODE, i);
+    const bool two = step_word(steps, n_steps, tc::COL_OP1_IMM, i) == 1 || is_op(opcode, tc::OP_SHIFT_MLOAD) || is_op(opcode, tc::OP_SHIFT_MSTORE);
+    return two ? 2 : 1;
+}
+// counts[n_steps] = 0: the exclusive scan then ends with the total
+__global__ __launch_bounds__(256) void exec_count_kernel(const u64* __restrict__ steps, u32 n_steps, u32* __restrict__ counts) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i <= n_steps) counts[i] = i < n_steps ? step_exec_rows(steps, n_steps, i) : 0;
+}
+// prog.rs:59-108 into a side of ola_generate_prog_trace: a0 .. a3, pc, inst, filter (n each); every row written is below n
+__global__ __launch_bounds__(256) void exec_scatter_kernel(const u64* __restrict__ steps, u32 n_steps, const u32* __restrict__ at, u32 n,
+                                                           u64* __restrict__ exec) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_steps) return;
+    const u32 rows = at[i + 1] - at[i], row = at[i];
+    if (rows == 0 || row + rows > n) return;
+    const u64 pc = step_word(steps, n_steps, tc::COL_PC, i);
+    for (u32 k = 0; k < rows; k++) {
+#pragma unroll
+        for (u32 j = 0; j < 4; j++) exec[(size_t)j * n + row + k] = step_word(steps, n_steps, tc::COL_ADDR_CODE_RANGE_START + j, i);
+        exec[(size_t)4 * n + row + k] = k ? gl_add(pc, 1) : pc;
+        exec[(size_t)5 * n + row + k] = step_word(steps, n_steps, k ? tc::COL_IMM_VAL : tc::COL_INST, i);
+        exec[(size_t)6 * n + row + k] = 1;
+    }
+}
+// rows total .. n: executed row 0 again with filter 0 (this project's filler, which keeps the lookup's inputs inside the listing), or zeros
+__global__ __launch_bounds__(256) void exec_filler_kernel(u32 total, u32 repeat_row0, u32 n, u64* __restrict__ exec) {
+    const u32 i = total + blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+#pragma unroll
+    for (u32 j = 0; j < 6; j++) exec[(size_t)j * n + i] = repeat_row0 ? exec[(size_t)j * n] : 0;
+    exec[(size_t)6 * n + i] = 0;
+}
+
 u32 log2_rows(u64 rows) {            // next power of two, at least 2 (the reference's ext_trace_len)
     u32 log_n = 1;
     while (((u64)1 << log_n) < rows) log_n++;
@@ -543,6 +665,40 @@ void generate_prog_trace_dev(DeviceCtx* ctx, const u64* exec, const u64* prog, u
     const PermutedPair pair = {out + (size_t)tg::COL_PROG_EXEC_COMP_PROG * n, 0, out + (size_t)tg::COL_PROG_EXEC_COMP_PROG_PERM * n,
                                out + (size_t)tg::COL_PROG_COMP_PROG_PERM * n};
     permuted_cols_batch_dev(ctx, n, &table, 1, &pair, 1);
+}
+
+void generate_cpu_trace_dev(DeviceCtx* ctx, const u64* steps, size_t n_steps, u32 log_n, u64* out) {
+    const u32 n = 1u << log_n;
+    hipLaunchKernelGGL(cpu_fill_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, steps, (u32)n_steps, n, out);
+    HIP_CHECK(hipGetLastError());
+}
+
+bool generate_prog_trace_steps_dev(DeviceCtx* ctx, const u64* steps, size_t n_steps_, const u64* prog, u32 log_n, u64 beta, bool zero_filler,
+                                   u64* out, u64* exec_rows) {
+    const u32 n = 1u << log_n, n_steps = (u32)n_steps_;
+    hipStream_t stream = ctx->stream;
+    Scratch mem(ctx);
+    u32 total = 0;
+    u32* at = nullptr;
+    if (n_steps) {
+        u32* counts = mem.alloc<u32>((size_t)n_steps + 1);
+        at = mem.alloc<u32>((size_t)n_steps + 1);
+        hipLaunchKernelGGL(exec_count_kernel, dim3(blocks((size_t)n_steps + 1)), dim3(256), 0, stream, steps, n_steps, counts);
+        HIP_CHECK(hipGetLastError());
+        scan_exclusive(mem, stream, counts, at, 0u, (size_t)n_steps + 1, rocprim::plus<u32>());
+        HIP_CHECK(hipMemcpyAsync(&total, at + n_steps, sizeof(u32), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+    }
+    *exec_rows = total;
+    if (total > n) return false;
+    u64* exec = mem.alloc<u64>((size_t)7 * n);
+    if (total) hipLaunchKernelGGL(exec_scatter_kernel, dim3(blocks(n_steps)), dim3(256), 0, stream, steps, n_steps, at, n, exec);
+    if (total < n)
+        hipLaunchKernelGGL(exec_filler_kernel, dim3(blocks(n - total)), dim3(256), 0, stream, total, (total && !zero_filler) ? 1u : 0u, n, exec);
+    HIP_CHECK(hipGetLastError());          // scatter, filler
+    generate_prog_trace_dev(ctx, exec, prog, log_n, beta, out);
+    HIP_CHECK(hipGetLastError());
+    return true;
 }
 
 }  // namespace ola

@@ -19,6 +19,7 @@
 #include "poseidon_host.h"
 #include "lookup.h"
 #include "tablegen_columns.h"
+#include "tablegen_cpu_columns.h"
 #include "peer_group.h"
 #include "rccl_carrier.h"
 
@@ -1342,6 +1343,45 @@ int32_t ola_generate_prog_trace(OlaCtx* ctx, const uint64_t* exec, const uint64_
     const u64* d_prog = table_input(ctx, mem, prog, 7 * n);
     TableOutput t(ctx, mem, out, (size_t)olatg::NUM_PROG_COLS * n);
     generate_prog_trace_dev(&ctx->dev, d_exec, d_prog, log_n, beta, t.dev);
+    t.finish();
+    OLA_CATCH
+}
+
+static_assert(OLA_CPU_STEP_WORDS == olatgc::STEP_WORDS, "include/ola_gpu.h and tablegen_cpu_columns.h disagree on the step record");
+int32_t ola_generate_cpu_trace(OlaCtx* ctx, const uint64_t* steps, size_t n_steps, uint32_t log_n, uint64_t* out) {
+    OLA_TRY
+    require(out && (steps || n_steps == 0), "null pointer");
+    require(log_n >= 1 && log_n <= 26, "log_n out of range (1 .. 26)");
+    require(n_steps <= ((size_t)1 << log_n), "more steps than 2^log_n rows");
+    require_context(ctx);
+    OLA_ON_DEVICE(ctx);
+    DevBuf mem(&ctx->dev);
+    const u64* d_steps = table_input(ctx, mem, steps, (size_t)OLA_CPU_STEP_WORDS * n_steps);
+    TableOutput t(ctx, mem, out, (size_t)olatgc::NUM_CPU_COLS << log_n);
+    generate_cpu_trace_dev(&ctx->dev, d_steps, n_steps, log_n, t.dev);
+    t.finish();
+    OLA_CATCH
+}
+
+int32_t ola_generate_prog_trace_steps(OlaCtx* ctx, const uint64_t* steps, size_t n_steps, const uint64_t* prog, uint32_t log_n, uint64_t beta,
+                                      uint32_t flags, uint64_t* out, uint64_t* exec_rows_out) {
+    OLA_TRY
+    require(prog && out && exec_rows_out && (steps || n_steps == 0), "null pointer");
+    require(log_n >= 1 && log_n <= 26, "log_n out of range (1 .. 26)");
+    require((flags & ~(uint32_t)OLA_TABLEGEN_ZERO_FILLER) == 0, "unknown flag");
+    require(n_steps < ((size_t)1 << 31), "2^31 steps or more");
+    require_context(ctx);
+    OLA_ON_DEVICE(ctx);
+    const size_t n = (size_t)1 << log_n;
+    DevBuf mem(&ctx->dev);
+    const u64* d_steps = table_input(ctx, mem, steps, (size_t)OLA_CPU_STEP_WORDS * n_steps);
+    const u64* d_prog = table_input(ctx, mem, prog, 7 * n);
+    TableOutput t(ctx, mem, out, (size_t)olatg::NUM_PROG_COLS * n);
+    u64 exec_rows = 0;
+    const bool fits = generate_prog_trace_steps_dev(&ctx->dev, d_steps, n_steps, d_prog, log_n, beta, (flags & OLA_TABLEGEN_ZERO_FILLER) != 0, t.dev,
+                                                    &exec_rows);
+    *exec_rows_out = exec_rows;
+    require(fits, "the steps give more executed rows than 2^log_n (the count is in *exec_rows_out)");
     t.finish();
     OLA_CATCH
 }

@@ -7,10 +7,15 @@ count = 70000 gives 980 k executed CPU rows (2^20), 280 k memory cells, a 2^21-r
 immediate word) and 280 k range-checked sort values.  The proof is checked with the oracle's verifier; with OLA_TIMING=1 the
 library prints its per-phase times (named after the reference's `timed!` scopes) to stderr.
 
-    python tools/bench_prove_real.py [count] [reps] [--json out.json] [--phases] [--oracle] [--python] [--storage-slots N] [--hasher blake3]
+    python tools/bench_prove_real.py [count] [reps] [--json out.json] [--phases] [--oracle] [--python] [--storage-slots N] [--hasher blake3] [--steps] [--shape readme]
 
---hasher blake3 proves under the reference's Blake3GoldilocksConfig (the configuration of its README numbers): BLAKE3 Merkle
-trees and challenger, Poseidon proof of work; the oracle checks under the same configuration.
+--steps compares the two ways from an execution to proof bytes, taken in alternation `reps` times in this process: the table path
+(the native generator fills all twelve tables, they are uploaded and proven) and the step path (the generator runs with
+OLA_TRACEGEN_STEPS_ONLY, the step records go up, ola_generate_cpu_trace and ola_generate_prog_trace_steps write the CPU and the program
+table into HBM and the proof runs on them as resident tables).  Timed apart: the native generator's call (ola_tracegen_run), the
+Python binding's copies of its output into numpy arrays (harness cost, larger on the table path: it copies the two tables the step
+path never builds), device table generation, and the proof.  --shape readme runs the README's Fibonacci shape
+(miniexec.fibonacci_loop(47, 3000): 864 002 CPU rows, every other table small) instead of the memory program.
 """
 import json
 import os
@@ -33,10 +38,18 @@ def main():
     t0 = time.time()
     gen = M if "--python" in sys.argv else fastexec          # the native generator reproduces the Python executor word for word
     slots = int(sys.argv[sys.argv.index("--storage-slots") + 1]) if "--storage-slots" in sys.argv else 0
+    shape = sys.argv[sys.argv.index("--shape") + 1] if "--shape" in sys.argv else "memory"
+    if shape not in ("readme", "memory"):
+        raise SystemExit("--shape is readme or memory")
     if slots:       # BASELINE config 4: a Poseidon table of 1026 * slots live rows next to the CPU / memory tables
         prog, kw = M.storage_heavy_program(slots, count), {"prove_program_hash": True}
+    elif shape == "readme":
+        prog, kw = M.fibonacci_loop(47, 3000), {}
     else:
         prog, kw = M.memory_program(count), {}
+    if "--steps" in sys.argv:
+        return steps_against_tables(prog, kw, blob, reps, hasher, out,
+                                    "fibonacci_loop(47, 3000)" if shape == "readme" else "memory_program(%d)" % count)
     traces, params, compress = gen.instance(prog, range_bits=16, limb_bits=8, max_steps=1 << 24, **kw)
     gen_s = time.time() - t0
     heights = [int(t.shape[1]).bit_length() - 1 for t in traces]
@@ -79,6 +92,56 @@ def main():
                        "oracle_verifier_rc": rc, "oracle_cpu_port_prove_s": None if oracle_s is None else round(oracle_s, 1)}, f, indent=1)
     if rc != 0:
         raise SystemExit(1)
+
+
+def steps_against_tables(prog, kw, blob, reps, hasher, out, workload):
+    import numpy as np
+    import torch
+    from olavm_amd.air import fastexec, ola_tables as T
+    from olavm_amd.backend import Backend
+    be = Backend(device=0, hasher=hasher)
+    runs = {"table_path": [], "step_path": []}
+    proofs = {}
+    for rep in range(reps + 1):                                  # rep 0 warms both paths up and is not kept
+        tm = {}
+        t0 = time.perf_counter()
+        traces, params, compress = fastexec.instance(prog, range_bits=16, limb_bits=8, max_steps=1 << 24, timings=tm, **kw)
+        t1 = time.perf_counter()
+        proofs["table_path"] = bytes(be.prove_with_traces(blob, traces, params, compress))
+        t2 = time.perf_counter()
+        a = {"native_trace_generation_s": tm["native_s"], "binding_copies_s": tm["copy_s"], "device_table_generation_s": 0.0, "prove_s": t2 - t1,
+             "total_s": t2 - t0, "total_without_binding_copies_s": t2 - t0 - tm["copy_s"]}
+        del traces
+        t0 = time.perf_counter()
+        lean, params, compress, rec = fastexec.instance(prog, range_bits=16, limb_bits=8, max_steps=1 << 24, steps_only=True, timings=tm, **kw)
+        t1 = time.perf_counter()
+        d_cpu = torch.empty((T.NUM_CPU_COLS, 1 << rec["cpu_log_n"]), dtype=torch.int64, device="cuda")
+        d_pg = torch.empty((T.NUM_PROG_COLS, 1 << rec["prog_log_n"]), dtype=torch.int64, device="cuda")
+        d_steps = torch.from_numpy(rec["steps"].view(np.int64)).cuda()
+        torch.cuda.synchronize()                                 # complete before the library's stream reads and writes them
+        be.generate_cpu_trace(d_steps, rec["cpu_log_n"], out=d_cpu)
+        be.generate_prog_trace_steps(d_steps, rec["listing"], params[1], out=d_pg)
+        t2 = time.perf_counter()
+        lean[T.CPU], lean[T.PROGRAM] = d_cpu, d_pg
+        proofs["step_path"] = bytes(be.prove_with_traces(blob, lean, params, compress))
+        t3 = time.perf_counter()
+        b = {"native_trace_generation_s": tm["native_s"], "binding_copies_s": tm["copy_s"], "device_table_generation_s": t2 - t1, "prove_s": t3 - t2,
+             "total_s": t3 - t0, "total_without_binding_copies_s": t3 - t0 - tm["copy_s"]}
+        del lean, d_cpu, d_pg, d_steps
+        assert proofs["step_path"] == proofs["table_path"], "the two paths give different proof bytes"
+        if rep:
+            runs["table_path"].append(a)
+            runs["step_path"].append(b)
+        print(("warm-up " if not rep else "") + "table path %s" % {k: round(v, 3) for k, v in a.items()}, flush=True)
+        print(("warm-up " if not rep else "") + "step path  %s" % {k: round(v, 3) for k, v in b.items()}, flush=True)
+    be.close()
+    med = lambda path, key: sorted(r[key] for r in runs[path])[len(runs[path]) // 2]
+    summary = {path: {key: round(med(path, key), 3) for key in runs[path][0]} for path in runs}
+    print(json.dumps(summary), flush=True)
+    if out:
+        os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+        json.dump({"workload": workload + ", ola_stark(range_bits=16, limb_bits=8)", "hasher": hasher, "reps": reps,
+                   "proof_bytes_identical": True, "median": summary, "runs": runs}, open(out, "w"), indent=1)
 
 
 if __name__ == "__main__":

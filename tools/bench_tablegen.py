@@ -1,4 +1,5 @@
-"""Times ola_generate_rc_trace / ola_generate_bitwise_trace / ola_generate_prog_trace with resident inputs and outputs, next to
+"""Times ola_generate_rc_trace / ola_generate_bitwise_trace / ola_generate_prog_trace -- and ola_generate_cpu_trace /
+ola_generate_prog_trace_steps, the cases cpu:20 cpu:22 progsteps:21 progsteps:23 -- with resident inputs and outputs, next to
 the same derived columns obtained without them: one ola_permuted_cols_dev call per pair (device) plus numpy for the other columns
 (host), and next to the oracle's sequential permuted_cols on one host core (as tools/bench_lookup.py measures it).
 
@@ -22,10 +23,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 
-from olavm_amd.air import ola_tables as T
+from olavm_amd.air import cpu_steps as S, ola_tables as T
 from olavm_amd.air.dsl import P
 
 CASES = ["bitwise:18", "rc:16", "rc:21", "prog:20", "prog:23"]
+STEP_CASES = ["cpu:20", "cpu:22", "progsteps:21", "progsteps:23"]       # named on the command line
 FN = (lambda x, y: x & y, lambda x, y: x | y, lambda x, y: x ^ y)
 
 
@@ -44,12 +46,26 @@ def inputs(kind, log_n, rng):
         res = np.choose(which, [x & y, x | y, x ^ y])
         tag = np.array([T.op_mask("AND"), T.op_mask("OR"), T.op_mask("XOR")], dtype=np.uint64)[which]
         return (np.stack([np.ones(rows, dtype=np.uint64), tag, x, y, res]),), {"limb_bits": 8, "beta": 0x123456789ABCDEF}
+    if kind == "cpu":          # 15/16 of the rows live, every word of the record random
+        return (rng.integers(0, P, (S.STEP_WORDS, n - n // 16), dtype=np.uint64),), {"log_n": log_n}
     listed = 3 * n // 4
     pr = np.zeros((7, n), dtype=np.uint64)
     pr[:4, :listed] = rng.integers(0, P, (4, 1), dtype=np.uint64)
     pr[4, :listed] = np.arange(listed, dtype=np.uint64)
     pr[5, :listed] = rng.integers(0, P, listed, dtype=np.uint64)
     pr[6, :listed] = 1
+    if kind == "progsteps":    # 5/8 n steps, every fifth an extension line, half of the others with an immediate word: about 0.75 n executed rows
+        k = 5 * n // 8
+        steps = np.zeros((S.STEP_WORDS, k), dtype=np.uint64)
+        w = lambda col: col - S.STEP_FIRST_COL
+        pick = rng.integers(0, listed // 2, k)
+        steps[w(T.COL_ADDR_CODE_RANGE.start):w(T.COL_ADDR_CODE_RANGE.stop)] = pr[:4, :1]
+        steps[w(T.COL_PC)], steps[w(T.COL_INST)] = pr[4, pick], pr[5, pick]
+        steps[w(T.COL_IMM_VAL)] = pr[5, (pick + 1) % listed]
+        steps[w(T.COL_OPCODE)] = T.op_mask("ADD")
+        steps[w(T.COL_OP1_IMM)] = rng.integers(0, 2, k)
+        steps[w(T.COL_IS_EXT_LINE), ::5] = 1
+        return (steps, pr), {"beta": 0x123456789ABCDEF}
     ex = np.ascontiguousarray(pr[:, rng.integers(0, listed // 2, n)])
     return (ex, pr), {"beta": 0x123456789ABCDEF}
 
@@ -66,10 +82,14 @@ def call(be, kind, dev, kw, out):
         return be.generate_rc_trace(dev[0], dev[1], range_bits=kw["range_bits"], out=out)
     if kind == "bitwise":
         return be.generate_bitwise_trace(dev[0], kw["beta"], limb_bits=kw["limb_bits"], out=out)
+    if kind == "cpu":
+        return be.generate_cpu_trace(dev[0], kw["log_n"], out=out)
+    if kind == "progsteps":
+        return be.generate_prog_trace_steps(dev[0], dev[1], kw["beta"], out=out)[0]
     return be.generate_prog_trace(dev[0], dev[1], kw["beta"], out=out)
 
 
-NCOLS = {"rc": T.COL_NUM_RC, "bitwise": T.COL_NUM_BITWISE, "prog": T.NUM_PROG_COLS}
+NCOLS = {"rc": T.COL_NUM_RC, "bitwise": T.COL_NUM_BITWISE, "prog": T.NUM_PROG_COLS, "cpu": T.NUM_CPU_COLS, "progsteps": T.NUM_PROG_COLS}
 
 
 def pairs_of(kind):
@@ -77,7 +97,9 @@ def pairs_of(kind):
     if kind == "rc":
         return [(T.RC_LIMB_LO, T.RC_FIX_RANGE_CHECK_U16, T.RC_LIMB_LO_PERMUTED, T.RC_FIX_RANGE_CHECK_U16_PERMUTED_LO),
                 (T.RC_LIMB_HI, T.RC_FIX_RANGE_CHECK_U16, T.RC_LIMB_HI_PERMUTED, T.RC_FIX_RANGE_CHECK_U16_PERMUTED_HI)]
-    if kind == "prog":
+    if kind == "cpu":
+        return []
+    if kind in ("prog", "progsteps"):
         return [(T.COL_PROG_EXEC_COMP_PROG, T.COL_PROG_COMP_PROG, T.COL_PROG_EXEC_COMP_PROG_PERM, T.COL_PROG_COMP_PROG_PERM)]
     out = []
     for g, (src, perm) in enumerate(((T.BW_OP0_LIMBS, T.BW_OP0_LIMBS_PERMUTED), (T.BW_OP1_LIMBS, T.BW_OP1_LIMBS_PERMUTED), (T.BW_RES_LIMBS, T.BW_RES_LIMBS_PERMUTED))):
@@ -150,6 +172,13 @@ def measure(kind, log_n, runs):
 
     rec = {"table": kind, "log_n": log_n, "runs": runs}
     rec["call_device_ms"], rec["call_wall_ms"] = timed(lambda: call(be, kind, dev, kw, out))
+    if kind in ("cpu", "progsteps"):       # no host-side counterpart to compare with: the table path never had these inputs
+        rec["steps"] = int(host[0].shape[1])
+        if kind == "cpu":                  # bytes read and written: the records and the table
+            rec["effective_GBps"] = 8 * (S.STEP_WORDS * rec["steps"] + T.NUM_CPU_COLS * n) / (rec["call_device_ms"] * 1e6)
+        rec["table_words"] = NCOLS[kind] * n
+        be.close()
+        return rec
     # the same permuted columns pair by pair, from the columns the call just wrote
     pairs = pairs_of(kind)
     tmp = torch.empty((2, n), dtype=torch.int64, device="cuda")

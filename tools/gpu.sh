@@ -250,11 +250,15 @@ PY
     matrix)      timeout 1200 python tools/bench_ntt_matrix.py --out $O/ntt_matrix.json 2>&1 | tail -40 ;;
     prof_bench)  cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o p -- python $R/bench.py --full --steps 20 --warmup 5 > $R/$O/bench.json 2> $R/$O/err.txt; cd $R
                  f=$(find $O/prof -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp "$f" $O/kernel_stats.csv && head -25 $O/kernel_stats.csv | cut -c1-160 ;;
-    tablegen)    # the range-check, bitwise and program tables completed in HBM: their tests (the batch of one included), then the timings and launch counts
+    tablegen)    # the range-check, bitwise and program tables completed in HBM, the CPU and program tables from step records: their tests (the batch of one included), then the timings and launch counts
                  # pipefail: the chain must see pytest's status, not tee's -- nothing more is started on the card after a fault or a time limit
                  ( set -o pipefail
-                   timeout -k 10 900 python -m pytest tests/test_gpu_tablegen.py tests/test_gpu_lookup.py -x -q 2>&1 | tail -15 | tee $O/pytest.log && \
-                   timeout -k 10 1500 python tools/bench_tablegen.py --json $O/tablegen.json 2>&1 | grep -v amdgpu | tee $O/tablegen.txt ) ;;
+                   timeout -k 10 900 python -m pytest tests/test_gpu_tablegen.py tests/test_gpu_lookup.py tests/test_gpu_cpu_tablegen.py tests/test_ref_cpu_steps.py -x -q 2>&1 | tail -15 | tee $O/pytest.log && \
+                   timeout -k 10 1500 python tools/bench_tablegen.py --json $O/tablegen.json 2>&1 | grep -v amdgpu | tee $O/tablegen.txt && \
+                   timeout -k 10 600 python tools/bench_tablegen.py --json $O/tablegen_steps.json cpu:20 cpu:22 progsteps:21 progsteps:23 2>&1 | grep -v amdgpu | tee $O/tablegen_steps.txt && \
+                   timeout -k 10 600 python tools/bench_prove_real.py 0 3 --steps --shape readme --json $O/steps_vs_tables_readme.json 2>&1 | grep -v amdgpu | tee $O/steps_vs_tables_readme.txt && \
+                   timeout -k 10 900 python tools/bench_prove_real.py 70000 3 --steps --json $O/steps_vs_tables_2p20.json 2>&1 | grep -v amdgpu | tee $O/steps_vs_tables_2p20.txt && \
+                   timeout -k 10 1500 python tools/bench_prove_real.py 290000 3 --steps --json $O/steps_vs_tables_2p22.json 2>&1 | grep -v amdgpu | tee $O/steps_vs_tables_2p22.txt ) ;;
     check_lookup) # ola_check_lookup: its tests, then the CPU -> memory and CPU -> program lookups of a 2^22-row executed instance, valid and with one looked row dropped
                  ( set -o pipefail
                    timeout -k 10 600 python -m pytest tests/test_gpu_check_lookup.py -x -q 2>&1 | tail -15 | tee $O/pytest.log && \

@@ -262,6 +262,11 @@ class Params(list):
     ret = None
 
 
+class Continue(Exception):
+    """`continue` of a `for` loop (generation/prog.rs:61).  Only `for` catches it: a `continue` inside `while` / `loop` is not implemented
+    and ends the run with this exception uncaught."""
+
+
 class Return(Exception):
     def __init__(self, v):
         self.v = v
@@ -1470,7 +1475,10 @@ class Interp:
             base = self.ev(n[1], env, src)
             return self.field(base, n[2], src, n[3])
         if k == "tfield":
-            return self.ev(n[1], env, src)[n[2]]
+            v = self.ev(n[1], env, src)
+            if isinstance(v, Fe) and n[2] == 0:            # GoldilocksField(pub u64): `.0` is the word
+                return TInt(v.v, 64)
+            return v[n[2]]
         if k == "tuple":
             return tuple(self.ev(x, env, src) for x in n[1])
         if k == "array":
@@ -1577,9 +1585,10 @@ class Interp:
             inner = dict(env)
             inner["__declared__"] = set()       # a fresh scope: what the enclosing block declared is OUTER here
             inner["__assigned__"] = set()
-        r = self.ev(node, inner, src)
-        self.write_back(env, inner)
-        return r
+        try:
+            return self.ev(node, inner, src)
+        finally:                            # also when a `continue` or `return` leaves the scope: what it assigned so far is kept
+            self.write_back(env, inner)
 
     @staticmethod
     def write_back(env, inner):
@@ -1630,7 +1639,10 @@ class Interp:
                 inner["__declared__"] = set(pattern_names(s[1]))
                 inner["__assigned__"] = set()
                 self.bind(s[1], item, inner, src)
-                self.ev(s[3], inner, src)
+                try:
+                    self.ev(s[3], inner, src)
+                except Continue:        # every scope it left has written back (block, scoped): the iteration ends as Rust's does
+                    pass
                 self.write_back(env, inner)
             return None
         if k == "while":
@@ -1744,6 +1756,8 @@ class Interp:
             return Enum(segs[-2], name)                   # OlaOpcode::ADD
         if re.match(r"^[a-z_]", name) and len(segs) >= 2:
             return FnRef(segs, env, src, line)            # `.map(F::Extension::from_basefield)`: a function named, not called
+        if segs == ["continue"]:
+            raise Continue()
         raise self.err(src, line, f"unknown name `{'::'.join(segs)}`")
 
     def call(self, n, env, src):
@@ -2899,6 +2913,91 @@ def tracegen_bitwise(reference, ops=BITWISE_OPS):
             "rows_head": [[c[i].v for c in tr] for i in range(len(ops))]}
 
 
+CPU_STEPS_FIXTURE = os.path.join(ROOT, "tests", "golden", "ref_cpu_steps.json")
+CPU_STEPS_LENGTHS = (37, 32, 0)
+
+
+def cpu_steps_synthetic():
+    """37 synthetic `Step`s (as dicts of integers) that reach every branch of generation/cpu.rs:62-179 and generation/prog.rs:31-108: each of
+    the 25 opcodes as a main line, an opcode word of 0, extension lines of SLOAD / SSTORE / SCCALL / TLOAD / TSTORE with ext_cnt equal and
+    unequal to ext_length, TLOAD with op0 in {0, 1} and op1 in {1, 3}, END with env_idx 0 and 2 with and without is_ext_line, op1_imm 0 and 1,
+    MLOAD and MSTORE with op1_imm = 0, filter_tape_looking set"""
+    shift = {"ADD": 31, "MUL": 30, "EQ": 29, "ASSERT": 28, "MOV": 27, "JMP": 26, "CJMP": 25, "CALL": 24, "RET": 23, "MLOAD": 22, "MSTORE": 21, "END": 20,
+             "RC": 19, "AND": 18, "OR": 17, "XOR": 16, "NOT": 15, "NEQ": 14, "GTE": 13, "POSEIDON": 12, "SLOAD": 11, "SSTORE": 10, "TLOAD": 9,
+             "TSTORE": 8, "SCCALL": 7}
+    words = iter(stream_for(9100, 5, 37 * 64))
+    addrs = ([11, 22, 33, 44], [55, 66, 77, 88])
+    steps = []
+
+    def step(op, ext=0, cnt=0, env=0, imm=0, op0=None, op1=None, tape=0):
+        k = len(steps)
+        w = lambda: next(words)
+        onehot = lambda j: [int(i == j) for i in range(10)]
+        carrier = lambda: [w() for _ in range(10)]
+        steps.append(dict(
+            env_idx=env, call_sc_cnt=k % 3, clk=k, pc=3 * k, tp=w() % 1000, addr_storage=[w() for _ in range(4)], addr_code=list(addrs[k % 2]),
+            instruction=0 if ext else w(), immediate_data=w() if (imm or op in ("MLOAD", "MSTORE")) else 0, opcode=(1 << shift[op]) if op else 0,
+            op1_imm=imm, regs=[w() for _ in range(10)], op0=w() if op0 is None else op0, op1=w() if op1 is None else op1, dst=w(), aux0=w(), aux1=w(),
+            op0_reg_sel=carrier() if ext else onehot(k % 10), op1_reg_sel=carrier() if ext else ([0] * 10 if imm else onehot((k + 3) % 10)),
+            dst_reg_sel=carrier() if ext else onehot((k + 7) % 10), is_ext_line=ext, ext_cnt=cnt, filter_tape_looking=tape, storage_access_idx=k // 4))
+    # extension lines and the END variants first, so that the run of 32 has them too
+    step("SLOAD", ext=1, cnt=1)
+    step("SSTORE", ext=1, cnt=2)
+    step("SCCALL", ext=1, cnt=1)
+    step("TLOAD", ext=1, cnt=3, op0=1, op1=3, tape=1)
+    step("TLOAD", ext=1, cnt=1, op0=0, op1=3, tape=1)
+    step("TLOAD", ext=1, cnt=2, op0=1, op1=1, tape=1)
+    step("TLOAD", ext=1, cnt=1, op0=0, op1=1, tape=1)
+    step("TSTORE", ext=1, cnt=1, op1=2, tape=1)
+    step("END", env=2)
+    step("END", env=2, ext=1, cnt=1)
+    step("END", env=0, ext=1)
+    step(None)
+    for k, op in enumerate(sorted(shift, key=lambda o: -shift[o])):
+        imm = int(op in ("ADD", "MOV", "JMP", "CALL", "AND", "TSTORE"))
+        if op == "TLOAD":
+            step(op, op0=1, op1=3)
+        elif op == "TSTORE":
+            step(op, imm=imm, op1=2)
+        else:
+            step(op, imm=imm)
+    assert len(steps) == 37
+    return steps
+
+
+def cpu_steps_record(s):
+    """the 66 words of include/ola_gpu.h's step record: CPU columns 1 .. 65 (cpu/columns.rs), then filter_tape_looking"""
+    return ([s["env_idx"], s["call_sc_cnt"]] + s["addr_storage"] + s["addr_code"] + [s["tp"], s["clk"], s["pc"], s["is_ext_line"], s["ext_cnt"]] + s["regs"] +
+            [s["instruction"], s["op1_imm"], s["opcode"], s["immediate_data"], s["op0"], s["op1"], s["dst"], s["aux0"], s["aux1"], s["storage_access_idx"]] +
+            s["op0_reg_sel"] + s["op1_reg_sel"] + s["dst_reg_sel"] + [s["filter_tape_looking"]])
+
+
+def cpu_steps_vectors(reference):
+    """generate_cpu_trace and generate_prog_trace of the reference on the synthetic steps, at 37 rows (padded to 64), 32 (no padding) and 0,
+    with a two-program listing"""
+    it = plonky2_interp(reference)
+    it.permutation_hook = FastPoseidonHook(it)
+    g = os.path.join(reference, "circuits", "src", "generation")
+    fe = lambda v: [Fe(x) for x in v] if isinstance(v, list) else Fe(v)
+    synthetic = cpu_steps_synthetic()
+    cells = []
+    for s in synthetic:
+        sel = Struct({"__name__": "RegisterSelector", **{k: fe(s[k]) for k in ("op0", "op1", "dst", "aux0", "aux1", "op0_reg_sel", "op1_reg_sel", "dst_reg_sel")}})
+        d = {k: fe(s[k]) for k in ("env_idx", "call_sc_cnt", "tp", "addr_storage", "addr_code", "instruction", "immediate_data", "opcode", "op1_imm", "regs",
+                                   "is_ext_line", "ext_cnt", "filter_tape_looking", "storage_access_idx")}
+        cells.append(Struct({"__name__": "Step", "clk": s["clk"], "pc": s["pc"], "register_selector": sel, **d}))
+    listing = [([11, 22, 33, 44], stream_for(9101, 1, 21)), ([55, 66, 77, 88], stream_for(9101, 2, 9))]
+    roots = (stream_for(9102, 1, 4), stream_for(9102, 2, 4))
+    out = {"generated_by": "tools/rust_air_eval.py --tracegen cpu_steps", "sources": "circuits/src/generation/cpu.rs: generate_cpu_trace; prog.rs: generate_prog_trace",
+           "steps": [cpu_steps_record(s) for s in synthetic], "listing": [[a, w] for a, w in listing], "start_end_roots": [roots[0], roots[1]], "runs": {}}
+    for k in CPU_STEPS_LENGTHS:
+        cpu = it.call_free(os.path.join(g, "cpu.rs"), "generate_cpu_trace", [cells[:k]])
+        progs = [(fe(a), fe(w)) for a, w in listing]
+        pg, beta = it.call_free(os.path.join(g, "prog.rs"), "generate_prog_trace", [cells[:k], progs, (fe(roots[0]), fe(roots[1]))])
+        out["runs"][str(k)] = {"cpu": [[x.v for x in c] for c in cpu], "prog": [[x.v for x in c] for c in pg], "beta": beta.v}
+    return out
+
+
 class FastPoseidonHook:
     """the permutation for the 393 216 sponge calls of the bitwise generator's transcript: built from the reference's constant tables and checked
     against the interpreted poseidon_naive before use (as tools/ref_verifier.py does)"""
@@ -2940,7 +3039,9 @@ def main():
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--primitives", action="store_true", help="the hashing / transcript / FRI-parameter vectors instead of the AIR vectors")
     ap.add_argument("--ntt", action="store_true", help="the transform vectors (cfft) instead of the AIR vectors")
-    ap.add_argument("--tracegen", action="store_true", help="the trace generators' outputs (generation/*.rs) instead of the AIR vectors")
+    ap.add_argument("--tracegen", nargs="?", const="all", choices=("all", "vectors", "cpu_steps"),
+                    help="the trace generators' outputs (generation/*.rs) instead of the AIR vectors: `vectors` (ref_tracegen_vectors.json), "
+                         "`cpu_steps` (generate_cpu_trace / generate_prog_trace on synthetic steps, ref_cpu_steps.json) or both")
     ap.add_argument("--tracegen-bitwise", action="store_true", help="the bitwise table's generator (2^18 rows: about 40 minutes)")
     a = ap.parse_args()
     sys.setrecursionlimit(20000)
@@ -2950,16 +3051,20 @@ def main():
         print("wrote", BITWISE_FIXTURE)
         return
     if a.tracegen:
-        out = TRACEGEN_FIXTURE if a.out == FIXTURE else a.out
-        data = tracegen_vectors(a.reference)
-        text = json.dumps(data, separators=(",", ":")) + "\n"
-        if a.check:
-            if open(out).read() != text:
-                raise SystemExit(out + " is stale")
-            print("fixture is up to date")
-            return
-        open(out, "w").write(text)
-        print("wrote", out, "(%d bytes)" % len(text))
+        cases = []
+        if a.tracegen in ("all", "vectors"):
+            cases.append((TRACEGEN_FIXTURE if a.out == FIXTURE else a.out, tracegen_vectors))
+        if a.tracegen in ("all", "cpu_steps"):
+            cases.append((CPU_STEPS_FIXTURE if a.out == FIXTURE or a.tracegen == "all" else a.out, cpu_steps_vectors))
+        for out, make in cases:
+            text = json.dumps(make(a.reference), separators=(",", ":")) + "\n"
+            if a.check:
+                if open(out).read() != text:
+                    raise SystemExit(out + " is stale")
+                print(out, "is up to date")
+                continue
+            open(out, "w").write(text)
+            print("wrote", out, "(%d bytes)" % len(text))
         return
     if a.ntt:
         out = NTT_FIXTURE if a.out == FIXTURE else a.out
