@@ -47,7 +47,9 @@ extern "C" {
  * and the entry point ola_check_constraints (which constraint of which table fails at which row); so were ola_generate_rc_trace,
  * ola_generate_bitwise_trace and ola_generate_prog_trace (the range-check, bitwise and program tables completed in HBM); so were
  * OlaLookupMismatch and the entry point ola_check_lookup (the tuples a failing cross-table lookup is missing); so were
- * ola_generate_cpu_trace and ola_generate_prog_trace_steps (the CPU table and the program table from the executor's step records). */
+ * ola_generate_cpu_trace and ola_generate_prog_trace_steps (the CPU table and the program table from the executor's step records); so
+ * were ola_generate_memory_trace and ola_generate_cmp_trace (the memory table from raw cells, sorted on the device, and the comparison
+ * table from operand pairs, both with their range-checked value lists). */
 #define OLA_GPU_ABI_VERSION 7
 #define OLA_OK 0
 #define OLA_E_INVALID_ARG (-1)
@@ -646,6 +648,49 @@ int32_t ola_generate_prog_trace(OlaCtx* ctx, const uint64_t* exec, const uint64_
 int32_t ola_generate_cpu_trace(OlaCtx* ctx, const uint64_t* steps, size_t n_steps, uint32_t log_n, uint64_t* out);
 int32_t ola_generate_prog_trace_steps(OlaCtx* ctx, const uint64_t* steps, size_t n_steps, const uint64_t* prog, uint32_t log_n,
                                       uint64_t beta, uint32_t flags, uint64_t* out, uint64_t* exec_rows_out);
+
+/* ---- the memory table from raw cells, the comparison table from operand pairs ------------------------------------------------
+ * The memory table is not a per-row function of the executor's records: it is a sort of the memory cells by (address, clock), per-row
+ * differences against the predecessor row, one field inversion per row, the padding rows of the prophet region and the two value lists
+ * the table sends to the range-check table (generation/memory.rs:5-153).  The comparison table is the other table whose rows need an
+ * inversion each (generation/builtin.rs:208-247).  Both are made on the device; with them three of the four segments of
+ * ola_generate_rc_trace's `vals` are in HBM already.  The contract is the one of the "whole derived tables" block above: every buffer
+ * may be host memory or memory of the context's GPU, words may be >= p, every word written is canonical, every column of `out` is
+ * written (no memset of the table), the work runs on the context's stream and is complete on return, arguments are validated first,
+ * out == NULL is a sizing call that also takes ctx == NULL (*log_n_out is set; rc_counts must be there all the same and is left
+ * alone), ctx == NULL in a call that would do work is OLA_E_NO_DEVICE on a machine without a HIP device and OLA_E_INVALID_ARG
+ * otherwise, a multi-device context works on its first device, and `out` can go into ola_prove_with_traces* as a resident table.
+ *
+ * ola_generate_memory_trace: out = 29 x n, n = next_pow2(max(n_cells + 1, 8)), log2 n in *log_n_out.
+ *   cells: OLA_MEM_CELL_WORDS = 5 words per cell, column-major 5 x n_cells, in any order: address, clock, op (the opcode's one-hot
+ *     word, as COL_MEM_OP holds it), value, is_write.  n_cells >= 2^31 is OLA_E_INVALID_ARG.
+ *   Row order: ascending in the key (canonical address, canonical clock, op rank, canonical value, canonical is_write); the op rank is
+ *     the op's position in CALL, MLOAD, MSTORE, POSEIDON, RET, SLOAD, SSTORE, TLOAD, TSTORE; an op word that is none of the nine ranks
+ *     behind them, ordered by its canonical word, and sets no selector.  Cells equal in all five are indistinguishable, so the table
+ *     does not depend on the order of `cells`.
+ *   Live rows: IS_RW, the five words, the op's selector; for an address >= ADDR_HEAP_PTR (memory/memory_stark.rs:81) REGION_HEAP,
+ *     DIFF_ADDR_COND = 0 - (2^32 - 1) - address and FILTER_LOOKING_RC_COND.  The first heap row behind a non-heap row gets DIFF_ADDR
+ *     and DIFF_ADDR_INV only (generation/memory.rs:77-86); every other row but the first gets DIFF_ADDR, DIFF_ADDR_INV, DIFF_CLK (on an
+ *     unchanged address), RW_ADDR_UNCHANGED, RC_VALUE (the clock difference on an unchanged address, else the address difference) and
+ *     FILTER_LOOKING_RC.  The inverse of 0 is 0.
+ *   Padding rows: prophet-region rows from address p - (2^32 - 1) upwards (S_PROPHET, IS_WRITE, REGION_PROPHET, DIFF_ADDR_COND =
+ *     RC_VALUE = 0 - address); the first takes DIFF_ADDR against the last live address, the others have 1.  A table without cells has
+ *     one stack-region row first that carries S_PROPHET and IS_WRITE only (include/ola_tracegen.h says why).
+ *   flags: OLA_TABLEGEN_REFERENCE_QUIRKS with n_cells == 0 gives generation/memory.rs:95-153's table as it is (every row a prophet row,
+ *     row 0 without selector and address step); the flag is ignored when there are cells.
+ *   rc_counts (not NULL) receives {number of range-checked sort values, number of range-checked region values}.  rc_out may be NULL;
+ *     otherwise it has room for 2 n_cells words and receives RC_VALUE of the rows with FILTER_LOOKING_RC in row order, immediately
+ *     followed by DIFF_ADDR_COND of the heap rows in row order -- the order in which they follow the CPU's and the comparison table's
+ *     values in the range-check table, so a caller points rc_out into its `vals` buffer and copies nothing.  Words of rc_out beyond
+ *     rc_counts[0] + rc_counts[1] are not written.
+ * ola_generate_cmp_trace: out = 6 x n, n = next_pow2(n_ops), at least 2.  ops: column-major 2 x n_ops (op0, op1); n_ops >= 2^31 is
+ *   OLA_E_INVALID_ARG.  Live rows: canonical OP0 and OP1, GTE = op0 >= op1, ABS_DIFF, ABS_DIFF_INV (0 for 0), FILTER_LOOKING_RC = 1;
+ *   padding rows: OP0 = GTE = ABS_DIFF = ABS_DIFF_INV = 1, the rest 0.  abs_diff_out may be NULL; otherwise it has room for n_ops
+ *   words and receives ABS_DIFF of the live rows in order. */
+#define OLA_MEM_CELL_WORDS 5
+int32_t ola_generate_memory_trace(OlaCtx* ctx, const uint64_t* cells, size_t n_cells, uint32_t flags, uint64_t* out, uint32_t* log_n_out,
+                                  uint64_t* rc_out, uint64_t rc_counts[2]);
+int32_t ola_generate_cmp_trace(OlaCtx* ctx, const uint64_t* ops, size_t n_ops, uint64_t* out, uint32_t* log_n_out, uint64_t* abs_diff_out);
 
 /* ---- coset-partitioned proving over several GPUs ---------------------------------------------------------
  * One process per GPU; every process calls ola_prove_with_traces with the SAME traces.  Because the transcript is a

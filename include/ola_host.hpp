@@ -16,6 +16,8 @@
 //   circuits/src/generation/poseidon.rs:5        generate_poseidon_trace  ola_host::generate_poseidon_trace
 //   circuits/src/generation/cpu.rs:11            generate_cpu_trace       ola_host::generate_cpu_trace
 //   circuits/src/generation/prog.rs:18           generate_prog_trace      ola_host::generate_prog_trace_steps
+//   circuits/src/generation/memory.rs:5          generate_memory_trace    ola_host::generate_memory_trace
+//   circuits/src/generation/builtin.rs:208       generate_cmp_trace       ola_host::generate_cmp_trace
 //
 // Errors: the Rust code returns anyhow::Result / panics on contract violations; here every failing call throws
 // ola_host::Error carrying the C ABI's code (OLA_E_*) and message.  Field elements are plain uint64_t words
@@ -488,6 +490,33 @@ inline std::vector<F> generate_prog_trace_steps(const Gpu& g, const std::vector<
                                                      out.data(), &rows);
     if (exec_rows) *exec_rows = rows;
     check(rc);
+    return out;
+}
+// raw memory cells (OLA_MEM_CELL_WORDS x n_cells column-major, any order) -> the 29 x n memory table (generation/memory.rs:5-153), sorted on
+// the device; rc_values, when given, receives the range-checked sort values followed by the region values, rc_counts how many of each
+inline std::vector<F> generate_memory_trace(const Gpu& g, const std::vector<F>& cells, size_t n_cells, std::vector<F>* rc_values = nullptr,
+                                            uint64_t rc_counts[2] = nullptr, uint32_t flags = 0) {
+    if (cells.size() != OLA_MEM_CELL_WORDS * n_cells) throw Error(OLA_E_INVALID_ARG, "shape");
+    uint32_t log_n = 0;
+    uint64_t counts[2] = {0, 0};
+    check(ola_generate_memory_trace(nullptr, nullptr, n_cells, flags, nullptr, &log_n, nullptr, counts));
+    std::vector<F> out((size_t)29 << log_n), rc(2 * n_cells);
+    check(ola_generate_memory_trace(g.ctx(), n_cells ? cells.data() : nullptr, n_cells, flags, out.data(), &log_n, n_cells ? rc.data() : nullptr,
+                                    counts));
+    rc.resize(counts[0] + counts[1]);
+    if (rc_values) *rc_values = std::move(rc);
+    if (rc_counts) { rc_counts[0] = counts[0]; rc_counts[1] = counts[1]; }
+    return out;
+}
+// operand pairs (2 x n_ops column-major) -> the 6 x n comparison table (generation/builtin.rs:208-247); abs_diffs, when given, receives
+// ABS_DIFF of the live rows
+inline std::vector<F> generate_cmp_trace(const Gpu& g, const std::vector<F>& ops, size_t n_ops, std::vector<F>* abs_diffs = nullptr) {
+    if (ops.size() != 2 * n_ops) throw Error(OLA_E_INVALID_ARG, "shape");
+    uint32_t log_n = 0;
+    check(ola_generate_cmp_trace(nullptr, nullptr, n_ops, nullptr, &log_n, nullptr));
+    std::vector<F> out((size_t)6 << log_n), diffs(n_ops);
+    check(ola_generate_cmp_trace(g.ctx(), n_ops ? ops.data() : nullptr, n_ops, out.data(), &log_n, n_ops ? diffs.data() : nullptr));
+    if (abs_diffs) *abs_diffs = std::move(diffs);
     return out;
 }
 

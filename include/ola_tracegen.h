@@ -47,6 +47,13 @@ typedef struct OlaTraceSet OlaTraceSet;
  * GPU generates from them (include/ola_gpu.h ola_generate_cpu_trace, ola_generate_prog_trace_steps).  ola_tracegen_table answers the
  * two with their shape and data = NULL; ola_tracegen_cpu_steps and ola_tracegen_prog_listing return what the GPU calls take. */
 #define OLA_TRACEGEN_STEPS_ONLY 8u
+/* flags: OLA_TRACEGEN_STEPS_ONLY (implied), and the memory, comparison and range-check tables are not built either -- no sort, no field
+ * inversions, no permuted columns on the host: the GPU makes the first two from raw cells and operand pairs (include/ola_gpu.h
+ * ola_generate_memory_trace, ola_generate_cmp_trace) and the third from the value lists those calls leave in HBM behind the CPU's
+ * (ola_generate_rc_trace).  ola_tracegen_table answers the three with their shape and data = NULL as well; ola_tracegen_mem_cells,
+ * ola_tracegen_cmp_ops and ola_tracegen_cpu_rc_values return what the GPU calls take.  A range-checked value too wide for two limbs,
+ * which the table path refuses, is not looked for. */
+#define OLA_TRACEGEN_CELLS_ONLY 16u
 
 /* Executes the program (at most max_steps CPU rows) and builds the 12 tables of ola_stark(range_bits, limb_bits) in
  * `enum Table` order.  range_bits / limb_bits are 16 / 8 in the reference; smaller values give structurally identical
@@ -54,12 +61,18 @@ typedef struct OlaTraceSet OlaTraceSet;
 int32_t ola_tracegen_run(const OlaInstr* program, size_t n_instr, const uint64_t code_addr[4], const uint64_t storage_addr[4],
                          uint32_t range_bits, uint32_t limb_bits, uint64_t bitwise_beta, uint64_t program_beta, uint64_t max_steps,
                          uint32_t flags, OlaTraceSet** out);
-/* Table t: column-major ncols x 2^log_n words, owned by the set (data = NULL for a table OLA_TRACEGEN_STEPS_ONLY left out). */
+/* Table t: column-major ncols x 2^log_n words, owned by the set (data = NULL for a table OLA_TRACEGEN_STEPS_ONLY or OLA_TRACEGEN_CELLS_ONLY left out). */
 int32_t ola_tracegen_table(const OlaTraceSet* set, uint32_t table, uint32_t* ncols, uint32_t* log_n, const uint64_t** data);
 /* OLA_TRACEGEN_STEPS_ONLY sets only (-1 otherwise): the step records, OLA_CPU_STEP_WORDS x n_steps column-major, and the program
  * table's listing side, 7 x 2^log_n column-major (four code-address words, pc, inst, filter); both owned by the set. */
 int32_t ola_tracegen_cpu_steps(const OlaTraceSet* set, uint64_t* n_steps, const uint64_t** data);
 int32_t ola_tracegen_prog_listing(const OlaTraceSet* set, uint32_t* log_n, const uint64_t** data);
+/* OLA_TRACEGEN_CELLS_ONLY sets only (-1 otherwise), all owned by the set: the memory cells in execution order, OLA_MEM_CELL_WORDS x
+ * n_cells column-major (address, clock, the op's one-hot word, value, is_write); the comparison operands, 2 x n_ops column-major (op0,
+ * op1); the values of the CPU's RC instructions, the first segment of the range-check table's input. */
+int32_t ola_tracegen_mem_cells(const OlaTraceSet* set, uint64_t* n_cells, const uint64_t** data);
+int32_t ola_tracegen_cmp_ops(const OlaTraceSet* set, uint64_t* n_ops, const uint64_t** data);
+int32_t ola_tracegen_cpu_rc_values(const OlaTraceSet* set, uint64_t* n_values, const uint64_t** data);
 /* Number of executed CPU rows (before padding). */
 uint64_t ola_tracegen_cpu_rows(const OlaTraceSet* set);
 /* out[0] = the bitwise table's compress challenge, out[1] = the program table's. */

@@ -47,6 +47,8 @@ pub const OLA_WARMUP_PINNED_RING: u32 = 1;
 pub const OLA_TABLEGEN_REFERENCE_QUIRKS: u32 = 1;
 /// Words of one step record of `ola_generate_cpu_trace` / `ola_generate_prog_trace_steps` (CPU columns 1 .. 65, filter_tape_looking).
 pub const OLA_CPU_STEP_WORDS: usize = 66;
+/// Words of one memory cell of `ola_generate_memory_trace` (address, clock, the op's one-hot word, value, is_write).
+pub const OLA_MEM_CELL_WORDS: usize = 5;
 /// `flags` of `ola_generate_prog_trace_steps`: zero rows beyond the executed ones, as the reference's generator leaves them.
 pub const OLA_TABLEGEN_ZERO_FILLER: u32 = 1;
 /// ola_check_constraints: `OlaConstraintFailure::section`
@@ -258,6 +260,10 @@ extern "C" {
     pub fn ola_generate_cpu_trace(ctx: *mut OlaCtx, steps: *const u64, n_steps: usize, log_n: u32, out: *mut u64) -> i32;
     pub fn ola_generate_prog_trace_steps(ctx: *mut OlaCtx, steps: *const u64, n_steps: usize, prog: *const u64, log_n: u32,
         beta: u64, flags: u32, out: *mut u64, exec_rows_out: *mut u64) -> i32;
+    pub fn ola_generate_memory_trace(ctx: *mut OlaCtx, cells: *const u64, n_cells: usize, flags: u32, out: *mut u64,
+        log_n_out: *mut u32, rc_out: *mut u64, rc_counts: *mut u64) -> i32;
+    pub fn ola_generate_cmp_trace(ctx: *mut OlaCtx, ops: *const u64, n_ops: usize, out: *mut u64, log_n_out: *mut u32,
+        abs_diff_out: *mut u64) -> i32;
     pub fn ola_set_shard(ctx: *mut OlaCtx, rank: u32, world: u32, all_gather: OlaAllGatherFn, user: *mut c_void) -> i32;
     pub fn ola_set_shard_options(ctx: *mut OlaCtx, flags: u32) -> i32;
     pub fn ola_gpu_get_stream(ctx: *mut OlaCtx, stream_out: *mut *mut c_void) -> i32;

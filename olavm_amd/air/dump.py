@@ -104,3 +104,30 @@ def tablegen_cpu_columns_header():
     out.append("constexpr uint32_t STEP_WORDS = %du;" % CPU_STEP_WORDS)
     out.append("}  // namespace olatgc")
     return "\n".join(out) + "\n"
+
+
+TABLEGEN_MEM_COLUMNS_H = "olavm_amd/csrc/tablegen_mem_columns.h"
+MEM_CELL_WORDS = 5       # include/ola_gpu.h OLA_MEM_CELL_WORDS: address, clock, op, value, is_write
+# the ops a memory cell can carry, in the order ties of (address, clock) sort by: alphabetical, as miniexec.memory_trace's sorted(cells)
+# and enum MemOp of olavm_amd/csrc/host/tracegen.cpp have it; the rank of an op is its position here
+MEM_OPS = ("CALL", "MLOAD", "MSTORE", "POSEIDON", "RET", "SLOAD", "SSTORE", "TLOAD", "TSTORE")
+
+
+def tablegen_mem_columns_header():
+    """The checked header olavm_amd/csrc/tablegen_mem_columns.h: the column indices of the memory and comparison tables, the start of the
+    heap region and the nine op masks of a memory cell with their ranks, for ola_generate_memory_trace / ola_generate_cmp_trace in
+    olavm_amd/csrc/lookup.hip.  Committed like its siblings; tests/test_mem_tablegen_abi.py compares it with this text.  Regenerate:
+        python -c "from olavm_amd.air import dump; print(dump.tablegen_mem_columns_header(), end='')" > olavm_amd/csrc/tablegen_mem_columns.h"""
+    from . import ola_tables as T
+    assert list(MEM_OPS) == sorted(MEM_OPS)
+    out = ["// generated from olavm_amd/air/ola_tables.py by olavm_amd.air.dump.tablegen_mem_columns_header() -- do not edit",
+           "#pragma once", "#include <cstdint>", "namespace olatgm {"]
+    for name in sorted(n for n in dir(T) if n.startswith(("COL_MEM_", "COL_CMP_"))):
+        out.append("constexpr uint32_t %s = %du;" % (name, getattr(T, name)))
+    out.append("constexpr uint32_t NUM_MEM_COLS = %du, COL_NUM_CMP = %du;" % (T.NUM_MEM_COLS, T.COL_NUM_CMP))
+    out.append("constexpr uint64_t ADDR_HEAP_PTR = %dull;" % T.ADDR_HEAP_PTR)
+    for rank, op in enumerate(MEM_OPS):
+        out.append("constexpr uint64_t MEM_OP_MASK_%s = %dull; constexpr uint32_t MEM_OP_RANK_%s = %du;" % (op, T.op_mask(op), op, rank))
+    out.append("constexpr uint32_t MEM_OPS = %du, MEM_CELL_WORDS = %du;" % (len(MEM_OPS), MEM_CELL_WORDS))
+    out.append("}  // namespace olatgm")
+    return "\n".join(out) + "\n"

@@ -16,8 +16,10 @@ class OlaInstr(C.Structure):
 
 
 EXPORTS = ["ola_tracegen_run", "ola_tracegen_table", "ola_tracegen_cpu_rows", "ola_tracegen_free", "ola_tracegen_last_error", "ola_tracegen_betas",
-           "ola_tracegen_cpu_steps", "ola_tracegen_prog_listing"]
+           "ola_tracegen_cpu_steps", "ola_tracegen_prog_listing", "ola_tracegen_mem_cells", "ola_tracegen_cmp_ops", "ola_tracegen_cpu_rc_values"]
 OLA_TRACEGEN_PROVE_PROGRAM_HASH, OLA_TRACEGEN_EXPLICIT_BETAS, OLA_TRACEGEN_REFERENCE_QUIRKS, OLA_TRACEGEN_STEPS_ONLY = 1, 2, 4, 8
+OLA_TRACEGEN_CELLS_ONLY = 16
+MEM_CELL_WORDS = 5       # include/ola_gpu.h OLA_MEM_CELL_WORDS
 
 
 def lib_path():
@@ -40,6 +42,8 @@ def load_library():
         L.ola_tracegen_betas.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.ola_tracegen_cpu_steps.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64))]
         L.ola_tracegen_prog_listing.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint64))]
+        for f in ("ola_tracegen_mem_cells", "ola_tracegen_cmp_ops", "ola_tracegen_cpu_rc_values"):
+            getattr(L, f).argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64))]
         _lib = L
     return _lib
 
@@ -55,11 +59,15 @@ def encode(prog):
 
 
 def instance(prog, range_bits=4, limb_bits=2, bitwise_beta=None, program_beta=None, prove_program_hash=False, max_steps=1 << 16, reference_quirks=False,
-             steps_only=False, timings=None):
+             steps_only=False, timings=None, cells_only=False):
     """Same contract as miniexec.instance(prog, ...).  -> (traces, params, compress).  Betas left at None are derived by the
     generator's own Fiat-Shamir transcript, as the reference does; explicit values (both or neither) are for tests.
     steps_only: the CPU and the program table are not built -- traces[0] and traces[10] are None -- and a fourth value is returned,
     dict(steps, cpu_log_n, listing, prog_log_n): what Backend.generate_cpu_trace / generate_prog_trace_steps make the two from.
+    cells_only: steps_only, and the memory, comparison and range-check tables are not built either -- traces[1], [3] and [4] are None --
+    and the fourth value also has cells (5 x n: address, clock, the op's one-hot word, value, is_write; execution order), cmp_ops (2 x n),
+    cpu_rc (the values of the RC instructions) and mem_log_n, cmp_log_n, rc_log_n: what Backend.generate_memory_trace, generate_cmp_trace
+    and generate_rc_trace make the three from.
     timings: a dict that receives native_s (ola_tracegen_run alone) and copy_s (this binding's copies of the set into numpy arrays)."""
     import time
     assert (bitwise_beta is None) == (program_beta is None), "give both compress challenges or neither"
@@ -69,8 +77,10 @@ def instance(prog, range_bits=4, limb_bits=2, bitwise_beta=None, program_beta=No
     code = (C.c_uint64 * 4)(*prog.code_addr)
     stor = (C.c_uint64 * 4)(*prog.storage_addr)
     handle = C.c_void_p()
+    steps_only = steps_only or cells_only
     flags = ((OLA_TRACEGEN_PROVE_PROGRAM_HASH if prove_program_hash else 0) | (OLA_TRACEGEN_EXPLICIT_BETAS if explicit else 0) |
-             (OLA_TRACEGEN_REFERENCE_QUIRKS if reference_quirks else 0) | (OLA_TRACEGEN_STEPS_ONLY if steps_only else 0))
+             (OLA_TRACEGEN_REFERENCE_QUIRKS if reference_quirks else 0) | (OLA_TRACEGEN_STEPS_ONLY if steps_only else 0) |
+             (OLA_TRACEGEN_CELLS_ONLY if cells_only else 0))
     t0 = time.perf_counter()
     rc = L.ola_tracegen_run(ins, len(prog.ins), code, stor, range_bits, limb_bits, bitwise_beta if explicit else 0, program_beta if explicit else 0,
                             max_steps, flags, C.byref(handle))
@@ -84,7 +94,7 @@ def instance(prog, range_bits=4, limb_bits=2, bitwise_beta=None, program_beta=No
             assert L.ola_tracegen_table(handle, t, C.byref(ncols), C.byref(log_n), C.byref(data)) == 0
             n = 1 << log_n.value
             if not data:
-                assert steps_only and t in (T.CPU, T.PROGRAM)
+                assert (steps_only and t in (T.CPU, T.PROGRAM)) or (cells_only and t in (T.MEMORY, T.CMP, T.RANGECHECK))
                 shapes[t] = log_n.value
                 traces.append(None)
                 continue
@@ -97,6 +107,14 @@ def instance(prog, range_bits=4, limb_bits=2, bitwise_beta=None, program_beta=No
             assert L.ola_tracegen_prog_listing(handle, C.byref(log_n), C.byref(data)) == 0 and log_n.value == shapes[T.PROGRAM]
             listing = np.ctypeslib.as_array(data, shape=(7, 1 << log_n.value)).copy()
             extra = dict(steps=steps, cpu_log_n=shapes[T.CPU], listing=listing, prog_log_n=shapes[T.PROGRAM])
+        if cells_only:
+            def words(get, rows):
+                count, data = C.c_uint64(), C.POINTER(C.c_uint64)()
+                assert get(handle, C.byref(count), C.byref(data)) == 0
+                return np.ctypeslib.as_array(data, shape=(rows, count.value)).copy() if count.value else np.zeros((rows, 0), dtype=np.uint64)
+            extra.update(cells=words(L.ola_tracegen_mem_cells, MEM_CELL_WORDS), cmp_ops=words(L.ola_tracegen_cmp_ops, 2),
+                         cpu_rc=words(L.ola_tracegen_cpu_rc_values, 1)[0], mem_log_n=shapes[T.MEMORY], cmp_log_n=shapes[T.CMP],
+                         rc_log_n=shapes[T.RANGECHECK])
         betas = (C.c_uint64 * 2)()
         assert L.ola_tracegen_betas(handle, betas) == 0
         bitwise_beta, program_beta = int(betas[0]), int(betas[1])

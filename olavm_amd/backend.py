@@ -167,8 +167,11 @@ def load_library():
     L.ola_generate_cpu_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
     L.ola_generate_prog_trace_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p,
                                                 C.POINTER(C.c_uint64)]
+    L.ola_generate_memory_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p,
+                                            C.POINTER(C.c_uint64)]
+    L.ola_generate_cmp_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
     for f in ("ola_generate_rc_trace", "ola_generate_bitwise_trace", "ola_generate_prog_trace", "ola_generate_cpu_trace",
-              "ola_generate_prog_trace_steps"):
+              "ola_generate_prog_trace_steps", "ola_generate_memory_trace", "ola_generate_cmp_trace"):
         getattr(L, f).restype = C.c_int32
     L.ola_set_shard.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, ALL_GATHER_FN, C.c_void_p]
     L.ola_set_shard_options.argtypes = [C.c_void_p, C.c_uint32]
@@ -204,7 +207,7 @@ EXPORTS = [
     "ola_gpu_collective", "ola_gpu_all_gather_check", "ola_prove_with_traces_cols", "ola_gpu_scope_times", "ola_gpu_upload_stats",
     "ola_gpu_warmup", "ola_gpu_warmup_wait", "ola_gpu_ntt_pass_times",
     "ola_check_constraints", "ola_check_lookup", "ola_generate_rc_trace", "ola_generate_bitwise_trace", "ola_generate_prog_trace",
-    "ola_generate_cpu_trace", "ola_generate_prog_trace_steps",
+    "ola_generate_cpu_trace", "ola_generate_prog_trace_steps", "ola_generate_memory_trace", "ola_generate_cmp_trace",
     "ola_open", "ola_fri_plan", "ola_fri_commit_begin", "ola_fri_commit_next_layer", "ola_fri_commit_finish", "ola_fri_query", "ola_fri_free",
 ]
 
@@ -237,6 +240,7 @@ OLA_WARMUP_PINNED_RING = 1
 OLA_TABLEGEN_REFERENCE_QUIRKS = 1
 OLA_TABLEGEN_ZERO_FILLER = 1
 OLA_CPU_STEP_WORDS = 66
+OLA_MEM_CELL_WORDS = 5
 
 
 def warmup(device=-1, pinned_ring=True, airset=None):
@@ -756,6 +760,70 @@ class Backend:
             e.exec_rows = rows.value
             raise
         return ret, rows.value
+
+    def _list_out(self, dst, words):
+        """A value list the memory / comparison generators fill -> (address or None, what the caller gets back): None = a new numpy array,
+        False = not wanted (NULL), else a numpy array, a 64-bit torch tensor on the GPU or a device address with room for `words` words."""
+        if dst is False:
+            return None, None
+        if dst is None:
+            h = np.empty(words, dtype=np.uint64)
+            return C.c_void_p(h.ctypes.data), h
+        if isinstance(dst, int):
+            return C.c_void_p(dst), dst
+        if hasattr(dst, "data_ptr"):
+            if not (dst.is_contiguous() and dst.element_size() == 8 and dst.numel() >= words):
+                raise ValueError("a value list must be a contiguous 64-bit tensor with room for every value")
+            return C.c_void_p(dst.data_ptr()), dst
+        h = np.ascontiguousarray(dst)
+        if h is not dst or h.dtype != np.uint64 or h.size < words:
+            raise ValueError("a value list must be a contiguous uint64 array with room for every value")
+        return C.c_void_p(h.ctypes.data), h
+
+    def memory_trace_log_n(self, n_cells):
+        log_n, counts = C.c_uint32(), (C.c_uint64 * 2)()
+        self._chk(self.lib.ola_generate_memory_trace(self.ctx, None, n_cells, 0, None, C.byref(log_n), None, counts))
+        return log_n.value
+
+    def cmp_trace_log_n(self, n_ops):
+        log_n = C.c_uint32()
+        self._chk(self.lib.ola_generate_cmp_trace(self.ctx, None, n_ops, None, C.byref(log_n), None))
+        return log_n.value
+
+    def generate_memory_trace(self, cells, reference_quirks=False, out=None, rc_out=None, n_cells=None):
+        """ola_generate_memory_trace: the memory table (29 x n) from raw cells (OLA_MEM_CELL_WORDS x n_cells column-major, any order:
+        address, clock, the op's one-hot word, value, is_write; None or zero columns for a table of padding rows), sorted on the device.
+        -> (table or log_n, value list, (sort values, region values)).  rc_out: None = the range-checked sort values followed by the
+        region values come back as a numpy array; False = they are not wanted; an array, GPU tensor or device address with room for
+        2 n_cells words = they are written to its head and it is returned.  n_cells must be given when cells is a device address."""
+        pc, kc, shape = _words(cells, None if n_cells is None else (OLA_MEM_CELL_WORDS, n_cells))
+        if shape is not None and (len(shape) != 2 or shape[0] != OLA_MEM_CELL_WORDS):
+            raise ValueError("cells must be OLA_MEM_CELL_WORDS x n_cells")
+        n_cells = int(shape[1]) if shape is not None else 0
+        log_n = self.memory_trace_log_n(n_cells)
+        po, ret = self._table_out(out, 29, log_n)
+        pr, rc = self._list_out(rc_out, 2 * n_cells)
+        got, counts = C.c_uint32(), (C.c_uint64 * 2)()
+        self._chk(self.lib.ola_generate_memory_trace(self.ctx, pc if n_cells else None, n_cells,
+                                                     OLA_TABLEGEN_REFERENCE_QUIRKS if reference_quirks else 0, po, C.byref(got), pr, counts))
+        if rc_out is None:
+            rc = rc[:counts[0] + counts[1]]
+        return ret, rc, (int(counts[0]), int(counts[1]))
+
+    def generate_cmp_trace(self, ops, out=None, abs_diff_out=None, n_ops=None):
+        """ola_generate_cmp_trace: the comparison table (6 x n) from operand pairs (2 x n_ops column-major: op0, op1; None or zero
+        columns for a table of padding rows).  -> (table or log_n, ABS_DIFF of the live rows); abs_diff_out as rc_out of
+        generate_memory_trace, with room for n_ops words.  n_ops must be given when ops is a device address."""
+        pp, kp, shape = _words(ops, None if n_ops is None else (2, n_ops))
+        if shape is not None and (len(shape) != 2 or shape[0] != 2):
+            raise ValueError("ops must be 2 x n_ops")
+        n_ops = int(shape[1]) if shape is not None else 0
+        log_n = self.cmp_trace_log_n(n_ops)
+        po, ret = self._table_out(out, 6, log_n)
+        pd, diff = self._list_out(abs_diff_out, n_ops)
+        got = C.c_uint32()
+        self._chk(self.lib.ola_generate_cmp_trace(self.ctx, pp if n_ops else None, n_ops, po, C.byref(got), pd))
+        return ret, diff
 
     def trim(self):
         """Return the context's cached device buffers to the driver (ola_gpu_trim)."""

@@ -869,6 +869,28 @@ void rc_table(const std::vector<RcRow>& rows, uint32_t range_bits, Table& t) {
     t.set_column(RC_LIMB_HI_PERMUTED, pi); t.set_column(RC_FIX_RANGE_CHECK_U16_PERMUTED_HI, pt);
 }
 
+// OLA_TRACEGEN_CELLS_ONLY: the memory cells (include/ola_gpu.h OLA_MEM_CELL_WORDS: address, clock, the op's one-hot word, value,
+// is_write) and the comparison operands, column-major in execution order, instead of the three tables; their shapes follow from counts
+// alone -- the heap cells end up a suffix of the sorted table, so the number of range-checked memory values needs no sort
+void cells_only(const Run& R, uint32_t range_bits, Table& mem, Table& cmp, Table& rc, std::vector<u64>& cells, std::vector<u64>& cmp_ops) {
+    const size_t n_cells = R.mem.size(), n_ops = R.cmp.size();
+    cells.resize(5 * n_cells);
+    size_t below_heap = 0;
+    for (size_t i = 0; i < n_cells; i++) {
+        const MemCell& c = R.mem[i];
+        cells[i] = c.addr; cells[n_cells + i] = c.clk; cells[2 * n_cells + i] = 1ULL << mem_opcode(c.op); cells[3 * n_cells + i] = c.value;
+        cells[4 * n_cells + i] = c.is_write;
+        below_heap += c.addr < ADDR_HEAP_PTR;
+    }
+    cmp_ops.resize(2 * n_ops);
+    for (size_t i = 0; i < n_ops; i++) { cmp_ops[i] = R.cmp[i].first; cmp_ops[n_ops + i] = R.cmp[i].second; }
+    mem.ncols = NUM_MEM_COLS; mem.n = next_pow2(std::max<size_t>(n_cells + 1, 8));
+    cmp.ncols = COL_NUM_CMP; cmp.n = next_pow2(n_ops);
+    // memory_table's lists: every row but the first and the first heap row behind a stack row; every heap row
+    const size_t sort_vals = n_cells ? n_cells - 1 - (below_heap > 0 && below_heap < n_cells) : 0, region_vals = n_cells - below_heap;
+    rc.ncols = COL_NUM_RC; rc.n = next_pow2(std::max(R.rc.size() + n_ops + sort_vals + region_vals, (size_t)1 << range_bits));
+}
+
 // generation/builtin.rs:35-205 with limb_bits-wide limbs
 // `derive`: the compress challenge is drawn from a transcript that has observed the twelve limb columns (OP0, OP1, RES limbs
 // over the whole padded height), as generation/builtin.rs:120-131 does; otherwise the caller's `beta` is used (tests only)
@@ -946,6 +968,8 @@ struct OlaTraceSet {
     uint64_t bitwise_beta = 0, program_beta = 0;   // the compress challenges the tables were built with
     bool steps_only = false;                       // OLA_TRACEGEN_STEPS_ONLY: tables CPU and PROGRAM have a shape and no data ...
     std::vector<u64> steps, listing;               // ... these stand for them
+    bool cells_only = false;                       // OLA_TRACEGEN_CELLS_ONLY: so have MEMORY, CMP and RANGECHECK ...
+    std::vector<u64> cells, cmp_ops, cpu_rc;       // ... and these stand for them
 };
 
 extern "C" {
@@ -985,7 +1009,8 @@ int32_t ola_tracegen_run(const OlaInstr* program, size_t n_instr, const uint64_t
         set->program_beta = program_beta % P;
         auto& T = set->tables;
         std::vector<u64> words;
-        set->steps_only = flags & OLA_TRACEGEN_STEPS_ONLY;
+        set->cells_only = flags & OLA_TRACEGEN_CELLS_ONLY;
+        set->steps_only = (flags & OLA_TRACEGEN_STEPS_ONLY) || set->cells_only;
         if (set->steps_only) {
             cpu_steps(R, T[CPU], set->steps);
             program_listing(R, code_addr, T[PROGRAM], set->listing, words);
@@ -1004,15 +1029,20 @@ int32_t ola_tracegen_run(const OlaInstr* program, size_t n_instr, const uint64_t
         }
         for (auto& pr : R.storage_psdn) builtin_rows.push_back(std::move(pr));
         prog_chunk_and_poseidon(code_addr, words, builtin_rows, prove_program_hash, T[PROG_CHUNK], T[POSEIDON]);
-        std::vector<u64> abs_diffs, mem_rc, mem_cond;
-        cmp_table(R.cmp, T[CMP], abs_diffs);
-        memory_table(R.mem, T[MEMORY], mem_rc, mem_cond, quirks);
-        std::vector<RcRow> rc;
-        for (u64 v : R.rc) rc.push_back({v, {1, 0, 0, 0}});
-        for (u64 v : abs_diffs) rc.push_back({v, {0, 0, 0, 1}});
-        for (u64 v : mem_rc) rc.push_back({v, {0, 1, 0, 0}});
-        for (u64 v : mem_cond) rc.push_back({v, {0, 0, 1, 0}});
-        rc_table(rc, range_bits, T[RANGECHECK]);
+        if (set->cells_only) {
+            cells_only(R, range_bits, T[MEMORY], T[CMP], T[RANGECHECK], set->cells, set->cmp_ops);
+            set->cpu_rc = R.rc;
+        } else {
+            std::vector<u64> abs_diffs, mem_rc, mem_cond;
+            cmp_table(R.cmp, T[CMP], abs_diffs);
+            memory_table(R.mem, T[MEMORY], mem_rc, mem_cond, quirks);
+            std::vector<RcRow> rc;
+            for (u64 v : R.rc) rc.push_back({v, {1, 0, 0, 0}});
+            for (u64 v : abs_diffs) rc.push_back({v, {0, 0, 0, 1}});
+            for (u64 v : mem_rc) rc.push_back({v, {0, 1, 0, 0}});
+            for (u64 v : mem_cond) rc.push_back({v, {0, 0, 1, 0}});
+            rc_table(rc, range_bits, T[RANGECHECK]);
+        }
         set->bitwise_beta = bitwise_table(bitwise_beta, !explicit_betas, limb_bits, R.bitwise, T[BITWISE], quirks);
         storage_table(R.storage, prog_reads, T[STORAGE_ACCESS]);
         tape_table(R.tape, T[TAPE]);
@@ -1048,6 +1078,23 @@ int32_t ola_tracegen_prog_listing(const OlaTraceSet* set, uint32_t* log_n, const
     while (((size_t)1 << l) < set->tables[PROGRAM].n) l++;
     *log_n = l; *data = set->listing.data();
     return 0;
+}
+
+static int32_t cells_only_list(const OlaTraceSet* set, std::vector<u64> OlaTraceSet::*member, size_t words, uint64_t* count, const uint64_t** data) {
+    if (!set || !count || !data) { g_err = "invalid argument"; return -1; }
+    if (!set->cells_only) { g_err = "the set was not generated with OLA_TRACEGEN_CELLS_ONLY"; return -1; }
+    const std::vector<u64>& list = set->*member;
+    *count = list.size() / words; *data = list.data();
+    return 0;
+}
+int32_t ola_tracegen_mem_cells(const OlaTraceSet* set, uint64_t* n_cells, const uint64_t** data) {
+    return cells_only_list(set, &OlaTraceSet::cells, 5, n_cells, data);
+}
+int32_t ola_tracegen_cmp_ops(const OlaTraceSet* set, uint64_t* n_ops, const uint64_t** data) {
+    return cells_only_list(set, &OlaTraceSet::cmp_ops, 2, n_ops, data);
+}
+int32_t ola_tracegen_cpu_rc_values(const OlaTraceSet* set, uint64_t* n_values, const uint64_t** data) {
+    return cells_only_list(set, &OlaTraceSet::cpu_rc, 1, n_values, data);
 }
 
 uint64_t ola_tracegen_cpu_rows(const OlaTraceSet* set) { return set ? set->cpu_rows : 0; }

@@ -50,4 +50,15 @@ void generate_cpu_trace_dev(DeviceCtx* ctx, const u64* steps, size_t n_steps, u3
 bool generate_prog_trace_steps_dev(DeviceCtx* ctx, const u64* steps, size_t n_steps, const u64* prog, u32 log_n, u64 beta, bool zero_filler,
                                    u64* out, u64* exec_rows);
 
+// The memory table (29 x 2^memory_trace_log_n) from raw cells and the comparison table (6 x 2^cmp_trace_log_n) from operand pairs
+// (ola_generate_memory_trace / ola_generate_cmp_trace): cells is device memory, 5 x n_cells column-major in any order, n_cells < 2^31;
+// ops is 2 x n_ops, n_ops < 2^31.  rc_out (device memory of 2 n_cells words, or null) receives counts[0] range-checked sort values and
+// behind them counts[1] region values, nothing else of it is written; abs_diff_out (n_ops words, or null) ABS_DIFF of the live rows.
+// The memory table waits for the stream once (the key statistics that size the sort passes) and is complete on return; the
+// comparison table is one launch and returns when it is enqueued.
+u32 memory_trace_log_n(u64 n_cells);
+u32 cmp_trace_log_n(u64 n_ops);
+void generate_memory_trace_dev(DeviceCtx* ctx, const u64* cells, size_t n_cells, bool reference_quirks, u64* out, u64* rc_out, u64 counts[2]);
+void generate_cmp_trace_dev(DeviceCtx* ctx, const u64* ops, size_t n_ops, u64* out, u64* abs_diff_out);
+
 }  // namespace ola

@@ -31,6 +31,7 @@
 #include "lookup.h"
 #include "tablegen_columns.h"
 #include "tablegen_cpu_columns.h"
+#include "tablegen_mem_columns.h"
 
 namespace ola {
 
@@ -408,6 +409,7 @@ namespace {
 
 namespace tg = olatg;
 namespace tc = olatgc;
+namespace tm = olatgm;
 
 __global__ __launch_bounds__(256) void rc_fill_kernel(const u64* __restrict__ vals, const u64* __restrict__ filters, u32 n_rows, u32 range_bits,
                                                       u32 n, u64* __restrict__ out) {
@@ -617,6 +619,175 @@ __global__ __launch_bounds__(256) void exec_filler_kernel(u32 total, u32 repeat_
     exec[(size_t)6 * n + i] = 0;
 }
 
+// ---- the memory table from raw cells and the comparison table from operand pairs (ola_generate_memory_trace / ola_generate_cmp_trace;
+// olavm_amd/air/miniexec.py memory_trace, tracegen.py generate_cmp_trace; generation/memory.rs:5-153, generation/builtin.rs:208-247)
+// A cell is tm::MEM_CELL_WORDS words, column-major: address, clock, op (the opcode's one-hot word), value, is_write.
+enum : u32 { CELL_ADDR = 0, CELL_CLK = 1, CELL_OP = 2, CELL_VALUE = 3, CELL_IS_WRITE = 4 };
+
+// the op's place in the row order: the rank of one of the nine ops (`sel`: its selector column), else -- behind them, in word order --
+// MEM_OPS + the canonical word (below 2^64: p + 9 is), and no selector (0)
+__device__ __forceinline__ u64 mem_op_key(u64 op, u32& sel) {
+    sel = 0;
+    switch (op) {
+        case tm::MEM_OP_MASK_CALL: sel = tm::COL_MEM_S_CALL; return tm::MEM_OP_RANK_CALL;
+        case tm::MEM_OP_MASK_MLOAD: sel = tm::COL_MEM_S_MLOAD; return tm::MEM_OP_RANK_MLOAD;
+        case tm::MEM_OP_MASK_MSTORE: sel = tm::COL_MEM_S_MSTORE; return tm::MEM_OP_RANK_MSTORE;
+        case tm::MEM_OP_MASK_POSEIDON: sel = tm::COL_MEM_S_POSEIDON; return tm::MEM_OP_RANK_POSEIDON;
+        case tm::MEM_OP_MASK_RET: sel = tm::COL_MEM_S_RET; return tm::MEM_OP_RANK_RET;
+        case tm::MEM_OP_MASK_SLOAD: sel = tm::COL_MEM_S_SLOAD; return tm::MEM_OP_RANK_SLOAD;
+        case tm::MEM_OP_MASK_SSTORE: sel = tm::COL_MEM_S_SSTORE; return tm::MEM_OP_RANK_SSTORE;
+        case tm::MEM_OP_MASK_TLOAD: sel = tm::COL_MEM_S_TLOAD; return tm::MEM_OP_RANK_TLOAD;
+        case tm::MEM_OP_MASK_TSTORE: sel = tm::COL_MEM_S_TSTORE; return tm::MEM_OP_RANK_TSTORE;
+        default: return tm::MEM_OPS + op;
+    }
+}
+__device__ __forceinline__ u64 mem_sort_key(const u64* __restrict__ canon, u32 n_cells, u32 field, u32 r) {
+    const u64 v = canon[(size_t)field * n_cells + r];
+    u32 sel;
+    return field == CELL_OP ? mem_op_key(v, sel) : v;
+}
+
+// What the host reads before it sorts: stats[f], f < 5 = the OR of every cell's sort key of field f (a pass of the sort covers the bits
+// set there, and a field whose keys are all 0 needs none), stats[MS_BELOW_HEAP] = cells below the heap region -- sorted by address the heap
+// rows are a suffix, so this is the index of the first heap row.
+enum : u32 { MS_BELOW_HEAP = tm::MEM_CELL_WORDS, MS_WORDS };
+// canonical cells, the identity index, and the statistics: reduced over the wave, then one atomic per wave and word
+__global__ __launch_bounds__(256) void mem_key_kernel(const u64* __restrict__ cells, u32 n_cells, u64* __restrict__ canon, u32* __restrict__ idx,
+                                                      unsigned long long* __restrict__ stats) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    const bool live = i < n_cells;
+    unsigned long long r[MS_WORDS] = {};
+    if (live) {
+        u32 sel;
+#pragma unroll
+        for (u32 f = 0; f < tm::MEM_CELL_WORDS; f++) {
+            const u64 w = gl_canon(cells[(size_t)f * n_cells + i]);
+            canon[(size_t)f * n_cells + i] = w;
+            r[f] = f == CELL_OP ? mem_op_key(w, sel) : w;
+        }
+        idx[i] = i;
+        r[MS_BELOW_HEAP] = r[CELL_ADDR] < tm::ADDR_HEAP_PTR ? 1 : 0;
+    }
+#pragma unroll
+    for (u32 f = 0; f < MS_WORDS; f++)
+        for (int off = warpSize / 2; off > 0; off >>= 1) {
+            const unsigned long long other = __shfl_xor(r[f], off);
+            r[f] = f == MS_BELOW_HEAP ? r[f] + other : r[f] | other;
+        }
+    if ((threadIdx.x & (warpSize - 1)) != 0) return;
+#pragma unroll
+    for (u32 f = 0; f < tm::MEM_CELL_WORDS; f++)
+        if (r[f]) atomicOr(&stats[f], r[f]);
+    if (r[MS_BELOW_HEAP]) atomicAdd(&stats[MS_BELOW_HEAP], r[MS_BELOW_HEAP]);
+}
+// the keys of one pass, in the order the passes before it left
+__global__ __launch_bounds__(256) void mem_pass_key_kernel(const u64* __restrict__ canon, u32 n_cells, const u32* __restrict__ idx, u32 field,
+                                                           u64* __restrict__ keys) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n_cells) keys[i] = mem_sort_key(canon, n_cells, field, idx[i]);
+}
+
+// thread = row: row i < n_cells reads its cell and its predecessor's address and clock through the sorted index, all 29 columns are stored
+// along rows, the prophet-region padding comes in the same pass.  The range-checked values go to their final places in rc_out (when given):
+// the sort values of rows 1 .. n_cells - 1 without the first heap row behind a stack row (generation/memory.rs:77-86), then the region
+// values of the heap rows.  Heap rows being a suffix, a sort value's place is i - 1, one less behind that boundary row, and a region
+// value's is i - first_heap behind the sort values.
+__global__ __launch_bounds__(256) void mem_fill_kernel(const u64* __restrict__ canon, const u32* __restrict__ idx, u32 n_cells, u32 first_heap,
+                                                       u32 quirks, u32 n, u64* __restrict__ out, u64* __restrict__ rc_out) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const u64 prophet_base = gl_neg(0xFFFFFFFFull);                    // p - (2^32 - 1): where the prophet region starts
+    const bool boundary_exists = first_heap > 0 && first_heap < n_cells;
+    u64 addr = 0, clk = 0, op = 0, value = 0, is_write = 0, d_addr = 0, d_clk = 0, cond = 0, rc = 0;
+    u32 sel = 0;
+    bool rw = false, heap = false, prophet = false, unchanged = false, looking = false;
+    if (i < n_cells) {
+        const u32 r = idx[i];
+        addr = canon[(size_t)CELL_ADDR * n_cells + r];
+        clk = canon[(size_t)CELL_CLK * n_cells + r];
+        op = canon[(size_t)CELL_OP * n_cells + r];
+        value = canon[(size_t)CELL_VALUE * n_cells + r];
+        is_write = canon[(size_t)CELL_IS_WRITE * n_cells + r];
+        (void)mem_op_key(op, sel);
+        rw = true;
+        heap = i >= first_heap;
+        if (heap) cond = gl_sub(prophet_base, addr);                   // 0 - (2^32 - 1) - address
+        if (i > 0) {
+            const u32 q = idx[i - 1];
+            const u64 prev_addr = canon[(size_t)CELL_ADDR * n_cells + q], prev_clk = canon[(size_t)CELL_CLK * n_cells + q];
+            d_addr = addr - prev_addr;
+            if (i != first_heap) {                                     // the first heap row behind a stack row gets DIFF_ADDR and its inverse only
+                unchanged = addr == prev_addr;
+                d_clk = unchanged ? clk - prev_clk : 0;
+                rc = unchanged ? d_clk : d_addr;
+                looking = true;
+            }
+        }
+        if (rc_out) {
+            const u32 n_sort = n_cells - 1 - (boundary_exists ? 1u : 0u);
+            if (looking) rc_out[i - 1 - ((boundary_exists && first_heap < i) ? 1u : 0u)] = rc;
+            if (heap) rc_out[(size_t)n_sort + (i - first_heap)] = cond;
+        }
+    } else if (quirks) {                                               // n_cells == 0: generation/memory.rs:95-153 as it is, every row a prophet row
+        addr = gl_add(prophet_base, i);
+        is_write = 1; prophet = true;
+        cond = rc = gl_neg(addr);
+        if (i) { sel = tm::COL_MEM_S_PROPHET; d_addr = 1; }
+    } else {
+        const u32 start = n_cells ? n_cells : 1;                       // a table without cells: row 0 carries S_PROPHET and IS_WRITE only
+        sel = tm::COL_MEM_S_PROPHET;
+        is_write = 1;
+        if (i >= start) {
+            addr = gl_add(prophet_base, i - start);
+            prophet = true;
+            // the first padding row continues from the last live address, the others step by 1
+            d_addr = i != start ? 1 : gl_sub(addr, n_cells ? canon[(size_t)CELL_ADDR * n_cells + idx[n_cells - 1]] : 0);
+            cond = rc = gl_neg(addr);
+        }
+    }
+    const u64 d_inv = d_addr <= 1 ? d_addr : gl_inv(d_addr);          // the inverse of 0 is 0
+    auto put = [&](u32 c, u64 v) { out[(size_t)c * n + i] = v; };
+    put(tm::COL_MEM_TX_IDX, 0);
+    put(tm::COL_MEM_ENV_IDX, 0);
+    put(tm::COL_MEM_IS_RW, rw ? 1 : 0);
+    put(tm::COL_MEM_ADDR, addr);
+    put(tm::COL_MEM_CLK, clk);
+    put(tm::COL_MEM_OP, op);
+#pragma unroll
+    for (u32 c = tm::COL_MEM_S_MLOAD; c <= tm::COL_MEM_S_PROPHET; c++) put(c, c == sel ? 1 : 0);
+    put(tm::COL_MEM_IS_WRITE, is_write);
+    put(tm::COL_MEM_VALUE, value);
+    put(tm::COL_MEM_DIFF_ADDR, d_addr);
+    put(tm::COL_MEM_DIFF_ADDR_INV, d_inv);
+    put(tm::COL_MEM_DIFF_CLK, d_clk);
+    put(tm::COL_MEM_DIFF_ADDR_COND, cond);
+    put(tm::COL_MEM_RW_ADDR_UNCHANGED, unchanged ? 1 : 0);
+    put(tm::COL_MEM_REGION_PROPHET, prophet ? 1 : 0);
+    put(tm::COL_MEM_REGION_HEAP, heap ? 1 : 0);
+    put(tm::COL_MEM_RC_VALUE, rc);
+    put(tm::COL_MEM_FILTER_LOOKING_RC, looking ? 1 : 0);
+    put(tm::COL_MEM_FILTER_LOOKING_RC_COND, heap ? 1 : 0);
+}
+static_assert(tm::COL_MEM_S_PROPHET - tm::COL_MEM_S_MLOAD == 10 && tm::COL_MEM_S_MLOAD == tm::COL_MEM_OP + 1 && tm::COL_MEM_IS_WRITE == tm::COL_MEM_S_PROPHET + 1,
+              "the eleven selector columns of the memory table lie between OP and IS_WRITE");
+
+// ops: op0, op1 (n_ops each); rows n_ops .. n are generation/builtin.rs:240-245's padding
+__global__ __launch_bounds__(256) void cmp_fill_kernel(const u64* __restrict__ ops, u32 n_ops, u32 n, u64* __restrict__ out,
+                                                       u64* __restrict__ abs_diff_out) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const bool live = i < n_ops;
+    const u64 a = live ? gl_canon(ops[i]) : 1, b = live ? gl_canon(ops[(size_t)n_ops + i]) : 0;
+    const u64 d = a >= b ? a - b : b - a;
+    out[(size_t)tm::COL_CMP_OP0 * n + i] = a;
+    out[(size_t)tm::COL_CMP_OP1 * n + i] = b;
+    out[(size_t)tm::COL_CMP_GTE * n + i] = a >= b ? 1 : 0;
+    out[(size_t)tm::COL_CMP_ABS_DIFF * n + i] = d;
+    out[(size_t)tm::COL_CMP_ABS_DIFF_INV * n + i] = d <= 1 ? d : gl_inv(d);
+    out[(size_t)tm::COL_CMP_FILTER_LOOKING_RC * n + i] = live ? 1 : 0;
+    if (live && abs_diff_out) abs_diff_out[i] = d;
+}
+
 u32 log2_rows(u64 rows) {            // next power of two, at least 2 (the reference's ext_trace_len)
     u32 log_n = 1;
     while (((u64)1 << log_n) < rows) log_n++;
@@ -699,6 +870,63 @@ bool generate_prog_trace_steps_dev(DeviceCtx* ctx, const u64* steps, size_t n_st
     generate_prog_trace_dev(ctx, exec, prog, log_n, beta, out);
     HIP_CHECK(hipGetLastError());
     return true;
+}
+
+u32 memory_trace_log_n(u64 n_cells) { return log2_rows(std::max<u64>(n_cells + 1, 8)); }
+u32 cmp_trace_log_n(u64 n_ops) { return log2_rows(n_ops); }
+
+void generate_memory_trace_dev(DeviceCtx* ctx, const u64* cells, size_t n_cells_, bool reference_quirks, u64* out, u64* rc_out, u64 counts[2]) {
+    const u32 n = 1u << memory_trace_log_n(n_cells_), n_cells = (u32)n_cells_;
+    hipStream_t stream = ctx->stream;
+    counts[0] = counts[1] = 0;
+    if (n_cells == 0) {
+        hipLaunchKernelGGL(mem_fill_kernel, dim3(blocks(n)), dim3(256), 0, stream, nullptr, nullptr, 0u, 0u, reference_quirks ? 1u : 0u, n, out, nullptr);
+        HIP_CHECK(hipGetLastError());
+        return;
+    }
+    Scratch mem(ctx);
+    u64* canon = mem.alloc<u64>((size_t)tm::MEM_CELL_WORDS * n_cells);
+    u64* keys = mem.alloc<u64>(2 * (size_t)n_cells);                       // a pass's keys, and where the sort leaves them
+    u32* idx[2] = {mem.alloc<u32>(n_cells), mem.alloc<u32>(n_cells)};
+    unsigned long long* stats = mem.alloc<unsigned long long>(MS_WORDS);
+    HIP_CHECK(hipMemsetAsync(stats, 0, MS_WORDS * sizeof(unsigned long long), stream));
+    hipLaunchKernelGGL(mem_key_kernel, dim3(blocks(n_cells)), dim3(256), 0, stream, cells, n_cells, canon, idx[0], stats);
+    HIP_CHECK(hipGetLastError());
+    unsigned long long host_stats[MS_WORDS];
+    HIP_CHECK(hipMemcpyAsync(host_stats, stats, sizeof(host_stats), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    // least significant key first; rocPRIM's radix sort is stable, so each pass keeps the order of the ones before it
+    const u32 order[tm::MEM_CELL_WORDS] = {CELL_IS_WRITE, CELL_VALUE, CELL_OP, CELL_CLK, CELL_ADDR};
+    // one temporary buffer for every pass: the largest any of their bit ranges asks for
+    u32 bits[tm::MEM_CELL_WORDS];
+    size_t tmp_bytes = 8;
+    for (u32 field : order) {
+        bits[field] = bit_length(host_stats[field]);
+        size_t bytes = 0;
+        if (bits[field]) HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, keys, keys + n_cells, idx[0], idx[1], n_cells, 0, bits[field], stream));
+        tmp_bytes = std::max(tmp_bytes, bytes);
+    }
+    void* tmp = mem.alloc<unsigned char>(tmp_bytes);
+    u32 cur = 0;
+    for (u32 field : order) {
+        if (bits[field] == 0) continue;                                     // every key of this field is 0
+        hipLaunchKernelGGL(mem_pass_key_kernel, dim3(blocks(n_cells)), dim3(256), 0, stream, canon, n_cells, idx[cur], field, keys);
+        HIP_CHECK(hipGetLastError());
+        size_t bytes = tmp_bytes;
+        HIP_CHECK(rocprim::radix_sort_pairs(tmp, bytes, keys, keys + n_cells, idx[cur], idx[cur ^ 1], n_cells, 0, bits[field], stream));
+        cur ^= 1;
+    }
+    const u32 first_heap = (u32)host_stats[MS_BELOW_HEAP];
+    hipLaunchKernelGGL(mem_fill_kernel, dim3(blocks(n)), dim3(256), 0, stream, canon, idx[cur], n_cells, first_heap, 0u, n, out, rc_out);
+    HIP_CHECK(hipGetLastError());
+    counts[0] = n_cells - 1 - ((first_heap > 0 && first_heap < n_cells) ? 1 : 0);
+    counts[1] = n_cells - first_heap;
+}
+
+void generate_cmp_trace_dev(DeviceCtx* ctx, const u64* ops, size_t n_ops, u64* out, u64* abs_diff_out) {
+    const u32 n = 1u << cmp_trace_log_n(n_ops);
+    hipLaunchKernelGGL(cmp_fill_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, ops, (u32)n_ops, n, out, abs_diff_out);
+    HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace ola

@@ -20,6 +20,7 @@
 #include "lookup.h"
 #include "tablegen_columns.h"
 #include "tablegen_cpu_columns.h"
+#include "tablegen_mem_columns.h"
 #include "peer_group.h"
 #include "rccl_carrier.h"
 
@@ -1382,6 +1383,53 @@ int32_t ola_generate_prog_trace_steps(OlaCtx* ctx, const uint64_t* steps, size_t
                                                     &exec_rows);
     *exec_rows_out = exec_rows;
     require(fits, "the steps give more executed rows than 2^log_n (the count is in *exec_rows_out)");
+    t.finish();
+    OLA_CATCH
+}
+
+static_assert(OLA_MEM_CELL_WORDS == olatgm::MEM_CELL_WORDS, "include/ola_gpu.h and tablegen_mem_columns.h disagree on the memory cell");
+int32_t ola_generate_memory_trace(OlaCtx* ctx, const uint64_t* cells, size_t n_cells, uint32_t flags, uint64_t* out, uint32_t* log_n_out,
+                                  uint64_t* rc_out, uint64_t rc_counts[2]) {
+    OLA_TRY
+    require(log_n_out && rc_counts, "null pointer");
+    require((flags & ~(uint32_t)OLA_TABLEGEN_REFERENCE_QUIRKS) == 0, "unknown flag");
+    require(n_cells < ((size_t)1 << 31), "2^31 cells or more");
+    *log_n_out = memory_trace_log_n(n_cells);
+    if (!out) return OLA_OK;       // the sizing call
+    require(cells || n_cells == 0, "null pointer");
+    require_context(ctx);
+    OLA_ON_DEVICE(ctx);
+    DevBuf mem(&ctx->dev);
+    const u64* d_cells = table_input(ctx, mem, cells, (size_t)OLA_MEM_CELL_WORDS * n_cells);
+    TableOutput t(ctx, mem, out, (size_t)olatgm::NUM_MEM_COLS << *log_n_out);
+    // the value lists: in place when rc_out is device memory, else through a device buffer; only the words the counts name are written
+    const bool rc_on_device = rc_out && n_cells && pointer_on_device(ctx, rc_out);
+    u64* d_rc = !rc_out || !n_cells ? nullptr : rc_on_device ? (u64*)rc_out : mem.alloc(2 * n_cells);
+    u64 counts[2] = {0, 0};
+    generate_memory_trace_dev(&ctx->dev, d_cells, n_cells, (flags & OLA_TABLEGEN_REFERENCE_QUIRKS) != 0, t.dev, d_rc, counts);
+    if (d_rc && !rc_on_device && counts[0] + counts[1])
+        HIP_CHECK(hipMemcpyAsync(rc_out, d_rc, (counts[0] + counts[1]) * 8, hipMemcpyDeviceToHost, ctx->dev.stream));
+    t.finish();
+    rc_counts[0] = counts[0]; rc_counts[1] = counts[1];
+    OLA_CATCH
+}
+
+int32_t ola_generate_cmp_trace(OlaCtx* ctx, const uint64_t* ops, size_t n_ops, uint64_t* out, uint32_t* log_n_out, uint64_t* abs_diff_out) {
+    OLA_TRY
+    require(log_n_out, "null pointer");
+    require(n_ops < ((size_t)1 << 31), "2^31 operand pairs or more");
+    *log_n_out = cmp_trace_log_n(n_ops);
+    if (!out) return OLA_OK;       // the sizing call
+    require(ops || n_ops == 0, "null pointer");
+    require_context(ctx);
+    OLA_ON_DEVICE(ctx);
+    DevBuf mem(&ctx->dev);
+    const u64* d_ops = table_input(ctx, mem, ops, 2 * n_ops);
+    TableOutput t(ctx, mem, out, (size_t)olatgm::COL_NUM_CMP << *log_n_out);
+    const bool diff_on_device = abs_diff_out && n_ops && pointer_on_device(ctx, abs_diff_out);
+    u64* d_diff = !abs_diff_out || !n_ops ? nullptr : diff_on_device ? (u64*)abs_diff_out : mem.alloc(n_ops);
+    generate_cmp_trace_dev(&ctx->dev, d_ops, n_ops, t.dev, d_diff);
+    if (d_diff && !diff_on_device) HIP_CHECK(hipMemcpyAsync(abs_diff_out, d_diff, n_ops * 8, hipMemcpyDeviceToHost, ctx->dev.stream));
     t.finish();
     OLA_CATCH
 }

@@ -7,14 +7,17 @@ count = 70000 gives 980 k executed CPU rows (2^20), 280 k memory cells, a 2^21-r
 immediate word) and 280 k range-checked sort values.  The proof is checked with the oracle's verifier; with OLA_TIMING=1 the
 library prints its per-phase times (named after the reference's `timed!` scopes) to stderr.
 
-    python tools/bench_prove_real.py [count] [reps] [--json out.json] [--phases] [--oracle] [--python] [--storage-slots N] [--hasher blake3] [--steps] [--shape readme]
+    python tools/bench_prove_real.py [count] [reps] [--json out.json] [--phases] [--oracle] [--python] [--storage-slots N] [--hasher blake3] [--steps | --cells] [--shape readme]
 
 --steps compares the two ways from an execution to proof bytes, taken in alternation `reps` times in this process: the table path
 (the native generator fills all twelve tables, they are uploaded and proven) and the step path (the generator runs with
 OLA_TRACEGEN_STEPS_ONLY, the step records go up, ola_generate_cpu_trace and ola_generate_prog_trace_steps write the CPU and the program
 table into HBM and the proof runs on them as resident tables).  Timed apart: the native generator's call (ola_tracegen_run), the
 Python binding's copies of its output into numpy arrays (harness cost, larger on the table path: it copies the two tables the step
-path never builds), device table generation, and the proof.  --shape readme runs the README's Fibonacci shape
+path never builds), device table generation, and the proof.  --cells adds a third way to the alternation, the cell path: the generator runs with OLA_TRACEGEN_CELLS_ONLY, and on top of the step path's
+two tables ola_generate_cmp_trace, ola_generate_memory_trace and ola_generate_rc_trace write the comparison, memory and range-check tables
+into HBM -- the range-check table from a `vals` buffer in HBM that holds the CPU's values and, behind them, the lists the first two calls
+leave there.  Identical proof bytes on every path are asserted in every round.  --shape readme runs the README's Fibonacci shape
 (miniexec.fibonacci_loop(47, 3000): 864 002 CPU rows, every other table small) instead of the memory program.
 """
 import json
@@ -47,8 +50,8 @@ def main():
         prog, kw = M.fibonacci_loop(47, 3000), {}
     else:
         prog, kw = M.memory_program(count), {}
-    if "--steps" in sys.argv:
-        return steps_against_tables(prog, kw, blob, reps, hasher, out,
+    if "--steps" in sys.argv or "--cells" in sys.argv:
+        return steps_against_tables(prog, kw, blob, reps, hasher, out, "--cells" in sys.argv,
                                     "fibonacci_loop(47, 3000)" if shape == "readme" else "memory_program(%d)" % count)
     traces, params, compress = gen.instance(prog, range_bits=16, limb_bits=8, max_steps=1 << 24, **kw)
     gen_s = time.time() - t0
@@ -94,13 +97,15 @@ def main():
         raise SystemExit(1)
 
 
-def steps_against_tables(prog, kw, blob, reps, hasher, out, workload):
+def steps_against_tables(prog, kw, blob, reps, hasher, out, cells, workload):
     import numpy as np
     import torch
     from olavm_amd.air import fastexec, ola_tables as T
     from olavm_amd.backend import Backend
     be = Backend(device=0, hasher=hasher)
     runs = {"table_path": [], "step_path": []}
+    if cells:
+        runs["cell_path"] = []
     proofs = {}
     for rep in range(reps + 1):                                  # rep 0 warms both paths up and is not kept
         tm = {}
@@ -129,11 +134,47 @@ def steps_against_tables(prog, kw, blob, reps, hasher, out, workload):
              "total_s": t3 - t0, "total_without_binding_copies_s": t3 - t0 - tm["copy_s"]}
         del lean, d_cpu, d_pg, d_steps
         assert proofs["step_path"] == proofs["table_path"], "the two paths give different proof bytes"
+        if cells:
+            t0 = time.perf_counter()
+            lean, params, compress, rec = fastexec.instance(prog, range_bits=16, limb_bits=8, max_steps=1 << 24, cells_only=True, timings=tm, **kw)
+            t1 = time.perf_counter()
+            d = {t: torch.empty((ncols, 1 << rec[key]), dtype=torch.int64, device="cuda")
+                 for t, ncols, key in ((T.CPU, T.NUM_CPU_COLS, "cpu_log_n"), (T.PROGRAM, T.NUM_PROG_COLS, "prog_log_n"), (T.MEMORY, T.NUM_MEM_COLS, "mem_log_n"),
+                                       (T.CMP, T.COL_NUM_CMP, "cmp_log_n"), (T.RANGECHECK, T.COL_NUM_RC, "rc_log_n"))}
+            n_cpu, n_cmp, n_cells = len(rec["cpu_rc"]), rec["cmp_ops"].shape[1], rec["cells"].shape[1]
+            vals = torch.empty((n_cpu + n_cmp + 2 * n_cells + 1,), dtype=torch.int64, device="cuda")
+            vals[:n_cpu] = torch.from_numpy(rec["cpu_rc"].view(np.int64)).cuda()
+            d_steps = torch.from_numpy(rec["steps"].view(np.int64)).cuda()
+            d_cells = torch.from_numpy(rec["cells"].view(np.int64)).cuda()
+            torch.cuda.synchronize()
+            be.generate_cpu_trace(d_steps, rec["cpu_log_n"], out=d[T.CPU])
+            be.generate_prog_trace_steps(d_steps, rec["listing"], params[1], out=d[T.PROGRAM])
+            be.generate_cmp_trace(rec["cmp_ops"], out=d[T.CMP], abs_diff_out=vals.data_ptr() + 8 * n_cpu)
+            _, _, (n_sort, n_region) = be.generate_memory_trace(d_cells, out=d[T.MEMORY], rc_out=vals.data_ptr() + 8 * (n_cpu + n_cmp))
+            n_rows = n_cpu + n_cmp + n_sort + n_region
+            filters = torch.zeros((4, n_rows), dtype=torch.int64, device="cuda")
+            for col, lo, hi in ((0, 0, n_cpu), (3, n_cpu, n_cpu + n_cmp), (1, n_cpu + n_cmp, n_cpu + n_cmp + n_sort), (2, n_cpu + n_cmp + n_sort, n_rows)):
+                filters[col, lo:hi] = 1
+            torch.cuda.synchronize()
+            be.generate_rc_trace(vals.data_ptr(), filters, range_bits=16, out=d[T.RANGECHECK], n_rows=n_rows)
+            t2 = time.perf_counter()
+            for t, table in d.items():
+                lean[t] = table
+            proofs["cell_path"] = bytes(be.prove_with_traces(blob, lean, params, compress))
+            t3 = time.perf_counter()
+            c = {"native_trace_generation_s": tm["native_s"], "binding_copies_s": tm["copy_s"], "device_table_generation_s": t2 - t1, "prove_s": t3 - t2,
+                 "total_s": t3 - t0, "total_without_binding_copies_s": t3 - t0 - tm["copy_s"]}
+            del lean, d, vals, d_steps, d_cells, filters
+            assert proofs["cell_path"] == proofs["table_path"], "the cell path gives different proof bytes"
         if rep:
             runs["table_path"].append(a)
             runs["step_path"].append(b)
+            if cells:
+                runs["cell_path"].append(c)
         print(("warm-up " if not rep else "") + "table path %s" % {k: round(v, 3) for k, v in a.items()}, flush=True)
         print(("warm-up " if not rep else "") + "step path  %s" % {k: round(v, 3) for k, v in b.items()}, flush=True)
+        if cells:
+            print(("warm-up " if not rep else "") + "cell path  %s" % {k: round(v, 3) for k, v in c.items()}, flush=True)
     be.close()
     med = lambda path, key: sorted(r[key] for r in runs[path])[len(runs[path]) // 2]
     summary = {path: {key: round(med(path, key), 3) for key in runs[path][0]} for path in runs}

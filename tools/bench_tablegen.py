@@ -1,5 +1,6 @@
 """Times ola_generate_rc_trace / ola_generate_bitwise_trace / ola_generate_prog_trace -- and ola_generate_cpu_trace /
-ola_generate_prog_trace_steps, the cases cpu:20 cpu:22 progsteps:21 progsteps:23 -- with resident inputs and outputs, next to
+ola_generate_prog_trace_steps, the cases cpu:20 cpu:22 progsteps:21 progsteps:23, and ola_generate_memory_trace / ola_generate_cmp_trace,
+the cases mem:19 mem:21 cmp:16 -- with resident inputs and outputs, next to
 the same derived columns obtained without them: one ola_permuted_cols_dev call per pair (device) plus numpy for the other columns
 (host), and next to the oracle's sequential permuted_cols on one host core (as tools/bench_lookup.py measures it).
 
@@ -28,6 +29,7 @@ from olavm_amd.air.dsl import P
 
 CASES = ["bitwise:18", "rc:16", "rc:21", "prog:20", "prog:23"]
 STEP_CASES = ["cpu:20", "cpu:22", "progsteps:21", "progsteps:23"]       # named on the command line
+CELL_CASES = ["mem:19", "mem:21", "cmp:16"]                              # named on the command line
 FN = (lambda x, y: x & y, lambda x, y: x | y, lambda x, y: x ^ y)
 
 
@@ -46,6 +48,19 @@ def inputs(kind, log_n, rng):
         res = np.choose(which, [x & y, x | y, x ^ y])
         tag = np.array([T.op_mask("AND"), T.op_mask("OR"), T.op_mask("XOR")], dtype=np.uint64)[which]
         return (np.stack([np.ones(rows, dtype=np.uint64), tag, x, y, res]),), {"limb_bits": 8, "beta": 0x123456789ABCDEF}
+    if kind == "mem":          # the synthetic pattern of docs/EXPERIMENTS.md's host figures, in execution order: every address stored once,
+        k = 290000 * n >> 21   # then loaded three times in reverse order; as many cells as memory_program(290000) has at 2^21 rows (1.16 M).
+        # Not memory_program's own cells (store, then load / store / load per address): the clocks differ; the values are random field
+        # elements, as wide as its Fibonacci numbers mod p, so that the value pass of the sort covers 64 bits as it does there
+        addr = np.arange(1, k + 1, dtype=np.uint64)
+        value = rng.integers(0, P, k, dtype=np.uint64)
+        cells = np.zeros((5, 4 * k), dtype=np.uint64)
+        cells[0], cells[1, :k], cells[2, :k], cells[4, :k] = np.concatenate([addr] + 3 * [addr[::-1]]), 10 + 2 * np.arange(k), T.op_mask("MSTORE"), 1
+        cells[1, k:], cells[2, k:] = 10 + 2 * k + 3 * np.arange(3 * k), T.op_mask("MLOAD")
+        cells[3] = np.concatenate([value] + 3 * [value[::-1]])
+        return (cells,), {}
+    if kind == "cmp":          # 15/16 of the rows live, 32-bit operands
+        return (rng.integers(0, 1 << 32, (2, n - n // 16), dtype=np.uint64),), {}
     if kind == "cpu":          # 15/16 of the rows live, every word of the record random
         return (rng.integers(0, P, (S.STEP_WORDS, n - n // 16), dtype=np.uint64),), {"log_n": log_n}
     listed = 3 * n // 4
@@ -84,12 +99,21 @@ def call(be, kind, dev, kw, out):
         return be.generate_bitwise_trace(dev[0], kw["beta"], limb_bits=kw["limb_bits"], out=out)
     if kind == "cpu":
         return be.generate_cpu_trace(dev[0], kw["log_n"], out=out)
+    if kind in ("mem", "cmp"):             # the value list stays in HBM as well
+        import torch
+        if "list" not in kw:
+            kw["list"] = torch.empty((2 * dev[0].shape[1] + 1,), dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()
+        if kind == "mem":
+            return be.generate_memory_trace(dev[0], out=out, rc_out=kw["list"])[0]
+        return be.generate_cmp_trace(dev[0], out=out, abs_diff_out=kw["list"])[0]
     if kind == "progsteps":
         return be.generate_prog_trace_steps(dev[0], dev[1], kw["beta"], out=out)[0]
     return be.generate_prog_trace(dev[0], dev[1], kw["beta"], out=out)
 
 
-NCOLS = {"rc": T.COL_NUM_RC, "bitwise": T.COL_NUM_BITWISE, "prog": T.NUM_PROG_COLS, "cpu": T.NUM_CPU_COLS, "progsteps": T.NUM_PROG_COLS}
+NCOLS = {"rc": T.COL_NUM_RC, "bitwise": T.COL_NUM_BITWISE, "prog": T.NUM_PROG_COLS, "cpu": T.NUM_CPU_COLS, "progsteps": T.NUM_PROG_COLS,
+         "mem": T.NUM_MEM_COLS, "cmp": T.COL_NUM_CMP}
 
 
 def pairs_of(kind):
@@ -97,7 +121,7 @@ def pairs_of(kind):
     if kind == "rc":
         return [(T.RC_LIMB_LO, T.RC_FIX_RANGE_CHECK_U16, T.RC_LIMB_LO_PERMUTED, T.RC_FIX_RANGE_CHECK_U16_PERMUTED_LO),
                 (T.RC_LIMB_HI, T.RC_FIX_RANGE_CHECK_U16, T.RC_LIMB_HI_PERMUTED, T.RC_FIX_RANGE_CHECK_U16_PERMUTED_HI)]
-    if kind == "cpu":
+    if kind in ("cpu", "mem", "cmp"):
         return []
     if kind in ("prog", "progsteps"):
         return [(T.COL_PROG_EXEC_COMP_PROG, T.COL_PROG_COMP_PROG, T.COL_PROG_EXEC_COMP_PROG_PERM, T.COL_PROG_COMP_PROG_PERM)]
@@ -172,6 +196,11 @@ def measure(kind, log_n, runs):
 
     rec = {"table": kind, "log_n": log_n, "runs": runs}
     rec["call_device_ms"], rec["call_wall_ms"] = timed(lambda: call(be, kind, dev, kw, out))
+    if kind in ("mem", "cmp"):             # no permuted pairs; the host-side counterpart is memory_table() / cmp_table() of the native generator (docs/EXPERIMENTS.md, the last section)
+        rec["cells" if kind == "mem" else "operand_pairs"] = int(host[0].shape[1])
+        rec["table_words"] = NCOLS[kind] * n
+        be.close()
+        return rec
     if kind in ("cpu", "progsteps"):       # no host-side counterpart to compare with: the table path never had these inputs
         rec["steps"] = int(host[0].shape[1])
         if kind == "cpu":                  # bytes read and written: the records and the table

@@ -259,6 +259,13 @@ PY
                    timeout -k 10 600 python tools/bench_prove_real.py 0 3 --steps --shape readme --json $O/steps_vs_tables_readme.json 2>&1 | grep -v amdgpu | tee $O/steps_vs_tables_readme.txt && \
                    timeout -k 10 900 python tools/bench_prove_real.py 70000 3 --steps --json $O/steps_vs_tables_2p20.json 2>&1 | grep -v amdgpu | tee $O/steps_vs_tables_2p20.txt && \
                    timeout -k 10 1500 python tools/bench_prove_real.py 290000 3 --steps --json $O/steps_vs_tables_2p22.json 2>&1 | grep -v amdgpu | tee $O/steps_vs_tables_2p22.txt ) ;;
+    memgen)      # the memory and comparison tables from raw cells: their tests, the timings and launch counts, then table, step and cell path in alternation
+                 ( set -o pipefail
+                   timeout -k 10 600 python -m pytest tests/test_gpu_mem_tablegen.py tests/test_mem_tablegen_abi.py -x -q 2>&1 | tail -15 | tee $O/pytest.log && \
+                   timeout -k 10 600 python tools/bench_tablegen.py --json $O/tablegen_cells.json mem:19 mem:21 cmp:16 2>&1 | grep -v amdgpu | tee $O/tablegen_cells.txt && \
+                   timeout -k 10 600 python tools/bench_prove_real.py 0 3 --cells --shape readme --json $O/cells_vs_steps_readme.json 2>&1 | grep -v amdgpu | tee $O/cells_vs_steps_readme.txt && \
+                   timeout -k 10 900 python tools/bench_prove_real.py 70000 3 --cells --json $O/cells_vs_steps_2p20.json 2>&1 | grep -v amdgpu | tee $O/cells_vs_steps_2p20.txt && \
+                   timeout -k 10 1500 python tools/bench_prove_real.py 290000 3 --cells --json $O/cells_vs_steps_2p22.json 2>&1 | grep -v amdgpu | tee $O/cells_vs_steps_2p22.txt ) ;;
     check_lookup) # ola_check_lookup: its tests, then the CPU -> memory and CPU -> program lookups of a 2^22-row executed instance, valid and with one looked row dropped
                  ( set -o pipefail
                    timeout -k 10 600 python -m pytest tests/test_gpu_check_lookup.py -x -q 2>&1 | tail -15 | tee $O/pytest.log && \
