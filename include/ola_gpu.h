@@ -49,7 +49,9 @@ extern "C" {
  * OlaLookupMismatch and the entry point ola_check_lookup (the tuples a failing cross-table lookup is missing); so were
  * ola_generate_cpu_trace and ola_generate_prog_trace_steps (the CPU table and the program table from the executor's step records); so
  * were ola_generate_memory_trace and ola_generate_cmp_trace (the memory table from raw cells, sorted on the device, and the comparison
- * table from operand pairs, both with their range-checked value lists). */
+ * table from operand pairs, both with their range-checked value lists); so were ola_generate_storage_trace and
+ * ola_generate_poseidon_table (the account-storage tree hashed on the device with the storage-access table and the Poseidon table's
+ * inputs, and the Poseidon table at its padded height, resident). */
 #define OLA_GPU_ABI_VERSION 7
 #define OLA_OK 0
 #define OLA_E_INVALID_ARG (-1)
@@ -691,6 +693,67 @@ int32_t ola_generate_prog_trace_steps(OlaCtx* ctx, const uint64_t* steps, size_t
 int32_t ola_generate_memory_trace(OlaCtx* ctx, const uint64_t* cells, size_t n_cells, uint32_t flags, uint64_t* out, uint32_t* log_n_out,
                                   uint64_t* rc_out, uint64_t rc_counts[2]);
 int32_t ola_generate_cmp_trace(OlaCtx* ctx, const uint64_t* ops, size_t n_ops, uint64_t* out, uint32_t* log_n_out, uint64_t* abs_diff_out);
+
+/* ---- the account-storage tree, the storage-access table and the Poseidon table ---------------------------------------------------
+ * What is left of trace generation on the host after the calls above is mostly Poseidon hashing for the account-storage tree: a write
+ * is 256 permutations, and every access contributes 512 rows -- the hash of every level in the tree after and before the access -- to
+ * the Poseidon table (builtins/storage/storage_access_stark.rs:110-334, generation/storage.rs:7-123).  A batch of accesses is
+ * 2 x 256 x n_access independent permutations per tree level with a dependency only from one level to the next, so the device hashes
+ * the tree, one launch per level, and writes the storage table and the Poseidon table's inputs; a second call turns those inputs into
+ * the 134-column table.  The contract is the one of the "whole derived tables" block above: every buffer may be host memory or memory
+ * of the context's GPU, words may be >= p, every word written is canonical, every column of `out` is written (no memset of the
+ * table), the work runs on the context's stream and is complete on return, arguments are validated first, out == NULL is a sizing
+ * call that also takes ctx == NULL, ctx == NULL in a call that would do work is OLA_E_NO_DEVICE on a machine without a HIP device and
+ * OLA_E_INVALID_ARG otherwise, a multi-device context works on its first device, and `out` can go into ola_prove_with_traces* as a
+ * resident table.
+ *
+ * ola_generate_storage_trace: out = 48 x n, n = next_pow2(max(256 m, 8)) with m the number of accesses without OLA_STORAGE_SILENT, log2 n
+ *   in *log_n_out.
+ *   accesses: OLA_STORAGE_ACCESS_WORDS = 14 words per access, column-major 14 x n_access, in execution order: words 0..3 the tree key,
+ *     4..7 `value` (the leaf after a write), 8..11 `pre_value` (used only with `siblings`), 12 flags, 13 psdn_row (the Poseidon-table row
+ *     of this access's first hash).  n_access >= 2^23 and a flag bit nobody defined are OLA_E_INVALID_ARG.  The flags and psdn_row words
+ *     are read by the host before any work (one copy when the records are in HBM).  In a sizing call `accesses` may be NULL: no access is
+ *     then taken to be silent.
+ *   The tree: 256 levels, the key's bits (most significant limb first) choose the child, an inner node is
+ *     Poseidon(left || right || 0,0,0,0)[0..4], the lowest level hashes the two 4-word values with capacity word 1, untouched leaves are
+ *     zero.  The hash is Poseidon whatever the context's hasher, because the AIR's is.
+ *   siblings == NULL, the self-contained batch: the tree is empty before access 0.  The sibling of access i at layer L is the layer-L node
+ *     of the latest access j < i whose key shares exactly L - 1 leading bits with key i (silent accesses included), the empty tree's node
+ *     if there is none; the leaf before access i is the value left by the latest write j < i of the same key, zero otherwise.  A read
+ *     leaves the leaf as it is: its `value` words and every `pre_value` are ignored.
+ *   siblings != NULL, for a host with a persistent tree of its own: 1024 x n_access column-major, word w of layer L of access a at
+ *     ((L - 1) * 4 + w) * n_access + a.  `pre_value` is the leaf before the access and `value` the leaf after it (for a read the caller
+ *     passes the same words twice: the call copies and does not compare).  OLA_STORAGE_SILENT is OLA_E_INVALID_ARG.  The accesses are
+ *     independent of each other; that one access's tree is the next one's is the caller's business (ola_check_constraints localises a
+ *     break).
+ *   out: 256 rows per access with rows, layer 1 (the root side) first, accesses in order; the columns of generation/storage.rs:23-82:
+ *     ACCESS_IDX counts from 1 over the accesses with rows, ADDR_ACC = limb (L - 1) / 64 of the key shifted right by 63 - (L - 1) % 64,
+ *     FILTER_IS_FOR_PROG on the layer-256 row of an access with OLA_STORAGE_FOR_PROG.  Padding rows (generation/storage.rs:84-114):
+ *     IS_PADDING = 1, ROOT = the last live row's root, the rest 0; m == 0 gives the all-padding table with zero roots.
+ *   psdn_inputs / psdn_filters: NULL together, or the 12 x psdn_stride and 4 x psdn_stride column-major input buffers of
+ *     ola_generate_poseidon_table, both in host memory or both on the device.  For every access with rows, layer L and version v (0 = the
+ *     tree after the access, 1 = before) the call writes row psdn_row + 2 (L - 1) + v -- StorageTree::access's order: the permutation's
+ *     twelve inputs (the children in bit order, the capacity word L == 256, then 0, 0, 0) and the filters (0, 0, L == 256, L != 256).
+ *     psdn_row + 512 > psdn_stride is OLA_E_INVALID_ARG, checked before any work.  Rows the call does not own keep what they hold (a host
+ *     buffer travels to the device and back whole); two accesses must not claim the same rows.
+ *   roots_out: NULL, or 8 words: 0..3 the root before the first access with rows (the root after the last access when none has rows),
+ *     4..7 the root after the last access; with n_access == 0 both are the empty tree's root.  The generators' program-table challenge
+ *     needs both (generation/prog.rs:23-29).
+ *   The work: a resolver (self-contained mode: one thread per access scans the earlier ones, O(n_access^2) pair steps), 256 launches of
+ *     one thread per (access, version), one launch that fills the remaining columns and the padding.
+ * ola_generate_poseidon_table: out = 134 x n, n = next_pow2(max(n_rows, 8)), log2 n in *log_n_out.  inputs: 12 x stride column-major,
+ *   filters: 4 x stride or NULL for zeros, stride >= n_rows (a smaller one and n_rows > 2^26 are OLA_E_INVALID_ARG); rows n_rows .. n are
+ *   the rows of all-zero inputs (generation/poseidon.rs's POSEIDON_ZERO_HASH rows).  The rows are ola_generate_poseidon_trace's. */
+#define OLA_STORAGE_ACCESS_WORDS 14
+#define OLA_STORAGE_WRITE 1u      /* flags word, bit 0 */
+#define OLA_STORAGE_FOR_PROG 2u   /* bit 1: a program-hash read (generation/storage.rs:74-80) */
+#define OLA_STORAGE_SILENT 4u     /* bit 2: a write that establishes the tree before the run and emits no rows */
+int32_t ola_generate_storage_trace(OlaCtx* ctx, const uint64_t* accesses, size_t n_access, const uint64_t* siblings,
+                                   uint64_t* out, uint32_t* log_n_out,
+                                   uint64_t* psdn_inputs, uint64_t* psdn_filters, size_t psdn_stride,
+                                   uint64_t roots_out[8]);
+int32_t ola_generate_poseidon_table(OlaCtx* ctx, const uint64_t* inputs, const uint64_t* filters, size_t n_rows, size_t stride,
+                                    uint64_t* out, uint32_t* log_n_out);
 
 /* ---- coset-partitioned proving over several GPUs ---------------------------------------------------------
  * One process per GPU; every process calls ola_prove_with_traces with the SAME traces.  Because the transcript is a

@@ -520,4 +520,35 @@ inline std::vector<F> generate_cmp_trace(const Gpu& g, const std::vector<F>& ops
     return out;
 }
 
+// access records (OLA_STORAGE_ACCESS_WORDS x n_access column-major, execution order) -> the 48 x n storage-access table
+// (generation/storage.rs:7-123), the state tree hashed on the device.  siblings: empty = the self-contained batch on an empty tree, else
+// 1024 x n_access from the caller's tree.  psdn_inputs / psdn_filters, when given, are the 12 x psdn_stride and 4 x psdn_stride input
+// buffers of generate_poseidon_table whose storage rows the call fills; roots, when given, receives the root before the first access
+// with rows and the root after the last access
+inline std::vector<F> generate_storage_trace(const Gpu& g, const std::vector<F>& accesses, size_t n_access, const std::vector<F>& siblings = {},
+                                             std::vector<F>* psdn_inputs = nullptr, std::vector<F>* psdn_filters = nullptr, size_t psdn_stride = 0,
+                                             uint64_t roots[8] = nullptr) {
+    if (accesses.size() != OLA_STORAGE_ACCESS_WORDS * n_access || (!siblings.empty() && siblings.size() != 1024 * n_access) ||
+        !psdn_inputs != !psdn_filters || (psdn_inputs && (psdn_inputs->size() != 12 * psdn_stride || psdn_filters->size() != 4 * psdn_stride)))
+        throw Error(OLA_E_INVALID_ARG, "shape");
+    uint32_t log_n = 0;
+    check(ola_generate_storage_trace(nullptr, n_access ? accesses.data() : nullptr, n_access, nullptr, nullptr, &log_n, nullptr, nullptr, 0, nullptr));
+    std::vector<F> out((size_t)48 << log_n);
+    check(ola_generate_storage_trace(g.ctx(), n_access ? accesses.data() : nullptr, n_access, siblings.empty() ? nullptr : siblings.data(), out.data(),
+                                     &log_n, psdn_inputs ? psdn_inputs->data() : nullptr, psdn_filters ? psdn_filters->data() : nullptr, psdn_stride, roots));
+    return out;
+}
+// permutation inputs (12 x stride column-major, the first n_rows of every column live) -> the 134 x n Poseidon table at its padded
+// height n = next_pow2(max(n_rows, 8)) (generation/poseidon.rs:5-80)
+inline std::vector<F> generate_poseidon_table(const Gpu& g, const std::vector<F>& inputs, size_t n_rows, size_t stride, const std::vector<F>& filters = {},
+                                              uint32_t* log_n_out = nullptr) {
+    if (inputs.size() != 12 * stride || (!filters.empty() && filters.size() != 4 * stride)) throw Error(OLA_E_INVALID_ARG, "shape");
+    uint32_t log_n = 0;
+    check(ola_generate_poseidon_table(nullptr, nullptr, nullptr, n_rows, stride, nullptr, &log_n));
+    std::vector<F> out((size_t)134 << log_n);
+    check(ola_generate_poseidon_table(g.ctx(), stride ? inputs.data() : nullptr, filters.empty() ? nullptr : filters.data(), n_rows, stride, out.data(), &log_n));
+    if (log_n_out) *log_n_out = log_n;
+    return out;
+}
+
 }  // namespace ola_host

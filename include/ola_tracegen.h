@@ -54,6 +54,13 @@ typedef struct OlaTraceSet OlaTraceSet;
  * ola_tracegen_cmp_ops and ola_tracegen_cpu_rc_values return what the GPU calls take.  A range-checked value too wide for two limbs,
  * which the table path refuses, is not looked for. */
 #define OLA_TRACEGEN_CELLS_ONLY 16u
+/* flags: OLA_TRACEGEN_CELLS_ONLY (implied), and neither the storage-access table nor the Poseidon table is built: the state tree is
+ * bypassed -- a key -> value map serves SLOAD, no node is hashed -- and the GPU hashes it from the access records (include/ola_gpu.h
+ * ola_generate_storage_trace, ola_generate_poseidon_table).  ola_tracegen_table answers the two with their shape and data = NULL;
+ * ola_tracegen_storage_accesses and ola_tracegen_poseidon_inputs return what the GPU calls take.  The program table's challenge needs
+ * the state roots before and after the run, which only the device's tree has: ola_tracegen_betas answers ~0 (-1) for it unless
+ * OLA_TRACEGEN_EXPLICIT_BETAS is set, and ola_tracegen_program_beta draws it from the roots the GPU call returns. */
+#define OLA_TRACEGEN_HASHES_ONLY 32u
 
 /* Executes the program (at most max_steps CPU rows) and builds the 12 tables of ola_stark(range_bits, limb_bits) in
  * `enum Table` order.  range_bits / limb_bits are 16 / 8 in the reference; smaller values give structurally identical
@@ -61,7 +68,7 @@ typedef struct OlaTraceSet OlaTraceSet;
 int32_t ola_tracegen_run(const OlaInstr* program, size_t n_instr, const uint64_t code_addr[4], const uint64_t storage_addr[4],
                          uint32_t range_bits, uint32_t limb_bits, uint64_t bitwise_beta, uint64_t program_beta, uint64_t max_steps,
                          uint32_t flags, OlaTraceSet** out);
-/* Table t: column-major ncols x 2^log_n words, owned by the set (data = NULL for a table OLA_TRACEGEN_STEPS_ONLY or OLA_TRACEGEN_CELLS_ONLY left out). */
+/* Table t: column-major ncols x 2^log_n words, owned by the set (data = NULL for a table OLA_TRACEGEN_STEPS_ONLY, _CELLS_ONLY or _HASHES_ONLY left out). */
 int32_t ola_tracegen_table(const OlaTraceSet* set, uint32_t table, uint32_t* ncols, uint32_t* log_n, const uint64_t** data);
 /* OLA_TRACEGEN_STEPS_ONLY sets only (-1 otherwise): the step records, OLA_CPU_STEP_WORDS x n_steps column-major, and the program
  * table's listing side, 7 x 2^log_n column-major (four code-address words, pc, inst, filter); both owned by the set. */
@@ -73,6 +80,16 @@ int32_t ola_tracegen_prog_listing(const OlaTraceSet* set, uint32_t* log_n, const
 int32_t ola_tracegen_mem_cells(const OlaTraceSet* set, uint64_t* n_cells, const uint64_t** data);
 int32_t ola_tracegen_cmp_ops(const OlaTraceSet* set, uint64_t* n_ops, const uint64_t** data);
 int32_t ola_tracegen_cpu_rc_values(const OlaTraceSet* set, uint64_t* n_values, const uint64_t** data);
+/* OLA_TRACEGEN_HASHES_ONLY sets only (-1 otherwise), owned by the set: the access records in execution order, OLA_STORAGE_ACCESS_WORDS x
+ * n_access column-major (tree key, value = the leaf after the access, pre_value = 0, flags, psdn_row) -- the silent write of the
+ * program hash first and its OLA_STORAGE_FOR_PROG read last when OLA_TRACEGEN_PROVE_PROGRAM_HASH is set; and the Poseidon table's
+ * inputs (12 x 2^log_n) and filters (4 x 2^log_n), column-major at full table height, with the program-chunk, POSEIDON-instruction and
+ * tree-key rows filled and the 512 rows of every access left zero, their first row in the record's psdn_row. */
+int32_t ola_tracegen_storage_accesses(const OlaTraceSet* set, uint64_t* n_access, const uint64_t** data);
+int32_t ola_tracegen_poseidon_inputs(const OlaTraceSet* set, uint32_t* log_n, const uint64_t** inputs, const uint64_t** filters);
+/* The program table's compress challenge from roots[0..3] = the state root before the run and roots[4..7] = after it
+ * (generation/prog.rs:23-29; the roots_out of ola_generate_storage_trace).  Host only. */
+int32_t ola_tracegen_program_beta(const uint64_t roots[8], uint64_t* beta);
 /* Number of executed CPU rows (before padding). */
 uint64_t ola_tracegen_cpu_rows(const OlaTraceSet* set);
 /* out[0] = the bitwise table's compress challenge, out[1] = the program table's. */

@@ -49,6 +49,11 @@ pub const OLA_TABLEGEN_REFERENCE_QUIRKS: u32 = 1;
 pub const OLA_CPU_STEP_WORDS: usize = 66;
 /// Words of one memory cell of `ola_generate_memory_trace` (address, clock, the op's one-hot word, value, is_write).
 pub const OLA_MEM_CELL_WORDS: usize = 5;
+/// Words of one access record of `ola_generate_storage_trace` (key[4], value[4], pre_value[4], flags, psdn_row) and its flag bits.
+pub const OLA_STORAGE_ACCESS_WORDS: usize = 14;
+pub const OLA_STORAGE_WRITE: u64 = 1;
+pub const OLA_STORAGE_FOR_PROG: u64 = 2;
+pub const OLA_STORAGE_SILENT: u64 = 4;
 /// `flags` of `ola_generate_prog_trace_steps`: zero rows beyond the executed ones, as the reference's generator leaves them.
 pub const OLA_TABLEGEN_ZERO_FILLER: u32 = 1;
 /// ola_check_constraints: `OlaConstraintFailure::section`
@@ -264,6 +269,10 @@ extern "C" {
         log_n_out: *mut u32, rc_out: *mut u64, rc_counts: *mut u64) -> i32;
     pub fn ola_generate_cmp_trace(ctx: *mut OlaCtx, ops: *const u64, n_ops: usize, out: *mut u64, log_n_out: *mut u32,
         abs_diff_out: *mut u64) -> i32;
+    pub fn ola_generate_storage_trace(ctx: *mut OlaCtx, accesses: *const u64, n_access: usize, siblings: *const u64, out: *mut u64,
+        log_n_out: *mut u32, psdn_inputs: *mut u64, psdn_filters: *mut u64, psdn_stride: usize, roots_out: *mut u64) -> i32;
+    pub fn ola_generate_poseidon_table(ctx: *mut OlaCtx, inputs: *const u64, filters: *const u64, n_rows: usize, stride: usize,
+        out: *mut u64, log_n_out: *mut u32) -> i32;
     pub fn ola_set_shard(ctx: *mut OlaCtx, rank: u32, world: u32, all_gather: OlaAllGatherFn, user: *mut c_void) -> i32;
     pub fn ola_set_shard_options(ctx: *mut OlaCtx, flags: u32) -> i32;
     pub fn ola_gpu_get_stream(ctx: *mut OlaCtx, stream_out: *mut *mut c_void) -> i32;

@@ -131,3 +131,28 @@ def tablegen_mem_columns_header():
     out.append("constexpr uint32_t MEM_OPS = %du, MEM_CELL_WORDS = %du;" % (len(MEM_OPS), MEM_CELL_WORDS))
     out.append("}  // namespace olatgm")
     return "\n".join(out) + "\n"
+
+
+TABLEGEN_STORAGE_COLUMNS_H = "olavm_amd/csrc/tablegen_storage_columns.h"
+STORAGE_ACCESS_WORDS = 14    # include/ola_gpu.h OLA_STORAGE_ACCESS_WORDS: key[4], value[4], pre_value[4], flags, psdn_row
+STORAGE_DEPTH = 256          # levels of the state tree (builtins/storage/storage_access_stark.rs)
+
+
+def tablegen_storage_columns_header():
+    """The checked header olavm_amd/csrc/tablegen_storage_columns.h: the column indices of the storage-access table, the Poseidon table's
+    column groups and the layout of an access record, for ola_generate_storage_trace / ola_generate_poseidon_table in
+    olavm_amd/csrc/storage.hip.  Committed like its siblings; tests/test_storage_tablegen_abi.py compares it with this text.  Regenerate:
+        python -c "from olavm_amd.air import dump; print(dump.tablegen_storage_columns_header(), end='')" > olavm_amd/csrc/tablegen_storage_columns.h"""
+    from . import ola_tables as T
+    out = ["// generated from olavm_amd/air/ola_tables.py by olavm_amd.air.dump.tablegen_storage_columns_header() -- do not edit",
+           "#pragma once", "#include <cstdint>", "namespace olatgs {"]
+    for name in sorted(n for n in dir(T) if n.startswith("COL_ST_")):
+        v = getattr(T, name)
+        if isinstance(v, range):
+            out.append("constexpr uint32_t %s_START = %du, %s_END = %du;" % (name, v.start, name, v.stop))
+        else:
+            out.append("constexpr uint32_t %s = %du;" % (name, v))
+    out.append("constexpr uint32_t NUM_COL_ST = %du, NUM_POSEIDON_COLS = %du;" % (T.NUM_COL_ST, T.NUM_POSEIDON_COLS))
+    out.append("constexpr uint32_t STORAGE_ACCESS_WORDS = %du, STORAGE_DEPTH = %du;" % (STORAGE_ACCESS_WORDS, STORAGE_DEPTH))
+    out.append("}  // namespace olatgs")
+    return "\n".join(out) + "\n"

@@ -16,10 +16,13 @@ class OlaInstr(C.Structure):
 
 
 EXPORTS = ["ola_tracegen_run", "ola_tracegen_table", "ola_tracegen_cpu_rows", "ola_tracegen_free", "ola_tracegen_last_error", "ola_tracegen_betas",
-           "ola_tracegen_cpu_steps", "ola_tracegen_prog_listing", "ola_tracegen_mem_cells", "ola_tracegen_cmp_ops", "ola_tracegen_cpu_rc_values"]
+           "ola_tracegen_cpu_steps", "ola_tracegen_prog_listing", "ola_tracegen_mem_cells", "ola_tracegen_cmp_ops", "ola_tracegen_cpu_rc_values",
+           "ola_tracegen_storage_accesses", "ola_tracegen_poseidon_inputs", "ola_tracegen_program_beta"]
 OLA_TRACEGEN_PROVE_PROGRAM_HASH, OLA_TRACEGEN_EXPLICIT_BETAS, OLA_TRACEGEN_REFERENCE_QUIRKS, OLA_TRACEGEN_STEPS_ONLY = 1, 2, 4, 8
 OLA_TRACEGEN_CELLS_ONLY = 16
+OLA_TRACEGEN_HASHES_ONLY = 32
 MEM_CELL_WORDS = 5       # include/ola_gpu.h OLA_MEM_CELL_WORDS
+STORAGE_ACCESS_WORDS = 14   # include/ola_gpu.h OLA_STORAGE_ACCESS_WORDS
 
 
 def lib_path():
@@ -44,8 +47,20 @@ def load_library():
         L.ola_tracegen_prog_listing.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint64))]
         for f in ("ola_tracegen_mem_cells", "ola_tracegen_cmp_ops", "ola_tracegen_cpu_rc_values"):
             getattr(L, f).argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64))]
+        L.ola_tracegen_storage_accesses.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64))]
+        L.ola_tracegen_poseidon_inputs.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint64))]
+        L.ola_tracegen_program_beta.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
+
+
+def program_beta(roots):
+    """ola_tracegen_program_beta: the program table's compress challenge from the state roots before and after the run (8 words, the
+    roots_out of Backend.generate_storage_trace)"""
+    r = (C.c_uint64 * 8)(*[int(x) for x in roots])
+    beta = C.c_uint64()
+    assert load_library().ola_tracegen_program_beta(r, C.byref(beta)) == 0
+    return int(beta.value)
 
 
 def encode(prog):
@@ -59,7 +74,7 @@ def encode(prog):
 
 
 def instance(prog, range_bits=4, limb_bits=2, bitwise_beta=None, program_beta=None, prove_program_hash=False, max_steps=1 << 16, reference_quirks=False,
-             steps_only=False, timings=None, cells_only=False):
+             steps_only=False, timings=None, cells_only=False, hashes_only=False):
     """Same contract as miniexec.instance(prog, ...).  -> (traces, params, compress).  Betas left at None are derived by the
     generator's own Fiat-Shamir transcript, as the reference does; explicit values (both or neither) are for tests.
     steps_only: the CPU and the program table are not built -- traces[0] and traces[10] are None -- and a fourth value is returned,
@@ -68,6 +83,12 @@ def instance(prog, range_bits=4, limb_bits=2, bitwise_beta=None, program_beta=No
     and the fourth value also has cells (5 x n: address, clock, the op's one-hot word, value, is_write; execution order), cmp_ops (2 x n),
     cpu_rc (the values of the RC instructions) and mem_log_n, cmp_log_n, rc_log_n: what Backend.generate_memory_trace, generate_cmp_trace
     and generate_rc_trace make the three from.
+    hashes_only: cells_only, and the storage-access and the Poseidon table are not built either -- traces[5] and [7] are None, no node of the
+    state tree is hashed -- and the fourth value also has accesses (14 x n records: key, value, pre_value, flags, psdn_row; the silent write
+    of the program hash first, its read last), psdn_inputs (12 x n) and psdn_filters (4 x n) at the Poseidon table's height with the
+    accesses' rows left zero, and storage_log_n, poseidon_log_n: what Backend.generate_storage_trace and generate_poseidon_table make the
+    two from.  The program table's challenge is then None in params and compress unless given: program_beta(roots) draws it from the
+    roots the storage call returns.
     timings: a dict that receives native_s (ola_tracegen_run alone) and copy_s (this binding's copies of the set into numpy arrays)."""
     import time
     assert (bitwise_beta is None) == (program_beta is None), "give both compress challenges or neither"
@@ -77,10 +98,11 @@ def instance(prog, range_bits=4, limb_bits=2, bitwise_beta=None, program_beta=No
     code = (C.c_uint64 * 4)(*prog.code_addr)
     stor = (C.c_uint64 * 4)(*prog.storage_addr)
     handle = C.c_void_p()
+    cells_only = cells_only or hashes_only
     steps_only = steps_only or cells_only
     flags = ((OLA_TRACEGEN_PROVE_PROGRAM_HASH if prove_program_hash else 0) | (OLA_TRACEGEN_EXPLICIT_BETAS if explicit else 0) |
              (OLA_TRACEGEN_REFERENCE_QUIRKS if reference_quirks else 0) | (OLA_TRACEGEN_STEPS_ONLY if steps_only else 0) |
-             (OLA_TRACEGEN_CELLS_ONLY if cells_only else 0))
+             (OLA_TRACEGEN_CELLS_ONLY if cells_only else 0) | (OLA_TRACEGEN_HASHES_ONLY if hashes_only else 0))
     t0 = time.perf_counter()
     rc = L.ola_tracegen_run(ins, len(prog.ins), code, stor, range_bits, limb_bits, bitwise_beta if explicit else 0, program_beta if explicit else 0,
                             max_steps, flags, C.byref(handle))
@@ -94,7 +116,8 @@ def instance(prog, range_bits=4, limb_bits=2, bitwise_beta=None, program_beta=No
             assert L.ola_tracegen_table(handle, t, C.byref(ncols), C.byref(log_n), C.byref(data)) == 0
             n = 1 << log_n.value
             if not data:
-                assert (steps_only and t in (T.CPU, T.PROGRAM)) or (cells_only and t in (T.MEMORY, T.CMP, T.RANGECHECK))
+                assert ((steps_only and t in (T.CPU, T.PROGRAM)) or (cells_only and t in (T.MEMORY, T.CMP, T.RANGECHECK)) or
+                        (hashes_only and t in (T.POSEIDON, T.STORAGE_ACCESS)))
                 shapes[t] = log_n.value
                 traces.append(None)
                 continue
@@ -115,9 +138,21 @@ def instance(prog, range_bits=4, limb_bits=2, bitwise_beta=None, program_beta=No
             extra.update(cells=words(L.ola_tracegen_mem_cells, MEM_CELL_WORDS), cmp_ops=words(L.ola_tracegen_cmp_ops, 2),
                          cpu_rc=words(L.ola_tracegen_cpu_rc_values, 1)[0], mem_log_n=shapes[T.MEMORY], cmp_log_n=shapes[T.CMP],
                          rc_log_n=shapes[T.RANGECHECK])
+        if hashes_only:
+            count, log_n, data, fdata = C.c_uint64(), C.c_uint32(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+            assert L.ola_tracegen_storage_accesses(handle, C.byref(count), C.byref(data)) == 0
+            accesses = (np.ctypeslib.as_array(data, shape=(STORAGE_ACCESS_WORDS, count.value)).copy() if count.value
+                        else np.zeros((STORAGE_ACCESS_WORDS, 0), dtype=np.uint64))
+            assert L.ola_tracegen_poseidon_inputs(handle, C.byref(log_n), C.byref(data), C.byref(fdata)) == 0 and log_n.value == shapes[T.POSEIDON]
+            extra.update(accesses=accesses, psdn_inputs=np.ctypeslib.as_array(data, shape=(12, 1 << log_n.value)).copy(),
+                         psdn_filters=np.ctypeslib.as_array(fdata, shape=(4, 1 << log_n.value)).copy(), storage_log_n=shapes[T.STORAGE_ACCESS],
+                         poseidon_log_n=shapes[T.POSEIDON])
         betas = (C.c_uint64 * 2)()
         assert L.ola_tracegen_betas(handle, betas) == 0
         bitwise_beta, program_beta = int(betas[0]), int(betas[1])
+        if hashes_only and not explicit:
+            assert program_beta == (1 << 64) - 1
+            program_beta = None                   # not known before the device has hashed the tree
     finally:
         L.ola_tracegen_free(handle)
     if timings is not None:

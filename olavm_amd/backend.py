@@ -170,8 +170,12 @@ def load_library():
     L.ola_generate_memory_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p,
                                             C.POINTER(C.c_uint64)]
     L.ola_generate_cmp_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
+    L.ola_generate_storage_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.c_void_p]
+    L.ola_generate_poseidon_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32)]
     for f in ("ola_generate_rc_trace", "ola_generate_bitwise_trace", "ola_generate_prog_trace", "ola_generate_cpu_trace",
-              "ola_generate_prog_trace_steps", "ola_generate_memory_trace", "ola_generate_cmp_trace"):
+              "ola_generate_prog_trace_steps", "ola_generate_memory_trace", "ola_generate_cmp_trace", "ola_generate_storage_trace",
+              "ola_generate_poseidon_table"):
         getattr(L, f).restype = C.c_int32
     L.ola_set_shard.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, ALL_GATHER_FN, C.c_void_p]
     L.ola_set_shard_options.argtypes = [C.c_void_p, C.c_uint32]
@@ -208,6 +212,7 @@ EXPORTS = [
     "ola_gpu_warmup", "ola_gpu_warmup_wait", "ola_gpu_ntt_pass_times",
     "ola_check_constraints", "ola_check_lookup", "ola_generate_rc_trace", "ola_generate_bitwise_trace", "ola_generate_prog_trace",
     "ola_generate_cpu_trace", "ola_generate_prog_trace_steps", "ola_generate_memory_trace", "ola_generate_cmp_trace",
+    "ola_generate_storage_trace", "ola_generate_poseidon_table",
     "ola_open", "ola_fri_plan", "ola_fri_commit_begin", "ola_fri_commit_next_layer", "ola_fri_commit_finish", "ola_fri_query", "ola_fri_free",
 ]
 
@@ -241,6 +246,8 @@ OLA_TABLEGEN_REFERENCE_QUIRKS = 1
 OLA_TABLEGEN_ZERO_FILLER = 1
 OLA_CPU_STEP_WORDS = 66
 OLA_MEM_CELL_WORDS = 5
+OLA_STORAGE_ACCESS_WORDS = 14
+OLA_STORAGE_WRITE, OLA_STORAGE_FOR_PROG, OLA_STORAGE_SILENT = 1, 2, 4
 
 
 def warmup(device=-1, pinned_ring=True, airset=None):
@@ -824,6 +831,80 @@ class Backend:
         got = C.c_uint32()
         self._chk(self.lib.ola_generate_cmp_trace(self.ctx, pp if n_ops else None, n_ops, po, C.byref(got), pd))
         return ret, diff
+
+    def storage_trace_log_n(self, accesses, n_access=None):
+        """log2 of the storage table's height for these records (a sizing call: the silent ones have no rows)"""
+        pa, ka, shape = _words(accesses, None if n_access is None else (OLA_STORAGE_ACCESS_WORDS, n_access))
+        n_access = int(shape[1]) if shape is not None else 0
+        log_n = C.c_uint32()
+        self._chk(self.lib.ola_generate_storage_trace(self.ctx, pa if n_access else None, n_access, None, None, C.byref(log_n), None, None, 0, None))
+        return log_n.value
+
+    def generate_storage_trace(self, accesses, siblings=None, out=None, psdn_inputs=None, psdn_filters=None, roots_out=None, n_access=None):
+        """ola_generate_storage_trace: the account-storage tree hashed on the device and the storage table (48 x n) from access records
+        (OLA_STORAGE_ACCESS_WORDS x n_access column-major: key[4], value[4], pre_value[4], flags, psdn_row; None or zero columns for a
+        table of padding rows).  siblings: None = the self-contained batch on an empty tree, else 1024 x n_access from the caller's tree.
+        psdn_inputs / psdn_filters: None, or the (12, stride) / (4, stride) input buffers of generate_poseidon_table -- numpy arrays, GPU
+        tensors or device addresses (then `psdn_stride` words per column is taken from the arrays' shape; for addresses pass a tuple
+        (address, stride)) -- whose storage rows the call fills in place.  roots_out: None = the two roots come back as a numpy array
+        of 8 words, False = not wanted, else as rc_out of generate_memory_trace.  -> (table or log_n, roots).  n_access must be given
+        when accesses is a device address."""
+        pa, ka, shape = _words(accesses, None if n_access is None else (OLA_STORAGE_ACCESS_WORDS, n_access))
+        if shape is not None and (len(shape) != 2 or shape[0] != OLA_STORAGE_ACCESS_WORDS):
+            raise ValueError("accesses must be OLA_STORAGE_ACCESS_WORDS x n_access")
+        n_access = int(shape[1]) if shape is not None else 0
+        ps, ks, sshape = _words(siblings, (1024, n_access))
+        if sshape is not None and int(np.prod(sshape)) != 1024 * n_access:
+            raise ValueError("siblings must be 1024 x n_access")
+        if (psdn_inputs is None) != (psdn_filters is None):
+            raise ValueError("psdn_inputs and psdn_filters go together")
+        pi = pf = None
+        stride = 0
+        if psdn_inputs is not None:
+            if isinstance(psdn_inputs, tuple):
+                (ai, stride), (af, fstride) = psdn_inputs, psdn_filters
+                pi, pf, ishape, fshape = C.c_void_p(ai), C.c_void_p(af), (12, stride), (4, fstride)
+            else:
+                for b in (psdn_inputs, psdn_filters):      # written in place: no silent copy
+                    if not hasattr(b, "data_ptr") and not (isinstance(b, np.ndarray) and b.dtype == np.uint64 and b.flags.c_contiguous):
+                        raise ValueError("psdn_inputs / psdn_filters must be contiguous uint64 arrays or GPU tensors")
+                pi, ki, ishape = _words(psdn_inputs)
+                pf, kf, fshape = _words(psdn_filters)
+            if len(ishape) != 2 or ishape[0] != 12 or tuple(fshape) != (4, ishape[1]):
+                raise ValueError("psdn_inputs must be 12 x stride and psdn_filters 4 x stride")
+            stride = int(ishape[1])
+        log_n = self.storage_trace_log_n(accesses, n_access)
+        po, ret = self._table_out(out, 48, log_n)
+        pr, roots = self._list_out(roots_out, 8)
+        got = C.c_uint32()
+        self._chk(self.lib.ola_generate_storage_trace(self.ctx, pa if n_access else None, n_access, ps if n_access else None, po, C.byref(got),
+                                                      pi, pf, stride, pr))
+        return ret, roots
+
+    def poseidon_table_log_n(self, n_rows):
+        log_n = C.c_uint32()
+        self._chk(self.lib.ola_generate_poseidon_table(self.ctx, None, None, n_rows, n_rows, None, C.byref(log_n)))
+        return log_n.value
+
+    def generate_poseidon_table(self, inputs, filters=None, n_rows=None, out=None, stride=None):
+        """ola_generate_poseidon_table: the Poseidon table (134 x n, n = next_pow2(max(n_rows, 8))) from permutation inputs (12 x stride)
+        and optional lookup filters (4 x stride); rows n_rows .. n are rows of all-zero inputs.  n_rows defaults to the stride;
+        stride must be given when inputs is a device address."""
+        pi, ki, shape = _words(inputs, None if stride is None else (12, stride))
+        if shape is None or len(shape) != 2 or shape[0] != 12:
+            raise ValueError("inputs must be 12 x stride")
+        stride = int(shape[1])
+        pf, kf, fshape = _words(filters, (4, stride))
+        if fshape is not None and tuple(fshape) != (4, stride):
+            raise ValueError("filters must be 4 x stride")
+        n_rows = stride if n_rows is None else int(n_rows)
+        if n_rows > stride:
+            raise ValueError("n_rows is larger than the stride")
+        log_n = self.poseidon_table_log_n(n_rows)
+        po, ret = self._table_out(out, 134, log_n)
+        got = C.c_uint32()
+        self._chk(self.lib.ola_generate_poseidon_table(self.ctx, pi if stride else None, pf if stride else None, n_rows, stride, po, C.byref(got)))
+        return ret
 
     def trim(self):
         """Return the context's cached device buffers to the driver (ola_gpu_trim)."""

@@ -252,6 +252,21 @@ struct Run {
     std::vector<TapeCell> tape;
     std::vector<std::vector<StorageRow>> storage;        // one 256-row proof per SSTORE / SLOAD
     std::vector<std::vector<u64>> storage_psdn;          // tree-key and state-tree rows of the Poseidon table
+    // OLA_TRACEGEN_HASHES_ONLY: no node of the state tree is hashed.  A key -> value map serves SLOAD, every access leaves a record
+    // (include/ola_gpu.h OLA_STORAGE_ACCESS_WORDS: key, value, pre_value, flags, psdn_row) and 512 EMPTY rows in storage_psdn, the
+    // places of its hashes in the Poseidon table
+    bool hashes_only = false;
+    std::map<Hash4, Hash4> leaves;
+    std::vector<std::array<u64, 14>> accesses;
+    Hash4 lean_access(const Hash4& addr, const Hash4* value, u64 flags, bool rows = true) {
+        const Hash4 k = StorageTree::key_of(addr);
+        if (value) leaves[k] = Hash4{(*value)[0] % P, (*value)[1] % P, (*value)[2] % P, (*value)[3] % P};
+        auto it = leaves.find(k);
+        const Hash4 leaf = it == leaves.end() ? Hash4{0, 0, 0, 0} : it->second;
+        accesses.push_back({k[0], k[1], k[2], k[3], leaf[0], leaf[1], leaf[2], leaf[3], 0, 0, 0, 0, flags, 0});
+        if (rows) storage_psdn.resize(storage_psdn.size() + 512);
+        return leaf;
+    }
     std::vector<u64> words;
 };
 
@@ -493,15 +508,17 @@ void execute(const OlaInstr* ins, size_t n_ins, const u64 code_addr[4], const u6
                         value[i] = mem_at(addm(v1, i), "stored value was never written");
                         R.mem.push_back({addm(v1, i), clk, mop, value[i], 0});
                     }
-                    tree.access(tree_key, &value, srows, prows);
+                    if (!R.hashes_only) tree.access(tree_key, &value, srows, prows);
                 } else {
-                    value = tree.access(tree_key, nullptr, srows, prows);
+                    if (!R.hashes_only) value = tree.access(tree_key, nullptr, srows, prows);
+                    else value = R.leaves.count(StorageTree::key_of(tree_key)) ? R.leaves[StorageTree::key_of(tree_key)] : Hash4{0, 0, 0, 0};
                     for (int i = 0; i < 4; i++) { memory[addm(v1, i)] = value[i]; R.mem.push_back({addm(v1, i), clk, mop, value[i], 1}); }
                 }
                 idx_storage += 1;
                 R.storage.push_back(std::move(srows));
                 R.storage_psdn.push_back(std::move(krow));
                 for (auto& pr : prows) R.storage_psdn.push_back(std::move(pr));
+                if (R.hashes_only) R.lean_access(tree_key, I.op == OP_SSTORE ? &value : nullptr, I.op == OP_SSTORE ? 1 : 0);
                 e[COL_EXT_CNT] = e[COL_IS_STORAGE_EXT_LINE] = e[COL_IS_NEXT_LINE_DIFF_INST] = 1;
                 e[COL_IDX_STORAGE] = idx_storage;
                 for (int i = 0; i < 4; i++) {
@@ -619,8 +636,10 @@ Hash4 program_hash(const std::vector<u64>& words) {
     return h;
 }
 
+// lean (OLA_TRACEGEN_HASHES_ONLY): the Poseidon table gets its shape only; its inputs (12 x n) and filters (4 x n) go to lean[0] / lean[1]
+// with the empty rows of extra_rows left zero, and lean[2] receives the index of every 512th empty row -- the first row of an access
 void prog_chunk_and_poseidon(const u64 code_addr[4], const std::vector<u64>& words, const std::vector<std::vector<u64>>& extra_rows,
-                             bool result_line, Table& chunk, Table& poseidon) {
+                             bool result_line, Table& chunk, Table& poseidon, std::vector<u64>* lean = nullptr) {
     const size_t nchunks = words.size() / 8;
     const size_t n = next_pow2(std::max<size_t>(nchunks, 8));
     chunk.init(NUM_PROG_CHUNK_COLS, n);
@@ -647,6 +666,17 @@ void prog_chunk_and_poseidon(const u64 code_addr[4], const std::vector<u64>& wor
     }
     for (const auto& r : extra_rows) prow.push_back(r);
     const size_t np = next_pow2(std::max<size_t>(prow.size(), 8));
+    if (lean) {
+        poseidon.ncols = NUM_POSEIDON_COLS; poseidon.n = np;
+        lean[0].assign(12 * np, 0); lean[1].assign(4 * np, 0);
+        size_t empty = 0;
+        for (size_t i = 0; i < prow.size(); i++) {
+            if (prow[i].empty()) { if (empty++ % 512 == 0) lean[2].push_back(i); continue; }
+            for (size_t k = 0; k < 4; k++) lean[1][k * np + i] = prow[i][k];
+            for (size_t k = 0; k < 12; k++) lean[0][k * np + i] = prow[i][COL_POSEIDON_INPUT_RANGE_START + k];
+        }
+        return;
+    }
     poseidon.init(NUM_POSEIDON_COLS, np);
     const u64 zero_in[12] = {0}, zero_f[4] = {0, 0, 0, 0};
     const std::vector<u64> zero_row = poseidon_row(zero_in, zero_f);               // generation/poseidon.rs: ZERO-hash padding rows
@@ -970,6 +1000,8 @@ struct OlaTraceSet {
     std::vector<u64> steps, listing;               // ... these stand for them
     bool cells_only = false;                       // OLA_TRACEGEN_CELLS_ONLY: so have MEMORY, CMP and RANGECHECK ...
     std::vector<u64> cells, cmp_ops, cpu_rc;       // ... and these stand for them
+    bool hashes_only = false;                      // OLA_TRACEGEN_HASHES_ONLY: so have STORAGE_ACCESS and POSEIDON ...
+    std::vector<u64> accesses, psdn[3];            // ... and the access records, the Poseidon inputs and filters (and the accesses' rows) stand for them
 };
 
 extern "C" {
@@ -987,6 +1019,7 @@ int32_t ola_tracegen_run(const OlaInstr* program, size_t n_instr, const uint64_t
         const bool explicit_betas = flags & OLA_TRACEGEN_EXPLICIT_BETAS;
         const bool quirks = flags & OLA_TRACEGEN_REFERENCE_QUIRKS;
         Run R;
+        R.hashes_only = set->hashes_only = flags & OLA_TRACEGEN_HASHES_ONLY;
         StorageTree tree;
         const Hash4 code_key{code_addr[0], code_addr[1], code_addr[2], code_addr[3]};
         if (prove_program_hash) {
@@ -994,22 +1027,27 @@ int32_t ola_tracegen_run(const OlaInstr* program, size_t n_instr, const uint64_t
             std::vector<size_t> pcs;
             program_words(program, n_instr, listing, pcs);
             while (listing.size() % 8) listing.push_back(0);
-            tree.write(StorageTree::key_of(code_key), program_hash(listing));
+            const Hash4 hash = program_hash(listing);
+            if (R.hashes_only) R.lean_access(code_key, &hash, 1 | 4, false);       // OLA_STORAGE_WRITE | OLA_STORAGE_SILENT
+            else tree.write(StorageTree::key_of(code_key), hash);
         }
         const Hash4 start_root = tree.root();
         execute(program, n_instr, code_addr, storage_addr, max_steps, tree, R);
         set->cpu_rows = R.nrows();
-        if (!explicit_betas) {
+        if (R.hashes_only) {
+            // the two state roots come out of the device's tree: the challenge is the caller's to draw (ola_tracegen_program_beta)
+            if (!explicit_betas) program_beta = ~0ull;
+        } else if (!explicit_betas) {
             // generation/prog.rs:23-29: the transcript observes the state roots before and after the run, limb by limb
             const Hash4 end_root = tree.root();
             HostChallenger ch;
             for (int i = 0; i < 4; i++) { ch.observe(start_root[i]); ch.observe(end_root[i]); }
             program_beta = ch.get();
         }
-        set->program_beta = program_beta % P;
+        set->program_beta = R.hashes_only && !explicit_betas ? ~0ull : program_beta % P;
         auto& T = set->tables;
         std::vector<u64> words;
-        set->cells_only = flags & OLA_TRACEGEN_CELLS_ONLY;
+        set->cells_only = (flags & OLA_TRACEGEN_CELLS_ONLY) || R.hashes_only;
         set->steps_only = (flags & OLA_TRACEGEN_STEPS_ONLY) || set->cells_only;
         if (set->steps_only) {
             cpu_steps(R, T[CPU], set->steps);
@@ -1021,14 +1059,28 @@ int32_t ola_tracegen_run(const OlaInstr* program, size_t n_instr, const uint64_t
         std::vector<std::vector<u64>> builtin_rows;
         poseidon_chunk_table(R.psdn, T[POSEIDON_CHUNK], builtin_rows);
         std::vector<std::vector<StorageRow>> prog_reads;
-        if (prove_program_hash) {
+        if (prove_program_hash && R.hashes_only) {
+            R.lean_access(code_key, nullptr, 2);                                    // OLA_STORAGE_FOR_PROG
+        } else if (prove_program_hash) {
             prog_reads.emplace_back();
             std::vector<std::vector<u64>> prows;
             tree.access(code_key, nullptr, prog_reads.back(), prows);
             for (auto& pr : prows) R.storage_psdn.push_back(std::move(pr));
         }
         for (auto& pr : R.storage_psdn) builtin_rows.push_back(std::move(pr));
-        prog_chunk_and_poseidon(code_addr, words, builtin_rows, prove_program_hash, T[PROG_CHUNK], T[POSEIDON]);
+        prog_chunk_and_poseidon(code_addr, words, builtin_rows, prove_program_hash, T[PROG_CHUNK], T[POSEIDON], R.hashes_only ? set->psdn : nullptr);
+        if (R.hashes_only) {
+            // the records column-major, the accesses with rows numbered through the Poseidon table in execution order
+            const size_t na = R.accesses.size();
+            set->accesses.assign(14 * na, 0);
+            size_t with_rows = 0;
+            for (size_t a = 0; a < na; a++) {
+                if (!(R.accesses[a][12] & 4)) R.accesses[a][13] = set->psdn[2].at(with_rows++);
+                for (size_t w = 0; w < 14; w++) set->accesses[w * na + a] = R.accesses[a][w];
+            }
+            need(with_rows == set->psdn[2].size(), "storage accesses and their Poseidon rows disagree");
+            T[STORAGE_ACCESS].ncols = NUM_COL_ST; T[STORAGE_ACCESS].n = next_pow2(std::max<size_t>(256 * with_rows, 8));
+        }
         if (set->cells_only) {
             cells_only(R, range_bits, T[MEMORY], T[CMP], T[RANGECHECK], set->cells, set->cmp_ops);
             set->cpu_rc = R.rc;
@@ -1044,7 +1096,7 @@ int32_t ola_tracegen_run(const OlaInstr* program, size_t n_instr, const uint64_t
             rc_table(rc, range_bits, T[RANGECHECK]);
         }
         set->bitwise_beta = bitwise_table(bitwise_beta, !explicit_betas, limb_bits, R.bitwise, T[BITWISE], quirks);
-        storage_table(R.storage, prog_reads, T[STORAGE_ACCESS]);
+        if (!R.hashes_only) storage_table(R.storage, prog_reads, T[STORAGE_ACCESS]);
         tape_table(R.tape, T[TAPE]);
         flag_padding(T[SCCALL], NUM_COL_SCCALL, 8, COL_SCCALL_IS_PADDING);
         *out = set.release();
@@ -1095,6 +1147,28 @@ int32_t ola_tracegen_cmp_ops(const OlaTraceSet* set, uint64_t* n_ops, const uint
 }
 int32_t ola_tracegen_cpu_rc_values(const OlaTraceSet* set, uint64_t* n_values, const uint64_t** data) {
     return cells_only_list(set, &OlaTraceSet::cpu_rc, 1, n_values, data);
+}
+
+int32_t ola_tracegen_storage_accesses(const OlaTraceSet* set, uint64_t* n_access, const uint64_t** data) {
+    if (!set || !n_access || !data) { g_err = "invalid argument"; return -1; }
+    if (!set->hashes_only) { g_err = "the set was not generated with OLA_TRACEGEN_HASHES_ONLY"; return -1; }
+    *n_access = set->accesses.size() / 14; *data = set->accesses.data();
+    return 0;
+}
+int32_t ola_tracegen_poseidon_inputs(const OlaTraceSet* set, uint32_t* log_n, const uint64_t** inputs, const uint64_t** filters) {
+    if (!set || !log_n || !inputs || !filters) { g_err = "invalid argument"; return -1; }
+    if (!set->hashes_only) { g_err = "the set was not generated with OLA_TRACEGEN_HASHES_ONLY"; return -1; }
+    uint32_t l = 0;
+    while (((size_t)1 << l) < set->tables[POSEIDON].n) l++;
+    *log_n = l; *inputs = set->psdn[0].data(); *filters = set->psdn[1].data();
+    return 0;
+}
+int32_t ola_tracegen_program_beta(const uint64_t roots[8], uint64_t* beta) {
+    if (!roots || !beta) { g_err = "invalid argument"; return -1; }
+    HostChallenger ch;                        // generation/prog.rs:23-29: start and end root, limb by limb
+    for (int i = 0; i < 4; i++) { ch.observe(roots[i] % P); ch.observe(roots[4 + i] % P); }
+    *beta = ch.get() % P;
+    return 0;
 }
 
 uint64_t ola_tracegen_cpu_rows(const OlaTraceSet* set) { return set ? set->cpu_rows : 0; }

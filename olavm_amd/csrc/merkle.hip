@@ -229,14 +229,17 @@ __global__ __launch_bounds__(1024) void merkle_top_kernel(u64* __restrict__ heap
 // input[12], output[12], S-box inputs of full rounds 1..3 [3x12], of the 22 partial rounds (lane 0) [22], of full rounds
 // 26..29 [4x12].  The S-box argument of a round does not depend on how the linear layers are factored, so the dense
 // lane-0 form of poseidon.cuh yields exactly the values the reference's sparse form records.
-__global__ __launch_bounds__(256) void poseidon_trace_kernel(const u64* __restrict__ inputs, const u64* __restrict__ filters, size_t n,
-                                                             u64* __restrict__ out) {
+// inputs / filters: n_live rows, column-major with `stride` words per column; rows n_live .. n of `out` are rows of all-zero inputs and
+// filters (the table's padding, generation/poseidon.rs).
+__global__ __launch_bounds__(256) void poseidon_trace_kernel(const u64* __restrict__ inputs, const u64* __restrict__ filters, size_t n_live,
+                                                             size_t stride, size_t n, u64* __restrict__ out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    const bool live = i < n_live;
     auto col = [&](int c) -> u64& { return out[(size_t)c * n + i]; };
-    for (int f = 0; f < 4; f++) col(f) = filters ? gl_canon(filters[(size_t)f * n + i]) : 0;
+    for (int f = 0; f < 4; f++) col(f) = filters && live ? gl_canon(filters[(size_t)f * stride + i]) : 0;
     u64 s[12];
-    for (int k = 0; k < 12; k++) { s[k] = gl_canon(inputs[(size_t)k * n + i]); col(4 + k) = s[k]; }
+    for (int k = 0; k < 12; k++) { s[k] = live ? gl_canon(inputs[(size_t)k * stride + i]) : 0; col(4 + k) = s[k]; }
     for (int r = 0; r < 4; r++) {
         for (int k = 0; k < 12; k++) {
             s[k] = gl_add(gl_canon(s[k]), c_rc[r * 12 + k]);
@@ -262,7 +265,7 @@ __global__ __launch_bounds__(256) void poseidon_trace_kernel(const u64* __restri
     for (int k = 0; k < 12; k++) col(16 + k) = gl_canon(s[k]);
 }
 void launch_poseidon_trace(DeviceCtx* ctx, const u64* inputs, const u64* filters, size_t n, u64* out) {
-    if (n) hipLaunchKernelGGL(poseidon_trace_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, inputs, filters, n, out);
+    if (n) hipLaunchKernelGGL(poseidon_trace_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, inputs, filters, n, n, n, out);
 }
 
 // quad-cooperative permutation of whole states (4 threads per state); used for small n

@@ -21,6 +21,7 @@
 #include "tablegen_columns.h"
 #include "tablegen_cpu_columns.h"
 #include "tablegen_mem_columns.h"
+#include "tablegen_storage_columns.h"
 #include "peer_group.h"
 #include "rccl_carrier.h"
 
@@ -32,6 +33,7 @@
 #include "fri.hip"
 #include "stark.hip"
 #include "check.hip"
+#include "storage.hip"
 #include "selftest.hip"
 
 using namespace ola;
@@ -1430,6 +1432,96 @@ int32_t ola_generate_cmp_trace(OlaCtx* ctx, const uint64_t* ops, size_t n_ops, u
     u64* d_diff = !abs_diff_out || !n_ops ? nullptr : diff_on_device ? (u64*)abs_diff_out : mem.alloc(n_ops);
     generate_cmp_trace_dev(&ctx->dev, d_ops, n_ops, t.dev, d_diff);
     if (d_diff && !diff_on_device) HIP_CHECK(hipMemcpyAsync(abs_diff_out, d_diff, n_ops * 8, hipMemcpyDeviceToHost, ctx->dev.stream));
+    t.finish();
+    OLA_CATCH
+}
+
+// words [first, first + count) of a caller's buffer, wherever it lives, into host memory (the validation pass of
+// ola_generate_storage_trace, which runs before there has to be a context)
+static void fetch_words(OlaCtx* ctx, u64* dst, const uint64_t* src, size_t count) {
+    if (count == 0) return;
+    const bool dev = ctx ? pointer_on_device(ctx, src) : is_device_pointer(src);
+    if (dev) HIP_CHECK(hipMemcpy(dst, src, count * 8, hipMemcpyDeviceToHost));
+    else memcpy(dst, src, count * 8);
+}
+
+static_assert(OLA_STORAGE_ACCESS_WORDS == olatgs::STORAGE_ACCESS_WORDS, "include/ola_gpu.h and tablegen_storage_columns.h disagree on the access record");
+int32_t ola_generate_storage_trace(OlaCtx* ctx, const uint64_t* accesses, size_t n_access, const uint64_t* siblings, uint64_t* out,
+                                   uint32_t* log_n_out, uint64_t* psdn_inputs, uint64_t* psdn_filters, size_t psdn_stride, uint64_t roots_out[8]) {
+    OLA_TRY
+    require(log_n_out, "null pointer");
+    require(n_access < ((size_t)1 << 23), "2^23 accesses or more");
+    require((psdn_inputs == nullptr) == (psdn_filters == nullptr), "psdn_inputs and psdn_filters go together");
+    require(accesses || n_access == 0 || !out, "null pointer");
+    OLA_ON_DEVICE(ctx);
+    // the validation pass: flags and Poseidon rows of every record, read on the host before any work
+    const size_t n = n_access;
+    std::vector<u64> meta(4 * n + 1, 0);
+    size_t m = 0;
+    if (accesses && n) {
+        fetch_words(ctx, meta.data() + n, accesses + 12 * n, 2 * n);
+        for (size_t a = 0; a < n; a++) {
+            const u64 flags = gl_canon(meta[n + a]), row = gl_canon(meta[2 * n + a]);
+            require((flags & ~(u64)(OLA_STORAGE_WRITE | OLA_STORAGE_FOR_PROG | OLA_STORAGE_SILENT)) == 0, "unknown flag in an access record");
+            const bool silent = flags & OLA_STORAGE_SILENT;
+            require(!(silent && siblings), "OLA_STORAGE_SILENT in a batch with the caller's siblings");
+            if (psdn_inputs && !silent)
+                require(row < psdn_stride && psdn_stride - row >= 2 * olatgs::STORAGE_DEPTH, "psdn_row + 512 is beyond psdn_stride");
+            meta[a] = silent ? ~0ull : m;
+            meta[n + a] = flags; meta[2 * n + a] = row;
+            if (!silent) meta[3 * n + m++] = a;
+        }
+    } else {
+        m = n;       // a sizing call without records: no access is taken to be silent
+    }
+    *log_n_out = storage_trace_log_n(m);
+    if (!out) return OLA_OK;       // the sizing call
+    require_context(ctx);
+    const size_t n_out = (size_t)1 << *log_n_out;
+    DevBuf mem(&ctx->dev);
+    const u64* d_acc = table_input(ctx, mem, accesses, (size_t)OLA_STORAGE_ACCESS_WORDS * n);
+    const u64* d_sib = n ? table_input(ctx, mem, siblings, (size_t)4 * olatgs::STORAGE_DEPTH * n) : nullptr;
+    TableOutput t(ctx, mem, out, (size_t)olatgs::NUM_COL_ST * n_out);
+    // the Poseidon inputs: rows the call does not own must survive, so a host buffer travels to the device and back whole
+    const bool psdn = psdn_inputs && m;
+    const bool psdn_on_device = psdn && pointer_on_device(ctx, psdn_inputs);
+    if (psdn) require(pointer_on_device(ctx, psdn_filters) == psdn_on_device, "psdn_inputs and psdn_filters: one in host memory, one on the device");
+    u64* d_pin = !psdn ? nullptr : psdn_on_device ? (u64*)psdn_inputs : mem.alloc(12 * psdn_stride);
+    u64* d_pf = !psdn ? nullptr : psdn_on_device ? (u64*)psdn_filters : mem.alloc(4 * psdn_stride);
+    if (psdn && !psdn_on_device) {
+        HIP_CHECK(hipMemcpyAsync(d_pin, psdn_inputs, 12 * psdn_stride * 8, hipMemcpyHostToDevice, ctx->dev.stream));
+        HIP_CHECK(hipMemcpyAsync(d_pf, psdn_filters, 4 * psdn_stride * 8, hipMemcpyHostToDevice, ctx->dev.stream));
+    }
+    const bool roots_on_device = roots_out && pointer_on_device(ctx, roots_out);
+    u64* d_roots = !roots_out ? nullptr : roots_on_device ? (u64*)roots_out : mem.alloc(8);
+    generate_storage_trace_dev(&ctx->dev, mem, d_acc, n, meta.data(), m, d_sib, t.dev, d_pin, d_pf, psdn_stride, d_roots);
+    if (psdn && !psdn_on_device) {
+        HIP_CHECK(hipMemcpyAsync(psdn_inputs, d_pin, 12 * psdn_stride * 8, hipMemcpyDeviceToHost, ctx->dev.stream));
+        HIP_CHECK(hipMemcpyAsync(psdn_filters, d_pf, 4 * psdn_stride * 8, hipMemcpyDeviceToHost, ctx->dev.stream));
+    }
+    if (d_roots && !roots_on_device) HIP_CHECK(hipMemcpyAsync(roots_out, d_roots, 64, hipMemcpyDeviceToHost, ctx->dev.stream));
+    t.finish();
+    OLA_CATCH
+}
+
+int32_t ola_generate_poseidon_table(OlaCtx* ctx, const uint64_t* inputs, const uint64_t* filters, size_t n_rows, size_t stride, uint64_t* out,
+                                    uint32_t* log_n_out) {
+    OLA_TRY
+    require(log_n_out, "null pointer");
+    require(n_rows <= ((size_t)1 << 26), "more than 2^26 rows");
+    require(stride >= n_rows, "stride is smaller than n_rows");
+    uint32_t log_n = 3;
+    while (((size_t)1 << log_n) < n_rows) log_n++;
+    *log_n_out = log_n;
+    if (!out) return OLA_OK;       // the sizing call
+    require(inputs || n_rows == 0, "null pointer");
+    require_context(ctx);
+    OLA_ON_DEVICE(ctx);
+    DevBuf mem(&ctx->dev);
+    const u64* d_in = n_rows ? table_input(ctx, mem, inputs, 12 * stride) : nullptr;
+    const u64* d_f = n_rows ? table_input(ctx, mem, filters, 4 * stride) : nullptr;
+    TableOutput t(ctx, mem, out, (size_t)olatgs::NUM_POSEIDON_COLS << log_n);
+    generate_poseidon_table_dev(&ctx->dev, d_in, d_f, n_rows, stride, (size_t)1 << log_n, t.dev);
     t.finish();
     OLA_CATCH
 }

@@ -7,7 +7,7 @@ count = 70000 gives 980 k executed CPU rows (2^20), 280 k memory cells, a 2^21-r
 immediate word) and 280 k range-checked sort values.  The proof is checked with the oracle's verifier; with OLA_TIMING=1 the
 library prints its per-phase times (named after the reference's `timed!` scopes) to stderr.
 
-    python tools/bench_prove_real.py [count] [reps] [--json out.json] [--phases] [--oracle] [--python] [--storage-slots N] [--hasher blake3] [--steps | --cells] [--shape readme]
+    python tools/bench_prove_real.py [count] [reps] [--json out.json] [--phases] [--oracle] [--python] [--storage-slots N] [--hasher blake3] [--steps | --cells | --hashes] [--shape readme]
 
 --steps compares the two ways from an execution to proof bytes, taken in alternation `reps` times in this process: the table path
 (the native generator fills all twelve tables, they are uploaded and proven) and the step path (the generator runs with
@@ -17,7 +17,11 @@ Python binding's copies of its output into numpy arrays (harness cost, larger on
 path never builds), device table generation, and the proof.  --cells adds a third way to the alternation, the cell path: the generator runs with OLA_TRACEGEN_CELLS_ONLY, and on top of the step path's
 two tables ola_generate_cmp_trace, ola_generate_memory_trace and ola_generate_rc_trace write the comparison, memory and range-check tables
 into HBM -- the range-check table from a `vals` buffer in HBM that holds the CPU's values and, behind them, the lists the first two calls
-leave there.  Identical proof bytes on every path are asserted in every round.  --shape readme runs the README's Fibonacci shape
+leave there.  --hashes adds a fourth way, the hashes path: the generator runs with OLA_TRACEGEN_HASHES_ONLY -- it hashes no node of the
+state tree and records no Poseidon row for it -- and on top of the cell path's five tables ola_generate_storage_trace hashes the tree on the
+device, writes the storage-access table and fills the accesses' rows of the Poseidon table's inputs, ola_generate_poseidon_table makes
+the Poseidon table from them, and the program table's challenge is drawn from the two roots the storage call returns; usable with
+--storage-slots.  Identical proof bytes on every path are asserted in every round.  --shape readme runs the README's Fibonacci shape
 (miniexec.fibonacci_loop(47, 3000): 864 002 CPU rows, every other table small) instead of the memory program.
 """
 import json
@@ -50,9 +54,10 @@ def main():
         prog, kw = M.fibonacci_loop(47, 3000), {}
     else:
         prog, kw = M.memory_program(count), {}
-    if "--steps" in sys.argv or "--cells" in sys.argv:
-        return steps_against_tables(prog, kw, blob, reps, hasher, out, "--cells" in sys.argv,
-                                    "fibonacci_loop(47, 3000)" if shape == "readme" else "memory_program(%d)" % count)
+    if "--steps" in sys.argv or "--cells" in sys.argv or "--hashes" in sys.argv:
+        return steps_against_tables(prog, kw, blob, reps, hasher, out, "--cells" in sys.argv or "--hashes" in sys.argv,
+                                    "storage_heavy_program(%d, %d)" % (slots, count) if slots else
+                                    "fibonacci_loop(47, 3000)" if shape == "readme" else "memory_program(%d)" % count, "--hashes" in sys.argv)
     traces, params, compress = gen.instance(prog, range_bits=16, limb_bits=8, max_steps=1 << 24, **kw)
     gen_s = time.time() - t0
     heights = [int(t.shape[1]).bit_length() - 1 for t in traces]
@@ -97,7 +102,7 @@ def main():
         raise SystemExit(1)
 
 
-def steps_against_tables(prog, kw, blob, reps, hasher, out, cells, workload):
+def steps_against_tables(prog, kw, blob, reps, hasher, out, cells, workload, hashes=False):
     import numpy as np
     import torch
     from olavm_amd.air import fastexec, ola_tables as T
@@ -106,7 +111,32 @@ def steps_against_tables(prog, kw, blob, reps, hasher, out, cells, workload):
     runs = {"table_path": [], "step_path": []}
     if cells:
         runs["cell_path"] = []
+    if hashes:
+        runs["hashes_path"] = []
     proofs = {}
+
+    def five_tables(rec, beta):
+        """the CPU, program, comparison, memory and range-check tables in HBM from the records of a cells-only (or hashes-only) run"""
+        d = {t: torch.empty((ncols, 1 << rec[key]), dtype=torch.int64, device="cuda")
+             for t, ncols, key in ((T.CPU, T.NUM_CPU_COLS, "cpu_log_n"), (T.PROGRAM, T.NUM_PROG_COLS, "prog_log_n"), (T.MEMORY, T.NUM_MEM_COLS, "mem_log_n"),
+                                   (T.CMP, T.COL_NUM_CMP, "cmp_log_n"), (T.RANGECHECK, T.COL_NUM_RC, "rc_log_n"))}
+        n_cpu, n_cmp, n_cells = len(rec["cpu_rc"]), rec["cmp_ops"].shape[1], rec["cells"].shape[1]
+        vals = torch.empty((n_cpu + n_cmp + 2 * n_cells + 1,), dtype=torch.int64, device="cuda")
+        vals[:n_cpu] = torch.from_numpy(rec["cpu_rc"].view(np.int64)).cuda()
+        d_steps = torch.from_numpy(rec["steps"].view(np.int64)).cuda()
+        d_cells = torch.from_numpy(rec["cells"].view(np.int64)).cuda()
+        torch.cuda.synchronize()
+        be.generate_cpu_trace(d_steps, rec["cpu_log_n"], out=d[T.CPU])
+        be.generate_prog_trace_steps(d_steps, rec["listing"], beta, out=d[T.PROGRAM])
+        be.generate_cmp_trace(rec["cmp_ops"], out=d[T.CMP], abs_diff_out=vals.data_ptr() + 8 * n_cpu)
+        _, _, (n_sort, n_region) = be.generate_memory_trace(d_cells, out=d[T.MEMORY], rc_out=vals.data_ptr() + 8 * (n_cpu + n_cmp))
+        n_rows = n_cpu + n_cmp + n_sort + n_region
+        filters = torch.zeros((4, n_rows), dtype=torch.int64, device="cuda")
+        for col, lo, hi in ((0, 0, n_cpu), (3, n_cpu, n_cpu + n_cmp), (1, n_cpu + n_cmp, n_cpu + n_cmp + n_sort), (2, n_cpu + n_cmp + n_sort, n_rows)):
+            filters[col, lo:hi] = 1
+        torch.cuda.synchronize()
+        be.generate_rc_trace(vals.data_ptr(), filters, range_bits=16, out=d[T.RANGECHECK], n_rows=n_rows)
+        return d
     for rep in range(reps + 1):                                  # rep 0 warms both paths up and is not kept
         tm = {}
         t0 = time.perf_counter()
@@ -138,25 +168,7 @@ def steps_against_tables(prog, kw, blob, reps, hasher, out, cells, workload):
             t0 = time.perf_counter()
             lean, params, compress, rec = fastexec.instance(prog, range_bits=16, limb_bits=8, max_steps=1 << 24, cells_only=True, timings=tm, **kw)
             t1 = time.perf_counter()
-            d = {t: torch.empty((ncols, 1 << rec[key]), dtype=torch.int64, device="cuda")
-                 for t, ncols, key in ((T.CPU, T.NUM_CPU_COLS, "cpu_log_n"), (T.PROGRAM, T.NUM_PROG_COLS, "prog_log_n"), (T.MEMORY, T.NUM_MEM_COLS, "mem_log_n"),
-                                       (T.CMP, T.COL_NUM_CMP, "cmp_log_n"), (T.RANGECHECK, T.COL_NUM_RC, "rc_log_n"))}
-            n_cpu, n_cmp, n_cells = len(rec["cpu_rc"]), rec["cmp_ops"].shape[1], rec["cells"].shape[1]
-            vals = torch.empty((n_cpu + n_cmp + 2 * n_cells + 1,), dtype=torch.int64, device="cuda")
-            vals[:n_cpu] = torch.from_numpy(rec["cpu_rc"].view(np.int64)).cuda()
-            d_steps = torch.from_numpy(rec["steps"].view(np.int64)).cuda()
-            d_cells = torch.from_numpy(rec["cells"].view(np.int64)).cuda()
-            torch.cuda.synchronize()
-            be.generate_cpu_trace(d_steps, rec["cpu_log_n"], out=d[T.CPU])
-            be.generate_prog_trace_steps(d_steps, rec["listing"], params[1], out=d[T.PROGRAM])
-            be.generate_cmp_trace(rec["cmp_ops"], out=d[T.CMP], abs_diff_out=vals.data_ptr() + 8 * n_cpu)
-            _, _, (n_sort, n_region) = be.generate_memory_trace(d_cells, out=d[T.MEMORY], rc_out=vals.data_ptr() + 8 * (n_cpu + n_cmp))
-            n_rows = n_cpu + n_cmp + n_sort + n_region
-            filters = torch.zeros((4, n_rows), dtype=torch.int64, device="cuda")
-            for col, lo, hi in ((0, 0, n_cpu), (3, n_cpu, n_cpu + n_cmp), (1, n_cpu + n_cmp, n_cpu + n_cmp + n_sort), (2, n_cpu + n_cmp + n_sort, n_rows)):
-                filters[col, lo:hi] = 1
-            torch.cuda.synchronize()
-            be.generate_rc_trace(vals.data_ptr(), filters, range_bits=16, out=d[T.RANGECHECK], n_rows=n_rows)
+            d = five_tables(rec, params[1])
             t2 = time.perf_counter()
             for t, table in d.items():
                 lean[t] = table
@@ -164,17 +176,43 @@ def steps_against_tables(prog, kw, blob, reps, hasher, out, cells, workload):
             t3 = time.perf_counter()
             c = {"native_trace_generation_s": tm["native_s"], "binding_copies_s": tm["copy_s"], "device_table_generation_s": t2 - t1, "prove_s": t3 - t2,
                  "total_s": t3 - t0, "total_without_binding_copies_s": t3 - t0 - tm["copy_s"]}
-            del lean, d, vals, d_steps, d_cells, filters
+            del lean, d
             assert proofs["cell_path"] == proofs["table_path"], "the cell path gives different proof bytes"
+        if hashes:
+            t0 = time.perf_counter()
+            lean, params, compress, rec = fastexec.instance(prog, range_bits=16, limb_bits=8, max_steps=1 << 24, hashes_only=True, timings=tm, **kw)
+            t1 = time.perf_counter()
+            d_st = torch.empty((T.NUM_COL_ST, 1 << rec["storage_log_n"]), dtype=torch.int64, device="cuda")
+            d_ps = torch.empty((T.NUM_POSEIDON_COLS, 1 << rec["poseidon_log_n"]), dtype=torch.int64, device="cuda")
+            d_in, d_f = torch.from_numpy(rec["psdn_inputs"].view(np.int64)).cuda(), torch.from_numpy(rec["psdn_filters"].view(np.int64)).cuda()
+            torch.cuda.synchronize()
+            _, roots = be.generate_storage_trace(rec["accesses"], out=d_st, psdn_inputs=d_in, psdn_filters=d_f)
+            be.generate_poseidon_table(d_in, d_f, out=d_ps)
+            params[1] = compress[T.PROGRAM] = fastexec.program_beta(roots)        # the challenge the table path drew from its own tree's roots
+            d = five_tables(rec, params[1])
+            t2 = time.perf_counter()
+            for t, table in d.items():
+                lean[t] = table
+            lean[T.STORAGE_ACCESS], lean[T.POSEIDON] = d_st, d_ps
+            proofs["hashes_path"] = bytes(be.prove_with_traces(blob, lean, params, compress))
+            t3 = time.perf_counter()
+            h = {"native_trace_generation_s": tm["native_s"], "binding_copies_s": tm["copy_s"], "device_table_generation_s": t2 - t1, "prove_s": t3 - t2,
+                 "total_s": t3 - t0, "total_without_binding_copies_s": t3 - t0 - tm["copy_s"]}
+            del lean, d, d_st, d_ps, d_in, d_f
+            assert proofs["hashes_path"] == proofs["table_path"], "the hashes path gives different proof bytes"
         if rep:
             runs["table_path"].append(a)
             runs["step_path"].append(b)
             if cells:
                 runs["cell_path"].append(c)
+            if hashes:
+                runs["hashes_path"].append(h)
         print(("warm-up " if not rep else "") + "table path %s" % {k: round(v, 3) for k, v in a.items()}, flush=True)
         print(("warm-up " if not rep else "") + "step path  %s" % {k: round(v, 3) for k, v in b.items()}, flush=True)
         if cells:
             print(("warm-up " if not rep else "") + "cell path  %s" % {k: round(v, 3) for k, v in c.items()}, flush=True)
+        if hashes:
+            print(("warm-up " if not rep else "") + "hashes path %s" % {k: round(v, 3) for k, v in h.items()}, flush=True)
     be.close()
     med = lambda path, key: sorted(r[key] for r in runs[path])[len(runs[path]) // 2]
     summary = {path: {key: round(med(path, key), 3) for key in runs[path][0]} for path in runs}

@@ -1,6 +1,8 @@
 """Times ola_generate_rc_trace / ola_generate_bitwise_trace / ola_generate_prog_trace -- and ola_generate_cpu_trace /
 ola_generate_prog_trace_steps, the cases cpu:20 cpu:22 progsteps:21 progsteps:23, and ola_generate_memory_trace / ola_generate_cmp_trace,
-the cases mem:19 mem:21 cmp:16 -- with resident inputs and outputs, next to
+the cases mem:19 mem:21 cmp:16, and ola_generate_storage_trace / ola_generate_poseidon_table, the cases storage:141 storage:8170
+storagesib:141 storagesib:8170 (the number is the number of accesses; `sib` = with the caller's siblings) poseidon:22 -- with resident
+inputs and outputs, next to
 the same derived columns obtained without them: one ola_permuted_cols_dev call per pair (device) plus numpy for the other columns
 (host), and next to the oracle's sequential permuted_cols on one host core (as tools/bench_lookup.py measures it).
 
@@ -30,12 +32,30 @@ from olavm_amd.air.dsl import P
 CASES = ["bitwise:18", "rc:16", "rc:21", "prog:20", "prog:23"]
 STEP_CASES = ["cpu:20", "cpu:22", "progsteps:21", "progsteps:23"]       # named on the command line
 CELL_CASES = ["mem:19", "mem:21", "cmp:16"]                              # named on the command line
+HASH_CASES = ["storage:141", "storage:8170", "storagesib:141", "storagesib:8170", "poseidon:22"]     # named on the command line
 FN = (lambda x, y: x & y, lambda x, y: x | y, lambda x, y: x ^ y)
 
 
 def inputs(kind, log_n, rng):
     """-> (primary inputs as numpy arrays, keyword arguments) of a table that fills 2^log_n rows"""
+    if kind in ("storage", "storagesib"):
+        # log_n is the number of accesses here: a third of them writes of fresh random keys, then a read and an overwrite of each in turn
+        # (storage_heavy_program's pattern); 512 Poseidon rows each, back to back.  With siblings the accesses are independent and any
+        # words do: the work does not depend on them
+        k = log_n
+        keys = rng.integers(0, P, (4, (k + 2) // 3), dtype=np.uint64)
+        recs = np.zeros((14, k), dtype=np.uint64)
+        which = np.concatenate([np.arange(keys.shape[1]), np.repeat(np.arange(keys.shape[1]), 2)])[:k]
+        recs[0:4] = keys[:, which]
+        recs[4:12] = rng.integers(0, P, (8, k), dtype=np.uint64)
+        recs[12] = 1
+        recs[12, keys.shape[1] + 1::2] = 0
+        recs[13] = 512 * np.arange(k)
+        sib = (rng.integers(0, P, (1024, k), dtype=np.uint64),) if kind == "storagesib" else ()
+        return (recs,) + sib, {"stride": 512 * k}
     n = 1 << log_n
+    if kind == "poseidon":
+        return (rng.integers(0, P, (12, n), dtype=np.uint64), rng.integers(0, 2, (4, n), dtype=np.uint64)), {}
     if kind == "rc":
         rows = n if log_n > 16 else n // 2
         vals = rng.integers(0, 1 << 32, rows, dtype=np.uint64)
@@ -107,13 +127,27 @@ def call(be, kind, dev, kw, out):
         if kind == "mem":
             return be.generate_memory_trace(dev[0], out=out, rc_out=kw["list"])[0]
         return be.generate_cmp_trace(dev[0], out=out, abs_diff_out=kw["list"])[0]
+    if kind in ("storage", "storagesib"):  # the Poseidon inputs stay in HBM as well
+        import torch
+        if "psdn" not in kw:
+            kw["psdn"] = torch.zeros((12, kw["stride"]), dtype=torch.int64, device="cuda"), torch.zeros((4, kw["stride"]), dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()
+        return be.generate_storage_trace(dev[0], siblings=dev[1] if kind == "storagesib" else None, out=out, psdn_inputs=kw["psdn"][0],
+                                         psdn_filters=kw["psdn"][1], roots_out=False)[0]
+    if kind == "poseidon":
+        return be.generate_poseidon_table(dev[0], dev[1], out=out)
     if kind == "progsteps":
         return be.generate_prog_trace_steps(dev[0], dev[1], kw["beta"], out=out)[0]
     return be.generate_prog_trace(dev[0], dev[1], kw["beta"], out=out)
 
 
 NCOLS = {"rc": T.COL_NUM_RC, "bitwise": T.COL_NUM_BITWISE, "prog": T.NUM_PROG_COLS, "cpu": T.NUM_CPU_COLS, "progsteps": T.NUM_PROG_COLS,
-         "mem": T.NUM_MEM_COLS, "cmp": T.COL_NUM_CMP}
+         "mem": T.NUM_MEM_COLS, "cmp": T.COL_NUM_CMP, "storage": T.NUM_COL_ST, "storagesib": T.NUM_COL_ST, "poseidon": T.NUM_POSEIDON_COLS}
+
+
+def table_log_n(kind, arg):
+    """log2 of the table's height: the case's number, but for the storage cases, whose number counts accesses"""
+    return max(3, (256 * arg - 1).bit_length()) if kind in ("storage", "storagesib") else arg
 
 
 def pairs_of(kind):
@@ -121,7 +155,7 @@ def pairs_of(kind):
     if kind == "rc":
         return [(T.RC_LIMB_LO, T.RC_FIX_RANGE_CHECK_U16, T.RC_LIMB_LO_PERMUTED, T.RC_FIX_RANGE_CHECK_U16_PERMUTED_LO),
                 (T.RC_LIMB_HI, T.RC_FIX_RANGE_CHECK_U16, T.RC_LIMB_HI_PERMUTED, T.RC_FIX_RANGE_CHECK_U16_PERMUTED_HI)]
-    if kind in ("cpu", "mem", "cmp"):
+    if kind in ("cpu", "mem", "cmp", "storage", "storagesib", "poseidon"):
         return []
     if kind in ("prog", "progsteps"):
         return [(T.COL_PROG_EXEC_COMP_PROG, T.COL_PROG_COMP_PROG, T.COL_PROG_EXEC_COMP_PROG_PERM, T.COL_PROG_COMP_PROG_PERM)]
@@ -170,8 +204,9 @@ def measure(kind, log_n, runs):
     from olavm_amd.backend import Backend
     from tests import oracle_lib
     rng = np.random.default_rng(log_n)
-    n = 1 << log_n
     host, kw = inputs(kind, log_n, rng)
+    arg, log_n = log_n, table_log_n(kind, log_n)
+    n = 1 << log_n
     be = Backend(device=0)
     sp = C.c_void_p()
     be._chk(be.lib.ola_gpu_get_stream(be.ctx, C.byref(sp)))
@@ -196,6 +231,14 @@ def measure(kind, log_n, runs):
 
     rec = {"table": kind, "log_n": log_n, "runs": runs}
     rec["call_device_ms"], rec["call_wall_ms"] = timed(lambda: call(be, kind, dev, kw, out))
+    if kind in ("storage", "storagesib", "poseidon"):      # the host-side counterpart is StorageTree::access / poseidon_row of the native generator
+        if kind == "poseidon":
+            rec["effective_GBps"] = 8 * (16 + T.NUM_POSEIDON_COLS) * n / (rec["call_device_ms"] * 1e6)
+        else:
+            rec["accesses"], rec["permutations"] = arg, 512 * arg
+        rec["table_words"] = NCOLS[kind] * n
+        be.close()
+        return rec
     if kind in ("mem", "cmp"):             # no permuted pairs; the host-side counterpart is memory_table() / cmp_table() of the native generator (docs/EXPERIMENTS.md, the last section)
         rec["cells" if kind == "mem" else "operand_pairs"] = int(host[0].shape[1])
         rec["table_words"] = NCOLS[kind] * n
@@ -242,7 +285,7 @@ def child(kind, log_n, calls, pair_by_pair):
     import torch
     from olavm_amd.backend import Backend
     host, kw = inputs(kind, log_n, np.random.default_rng(log_n))
-    n = 1 << log_n
+    n = 1 << table_log_n(kind, log_n)
     be = Backend(device=0)
     dev = [to_dev(a) for a in host]
     out = torch.empty((NCOLS[kind], n), dtype=torch.int64, device="cuda")
@@ -276,6 +319,8 @@ def traced_kernels(kind, log_n, calls, pair_by_pair):
 def launches(kind, log_n):
     rec = {}
     for label, pbp in (("call", False), ("pair_by_pair", True)):
+        if pbp and kind in ("storage", "storagesib", "poseidon"):      # no lookup pairs: nothing to compare with
+            continue
         one, two = traced_kernels(kind, log_n, 1, pbp), traced_kernels(kind, log_n, 2, pbp)
         per = {k: two.get(k, 0) - one.get(k, 0) for k in two}
         rec[label + "_launches"] = sum(per.values())

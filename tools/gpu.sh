@@ -266,6 +266,11 @@ PY
                    timeout -k 10 600 python tools/bench_prove_real.py 0 3 --cells --shape readme --json $O/cells_vs_steps_readme.json 2>&1 | grep -v amdgpu | tee $O/cells_vs_steps_readme.txt && \
                    timeout -k 10 900 python tools/bench_prove_real.py 70000 3 --cells --json $O/cells_vs_steps_2p20.json 2>&1 | grep -v amdgpu | tee $O/cells_vs_steps_2p20.txt && \
                    timeout -k 10 1500 python tools/bench_prove_real.py 290000 3 --cells --json $O/cells_vs_steps_2p22.json 2>&1 | grep -v amdgpu | tee $O/cells_vs_steps_2p22.txt ) ;;
+    hashgen)     # the storage-access table with the state tree hashed on the device, and the Poseidon table: their tests, the timings and launch counts, then table, step, cell and hashes path in alternation
+                 ( set -o pipefail
+                   timeout -k 10 600 python -m pytest tests/test_gpu_storage_tablegen.py tests/test_storage_tablegen_abi.py -x -q 2>&1 | tail -15 | tee $O/pytest.log && \
+                   timeout -k 10 900 python tools/bench_tablegen.py --json $O/tablegen_hashes.json storage:141 storage:8170 storagesib:141 storagesib:8170 poseidon:22 2>&1 | grep -v amdgpu | tee $O/tablegen_hashes.txt && \
+                   timeout -k 10 900 python tools/bench_prove_real.py 29600 2 --hashes --storage-slots 408 --json $O/hashes_vs_cells_slots408.json 2>&1 | grep -v amdgpu | tee $O/hashes_vs_cells_slots408.txt ) ;;
     check_lookup) # ola_check_lookup: its tests, then the CPU -> memory and CPU -> program lookups of a 2^22-row executed instance, valid and with one looked row dropped
                  ( set -o pipefail
                    timeout -k 10 600 python -m pytest tests/test_gpu_check_lookup.py -x -q 2>&1 | tail -15 | tee $O/pytest.log && \

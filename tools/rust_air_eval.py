@@ -2998,6 +2998,49 @@ def cpu_steps_vectors(reference):
     return out
 
 
+STORAGE_FIXTURE = os.path.join(ROOT, "tests", "golden", "ref_storage_rows.json")
+STORAGE_KEY, STORAGE_VALUE = (1, 2, 3, 4), (10, 11, 12, 13)
+STORAGE_ROWS_KEPT = (0, 63, 64, 127, 128, 255, 256, 511)
+
+
+def storage_hash_rows():
+    """one write of STORAGE_VALUE at STORAGE_KEY into an empty tree and its read-back as `StorageHashRow`s (core/src/trace/trace.rs:280),
+    dicts of integers: 512 rows taken from olavm_amd/air/miniexec.py's StorageTree, addr_acc as the executor accumulates it"""
+    sys.path.insert(0, ROOT)
+    from olavm_amd.air import miniexec as M
+    tree, rows = M.StorageTree(), []
+    for idx, value in ((1, STORAGE_VALUE), (2, None)):
+        acc = 0
+        for r in tree.access(STORAGE_KEY, value)[0]:
+            acc = r["bit"] if r["layer"] % 64 == 1 else (2 * acc + r["bit"]) % P
+            rows.append(dict(storage_access_idx=idx, pre_root=list(r["pre_root"]), root=list(r["root"]), is_write=r["is_write"], layer=r["layer"],
+                             layer_bit=r["bit"], addr_acc=acc, addr=list(r["addr"]), pre_path=list(r["pre_path"]), path=list(r["path"]),
+                             hash_type=int(r["layer"] == 256), pre_hash=list(r["pre_hash"]), hash=list(r["hash"]), sibling=list(r["sib"])))
+    return rows
+
+
+def storage_vectors(reference):
+    """generate_storage_access_trace of the reference (generation/storage.rs:7-123) on storage_hash_rows(): the 512 rows as accesses, no row at
+    all, and the write as the access with the read-back as the program-hash read"""
+    it = plonky2_interp(reference)
+    src = os.path.join(reference, "circuits", "src", "generation", "storage.rs")
+    plain = ("storage_access_idx", "layer", "layer_bit")
+    cells = [Struct({"__name__": "StorageHashRow", **{k: v if k in plain else [Fe(x) for x in v] if isinstance(v, list) else Fe(v) for k, v in r.items()}})
+             for r in storage_hash_rows()]
+    out = {"generated_by": "tools/rust_air_eval.py --tracegen storage", "sources": "circuits/src/generation/storage.rs: generate_storage_access_trace",
+           "key": list(STORAGE_KEY), "value": list(STORAGE_VALUE), "rows_kept": list(STORAGE_ROWS_KEPT)}
+    call = lambda accesses, prog: it.call_free(src, "generate_storage_access_trace", [accesses, prog])
+    # the 512-row table as one digest per column (a mismatch names its column) and a few whole rows (the limb boundaries, the leaf rows)
+    tr = call(cells, [])
+    out["accesses"] = {"rows": len(tr[0]), "column_sha256": [trace_digest([c])["sha256"] for c in tr], "kept": [[c[i].v for c in tr] for i in STORAGE_ROWS_KEPT]}
+    out["none"] = [[x.v for x in c] for c in call([], [])]
+    # the read-back as the program-hash read: the same table but for one column, of which the fixture keeps the rows that are set
+    prog = call(cells[:256], cells[256:])
+    differ = [c for c in range(len(prog)) if [x.v for x in prog[c]] != [x.v for x in tr[c]]]
+    out["write_then_prog_read"] = {"columns_that_differ": differ, "rows_set": [[i for i, x in enumerate(prog[c]) if x.v] for c in differ]}
+    return out
+
+
 class FastPoseidonHook:
     """the permutation for the 393 216 sponge calls of the bitwise generator's transcript: built from the reference's constant tables and checked
     against the interpreted poseidon_naive before use (as tools/ref_verifier.py does)"""
@@ -3039,9 +3082,10 @@ def main():
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--primitives", action="store_true", help="the hashing / transcript / FRI-parameter vectors instead of the AIR vectors")
     ap.add_argument("--ntt", action="store_true", help="the transform vectors (cfft) instead of the AIR vectors")
-    ap.add_argument("--tracegen", nargs="?", const="all", choices=("all", "vectors", "cpu_steps"),
+    ap.add_argument("--tracegen", nargs="?", const="all", choices=("all", "vectors", "cpu_steps", "storage"),
                     help="the trace generators' outputs (generation/*.rs) instead of the AIR vectors: `vectors` (ref_tracegen_vectors.json), "
-                         "`cpu_steps` (generate_cpu_trace / generate_prog_trace on synthetic steps, ref_cpu_steps.json) or both")
+                         "`cpu_steps` (generate_cpu_trace / generate_prog_trace on synthetic steps, ref_cpu_steps.json) or both; `storage` "
+                         "(generate_storage_access_trace on a write and its read-back, ref_storage_rows.json) by itself")
     ap.add_argument("--tracegen-bitwise", action="store_true", help="the bitwise table's generator (2^18 rows: about 40 minutes)")
     a = ap.parse_args()
     sys.setrecursionlimit(20000)
@@ -3056,6 +3100,8 @@ def main():
             cases.append((TRACEGEN_FIXTURE if a.out == FIXTURE else a.out, tracegen_vectors))
         if a.tracegen in ("all", "cpu_steps"):
             cases.append((CPU_STEPS_FIXTURE if a.out == FIXTURE or a.tracegen == "all" else a.out, cpu_steps_vectors))
+        if a.tracegen == "storage":
+            cases.append((STORAGE_FIXTURE if a.out == FIXTURE else a.out, storage_vectors))
         for out, make in cases:
             text = json.dumps(make(a.reference), separators=(",", ":")) + "\n"
             if a.check:
