@@ -189,6 +189,8 @@ be = Backend(device=0); print('$v library: ola_gpu_selftest(2^31) mismatches =',
                    OLA_NTT2_GROUP_MB=$mb timeout 300 python tools/bench_ntt_matrix.py --log-n 22 --cols 94 --reps 3 --out $O/m_$mb.json 2>&1 | grep -E "lde|intt|ntt" | cut -c1-120
                  done 2>&1 | tee $O/sweep.txt ;;
     canon_passes) # the canonical-arithmetic passes (OLA_NTT2_TFORM=0: the A/B control, and the path of transforms beyond 2^28) against the oracle
+                 # (the suite runs them itself at 2^14 .. 2^18, every plan x operation: tests/test_gpu_fallback_paths.py::test_canonical_passes_match_oracle;
+                 # this step puts the older transform and commitment tests, full sizes included, on them)
                  OLA_NTT2_TFORM=0 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fullsize.py -x -q -k "ntt or lde or NTT or coset or commit" 2>&1 | tail -4 | tee $O/pytest.log ;;
     tform_ab)    # T-form passes against the canonical-arithmetic passes, same box, alternating (OLA_NTT2_TFORM=0/1)
                  timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fullsize.py -x -q -k "ntt or lde or NTT or coset" 2>&1 | tail -8 | tee $O/pytest.log
