@@ -390,6 +390,10 @@ int32_t ola_pow(OlaCtx* ctx, const uint64_t h[4], uint32_t bits, uint64_t* witne
  *   ola_open                   StarkOpeningSet::new (circuits/src/stark/proof.rs:198-233) at the caller's zeta: the opening set in
  *                              wire format (serialization.rs:164-175 write_opening_set; read it back with read_opening_set, :176-193) -- decode, then
  *                              challenger.observe_openings(&openings.to_fri_openings()) (fri/challenges.rs:16-23)
+ *                              zeta is the caller's, any two words (reduced mod p).  Refused: a zeta with zeta^n = 1
+ *                              (OLA_E_ZETA_IN_SUBGROUP, prover.rs:508-511) and zeta = 0 (OLA_E_INVALID_ARG: the division by
+ *                              X - zeta goes through powers of 1 / zeta); ola_open_and_prove refuses the same two of a zeta
+ *                              drawn from its transcript
  *   ola_fri_plan               fri_params.reduction_arity_bits (fri/reduction_strategies.rs:40-52) and the final polynomial's length
  *   ola_fri_commit_begin       PolynomialBatch::prove_openings up to the final polynomial (fri/oracle.rs:178-219), alpha =
  *                              challenger.get_extension_challenge()

@@ -11,6 +11,7 @@
 #include <set>
 #include <thread>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -400,7 +401,19 @@ struct DeviceCtx {
         cache.clear();
         cached_bytes = 0;
     }
+    // OLA_POOL_POISON=1 (tests): every block is handed out filled with 0xFF bytes, on the context's stream, so that a kernel which
+    // reads words nobody wrote meets all-ones words instead of what the block's previous user -- or the driver's scrubbing -- left
+    // there.  The pool gives a call sequence the same blocks in the same roles every time, which hides such reads otherwise.
     void* alloc(size_t bytes) {
+        static const bool poison = getenv("OLA_POOL_POISON") && !strcmp(getenv("OLA_POOL_POISON"), "1");
+        void* p = alloc_block(bytes);
+        if (poison) {
+            const hipError_t e = hipMemsetAsync(p, 0xFF, round_size(bytes), stream);
+            if (e != hipSuccess) { free(p); throw OlaError(-5, std::string("hipMemsetAsync (OLA_POOL_POISON): ") + hipGetErrorString(e)); }
+        }
+        return p;
+    }
+    void* alloc_block(size_t bytes) {
         const size_t want = round_size(bytes);
         {
             std::unique_lock<std::mutex> lk(mu);

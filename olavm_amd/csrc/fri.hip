@@ -24,6 +24,7 @@
 
 #include "../../include/ola_gpu.h"
 #include "device_ctx.h"
+#include "eval_plan.h"
 #include "gl.cuh"
 #include "poseidon_host.h"
 #include "poseidon2_host.h"
@@ -653,19 +654,15 @@ __global__ __launch_bounds__(64) void eval_reduce_kernel(const u64* __restrict__
 }
 // one batch of columns at one or two points -> chunk partials; returns the number of chunks
 #define EVALW_C 4
+static_assert(EVALW_C == kEvalWideCols && EVALW_MAX_KH == kEvalWideMaxKh, "eval_plan.h plans for this kernel");
 static unsigned eval_points_plan(size_t n, int log_n, uint32_t ncols, const ExtPow& p0, const ExtPow& p1, size_t* chunk_len, unsigned* khpb) {
     static const bool wide_off = getenv("OLA_EVAL_WIDE") && !strcmp(getenv("OLA_EVAL_WIDE"), "0");
+    static const unsigned forced_kh = eval_wide_forced_kh(getenv("OLA_EVAL_WIDE_KH"));     // tests: the long accumulation loops at small sizes
     *khpb = 0;
-    if (!wide_off && log_n >= 15 && p0.hi_limbs && p1.hi_limbs && ncols) {
-        const int h = p0.h;
-        const size_t nlo_blocks = ((size_t)1 << h) / 256, nhi = (size_t)1 << (log_n - h), groups = (ncols + EVALW_C - 1) / EVALW_C;
-        // enough workgroups to fill the chip several times over, as many steps per workgroup as that leaves (the fold, the
-        // multiplication by lo[kl] and the sum over the workgroup cost about twenty steps)
-        size_t per = EVALW_MAX_KH;
-        while (per > 32 && nlo_blocks * groups * (nhi / per) < 2048) per >>= 1;
-        per = std::min(per, nhi);
-        *khpb = (unsigned)per;
-        return (unsigned)(nlo_blocks * (nhi / per));
+    if (!wide_off && log_n >= kEvalWideMinLogN && p0.hi_limbs && p1.hi_limbs && ncols) {
+        const EvalWidePlan plan = eval_wide_plan(log_n, ncols, forced_kh);      // (eval_plan.h)
+        *khpb = plan.kh_per_block;
+        return plan.nchunks;
     }
     *chunk_len = std::max<size_t>(4096, (n + 255) / 256);
     return (unsigned)((n + *chunk_len - 1) / *chunk_len);
@@ -861,6 +858,8 @@ static void fri_check_arities(const std::vector<int>& arities, const OlaGpuConfi
 struct OpenPoints { ExtPow zpow[3], zinv[3]; };
 static OpenPoints open_points(DevBuf& mem, Ext2 zeta, int degree_bits) {
     if (ext_eq(ext_pow(zeta, (u64)1 << degree_bits), ext_make(1, 0))) throw OlaError(OLA_E_ZETA_IN_SUBGROUP, "Opening point is in the subgroup.");
+    // the quotients are weighted by powers of 1 / zeta (finalize_kernel), and ext_inv(0) = 0 would make them zero without an error
+    if (gl_canon(zeta.a) == 0 && gl_canon(zeta.b) == 0) throw OlaError(OLA_E_INVALID_ARG, "invalid argument: the opening point zeta is zero (the division by X - zeta goes through powers of 1 / zeta)");
     const u64 g = gl_root_of_unity(degree_bits);
     const Ext2 zeta_next = ext_scalar_mul(zeta, g), g_inv = ext_make(gl_inv(g), 0);
     const Ext2 six[6] = {zeta, zeta_next, g_inv, ext_inv(zeta), ext_inv(zeta_next), ext_inv(g_inv)};

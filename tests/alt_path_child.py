@@ -1,14 +1,18 @@
 """One job on the GPU in a process of its own: `python -m tests.alt_path_child [--dry] JOB OUT.json`.
 
-The library reads its path switches (OLA_NTT2_TFORM, OLA_EVAL_WIDE, OLA_FOLD16, OLA_LEAF_EXT_STAGED, OLA_MERKLE_FUSED_LEVELS,
-OLA_POW_DEFER) once per process, so tests/test_gpu_fallback_paths.py sets one in this process' environment, runs one job and
+The library reads its path switches (OLA_NTT2_TFORM, OLA_EVAL_WIDE, OLA_EVAL_WIDE_KH, OLA_FOLD16, OLA_LEAF_EXT_STAGED,
+OLA_MERKLE_FUSED_LEVELS, OLA_POW_DEFER, OLA_POOL_POISON) once per process, so tests/test_gpu_fallback_paths.py sets one in this process' environment, runs one job and
 reads the JSON file it leaves:
 
   transforms:L   the transform matrix of tests/transform_cases.py at 2^L against the oracle, with the pass kernels that
                  ola_gpu_ntt_pass_times saw (none when the canonical-arithmetic passes ran);
   open:HASHER    three seeded commitments of 2^15 rows (6, 3 and 2 columns, one permutation Z), ola_open_and_prove, the bytes
                  and the transcript's next challenge;
-  prove          the 12-table padding instances of test_twelve_table_all_proof_bytes_match_oracle, the AllProof bytes.
+  prove          the 12-table padding instances of test_twelve_table_all_proof_bytes_match_oracle, the AllProof bytes;
+  openeval:L     the stress columns of tests/opening_cases.py at 2^L rows (9, 5 and 4 columns, two permutation Zs) through the
+                 stepped opening (ola_open .. ola_fri_commit_finish) at the challenge sets OPENEVAL_SETS, the opening-set bytes
+                 the final polynomials and the layers' caps; the expected side is tests/opening_reference.py, not the oracle
+                 (whose transform and tree turn the reference's folded polynomials into the expected caps).
 
 The inputs and the oracle's side of each job are functions of this module, so that the parent computes the expected bytes
 from the same inputs.  --dry builds both and opens no context (the GPU library is not even loaded)."""
@@ -19,8 +23,9 @@ import time
 
 import numpy as np
 
-from tests import oracle_lib, transform_cases as TC
+from tests import opening_cases as OC, opening_reference, oracle_lib, transform_cases as TC
 
+OPENEVAL_SETS = ("random", "minus_ones", "order3_zeta")
 OPEN_LOG_N, OPEN_COLS, OPEN_NUM_PERM_ZS = 15, (6, 3, 2), 1
 PROVE_LOG_NS = (3, 8)
 
@@ -53,6 +58,27 @@ def prove_inputs():
 def prove_expected(oracle):
     blob, instances = prove_inputs()
     return [oracle.prove_with_traces(blob, traces, params, compress) for traces, params, compress in instances]
+
+
+def openeval_inputs(L):
+    """(coefficient columns of the three batches, [(name, zeta, alpha, betas)])"""
+    sets = [c for c in OC.challenge_sets(L, len(opening_reference.fri_arity_bits(L))) if c[0] in OPENEVAL_SETS]
+    return OC.stress_batches(L, OC.MAIN_COLS), sets
+
+
+def openeval_expected(L, oracle=None):
+    """{set name: (opening-set bytes, final polynomial as a list of pairs, layer caps)} on Python integers; the caps (None without
+    `oracle`) are the oracle's transform and Merkle tree over the reference's folded polynomials"""
+    R = opening_reference
+    batches, sets = openeval_inputs(L)
+    coeffs = [b.tolist() for b in batches]
+    out = {}
+    for name, zeta, alpha, betas in sets:
+        layers = R.fri_layers(*coeffs, OC.MAIN_NPERM, zeta, alpha, betas)
+        out[name] = (R.open_set_bytes(R.open_set(*coeffs, OC.MAIN_NPERM, zeta)),
+                     R.final_poly(*coeffs, OC.MAIN_NPERM, zeta, alpha, betas, layers=layers),
+                     None if oracle is None else [c.tolist() for c in R.layer_caps(oracle, layers)])
+    return out
 
 
 def transform_inputs(L):
@@ -127,11 +153,41 @@ def job_prove(dry):
     return {"proofs": [p.hex() for p in proofs], "seconds": time.perf_counter() - t0}
 
 
+def job_openeval(L, dry):
+    (trace_c, zs_c, quot_c), sets = openeval_inputs(L)
+    if dry:
+        want = openeval_expected(L)
+        return {"sets": [c[0] for c in sets], "reference_sha256": {k: _sha(v[0], np.array(v[1], dtype=np.uint64)) for k, v in want.items()}}
+    oracle = oracle_lib.load()              # (for the values of the trace and Z columns: the library interpolates them back)
+    from olavm_amd.backend import Backend
+    be = Backend(device=0)
+    t0 = time.perf_counter()
+    gt = be.commit(np.stack([oracle.evaluate_poly(c) for c in trace_c]))
+    gz = be.commit(np.stack([oracle.evaluate_poly(c) for c in zs_c]))
+    gq = be.commit(quot_c, from_coeffs=True)
+    out = {"sets": [c[0] for c in sets], "open": {}, "final": {}, "caps": {},
+           "coeffs_kept": all(np.array_equal(b.coeffs(), c) for b, c in ((gt, trace_c), (gz, zs_c), (gq, quot_c)))}
+    for name, zeta, alpha, betas in sets:
+        opened, fri = be.open(gt, gz, gq, OC.MAIN_NPERM, zeta)
+        fri.begin(alpha)
+        beta, caps = None, []
+        for b in betas:
+            caps.append(fri.next_layer(beta).tolist())
+            beta = b
+        out["open"][name], out["final"][name], out["caps"][name] = opened.hex(), fri.finish(beta).tolist(), caps
+        fri.free()
+    out["seconds"] = time.perf_counter() - t0
+    for b in (gt, gz, gq):
+        b.free()
+    be.close()
+    return out
+
+
 def main(argv):
     dry = "--dry" in argv
     args = [a for a in argv if a != "--dry"]
     if len(args) != 2:
-        print("usage: python -m tests.alt_path_child [--dry] transforms:L | open:HASHER | prove  OUT.json", file=sys.stderr)
+        print("usage: python -m tests.alt_path_child [--dry] transforms:L | open:HASHER | prove | openeval:L  OUT.json", file=sys.stderr)
         return 2
     job, out_path = args
     kind, _, arg = job.partition(":")
@@ -141,6 +197,8 @@ def main(argv):
         out = job_open(arg, dry)
     elif kind == "prove":
         out = job_prove(dry)
+    elif kind == "openeval":
+        out = job_openeval(int(arg), dry)
     else:
         print("unknown job %r" % job, file=sys.stderr)
         return 2

@@ -1,6 +1,9 @@
 """The paths that an environment switch selects once per process: the canonical-arithmetic transform passes
 (OLA_NTT2_TFORM=0: the A/B control, and the only path of transforms of 2^29 points and more) and the kernels that the opening
-proof's newer ones replaced (OLA_EVAL_WIDE=0, OLA_FOLD16=0, OLA_LEAF_EXT_STAGED=0, OLA_MERKLE_FUSED_LEVELS, OLA_POW_DEFER=0).
+proof's newer ones replaced (OLA_EVAL_WIDE=0, OLA_FOLD16=0, OLA_LEAF_EXT_STAGED=0, OLA_MERKLE_FUSED_LEVELS, OLA_POW_DEFER=0), and
+the wide evaluation's steps per workgroup (OLA_EVAL_WIDE_KH), which the occupancy rule raises above 32 only from 2^22 rows on, and
+the pool's blocks handed out filled with 0xFF bytes (OLA_POOL_POISON=1), which turns a word that a kernel reads and nobody wrote
+into a wrong result.
 DESIGN.md and PARITY.md call every one of them bit-exact; here each runs in a child process (tests/alt_path_child.py) with the
 switch in its environment and its words / bytes are compared with the CPU oracle's.
 
@@ -82,6 +85,51 @@ def test_opening_proof_fallback_bytes_match_oracle(oracle, open_expected, hasher
     assert bytes.fromhex(got["open"]) == o_open, "opening set bytes differ"
     assert bytes.fromhex(got["fri"]) == o_fri, "FRI proof bytes differ"
     assert got["challenge"] == o_next, "the transcripts end in different states"
+
+
+# ------------------------------------------------------------------------------------------------ wide evaluation, long loops
+@pytest.fixture(scope="module")
+def openeval_expected():
+    memo = {}
+
+    def get(log_n):
+        if log_n not in memo:
+            memo[log_n] = child.openeval_expected(log_n)
+        return memo[log_n]
+    return get
+
+
+@pytest.mark.parametrize("log_n,kh", [(15, 2), (18, 64), (18, 512), (15, 512)])
+def test_wide_evaluation_steps_per_workgroup_match_the_integer_reference(openeval_expected, log_n, kh, tmp_path):
+    """eval_points_wide_kernel's load, step and split loop at lengths the occupancy rule (olavm_amd/csrc/eval_plan.h) reaches only
+    at 2^22 rows and more: 2 steps at 2^15 rows (64 splits), 64 and 512 at 2^18 (nhi = 512: the whole 1024-product sum in one
+    workgroup), 512 at 2^15 (clamped to nhi = 128) -- on columns whose 32-bit halves are at their maximum, at a random zeta,
+    zeta = (p-1, p-1) and a zeta of order 3.  The hi-table limbs of a chosen zeta cannot all be at their maximum: the 2^64 bound of
+    the sums stays with the device self-test."""
+    got = run_child("openeval:%d" % log_n, {"OLA_EVAL_WIDE_KH": str(kh)}, tmp_path)
+    want = openeval_expected(log_n)
+    assert got["coeffs_kept"] and got["sets"] == list(child.OPENEVAL_SETS)
+    for name in child.OPENEVAL_SETS:
+        assert bytes.fromhex(got["open"][name]) == want[name][0], "opening set bytes differ at the challenge set %s" % name
+        assert [tuple(r) for r in got["final"][name]] == want[name][1], "final polynomial differs at the challenge set %s" % name
+
+
+@pytest.mark.parametrize("log_n", [12, 16])
+def test_stepped_opening_on_poisoned_pool_blocks(oracle, log_n, tmp_path):
+    """OLA_POOL_POISON=1: the stepped opening of the stress columns where every block of the pool starts as all-ones words.  The
+    pool gives a call sequence the same blocks in the same roles, and the driver's fresh blocks are zero, so without the switch a
+    kernel that reads what nobody wrote reads zeros run after run.  What depends on it here: fold16_kernel writes nz / 16 outputs
+    and leaves the rest of the layer's planes to a memset (2^12 rows: the first fold; 2^16 rows: the first two); those words enter
+    no word of the final polynomial, only the NEXT layer's committed values -- so the caps are compared, with the oracle's
+    transform and tree over the integer reference's folded polynomials."""
+    got = run_child("openeval:%d" % log_n, {"OLA_POOL_POISON": "1"}, tmp_path)
+    want = child.openeval_expected(log_n, oracle)
+    assert got["coeffs_kept"] and got["sets"] == list(child.OPENEVAL_SETS)
+    for name in child.OPENEVAL_SETS:
+        assert bytes.fromhex(got["open"][name]) == want[name][0], "opening set bytes differ at the challenge set %s" % name
+        assert [tuple(r) for r in got["final"][name]] == want[name][1], "final polynomial differs at the challenge set %s" % name
+        wrong = [i for i, (g, w) in enumerate(zip(got["caps"][name], want[name][2])) if g != w]
+        assert len(got["caps"][name]) == len(want[name][2]) and not wrong, "the caps of the layers %s differ at the challenge set %s" % (wrong, name)
 
 
 # ------------------------------------------------------------------------------------------------ proof of work in line

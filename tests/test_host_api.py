@@ -59,3 +59,17 @@ def test_tform_arithmetic_on_the_host(tmp_path):
                            os.path.join(here, "host_tform_check.cpp"), "-o", exe])
     r = subprocess.run([exe, "300000"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "tform ok" in r.stdout, r.stdout + r.stderr
+
+
+def test_wide_evaluation_plan_on_the_host(tmp_path):
+    """olavm_amd/csrc/eval_plan.h -- the launch plan of eval_points_wide_kernel -- is host code: tests/host_eval_plan_check.cpp checks,
+    for 2^15 .. 2^30 rows and 1 .. 200 columns, by the occupancy rule and with every OLA_EVAL_WIDE_KH, that the steps per workgroup are
+    even, divide the hi table, stay within the 64-bit sums' 512 and leave the chunk count the kernel's grid has; that the rule gives
+    32 at every shape whose proof bytes the suite compares and 128 / 256 / 512 only at 2^22 / 2^23 / 2^24 rows x 94 columns; and
+    which values the switch accepts."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = os.path.join(str(tmp_path), "host_eval_plan_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(os.path.dirname(here), "olavm_amd", "csrc"),
+                           os.path.join(here, "host_eval_plan_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "eval plan ok" in r.stdout, r.stdout + r.stderr

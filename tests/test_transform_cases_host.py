@@ -91,6 +91,37 @@ def test_child_dry_run_builds_inputs_and_oracle_side_without_the_gpu_library(job
         assert got["ops"] == TC.operations(14) and sorted(got["oracle_sha256"]) == sorted(TC.operations(14))
 
 
+def test_child_dry_run_of_the_opening_evaluation_job(tmp_path):
+    """openeval:15 without a GPU: the inputs and the integer reference's side, which is a function of the size alone."""
+    from tests import alt_path_child as child, opening_cases as OC
+    out = tmp_path / "dry.json"
+    r = subprocess.run([sys.executable, "-m", "tests.alt_path_child", "--dry", "openeval:15", str(out)], cwd=ROOT, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    got = json.loads(out.read_text())
+    assert got["job"] == "openeval:15" and got["dry"] is True and got["gpu_library_loaded"] is False
+    assert got["sets"] == list(child.OPENEVAL_SETS) and sorted(got["reference_sha256"]) == sorted(child.OPENEVAL_SETS)
+    assert len(set(got["reference_sha256"].values())) == 3
+    batches, sets = child.openeval_inputs(15)
+    assert [b.shape for b in batches] == [(c, 1 << 15) for c in OC.MAIN_COLS] and all(b.dtype == np.uint64 and b.max() < P for b in batches)
+    assert [len(c[3]) for c in sets] == [3, 3, 3]
+
+
+@pytest.mark.parametrize("log_n", [3, 15, 18])
+def test_opening_stress_columns_are_what_the_table_says(log_n):
+    from tests import opening_cases as OC
+    n, h = 1 << log_n, (log_n + 1) // 2
+    t, z, q = OC.stress_batches(log_n, OC.MAIN_COLS)
+    assert (t[0] == P - 1).all() and (t[1] == 0xFFFFFFFEFFFFFFFF).all() and (t[2] == 0xFFFFFFFF).all() and t.max() < P
+    for col, k in zip(list(t[3:8]) + list(q), [0, (1 << h) - 1, 1 << h, n - (1 << h), n - 1, (1 << h) - 1, 1 << h, n - (1 << h), n - 1]):
+        assert col[k] == 1 and col.sum() == 1
+    assert np.array_equal(t[8], np.arange(n, dtype=np.uint64)) and (z[1] == P - 1).all() and z[0].max() < P
+    assert all(np.array_equal(a, b) for a, b in zip((t, z, q), OC.stress_batches(log_n, OC.MAIN_COLS)))
+    names = [c[0] for c in OC.challenge_sets(log_n, 2)]
+    assert names == ["random", "base_zeta", "x_zeta", "minus_ones", "order3_zeta", "non_canonical"]
+    assert pow(OC.U3, 3, P) == 1 and OC.U3 != 1
+
+
 def test_child_refuses_an_unknown_job(tmp_path):
     r = subprocess.run([sys.executable, "-m", "tests.alt_path_child", "--dry", "nonsense", str(tmp_path / "x.json")], cwd=ROOT,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
