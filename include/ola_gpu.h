@@ -254,7 +254,13 @@ int32_t ola_gpu_reserve(OlaCtx* ctx, const uint64_t* airset, size_t airset_words
 int32_t ola_table_shape(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, uint32_t table, uint32_t out[6]);
 /* compute_permutation_z_polys (permutation.rs:103-187).  trace_cols: host columns of 2^log_n rows; perm_challenges:
  * [permutation_batch_size][num_challenges][2] = (beta, gamma) in get_n_grand_product_challenge_sets order (prover.rs:360-367);
- * z_out: [permutation Z columns][n], column-major values (the head of the reference's `z_polys`). */
+ * z_out: [permutation Z columns][n], column-major values (the head of the reference's `z_polys`).
+ * A row at which the product of the right-hand sides gamma + sum beta^k rhs_k of a batch is zero has no quotient: the reference
+ * panics "Tried to invert zero" there (permutation.rs:143, plonky2/field/src/types.rs:99-101).  Here that is OLA_E_INVALID_ARG with
+ * the message "Tried to invert zero: table T, permutation batch B ..." (the first such batch), from this call, from
+ * ola_prove_single_table and from ola_prove_with_traces alike; the context stays usable.  ola_ctl_z does not report it: it has no
+ * permutation challenges and returns no permutation column.  A table without permutation arguments has no Z column here:
+ * nothing is written, the call succeeds. */
 int32_t ola_perm_z(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, uint32_t table, uint32_t log_n,
                    const uint64_t* const* trace_cols, const uint64_t* perm_challenges, uint64_t* z_out);
 /* The table's columns of cross_table_lookup_data (cross_table_lookup.rs:224-311), looking sides before looked sides, lookups in

@@ -223,6 +223,10 @@ void check_constraints(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airse
         u64* tot = tm.alloc(pscan_tot_stride(n) * std::max<size_t>(1, jobs[t].size()));
         if (nperm) {
             u64* tmpcol = tm.alloc(n);
+            // a row with a zero denominator gets the factor 0 (perm_factor_kernel): the batch's product is then 0, not 1, and the
+            // batch is reported below like any other failing permutation argument -- the kernel's own flag is not read here
+            unsigned* d_zero_den = (unsigned*)tm.alloc(1);
+            HIP_CHECK(hipMemsetAsync(d_zero_den, 0xFF, 8, ctx->stream));
             const int total = (int)air.perm_pairs.size() * nch;
             int inst = 0;
             for (int b = 0; b < nperm; b++) {
@@ -236,7 +240,8 @@ void check_constraints(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airse
                 }
                 pd[0] = cnt;
                 u64* d_pd = tm.upload(pd);
-                hipLaunchKernelGGL(perm_factor_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, dev[t].vals, n, d_pd, tmpcol);
+                hipLaunchKernelGGL(perm_factor_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, dev[t].vals, n, d_pd, tmpcol,
+                                   (unsigned)b, d_zero_den);
                 product_scan_inclusive(ctx, tmpcol, n, tot);
                 HIP_CHECK(hipMemcpyAsync(&perm_tot[b], tmpcol + (n - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
             }

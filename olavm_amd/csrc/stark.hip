@@ -190,8 +190,11 @@ __global__ __launch_bounds__(256) void ctl_factor_kernel(const u64* __restrict__
 
 // permutation quotient column: out[i] = prod_inst (gamma + sum beta^k lhs_k) / prod_inst (gamma + sum beta^k rhs_k)
 // desc: [n_inst, (beta, gamma, npairs, (lhs, rhs)*)*]
+// A row whose denominator is zero has no quotient: the reference inverts the denominators in one batch_multiplicative_inverse and
+// panics "Tried to invert zero" (permutation.rs:143).  Here gl_inv(0) = 0 and the row's factor is written as 0; the smallest `batch`
+// with such a row is left in *zero_den (initialised to ~0u by the caller), who decides what a zero means for it.
 __global__ __launch_bounds__(256) void perm_factor_kernel(const u64* __restrict__ trace, size_t n, const u64* __restrict__ desc,
-                                                          u64* __restrict__ out) {
+                                                          u64* __restrict__ out, unsigned batch, unsigned* __restrict__ zero_den) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     u32 p = 0;
@@ -210,6 +213,7 @@ __global__ __launch_bounds__(256) void perm_factor_kernel(const u64* __restrict_
         num = gl_mul(num, l);
         den = gl_mul(den, r);
     }
+    if (den == 0) atomicMin(zero_den, batch);
     out[i] = gl_mul(num, gl_inv(den));
 }
 
@@ -463,6 +467,7 @@ struct PhaseTap {
     const u64* perm_challenges = nullptr;    // [batch_size][num_challenges][2] (beta, gamma)
     const u64* alphas = nullptr;             // [num_challenges]
     const OlaBatch* zs = nullptr;            // the caller's Z commitment (quotient phase: the Z columns are not recomputed)
+    bool perm_wanted = true;                 // false: perm_challenges are stand-ins, the permutation Z columns are thrown away
     int stop_after = 0;                      // 1: after the Z columns, 2: after the quotient chunks
     std::vector<u64>* zs_out = nullptr;      // [nz][n] column-major
     std::vector<u64>* chunks_out = nullptr;  // [num_challenges * q][n] coefficients
@@ -518,8 +523,8 @@ static bool table_is_sharded(const DeviceCtx* ctx, const OlaGpuConfig& cfg, cons
 
 static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, const HTable& air, const DevTable& tv,
                                const OlaBatch& trace_c, const std::vector<u64>& trace_cap, const std::vector<CtlJob>& ctl,
-                               const u64* params, OlaChallenger& ch, std::vector<uint8_t>& bytes, bool sharded, PhaseTap* tap = nullptr,
-                               PowDefer* pow_defer = nullptr) {
+                               const u64* params, OlaChallenger& ch, std::vector<uint8_t>& bytes, bool sharded, int table_index,
+                               PhaseTap* tap = nullptr, PowDefer* pow_defer = nullptr) {
     DevBuf mem(ctx);
     const int nch = (int)cfg.num_challenges;
     if (nch != 2) throw OlaError(OLA_E_INVALID_ARG, "num_challenges must be 2");
@@ -575,13 +580,19 @@ static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuCo
             perm_desc[at] = cnt;
         }
     }
+    // two device flags: [0] a non-binary CTL filter, [1] the first permutation batch with a zero denominator (~0u: none)
+    unsigned* d_flags = (unsigned*)mem.alloc(1);
+    unsigned* d_bad_filter = d_flags;
+    HIP_CHECK(hipMemsetAsync(d_flags, 0, 4, ctx->stream));
+    HIP_CHECK(hipMemsetAsync(d_flags + 1, 0xFF, 4, ctx->stream));
     if (nperm && !have_zs) {
         u64* d_pd = mem.alloc(perm_desc.size());
         HIP_CHECK(hipMemcpyAsync(d_pd, perm_desc.data(), perm_desc.size() * 8, hipMemcpyHostToDevice, ctx->stream));
         // offsets of each batch descriptor
         size_t off = 0;
         for (int b = 0; b < nperm; b++) {
-            hipLaunchKernelGGL(perm_factor_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, tv.vals, n, d_pd + off, tmpcol);
+            hipLaunchKernelGGL(perm_factor_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, tv.vals, n, d_pd + off, tmpcol,
+                               (unsigned)b, d_flags + 1);
             product_scan_inclusive(ctx, tmpcol, n, tot);
             hipLaunchKernelGGL(shift_right_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, tmpcol, zvals + (size_t)b * n, n);
             // advance to the next batch descriptor
@@ -597,8 +608,6 @@ static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuCo
     for (auto& j : ctl) { ctl_off.push_back(ctl_desc.size()); push_ctl_desc(ctl_desc, *j.twc, j.ch.beta, j.ch.gamma); }
     u64* d_cd = mem.alloc(ctl_desc.size() + 1);
     if (!ctl_desc.empty()) HIP_CHECK(hipMemcpyAsync(d_cd, ctl_desc.data(), ctl_desc.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    unsigned* d_bad_filter = (unsigned*)mem.alloc(1);
-    HIP_CHECK(hipMemsetAsync(d_bad_filter, 0, 8, ctx->stream));
     if (!ctl.empty() && !have_zs) {   // all CTL Z columns of the table in one launch per step
         std::vector<u64> offs(ctl_off.begin(), ctl_off.end());
         // the columns of one lookup side under the two challenges share their linear combinations: pair them (ctl_factor_kernel)
@@ -622,17 +631,26 @@ static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuCo
                            d_offs, d_pairs, zc, d_bad_filter);
         product_scan_inclusive(ctx, zc, n, tot, ctl.size());
     }
-    // the filter flag travels with the next read-back the host waits for anyway (the Z commitment's cap)
+    // the two flags travel with the next read-back the host waits for anyway (the Z commitment's cap)
     HostSpan h_flags = mem.host(2);
     h_flags[0] = h_flags[1] = 0;
     const bool check_filter = !ctl.empty() && !have_zs;
-    if (check_filter) HIP_CHECK(hipMemcpyAsync(&h_flags[0], d_bad_filter, 4, hipMemcpyDeviceToHost, ctx->stream));
+    const bool check_den = nperm && !have_zs && (!tap || tap->perm_wanted);
+    if (check_filter || check_den) HIP_CHECK(hipMemcpyAsync(&h_flags[0], d_flags, 8, hipMemcpyDeviceToHost, ctx->stream));
+    // call after the wait.  The reference meets the filter first (cross_table_lookup_data runs before any prove_single_table)
+    auto check_z_flags = [&] {
+        if (check_filter && (unsigned)h_flags[0]) throw OlaError(OLA_E_INVALID_ARG, "Non-binary filter?");
+        const unsigned zero_batch = (unsigned)(h_flags[0] >> 32);
+        if (check_den && zero_batch != ~0u)
+            throw OlaError(OLA_E_INVALID_ARG, "Tried to invert zero: table " + std::to_string(table_index) + ", permutation batch " +
+                                                  std::to_string(zero_batch) + " has a row whose denominator is zero");
+    };
     if (tap) { tap->nperm = nperm; tap->nz = nz; tap->q = air.quotient_degree_factor(); }
     if (tap && tap->stop_after == 1) {
         tap->zs_out->resize((size_t)nz * n);
         HIP_CHECK(hipMemcpyAsync(tap->zs_out->data(), zvals, (size_t)nz * n * 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (check_filter && (unsigned)h_flags[0]) throw OlaError(OLA_E_INVALID_ARG, "Non-binary filter?");
+        check_z_flags();
         return;
     }
     // ---- Zs commitment ----
@@ -649,7 +667,7 @@ static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuCo
     } else {
         zs_c.own.b = commit_shared(ctx, tables, zvals, (uint32_t)nz, (uint32_t)degree_bits, cfg, true, sharded, nullptr, zs_cap, lean);
         zs_c.b = zs_c.own.b;
-        if (check_filter && (unsigned)h_flags[0]) throw OlaError(OLA_E_INVALID_ARG, "Non-binary filter?");   // commit_shared has waited for the cap
+        check_z_flags();                                 // commit_shared has waited for the cap
         challenger_observe_cap(ch, zs_cap.data(), zs_cap.size() / 4);
     }
     const u64 alpha0 = (tap && tap->alphas) ? gl_canon(tap->alphas[0]) : challenger_get(ch);
@@ -915,7 +933,7 @@ void prove_single_table_host(DeviceCtx* ctx, NttTables& tables, const OlaGpuConf
     const HTable& air = set.tables[table];
     if (trace_c.ncols != (uint32_t)air.ncols || trace_c.is_shard()) throw OlaError(OLA_E_INVALID_ARG, "trace commitment does not match the table");
     std::vector<GpChallenge> ctl_ch;
-    for (uint32_t c = 0; c < cfg.num_challenges; c++) ctl_ch.push_back({ctl_challenges[2 * c], ctl_challenges[2 * c + 1]});
+    for (uint32_t c = 0; c < cfg.num_challenges; c++) ctl_ch.push_back({gl_canon(ctl_challenges[2 * c]), gl_canon(ctl_challenges[2 * c + 1])});
     const std::vector<std::vector<CtlJob>> jobs = ctl_jobs(set, ctl_ch);
     DevBuf mem(ctx);
     DevTable tv;
@@ -929,7 +947,7 @@ void prove_single_table_host(DeviceCtx* ctx, NttTables& tables, const OlaGpuConf
     const std::vector<u64> cap(trace_cap, trace_cap + 4 * len_cap);
     std::vector<u64> zero_params(64, 0);
     if (!params && air.n_params > 64) throw OlaError(OLA_E_INVALID_ARG, "params required");
-    prove_single_table(ctx, tables, cfg, air, tv, trace_c, cap, jobs[table], params ? params : zero_params.data(), ch, bytes, false);
+    prove_single_table(ctx, tables, cfg, air, tv, trace_c, cap, jobs[table], params ? params : zero_params.data(), ch, bytes, false, (int)table);
 }
 
 // Widths of a table's three batches (trace, Z, quotient chunks)
@@ -979,6 +997,7 @@ void phase_zs_host(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, c
     std::vector<u64> dummy_perm((size_t)air.permutation_batch_size() * cfg.num_challenges * 2, 1);
     PhaseTap tap;
     tap.perm_challenges = perm_challenges ? perm_challenges : dummy_perm.data();
+    tap.perm_wanted = which == 0;     // ola_ctl_z: the (1, 1) stand-ins may well meet a zero denominator, and nobody reads those columns
     tap.stop_after = 1;
     std::vector<u64> zs;
     tap.zs_out = &zs;
@@ -988,7 +1007,7 @@ void phase_zs_host(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, c
     challenger_init(ch, (uint32_t)ctx->hasher);
     std::vector<uint8_t> bytes;
     std::vector<u64> zero_params(64, 0), cap;
-    prove_single_table(ctx, tables, cfg, air, tv, shape, cap, jobs[table], zero_params.data(), ch, bytes, false, &tap);
+    prove_single_table(ctx, tables, cfg, air, tv, shape, cap, jobs[table], zero_params.data(), ch, bytes, false, (int)table, &tap);
     const size_t first = which == 0 ? 0 : (size_t)tap.nperm, count = which == 0 ? (size_t)tap.nperm : (size_t)(tap.nz - tap.nperm);
     out_cols.assign(zs.begin() + first * n, zs.begin() + (first + count) * n);
 }
@@ -1016,7 +1035,7 @@ void phase_quotient_host(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& 
     std::vector<uint8_t> bytes;
     std::vector<u64> zero_params(64, 0), cap;
     if (!params && air.n_params > 64) throw OlaError(OLA_E_INVALID_ARG, "params required");
-    prove_single_table(ctx, tables, cfg, air, tv, trace_c, cap, jobs[table], params ? params : zero_params.data(), ch, bytes, false, &tap);
+    prove_single_table(ctx, tables, cfg, air, tv, trace_c, cap, jobs[table], params ? params : zero_params.data(), ch, bytes, false, (int)table, &tap);
 }
 
 // Memory-lean tables (OLA_LEAN=1 forces, =0 forbids, default: when keeping every LDE resident would not fit): the LDEs of the
@@ -1233,7 +1252,7 @@ void prove_with_traces(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cf
         PhaseTimer tt(ctx, "  table " + std::to_string(t) + " prove_single_table");
         ctx->acct.shardable = log_n[t] >= ctx->shard.min_log_n;
         prove_single_table(ctx, tables, cfg, set.tables[t], dev[t], *commits[t]->b, caps[t], jobs[t], pr, ch, bytes,
-                           table_is_sharded(ctx, cfg, set.tables[t], log_n[t]), nullptr, &pow);
+                           table_is_sharded(ctx, cfg, set.tables[t], log_n[t]), (int)t, nullptr, &pow);
     }
     pow_finish(ctx, pow, bytes);
     ctx->acct.shardable = false;

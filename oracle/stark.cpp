@@ -264,6 +264,9 @@ static std::vector<std::vector<u64>> compute_permutation_z_polys(const AirTable&
                 den[r] = gl_mul(den[r], rr);
             }
         }
+        // batch_multiplicative_inverse(&denominator.values) ends in inverse(), which panics on zero (permutation.rs:143, types.rs:99-101)
+        for (size_t r = 0; r < degree; r++)
+            if (den[r] == 0) throw std::runtime_error("Tried to invert zero: permutation batch " + std::to_string(b) + ", row " + std::to_string(r));
         std::vector<u64> z(degree);
         u64 acc = 1;
         for (size_t r = 0; r < degree; r++) { z[r] = acc; acc = gl_mul(acc, gl_mul(num[r], gl_inv(den[r]))); }
@@ -572,6 +575,36 @@ size_t oracle_prove_with_traces(const u64* airset, size_t airset_words, const u6
     } catch (const std::exception& e) {
         if (err && err_cap) { strncpy(err, e.what(), err_cap - 1); err[err_cap - 1] = 0; }
         return 0;
+    }
+}
+
+// compute_permutation_z_polys of one table at the caller's challenges: perm_challenges = [permutation_batch_size][num_challenges]
+// (beta, gamma), trace column-major ncols x 2^log_n, out = [permutation batches][2^log_n].  Returns the number of Z columns, -1 on
+// failure (message in err).
+long oracle_permutation_z(const u64* airset, size_t airset_words, int table, const u64* trace, uint32_t log_n, const u64* perm_challenges,
+                          u64* out, char* err, size_t err_cap) {
+    try {
+        AirSet set = parse_airset(airset, airset_words);
+        const AirTable& air = set.tables.at(table);
+        const ProverConfig cfg;
+        const size_t n = (size_t)1 << log_n;
+        std::vector<std::vector<u64>> cols(air.ncols);
+        for (int c = 0; c < air.ncols; c++) { cols[c].assign(trace + (size_t)c * n, trace + (size_t)(c + 1) * n); for (auto& x : cols[c]) x = gl_canon(x); }
+        std::vector<ChallengeSet> sets;
+        for (int i = 0; i < air.permutation_batch_size(); i++) {
+            ChallengeSet s;
+            for (int c = 0; c < cfg.num_challenges; c++) {
+                const u64* w = perm_challenges + 2 * (i * cfg.num_challenges + c);
+                s.push_back({gl_canon(w[0]), gl_canon(w[1])});
+            }
+            sets.push_back(s);
+        }
+        const std::vector<std::vector<u64>> zs = compute_permutation_z_polys(air, cfg, cols, sets);
+        for (size_t b = 0; b < zs.size(); b++) memcpy(out + b * n, zs[b].data(), n * 8);
+        return (long)zs.size();
+    } catch (const std::exception& e) {
+        if (err && err_cap) { strncpy(err, e.what(), err_cap - 1); err[err_cap - 1] = 0; }
+        return -1;
     }
 }
 

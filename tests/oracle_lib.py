@@ -84,6 +84,8 @@ class Oracle:
         L.oracle_verify_all_proof.restype = C.c_int
         L.oracle_check_constraints.argtypes = [U64P, C.c_size_t, C.c_int, U64P, C.c_uint32, U64P]
         L.oracle_check_constraints.restype = C.c_long
+        L.oracle_permutation_z.argtypes = [U64P, C.c_size_t, C.c_int, U64P, C.c_uint32, U64P, U64P, C.c_char_p, C.c_size_t]
+        L.oracle_permutation_z.restype = C.c_long
         L.oracle_set_hasher.argtypes = [C.c_int]
         L.oracle_get_hasher.restype = C.c_int
         L.oracle_blake3.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p]
@@ -302,6 +304,19 @@ class Oracle:
         rc = self.lib.oracle_verify_all_proof(ptr(blob), blob.size, ptr(pr) if pr.size else None, c, proof_bytes, len(proof_bytes),
                                               msg, 512)
         return rc, msg.value.decode()
+
+    def permutation_z(self, blob, table, trace, perm_challenges, nperm):
+        """compute_permutation_z_polys of one table at the caller's challenges, [permutation_batch_size][num_challenges] (beta, gamma)."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint64)
+        tr = np.ascontiguousarray(trace, dtype=np.uint64)
+        cc = np.ascontiguousarray(np.array(perm_challenges, dtype=np.uint64).reshape(-1))
+        out = np.zeros((max(nperm, 1), tr.shape[1]), dtype=np.uint64)
+        err = C.create_string_buffer(512)
+        k = self.lib.oracle_permutation_z(ptr(blob), blob.size, table, ptr(tr), int(tr.shape[1]).bit_length() - 1, ptr(cc), ptr(out), err, 512)
+        if k < 0:
+            raise RuntimeError("oracle prover: " + err.value.decode())
+        assert k == nperm
+        return out[:nperm]
 
     def check_constraints(self, blob, table, trace, params=None):
         blob = np.ascontiguousarray(blob, dtype=np.uint64)

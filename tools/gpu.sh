@@ -277,6 +277,9 @@ PY
                  ( set -o pipefail
                    timeout -k 10 600 python -m pytest tests/test_gpu_check_lookup.py -x -q 2>&1 | tail -15 | tee $O/pytest.log && \
                    timeout -k 10 900 python tools/bench_check_lookup.py --json $O/check_lookup.json 2>&1 | grep -v amdgpu | tee $O/check_lookup.txt ) ;;
+    zcolumns)    # the Z-column kernels word for word against the integer reference, at caller-chosen challenges
+                 ( set -o pipefail
+                   timeout -k 10 600 python -m pytest tests/test_gpu_zcolumns.py -q --durations=12 2>&1 | tail -30 | tee $O/pytest.log ) ;;
     *)           echo "unknown step $step" ;;
   esac
 done
