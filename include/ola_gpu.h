@@ -51,7 +51,10 @@ extern "C" {
  * were ola_generate_memory_trace and ola_generate_cmp_trace (the memory table from raw cells, sorted on the device, and the comparison
  * table from operand pairs, both with their range-checked value lists); so were ola_generate_storage_trace and
  * ola_generate_poseidon_table (the account-storage tree hashed on the device with the storage-access table and the Poseidon table's
- * inputs, and the Poseidon table at its padded height, resident). */
+ * inputs, and the Poseidon table at its padded height, resident); so were ola_generate_tape_trace, ola_generate_poseidon_chunk_trace
+ * and ola_generate_prog_chunk_trace (the tape table sorted on the device, and the two chunk tables gathered from the resident Poseidon
+ * table); so were OlaExecRecords, ola_tables_from_records, ola_tables_get, ola_tables_free and ola_prove_from_records (the twelve
+ * generators composed in one call, from the executor's records to resident tables and to proof bytes). */
 #define OLA_GPU_ABI_VERSION 7
 #define OLA_OK 0
 #define OLA_E_INVALID_ARG (-1)
@@ -764,6 +767,133 @@ int32_t ola_generate_storage_trace(OlaCtx* ctx, const uint64_t* accesses, size_t
                                    uint64_t roots_out[8]);
 int32_t ola_generate_poseidon_table(OlaCtx* ctx, const uint64_t* inputs, const uint64_t* filters, size_t n_rows, size_t stride,
                                     uint64_t* out, uint32_t* log_n_out);
+
+/* ---- the tape, Poseidon-chunk and program-chunk tables ---------------------------------------------------------------------------
+ * The narrow tables that were still assembled on the host.  None needs hashing the host has not done: every hash they hold is an
+ * output word of a row of the Poseidon table that ola_generate_poseidon_table leaves resident (inputs in its columns 4..15, outputs in
+ * 16..27), so a row is a gather -- thread = row, every column stored along rows.  The contract is the one of the "whole derived tables"
+ * block above: every buffer may be host memory or memory of the context's GPU, words may be >= p, every word written is canonical,
+ * every column of `out` is written (no memset of the table), the work runs on the context's stream and is complete on return,
+ * arguments are validated first, out == NULL is a sizing call that also takes ctx == NULL, ctx == NULL in a call that would do work is
+ * OLA_E_NO_DEVICE on a machine without a HIP device and OLA_E_INVALID_ARG otherwise, a multi-device context works on its first device,
+ * and `out` can go into ola_prove_with_traces* as a resident table.  (The SCCALL table has no entry point: the executor produces no
+ * cross-contract call, so it is the 26 x 8 padding table.)
+ *
+ * ola_generate_tape_trace (builtins/tape/tape_stark.rs:44-143): out = 6 x n, n = next_pow2(max(n_cells, 8)), log2 n in *log_n_out.
+ *   cells: OLA_TAPE_CELL_WORDS = 3 words per cell, column-major 3 x n_cells, in execution order: the tape address, the opcode's one-hot
+ *     word, the value.  n_cells >= 2^31 is OLA_E_INVALID_ARG.
+ *   Rows ascend in the canonical address; cells of one address keep execution order (a stable radix sort of (address, 32-bit index)
+ *   over the bits the addresses use).  Live rows: OPCODE, ADDR, VALUE, FILTER_LOOKED = 1, TX_IDX = IS_INIT_SEG = 0; padding rows repeat
+ *   the last sorted cell's address and value with the TLOAD mask and filter 0; no cells: every row a TLOAD of address 0, value 0.
+ *   Host waits: three.  One after the key pass, for the OR of the addresses that sizes the sort (all zero: no sort); one before the
+ *   sort's work space goes back to the pool, which another thread's call on another stream could take at once; one at the end,
+ *   behind the copy to a host `out`, because the table is complete on return (the stream is idle by then when `out` is device memory).
+ * ola_generate_poseidon_chunk_trace (generation/poseidon_chunk.rs): out = 53 x n, n = next_pow2(max(rows, 8)), rows = the sum of
+ *   1 + len / 8 over the calls, log2 n in *log_n_out.
+ *   calls: OLA_POSEIDON_CALL_WORDS = 5 words per POSEIDON instruction, column-major 5 x n_calls, in execution order: clk, src, len, dst,
+ *     psdn_row (the Poseidon-table row of the call's first block; block j is row psdn_row + j).
+ *   poseidon_table: 134 x 2^psdn_log_n column-major (3 <= psdn_log_n <= 26); may be NULL in a sizing call.
+ *   A call gives a header row (OP0 = src, FILTER_LOOKED_CPU = 1) and len / 8 extension rows; extension row j has OP0 = src + 8 j,
+ *   ACC_CNT = 8 (j + 1), VALUE = inputs 0..7 of table row psdn_row + j, CAP = inputs 8..11, HASH = its twelve outputs, IS_EXT_LINE = 1,
+ *   IS_RESULT_LINE on the last one, the eight memory filters and the Poseidon filter; both kinds carry CLK, OPCODE = the POSEIDON mask,
+ *   OP1 = len, DST.  Row offsets are an exclusive scan over 1 + len / 8.  Padding rows: IS_PADDING_LINE = 1, the rest 0.
+ *   The host reads the len and psdn_row words once before any work (one copy when the records are in HBM; also in a sizing call):
+ *   len == 0, len % 8 != 0, psdn_row + len / 8 > 2^psdn_log_n (checked when the table is given), n_calls >= 2^26 and more than 2^26 rows
+ *   are OLA_E_INVALID_ARG.
+ *   Host waits: three, two without calls.  That read (it sizes the table and keeps every gather inside the Poseidon table; a
+ *   blocking copy when the records are in HBM), one before the scan's work space goes back to the pool, and the one at the end, behind
+ *   the copy to a host `out`.
+ * ola_generate_prog_chunk_trace (generation/prog.rs, program/prog_chunk_stark.rs): out = 40 x n, n = next_pow2(max(n_words / 8, 8)),
+ *   log2 n in *log_n_out.
+ *   words: the zero-padded listing, n_words words; code_addr: 4 words; poseidon_table as above, whose row i hashed words 8 i .. 8 i + 7
+ *   (may be NULL in a sizing call).
+ *   Row i: CODE_ADDR, START_PC = 8 i, INST = the eight words, CAP = inputs 8..11 of table row i, HASH = its twelve outputs, IS_FIRST_LINE
+ *   on row 0, IS_RESULT_LINE on the last row with OLA_PROG_CHUNK_RESULT_LINE, the eight looking filters 1.  Padding rows:
+ *   IS_PADDING_LINE = 1, the rest 0.  n_words % 8 != 0, n_words / 8 > 2^psdn_log_n, n_words > 2^29 and a flag bit nobody defined are
+ *   OLA_E_INVALID_ARG.
+ *   Host waits: one, at the end (code_addr in HBM adds a 32-byte copy before the launch). */
+#define OLA_TAPE_CELL_WORDS 3
+#define OLA_POSEIDON_CALL_WORDS 5
+#define OLA_PROG_CHUNK_RESULT_LINE 1u
+int32_t ola_generate_tape_trace(OlaCtx* ctx, const uint64_t* cells, size_t n_cells, uint64_t* out, uint32_t* log_n_out);
+int32_t ola_generate_poseidon_chunk_trace(OlaCtx* ctx, const uint64_t* calls, size_t n_calls, const uint64_t* poseidon_table,
+                                          uint32_t psdn_log_n, uint64_t* out, uint32_t* log_n_out);
+int32_t ola_generate_prog_chunk_trace(OlaCtx* ctx, const uint64_t* words, size_t n_words, const uint64_t* code_addr, uint32_t flags,
+                                      const uint64_t* poseidon_table, uint32_t psdn_log_n, uint64_t* out, uint32_t* log_n_out);
+
+/* ---- from the executor's records to the twelve tables, and to proof bytes -------------------------------------------------------
+ * One call composes the generators above, so that a host restates none of it: their order, the range-check value buffer the
+ * comparison and memory calls share with the CPU's values, the range-check filters, the Poseidon row numbering and the two compress
+ * challenges.  OlaExecRecords is what the executor recorded -- what the native generator hands out under OLA_TRACEGEN_RECORDS_ONLY
+ * (include/ola_tracegen.h).  `size` is sizeof(OlaExecRecords) as the caller compiled it, so that the struct can grow; every pointer may
+ * be host memory or memory of the context's GPU (a device buffer must be complete when the call is made), and may be NULL where its
+ * count is 0.
+ *   steps / n_steps / cpu_log_n: ola_generate_cpu_trace's; prog_listing / prog_log_n: the listing side of ola_generate_prog_trace_steps
+ *   mem_cells, cmp_ops, cpu_rc (the values of the RC instructions), bitwise_ops (5 x n: filter, tag, op0, op1, res), accesses with
+ *   optional siblings, tape_cells, psdn_calls, listing_words / code_addr: as the generators take them
+ *   psdn_inputs / psdn_filters: 12 x psdn_stride and 4 x psdn_stride with the accesses' rows free, psdn_rows <= psdn_stride live rows;
+ *     the call works on copies, the caller's buffers are not written
+ *   range_bits, limb_bits: of the AIR set's fixed tables (16 and 8 in the reference)
+ *   flags: OLA_RECORDS_REFERENCE_QUIRKS (the bitwise and memory generators' OLA_TABLEGEN_REFERENCE_QUIRKS), OLA_RECORDS_ZERO_FILLER
+ *     (OLA_TABLEGEN_ZERO_FILLER), OLA_RECORDS_RESULT_LINE (OLA_PROG_CHUNK_RESULT_LINE), OLA_RECORDS_EXPLICIT_BETAS: bitwise_beta and
+ *     program_beta are taken as given; without it both are drawn inside the call by the host challenger, the bitwise one from the
+ *     twelve limb columns of the operations (generation/builtin.rs:120-131), the program one from the storage call's two roots
+ *     (generation/prog.rs:23-29)
+ * ola_tables_from_records makes all twelve tables resident, in pool memory of the context's (first) device, each at its generator's own
+ * height: the storage tree with the Poseidon inputs, the Poseidon table, the two chunk tables, the comparison and memory tables with
+ * their value lists behind the CPU's, the four range-check filter columns from the four segment lengths (one fill kernel), then the
+ * range-check, CPU, tape, SCCALL (the 26 x 8 padding table), bitwise and program tables.  A failure returns the failing generator's
+ * code with its message behind the name of the step ("CPU table: ..."), and frees everything the call took.
+ * ola_tables_get: the twelve device pointers and heights in `enum Table` order, params[2] = (bitwise, program) challenge and the
+ * twelve compress_challenges -- what ola_check_constraints, ola_check_lookup and ola_prove_with_traces take.  ola_tables_free returns
+ * the memory to the context's pool (before ola_gpu_free).
+ * ola_prove_from_records: the tables, ola_prove_with_traces on them, the set freed; the too-small buffer and ola_take_pending_proof
+ * behave as there.  No table crosses the link. */
+#define OLA_RECORDS_REFERENCE_QUIRKS 1u
+#define OLA_RECORDS_ZERO_FILLER 2u
+#define OLA_RECORDS_RESULT_LINE 4u
+#define OLA_RECORDS_EXPLICIT_BETAS 8u
+typedef struct OlaExecRecords {
+    uint32_t size;
+    uint32_t flags;
+    uint32_t cpu_log_n;
+    uint32_t prog_log_n;
+    uint32_t range_bits;
+    uint32_t limb_bits;
+    const uint64_t* steps;
+    uint64_t n_steps;
+    const uint64_t* prog_listing;
+    const uint64_t* mem_cells;
+    uint64_t n_mem_cells;
+    const uint64_t* cmp_ops;
+    uint64_t n_cmp_ops;
+    const uint64_t* cpu_rc;
+    uint64_t n_cpu_rc;
+    const uint64_t* bitwise_ops;
+    uint64_t n_bitwise_ops;
+    const uint64_t* accesses;
+    uint64_t n_access;
+    const uint64_t* siblings;
+    const uint64_t* psdn_inputs;
+    const uint64_t* psdn_filters;
+    uint64_t psdn_stride;
+    uint64_t psdn_rows;
+    const uint64_t* tape_cells;
+    uint64_t n_tape_cells;
+    const uint64_t* psdn_calls;
+    uint64_t n_psdn_calls;
+    const uint64_t* listing_words;
+    uint64_t n_listing_words;
+    uint64_t code_addr[4];
+    uint64_t bitwise_beta;
+    uint64_t program_beta;
+} OlaExecRecords;
+typedef struct OlaTableSet OlaTableSet;
+int32_t ola_tables_from_records(OlaCtx* ctx, const OlaExecRecords* rec, OlaTableSet** out);
+int32_t ola_tables_get(const OlaTableSet* set, const uint64_t* ptrs[12], uint32_t log_n[12], uint64_t params[2], uint64_t compress[12]);
+int32_t ola_tables_free(OlaTableSet* set);
+int32_t ola_prove_from_records(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, const OlaExecRecords* rec, uint8_t* out,
+                               size_t cap, size_t* out_len);
 
 /* ---- coset-partitioned proving over several GPUs ---------------------------------------------------------
  * One process per GPU; every process calls ola_prove_with_traces with the SAME traces.  Because the transcript is a

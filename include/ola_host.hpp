@@ -349,6 +349,21 @@ inline std::vector<uint8_t> prove_with_traces(const Gpu& g, const std::vector<F>
     return out;
 }
 
+// From the executor's records (OlaExecRecords: set `size` to sizeof, pointers host or device memory) to the AllProof wire bytes: the
+// twelve tables are generated resident and proven, no table crosses the link (ola_prove_from_records).
+inline std::vector<uint8_t> prove_from_records(const Gpu& g, const std::vector<F>& airset, const OlaExecRecords& rec) {
+    std::vector<uint8_t> out((size_t)8 << 20);
+    size_t len = 0;
+    int32_t rc = ola_prove_from_records(g.ctx(), airset.data(), airset.size(), &rec, out.data(), out.size(), &len);
+    if (rc == OLA_E_INVALID_ARG && len > out.size()) {      // buffer too small: the finished proof waits in the context
+        out.resize(len);
+        rc = ola_take_pending_proof(g.ctx(), out.data(), out.size(), &len);
+    }
+    check(rc);
+    out.resize(len);
+    return out;
+}
+
 // ---- circuits/src/stark/prover.rs:711-819, cross_table_lookup.rs:551-584, test_utils.rs:152-195 ------------------------------------
 // Why a trace does not prove: the constraint programs, permutation arguments and cross-table lookups of the tables in `table_mask`
 // on the trace domain (ola_check_constraints).  traces / log_n / params as for prove_with_traces (a table outside the mask may be
@@ -547,6 +562,40 @@ inline std::vector<F> generate_poseidon_table(const Gpu& g, const std::vector<F>
     check(ola_generate_poseidon_table(nullptr, nullptr, nullptr, n_rows, stride, nullptr, &log_n));
     std::vector<F> out((size_t)134 << log_n);
     check(ola_generate_poseidon_table(g.ctx(), stride ? inputs.data() : nullptr, filters.empty() ? nullptr : filters.data(), n_rows, stride, out.data(), &log_n));
+    if (log_n_out) *log_n_out = log_n;
+    return out;
+}
+
+// tape cells (OLA_TAPE_CELL_WORDS x n_cells column-major, execution order) -> the 6 x n tape table, sorted by address on the device
+inline std::vector<F> generate_tape_trace(const Gpu& g, const std::vector<F>& cells, size_t n_cells, uint32_t* log_n_out = nullptr) {
+    if (cells.size() != OLA_TAPE_CELL_WORDS * n_cells) throw Error(OLA_E_INVALID_ARG, "shape");
+    uint32_t log_n = 0;
+    check(ola_generate_tape_trace(nullptr, nullptr, n_cells, nullptr, &log_n));
+    std::vector<F> out((size_t)6 << log_n);
+    check(ola_generate_tape_trace(g.ctx(), n_cells ? cells.data() : nullptr, n_cells, out.data(), &log_n));
+    if (log_n_out) *log_n_out = log_n;
+    return out;
+}
+// POSEIDON call records (OLA_POSEIDON_CALL_WORDS x n_calls column-major: clk, src, len, dst, psdn_row) and the Poseidon table
+// (134 x 2^psdn_log_n; host or device memory) -> the 53 x n Poseidon-chunk table
+inline std::vector<F> generate_poseidon_chunk_trace(const Gpu& g, const std::vector<F>& calls, size_t n_calls, const F* poseidon_table,
+                                                    uint32_t psdn_log_n, uint32_t* log_n_out = nullptr) {
+    if (calls.size() != OLA_POSEIDON_CALL_WORDS * n_calls) throw Error(OLA_E_INVALID_ARG, "shape");
+    uint32_t log_n = 0;
+    check(ola_generate_poseidon_chunk_trace(nullptr, n_calls ? calls.data() : nullptr, n_calls, nullptr, psdn_log_n, nullptr, &log_n));
+    std::vector<F> out((size_t)53 << log_n);
+    check(ola_generate_poseidon_chunk_trace(g.ctx(), n_calls ? calls.data() : nullptr, n_calls, poseidon_table, psdn_log_n, out.data(), &log_n));
+    if (log_n_out) *log_n_out = log_n;
+    return out;
+}
+// the zero-padded listing, the code address and the Poseidon table whose row i hashed words 8 i .. 8 i + 7 -> the 40 x n program-chunk table
+inline std::vector<F> generate_prog_chunk_trace(const Gpu& g, const std::vector<F>& words, const uint64_t code_addr[4], bool result_line,
+                                                const F* poseidon_table, uint32_t psdn_log_n, uint32_t* log_n_out = nullptr) {
+    const uint32_t flags = result_line ? OLA_PROG_CHUNK_RESULT_LINE : 0u;
+    uint32_t log_n = 0;
+    check(ola_generate_prog_chunk_trace(nullptr, nullptr, words.size(), nullptr, flags, nullptr, psdn_log_n, nullptr, &log_n));
+    std::vector<F> out((size_t)40 << log_n);
+    check(ola_generate_prog_chunk_trace(g.ctx(), words.empty() ? nullptr : words.data(), words.size(), code_addr, flags, poseidon_table, psdn_log_n, out.data(), &log_n));
     if (log_n_out) *log_n_out = log_n;
     return out;
 }

@@ -61,6 +61,15 @@ typedef struct OlaTraceSet OlaTraceSet;
  * the state roots before and after the run, which only the device's tree has: ola_tracegen_betas answers ~0 (-1) for it unless
  * OLA_TRACEGEN_EXPLICIT_BETAS is set, and ola_tracegen_program_beta draws it from the roots the GPU call returns. */
 #define OLA_TRACEGEN_HASHES_ONLY 32u
+/* flags: OLA_TRACEGEN_HASHES_ONLY (implied), and no table at all is built: ola_tracegen_table answers every table with its shape and
+ * data = NULL.  The bitwise, tape, Poseidon-chunk and program-chunk tables are the GPU's to make as well (include/ola_gpu.h
+ * ola_generate_bitwise_trace, ola_generate_tape_trace, ola_generate_poseidon_chunk_trace, ola_generate_prog_chunk_trace; the SCCALL table is
+ * the 26 x 8 padding table): ola_tracegen_bitwise_ops, ola_tracegen_tape_cells, ola_tracegen_poseidon_calls and ola_tracegen_listing_words
+ * return what those calls take.  The Poseidon inputs keep coming from ola_tracegen_poseidon_inputs -- the host hashes the listing and the
+ * POSEIDON instructions' blocks anyway in order to execute.  The bitwise table's challenge observes that table's limb columns, which
+ * only the device has then: ola_tracegen_betas answers ~0 (-1) for it, as for the program table's, unless OLA_TRACEGEN_EXPLICIT_BETAS
+ * is set. */
+#define OLA_TRACEGEN_RECORDS_ONLY 64u
 
 /* Executes the program (at most max_steps CPU rows) and builds the 12 tables of ola_stark(range_bits, limb_bits) in
  * `enum Table` order.  range_bits / limb_bits are 16 / 8 in the reference; smaller values give structurally identical
@@ -68,7 +77,7 @@ typedef struct OlaTraceSet OlaTraceSet;
 int32_t ola_tracegen_run(const OlaInstr* program, size_t n_instr, const uint64_t code_addr[4], const uint64_t storage_addr[4],
                          uint32_t range_bits, uint32_t limb_bits, uint64_t bitwise_beta, uint64_t program_beta, uint64_t max_steps,
                          uint32_t flags, OlaTraceSet** out);
-/* Table t: column-major ncols x 2^log_n words, owned by the set (data = NULL for a table OLA_TRACEGEN_STEPS_ONLY, _CELLS_ONLY or _HASHES_ONLY left out). */
+/* Table t: column-major ncols x 2^log_n words, owned by the set (data = NULL for a table OLA_TRACEGEN_STEPS_ONLY, _CELLS_ONLY, _HASHES_ONLY or _RECORDS_ONLY left out). */
 int32_t ola_tracegen_table(const OlaTraceSet* set, uint32_t table, uint32_t* ncols, uint32_t* log_n, const uint64_t** data);
 /* OLA_TRACEGEN_STEPS_ONLY sets only (-1 otherwise): the step records, OLA_CPU_STEP_WORDS x n_steps column-major, and the program
  * table's listing side, 7 x 2^log_n column-major (four code-address words, pc, inst, filter); both owned by the set. */
@@ -87,6 +96,15 @@ int32_t ola_tracegen_cpu_rc_values(const OlaTraceSet* set, uint64_t* n_values, c
  * tree-key rows filled and the 512 rows of every access left zero, their first row in the record's psdn_row. */
 int32_t ola_tracegen_storage_accesses(const OlaTraceSet* set, uint64_t* n_access, const uint64_t** data);
 int32_t ola_tracegen_poseidon_inputs(const OlaTraceSet* set, uint32_t* log_n, const uint64_t** inputs, const uint64_t** filters);
+/* OLA_TRACEGEN_RECORDS_ONLY sets only (-1 otherwise), all owned by the set, column-major in execution order: the bitwise operations,
+ * 5 x n_ops (filter = 1, the opcode's one-hot word, op0, op1, res); the tape cells, OLA_TAPE_CELL_WORDS x n_cells (tape address, the
+ * opcode's one-hot word, value); the POSEIDON calls, OLA_POSEIDON_CALL_WORDS x n_calls (clk, src, len, dst, psdn_row -- the row of the
+ * call's first block in the numbering ola_tracegen_poseidon_inputs uses: the program chunks first, then the calls' blocks); the
+ * listing zero-padded to whole 8-word chunks, with the code address in code_addr[0..3]. */
+int32_t ola_tracegen_bitwise_ops(const OlaTraceSet* set, uint64_t* n_ops, const uint64_t** data);
+int32_t ola_tracegen_tape_cells(const OlaTraceSet* set, uint64_t* n_cells, const uint64_t** data);
+int32_t ola_tracegen_poseidon_calls(const OlaTraceSet* set, uint64_t* n_calls, const uint64_t** data);
+int32_t ola_tracegen_listing_words(const OlaTraceSet* set, uint64_t* n_words, const uint64_t** data, uint64_t code_addr[4]);
 /* The program table's compress challenge from roots[0..3] = the state root before the run and roots[4..7] = after it
  * (generation/prog.rs:23-29; the roots_out of ola_generate_storage_trace).  Host only. */
 int32_t ola_tracegen_program_beta(const uint64_t roots[8], uint64_t* beta);

@@ -225,6 +225,35 @@ fn describe_failures(c: *mut OlaCtx, words: &[u64], tables: &[*const *const u64]
     lines.join("; ")
 }
 
+/// From the executor's records to the proof: the twelve tables are generated in HBM by `ola_prove_from_records` and proven there, no
+/// table crosses the link.  `rec.size` must be `size_of::<OlaExecRecords>()`; its pointers must outlive the call.
+pub fn prove_from_records<F, C, const D: usize>(config: &StarkConfig, rec: &OlaExecRecords, public_values: PublicValues) -> Result<AllProof<F, C, D>>
+where
+    F: RichField + Extendable<D>,
+    C: GenericConfig<D, F = F>,
+{
+    ensure!(D == 2, "the backend proves over the quadratic extension");
+    ensure!(rec.size as usize == std::mem::size_of::<OlaExecRecords>(), "OlaExecRecords.size is not the size of the struct");
+    let words = airset();
+    let out = with_ctx(hasher_of::<F, C, D>()?, config, |c| {
+        let mut out = vec![0u8; 8 << 20];
+        let mut len = 0usize;
+        let rc = unsafe { ola_prove_from_records(c, words.as_ptr(), words.len(), rec as *const OlaExecRecords, out.as_mut_ptr(), out.len(), &mut len) };
+        if rc == OLA_E_INVALID_ARG && len > out.len() {
+            // the proof is larger than the buffer: it was kept, fetch it without proving again
+            out.resize(len, 0);
+            check(unsafe { ola_take_pending_proof(c, out.as_mut_ptr(), out.len(), &mut len) })?;
+        } else {
+            check(rc)?;
+        }
+        out.truncate(len);
+        Ok(out)
+    })?;
+    let mut proof: AllProof<F, C, D> = Buffer::new(out).read_all_proof()?;
+    proof.public_values = public_values; // not part of the wire format (serialization.rs:391)
+    Ok(proof)
+}
+
 pub fn prove_with_traces_hip<F, C, const D: usize>(
     ola_stark: &OlaStark<F, D>,
     config: &StarkConfig,

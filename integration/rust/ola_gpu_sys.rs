@@ -54,6 +54,16 @@ pub const OLA_STORAGE_ACCESS_WORDS: usize = 14;
 pub const OLA_STORAGE_WRITE: u64 = 1;
 pub const OLA_STORAGE_FOR_PROG: u64 = 2;
 pub const OLA_STORAGE_SILENT: u64 = 4;
+/// Words of one tape cell of `ola_generate_tape_trace` (tape address, the opcode's one-hot word, value) and of one POSEIDON call record
+/// of `ola_generate_poseidon_chunk_trace` (clk, src, len, dst, psdn_row); `flags` of `ola_generate_prog_chunk_trace`.
+pub const OLA_TAPE_CELL_WORDS: usize = 3;
+pub const OLA_POSEIDON_CALL_WORDS: usize = 5;
+pub const OLA_PROG_CHUNK_RESULT_LINE: u32 = 1;
+/// `OlaExecRecords::flags`
+pub const OLA_RECORDS_REFERENCE_QUIRKS: u32 = 1;
+pub const OLA_RECORDS_ZERO_FILLER: u32 = 2;
+pub const OLA_RECORDS_RESULT_LINE: u32 = 4;
+pub const OLA_RECORDS_EXPLICIT_BETAS: u32 = 8;
 /// `flags` of `ola_generate_prog_trace_steps`: zero rows beyond the executed ones, as the reference's generator leaves them.
 pub const OLA_TABLEGEN_ZERO_FILLER: u32 = 1;
 /// ola_check_constraints: `OlaConstraintFailure::section`
@@ -69,6 +79,49 @@ pub const OLA_CONSTRAINT_LAST_ROW: u32 = 3;
 #[repr(C)]
 pub struct OlaCtx {
     _p: [u8; 0],
+}
+#[repr(C)]
+pub struct OlaTableSet {
+    _p: [u8; 0],
+}
+/// What the executor recorded (`ola_tables_from_records`, `ola_prove_from_records`): every pointer host or device memory, NULL where
+/// its count is 0; `size` = `size_of::<OlaExecRecords>()`.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct OlaExecRecords {
+    pub size: u32,
+    pub flags: u32,
+    pub cpu_log_n: u32,
+    pub prog_log_n: u32,
+    pub range_bits: u32,
+    pub limb_bits: u32,
+    pub steps: *const u64,
+    pub n_steps: u64,
+    pub prog_listing: *const u64,
+    pub mem_cells: *const u64,
+    pub n_mem_cells: u64,
+    pub cmp_ops: *const u64,
+    pub n_cmp_ops: u64,
+    pub cpu_rc: *const u64,
+    pub n_cpu_rc: u64,
+    pub bitwise_ops: *const u64,
+    pub n_bitwise_ops: u64,
+    pub accesses: *const u64,
+    pub n_access: u64,
+    pub siblings: *const u64,
+    pub psdn_inputs: *const u64,
+    pub psdn_filters: *const u64,
+    pub psdn_stride: u64,
+    pub psdn_rows: u64,
+    pub tape_cells: *const u64,
+    pub n_tape_cells: u64,
+    pub psdn_calls: *const u64,
+    pub n_psdn_calls: u64,
+    pub listing_words: *const u64,
+    pub n_listing_words: u64,
+    pub code_addr: [u64; 4],
+    pub bitwise_beta: u64,
+    pub program_beta: u64,
 }
 #[repr(C)]
 pub struct OlaBatch {
@@ -273,6 +326,16 @@ extern "C" {
         log_n_out: *mut u32, psdn_inputs: *mut u64, psdn_filters: *mut u64, psdn_stride: usize, roots_out: *mut u64) -> i32;
     pub fn ola_generate_poseidon_table(ctx: *mut OlaCtx, inputs: *const u64, filters: *const u64, n_rows: usize, stride: usize,
         out: *mut u64, log_n_out: *mut u32) -> i32;
+    pub fn ola_generate_tape_trace(ctx: *mut OlaCtx, cells: *const u64, n_cells: usize, out: *mut u64, log_n_out: *mut u32) -> i32;
+    pub fn ola_generate_poseidon_chunk_trace(ctx: *mut OlaCtx, calls: *const u64, n_calls: usize, poseidon_table: *const u64,
+        psdn_log_n: u32, out: *mut u64, log_n_out: *mut u32) -> i32;
+    pub fn ola_generate_prog_chunk_trace(ctx: *mut OlaCtx, words: *const u64, n_words: usize, code_addr: *const u64, flags: u32,
+        poseidon_table: *const u64, psdn_log_n: u32, out: *mut u64, log_n_out: *mut u32) -> i32;
+    pub fn ola_tables_from_records(ctx: *mut OlaCtx, rec: *const OlaExecRecords, out: *mut *mut OlaTableSet) -> i32;
+    pub fn ola_tables_get(set: *const OlaTableSet, ptrs: *mut *const u64, log_n: *mut u32, params: *mut u64, compress: *mut u64) -> i32;
+    pub fn ola_tables_free(set: *mut OlaTableSet) -> i32;
+    pub fn ola_prove_from_records(ctx: *mut OlaCtx, airset: *const u64, airset_words: usize, rec: *const OlaExecRecords, out: *mut u8,
+        cap: usize, out_len: *mut usize) -> i32;
     pub fn ola_set_shard(ctx: *mut OlaCtx, rank: u32, world: u32, all_gather: OlaAllGatherFn, user: *mut c_void) -> i32;
     pub fn ola_set_shard_options(ctx: *mut OlaCtx, flags: u32) -> i32;
     pub fn ola_gpu_get_stream(ctx: *mut OlaCtx, stream_out: *mut *mut c_void) -> i32;

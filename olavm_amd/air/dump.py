@@ -156,3 +156,34 @@ def tablegen_storage_columns_header():
     out.append("constexpr uint32_t STORAGE_ACCESS_WORDS = %du, STORAGE_DEPTH = %du;" % (STORAGE_ACCESS_WORDS, STORAGE_DEPTH))
     out.append("}  // namespace olatgs")
     return "\n".join(out) + "\n"
+
+
+TABLEGEN_SMALL_COLUMNS_H = "olavm_amd/csrc/tablegen_small_columns.h"
+TAPE_CELL_WORDS = 3          # include/ola_gpu.h OLA_TAPE_CELL_WORDS: tape address, the opcode's one-hot word, value
+POSEIDON_CALL_WORDS = 5      # include/ola_gpu.h OLA_POSEIDON_CALL_WORDS: clk, src, len, dst, psdn_row
+
+
+def tablegen_small_columns_header():
+    """The checked header olavm_amd/csrc/tablegen_small_columns.h: the column indices of the tape, Poseidon-chunk, program-chunk and SCCALL
+    tables, where the Poseidon table keeps a permutation's inputs and outputs, the two opcode masks and the layout of a tape cell and of
+    a POSEIDON call record, for ola_generate_tape_trace / _poseidon_chunk_trace / _prog_chunk_trace in olavm_amd/csrc/lookup.hip.
+    Committed like its siblings; tests/test_small_tablegen_abi.py compares it with this text.  Regenerate:
+        python -c "from olavm_amd.air import dump; print(dump.tablegen_small_columns_header(), end='')" > olavm_amd/csrc/tablegen_small_columns.h"""
+    from . import ola_tables as T
+    out = ["// generated from olavm_amd/air/ola_tables.py by olavm_amd.air.dump.tablegen_small_columns_header() -- do not edit",
+           "#pragma once", "#include <cstdint>", "namespace olatgx {"]
+    for name in sorted(n for n in dir(T) if n.startswith(("COL_TAPE_", "COL_POSEIDON_CHUNK_", "COL_PROG_CHUNK_", "COL_SCCALL_"))
+                       or n in ("COL_POSEIDON_INPUT_RANGE", "COL_POSEIDON_OUTPUT_RANGE")):
+        v = getattr(T, name)
+        if isinstance(v, range):
+            out.append("constexpr uint32_t %s_START = %du, %s_END = %du;" % (name, v.start, name, v.stop))
+        else:
+            out.append("constexpr uint32_t %s = %du;" % (name, v))
+    out.append("constexpr uint32_t NUM_COL_TAPE = %du, NUM_POSEIDON_CHUNK_COLS = %du, NUM_PROG_CHUNK_COLS = %du, NUM_COL_SCCALL = %du;"
+               % (T.NUM_COL_TAPE, T.NUM_POSEIDON_CHUNK_COLS, T.NUM_PROG_CHUNK_COLS, T.NUM_COL_SCCALL))
+    out.append("constexpr uint32_t NUM_POSEIDON_COLS = %du;" % T.NUM_POSEIDON_COLS)
+    for op in ("TLOAD", "POSEIDON"):
+        out.append("constexpr uint64_t OP_MASK_%s = %dull;" % (op, T.op_mask(op)))
+    out.append("constexpr uint32_t TAPE_CELL_WORDS = %du, POSEIDON_CALL_WORDS = %du;" % (TAPE_CELL_WORDS, POSEIDON_CALL_WORDS))
+    out.append("}  // namespace olatgx")
+    return "\n".join(out) + "\n"

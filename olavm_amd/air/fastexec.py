@@ -17,10 +17,14 @@ class OlaInstr(C.Structure):
 
 EXPORTS = ["ola_tracegen_run", "ola_tracegen_table", "ola_tracegen_cpu_rows", "ola_tracegen_free", "ola_tracegen_last_error", "ola_tracegen_betas",
            "ola_tracegen_cpu_steps", "ola_tracegen_prog_listing", "ola_tracegen_mem_cells", "ola_tracegen_cmp_ops", "ola_tracegen_cpu_rc_values",
-           "ola_tracegen_storage_accesses", "ola_tracegen_poseidon_inputs", "ola_tracegen_program_beta"]
+           "ola_tracegen_storage_accesses", "ola_tracegen_poseidon_inputs", "ola_tracegen_program_beta",
+           "ola_tracegen_bitwise_ops", "ola_tracegen_tape_cells", "ola_tracegen_poseidon_calls", "ola_tracegen_listing_words"]
 OLA_TRACEGEN_PROVE_PROGRAM_HASH, OLA_TRACEGEN_EXPLICIT_BETAS, OLA_TRACEGEN_REFERENCE_QUIRKS, OLA_TRACEGEN_STEPS_ONLY = 1, 2, 4, 8
 OLA_TRACEGEN_CELLS_ONLY = 16
 OLA_TRACEGEN_HASHES_ONLY = 32
+OLA_TRACEGEN_RECORDS_ONLY = 64
+TAPE_CELL_WORDS = 3      # include/ola_gpu.h OLA_TAPE_CELL_WORDS
+POSEIDON_CALL_WORDS = 5  # include/ola_gpu.h OLA_POSEIDON_CALL_WORDS
 MEM_CELL_WORDS = 5       # include/ola_gpu.h OLA_MEM_CELL_WORDS
 STORAGE_ACCESS_WORDS = 14   # include/ola_gpu.h OLA_STORAGE_ACCESS_WORDS
 
@@ -49,6 +53,9 @@ def load_library():
             getattr(L, f).argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64))]
         L.ola_tracegen_storage_accesses.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64))]
         L.ola_tracegen_poseidon_inputs.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint64))]
+        for f in ("ola_tracegen_bitwise_ops", "ola_tracegen_tape_cells", "ola_tracegen_poseidon_calls"):
+            getattr(L, f).argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64))]
+        L.ola_tracegen_listing_words.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]
         L.ola_tracegen_program_beta.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
@@ -74,7 +81,7 @@ def encode(prog):
 
 
 def instance(prog, range_bits=4, limb_bits=2, bitwise_beta=None, program_beta=None, prove_program_hash=False, max_steps=1 << 16, reference_quirks=False,
-             steps_only=False, timings=None, cells_only=False, hashes_only=False):
+             steps_only=False, timings=None, cells_only=False, hashes_only=False, records_only=False):
     """Same contract as miniexec.instance(prog, ...).  -> (traces, params, compress).  Betas left at None are derived by the
     generator's own Fiat-Shamir transcript, as the reference does; explicit values (both or neither) are for tests.
     steps_only: the CPU and the program table are not built -- traces[0] and traces[10] are None -- and a fourth value is returned,
@@ -89,6 +96,11 @@ def instance(prog, range_bits=4, limb_bits=2, bitwise_beta=None, program_beta=No
     accesses' rows left zero, and storage_log_n, poseidon_log_n: what Backend.generate_storage_trace and generate_poseidon_table make the
     two from.  The program table's challenge is then None in params and compress unless given: program_beta(roots) draws it from the
     roots the storage call returns.
+    records_only: hashes_only, and no table at all is built -- every entry of traces is None -- and the fourth value also has bitwise_ops
+    (5 x n: filter, the opcode's one-hot word, op0, op1, res), tape_cells (3 x n: tape address, the opcode's one-hot word, value), psdn_calls
+    (5 x n: clk, src, len, dst, psdn_row), words (the zero-padded listing), code_addr and log_n, the twelve heights: what
+    Backend.generate_bitwise_trace, generate_tape_trace, generate_poseidon_chunk_trace and generate_prog_chunk_trace make the rest from.
+    The bitwise table's challenge is then None as well unless given: backend.bitwise_beta(bitwise_ops, limb_bits) draws it.
     timings: a dict that receives native_s (ola_tracegen_run alone) and copy_s (this binding's copies of the set into numpy arrays)."""
     import time
     assert (bitwise_beta is None) == (program_beta is None), "give both compress challenges or neither"
@@ -98,11 +110,13 @@ def instance(prog, range_bits=4, limb_bits=2, bitwise_beta=None, program_beta=No
     code = (C.c_uint64 * 4)(*prog.code_addr)
     stor = (C.c_uint64 * 4)(*prog.storage_addr)
     handle = C.c_void_p()
+    hashes_only = hashes_only or records_only
     cells_only = cells_only or hashes_only
     steps_only = steps_only or cells_only
     flags = ((OLA_TRACEGEN_PROVE_PROGRAM_HASH if prove_program_hash else 0) | (OLA_TRACEGEN_EXPLICIT_BETAS if explicit else 0) |
              (OLA_TRACEGEN_REFERENCE_QUIRKS if reference_quirks else 0) | (OLA_TRACEGEN_STEPS_ONLY if steps_only else 0) |
-             (OLA_TRACEGEN_CELLS_ONLY if cells_only else 0) | (OLA_TRACEGEN_HASHES_ONLY if hashes_only else 0))
+             (OLA_TRACEGEN_CELLS_ONLY if cells_only else 0) | (OLA_TRACEGEN_HASHES_ONLY if hashes_only else 0) |
+             (OLA_TRACEGEN_RECORDS_ONLY if records_only else 0))
     t0 = time.perf_counter()
     rc = L.ola_tracegen_run(ins, len(prog.ins), code, stor, range_bits, limb_bits, bitwise_beta if explicit else 0, program_beta if explicit else 0,
                             max_steps, flags, C.byref(handle))
@@ -116,7 +130,7 @@ def instance(prog, range_bits=4, limb_bits=2, bitwise_beta=None, program_beta=No
             assert L.ola_tracegen_table(handle, t, C.byref(ncols), C.byref(log_n), C.byref(data)) == 0
             n = 1 << log_n.value
             if not data:
-                assert ((steps_only and t in (T.CPU, T.PROGRAM)) or (cells_only and t in (T.MEMORY, T.CMP, T.RANGECHECK)) or
+                assert records_only or ((steps_only and t in (T.CPU, T.PROGRAM)) or (cells_only and t in (T.MEMORY, T.CMP, T.RANGECHECK)) or
                         (hashes_only and t in (T.POSEIDON, T.STORAGE_ACCESS)))
                 shapes[t] = log_n.value
                 traces.append(None)
@@ -147,12 +161,23 @@ def instance(prog, range_bits=4, limb_bits=2, bitwise_beta=None, program_beta=No
             extra.update(accesses=accesses, psdn_inputs=np.ctypeslib.as_array(data, shape=(12, 1 << log_n.value)).copy(),
                          psdn_filters=np.ctypeslib.as_array(fdata, shape=(4, 1 << log_n.value)).copy(), storage_log_n=shapes[T.STORAGE_ACCESS],
                          poseidon_log_n=shapes[T.POSEIDON])
+        if records_only:
+            addr = (C.c_uint64 * 4)()
+            count, data = C.c_uint64(), C.POINTER(C.c_uint64)()
+            assert L.ola_tracegen_listing_words(handle, C.byref(count), C.byref(data), addr) == 0
+            extra.update(bitwise_ops=words(L.ola_tracegen_bitwise_ops, 5), tape_cells=words(L.ola_tracegen_tape_cells, TAPE_CELL_WORDS),
+                         psdn_calls=words(L.ola_tracegen_poseidon_calls, POSEIDON_CALL_WORDS),
+                         words=np.ctypeslib.as_array(data, shape=(count.value,)).copy(), code_addr=[int(x) for x in addr],
+                         log_n=[shapes[t] for t in range(12)])
         betas = (C.c_uint64 * 2)()
         assert L.ola_tracegen_betas(handle, betas) == 0
         bitwise_beta, program_beta = int(betas[0]), int(betas[1])
         if hashes_only and not explicit:
             assert program_beta == (1 << 64) - 1
             program_beta = None                   # not known before the device has hashed the tree
+        if records_only and not explicit:
+            assert bitwise_beta == (1 << 64) - 1
+            bitwise_beta = None                   # observes the bitwise table's limb columns, which the device makes
     finally:
         L.ola_tracegen_free(handle)
     if timings is not None:

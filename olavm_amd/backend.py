@@ -20,6 +20,64 @@ class OlaGpuError(RuntimeError):
         self.code = code
 
 
+class OlaExecRecords(C.Structure):
+    """include/ola_gpu.h OlaExecRecords: what the executor recorded, every pointer host or device memory"""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("cpu_log_n", C.c_uint32), ("prog_log_n", C.c_uint32), ("range_bits", C.c_uint32),
+                ("limb_bits", C.c_uint32), ("steps", C.c_void_p), ("n_steps", C.c_uint64), ("prog_listing", C.c_void_p), ("mem_cells", C.c_void_p),
+                ("n_mem_cells", C.c_uint64), ("cmp_ops", C.c_void_p), ("n_cmp_ops", C.c_uint64), ("cpu_rc", C.c_void_p), ("n_cpu_rc", C.c_uint64),
+                ("bitwise_ops", C.c_void_p), ("n_bitwise_ops", C.c_uint64), ("accesses", C.c_void_p), ("n_access", C.c_uint64),
+                ("siblings", C.c_void_p), ("psdn_inputs", C.c_void_p), ("psdn_filters", C.c_void_p), ("psdn_stride", C.c_uint64),
+                ("psdn_rows", C.c_uint64), ("tape_cells", C.c_void_p), ("n_tape_cells", C.c_uint64), ("psdn_calls", C.c_void_p),
+                ("n_psdn_calls", C.c_uint64), ("listing_words", C.c_void_p), ("n_listing_words", C.c_uint64), ("code_addr", C.c_uint64 * 4),
+                ("bitwise_beta", C.c_uint64), ("program_beta", C.c_uint64)]
+
+
+OLA_RECORDS_REFERENCE_QUIRKS, OLA_RECORDS_ZERO_FILLER, OLA_RECORDS_RESULT_LINE, OLA_RECORDS_EXPLICIT_BETAS = 1, 2, 4, 8
+TABLE_WIDTHS = (94, 29, 59, 6, 12, 134, 53, 48, 6, 26, 18, 40)      # `enum Table` order
+
+
+class ResidentTable:
+    """One table of a TableSet: device memory of the library's pool, with the few attributes of a GPU tensor that prove_with_traces,
+    check_constraints and check_lookup read."""
+
+    def __init__(self, ptr, ncols, log_n):
+        self.ptr, self.shape = int(ptr), (int(ncols), 1 << int(log_n))
+
+    def data_ptr(self):
+        return self.ptr
+
+    def is_contiguous(self):
+        return True
+
+    def element_size(self):
+        return 8
+
+    def numel(self):
+        return self.shape[0] * self.shape[1]
+
+    def to_host(self):
+        import torch
+        t = torch.as_tensor(_DeviceBytes(self.ptr, 8 * self.numel()), device="cuda")
+        return t.cpu().numpy().view(np.uint64).reshape(self.shape)
+
+
+class TableSet:
+    """ola_tables_from_records' twelve resident tables with their challenges; free() returns them to the context's pool."""
+
+    def __init__(self, backend, handle):
+        self.backend, self.handle = backend, handle
+        ptrs, logs, params, compress = (C.c_void_p * 12)(), (C.c_uint32 * 12)(), (C.c_uint64 * 2)(), (C.c_uint64 * 12)()
+        backend._chk(backend.lib.ola_tables_get(handle, ptrs, logs, params, compress))
+        self.tables = [ResidentTable(ptrs[t], TABLE_WIDTHS[t], logs[t]) for t in range(12)]
+        self.log_n = [int(x) for x in logs]
+        self.params, self.compress = [int(x) for x in params], [int(x) for x in compress]
+
+    def free(self):
+        if self.handle:
+            self.backend._chk(self.backend.lib.ola_tables_free(self.handle))
+            self.handle, self.tables = None, []
+
+
 class OlaGpuConfig(C.Structure):
     _fields_ = [("device", C.c_int32), ("stream", C.c_void_p), ("rate_bits", C.c_uint32), ("cap_height", C.c_uint32),
                 ("proof_of_work_bits", C.c_uint32), ("fri_arity_bits", C.c_uint32), ("fri_final_poly_bits", C.c_uint32),
@@ -173,9 +231,19 @@ def load_library():
     L.ola_generate_storage_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p,
                                              C.c_void_p, C.c_size_t, C.c_void_p]
     L.ola_generate_poseidon_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.ola_generate_tape_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.ola_generate_poseidon_chunk_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.ola_generate_prog_chunk_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                C.POINTER(C.c_uint32)]
+    L.ola_tables_from_records.argtypes = [C.c_void_p, C.POINTER(OlaExecRecords), C.POINTER(C.c_void_p)]
+    L.ola_tables_get.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.ola_tables_free.argtypes = [C.c_void_p]
+    L.ola_prove_from_records.argtypes = [C.c_void_p, U64P, C.c_size_t, C.POINTER(OlaExecRecords), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    for f in ("ola_tables_from_records", "ola_tables_get", "ola_tables_free", "ola_prove_from_records"):
+        getattr(L, f).restype = C.c_int32
     for f in ("ola_generate_rc_trace", "ola_generate_bitwise_trace", "ola_generate_prog_trace", "ola_generate_cpu_trace",
               "ola_generate_prog_trace_steps", "ola_generate_memory_trace", "ola_generate_cmp_trace", "ola_generate_storage_trace",
-              "ola_generate_poseidon_table"):
+              "ola_generate_poseidon_table", "ola_generate_tape_trace", "ola_generate_poseidon_chunk_trace", "ola_generate_prog_chunk_trace"):
         getattr(L, f).restype = C.c_int32
     L.ola_set_shard.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, ALL_GATHER_FN, C.c_void_p]
     L.ola_set_shard_options.argtypes = [C.c_void_p, C.c_uint32]
@@ -213,6 +281,8 @@ EXPORTS = [
     "ola_check_constraints", "ola_check_lookup", "ola_generate_rc_trace", "ola_generate_bitwise_trace", "ola_generate_prog_trace",
     "ola_generate_cpu_trace", "ola_generate_prog_trace_steps", "ola_generate_memory_trace", "ola_generate_cmp_trace",
     "ola_generate_storage_trace", "ola_generate_poseidon_table",
+    "ola_generate_tape_trace", "ola_generate_poseidon_chunk_trace", "ola_generate_prog_chunk_trace",
+    "ola_tables_from_records", "ola_tables_get", "ola_tables_free", "ola_prove_from_records",
     "ola_open", "ola_fri_plan", "ola_fri_commit_begin", "ola_fri_commit_next_layer", "ola_fri_commit_finish", "ola_fri_query", "ola_fri_free",
 ]
 
@@ -248,6 +318,9 @@ OLA_CPU_STEP_WORDS = 66
 OLA_MEM_CELL_WORDS = 5
 OLA_STORAGE_ACCESS_WORDS = 14
 OLA_STORAGE_WRITE, OLA_STORAGE_FOR_PROG, OLA_STORAGE_SILENT = 1, 2, 4
+OLA_TAPE_CELL_WORDS = 3
+OLA_POSEIDON_CALL_WORDS = 5
+OLA_PROG_CHUNK_RESULT_LINE = 1
 
 
 def warmup(device=-1, pinned_ring=True, airset=None):
@@ -905,6 +978,123 @@ class Backend:
         got = C.c_uint32()
         self._chk(self.lib.ola_generate_poseidon_table(self.ctx, pi if stride else None, pf if stride else None, n_rows, stride, po, C.byref(got)))
         return ret
+
+    def _poseidon_table(self, poseidon_table, psdn_log_n):
+        """the resident (or host) Poseidon table of the two chunk generators -> (address, keep-alive, log2 of its height)"""
+        pt, kt, shape = _words(poseidon_table, None if psdn_log_n is None else (134, 1 << psdn_log_n))
+        if shape is None or len(shape) != 2 or shape[0] != 134 or shape[1] & (shape[1] - 1) or shape[1] < 8:
+            raise ValueError("poseidon_table must be 134 x 2^psdn_log_n")
+        return pt, kt, int(shape[1]).bit_length() - 1
+
+    def generate_tape_trace(self, cells, out=None, n_cells=None):
+        """ola_generate_tape_trace: the tape table (6 x n, n = next_pow2(max(n_cells, 8))) from cells in execution order
+        (OLA_TAPE_CELL_WORDS x n_cells column-major: tape address, the opcode's one-hot word, value; None or zero columns for the
+        padding table), sorted by address on the device.  n_cells must be given when cells is a device address."""
+        pc, kc, shape = _words(cells, None if n_cells is None else (OLA_TAPE_CELL_WORDS, n_cells))
+        if shape is not None and (len(shape) != 2 or shape[0] != OLA_TAPE_CELL_WORDS):
+            raise ValueError("cells must be OLA_TAPE_CELL_WORDS x n_cells")
+        n_cells = int(shape[1]) if shape is not None else 0
+        log_n = C.c_uint32()
+        self._chk(self.lib.ola_generate_tape_trace(self.ctx, None, n_cells, None, C.byref(log_n)))
+        po, ret = self._table_out(out, 6, log_n.value)
+        self._chk(self.lib.ola_generate_tape_trace(self.ctx, pc if n_cells else None, n_cells, po, C.byref(log_n)))
+        return ret
+
+    def generate_poseidon_chunk_trace(self, calls, poseidon_table, out=None, n_calls=None, psdn_log_n=None):
+        """ola_generate_poseidon_chunk_trace: the Poseidon-chunk table (53 x n) from POSEIDON call records (OLA_POSEIDON_CALL_WORDS x
+        n_calls column-major: clk, src, len, dst, psdn_row; None or zero columns for the padding table) and the Poseidon table
+        (134 x 2^psdn_log_n) whose rows psdn_row .. psdn_row + len / 8 hashed each call's blocks.  n_calls / psdn_log_n must be given
+        for device addresses."""
+        pc, kc, shape = _words(calls, None if n_calls is None else (OLA_POSEIDON_CALL_WORDS, n_calls))
+        if shape is not None and (len(shape) != 2 or shape[0] != OLA_POSEIDON_CALL_WORDS):
+            raise ValueError("calls must be OLA_POSEIDON_CALL_WORDS x n_calls")
+        n_calls = int(shape[1]) if shape is not None else 0
+        pt, kt, psdn_log_n = self._poseidon_table(poseidon_table, psdn_log_n)
+        log_n = C.c_uint32()
+        self._chk(self.lib.ola_generate_poseidon_chunk_trace(self.ctx, pc if n_calls else None, n_calls, pt, psdn_log_n, None, C.byref(log_n)))
+        po, ret = self._table_out(out, 53, log_n.value)
+        self._chk(self.lib.ola_generate_poseidon_chunk_trace(self.ctx, pc if n_calls else None, n_calls, pt, psdn_log_n, po, C.byref(log_n)))
+        return ret
+
+    def generate_prog_chunk_trace(self, words, code_addr, poseidon_table, result_line=False, out=None, n_words=None, psdn_log_n=None):
+        """ola_generate_prog_chunk_trace: the program-chunk table (40 x n, n = next_pow2(max(n_words / 8, 8))) from the zero-padded
+        listing, the four code-address words and the Poseidon table whose row i hashed listing words 8 i .. 8 i + 7.  n_words /
+        psdn_log_n must be given for device addresses."""
+        pw, kw, shape = _words(words, None if n_words is None else (n_words,))
+        n_words = int(np.prod(shape)) if shape is not None else 0
+        pa, ka, ashape = _words(code_addr, (4,))
+        if ashape is None or int(np.prod(ashape)) != 4:
+            raise ValueError("code_addr must be 4 words")
+        pt, kt, psdn_log_n = self._poseidon_table(poseidon_table, psdn_log_n)
+        flags = OLA_PROG_CHUNK_RESULT_LINE if result_line else 0
+        log_n = C.c_uint32()
+        self._chk(self.lib.ola_generate_prog_chunk_trace(self.ctx, None, n_words, None, flags, None, psdn_log_n, None, C.byref(log_n)))
+        po, ret = self._table_out(out, 40, log_n.value)
+        self._chk(self.lib.ola_generate_prog_chunk_trace(self.ctx, pw if n_words else None, n_words, pa, flags, pt, psdn_log_n, po, C.byref(log_n)))
+        return ret
+
+    def exec_records(self, rec, range_bits=16, limb_bits=8, reference_quirks=False, zero_filler=False, result_line=False, bitwise_beta=None,
+                     program_beta=None, siblings=None):
+        """The OlaExecRecords struct for the records of fastexec.instance(records_only=True) (numpy arrays, GPU tensors, or a mix).
+        -> (struct, keep-alive list)"""
+        assert (bitwise_beta is None) == (program_beta is None), "give both compress challenges or neither"
+        keep = []
+
+        def arr(key, rows):
+            p, k, shape = _words(rec[key])
+            keep.append(k)
+            if rows is not None and (len(shape) != 2 or shape[0] != rows):
+                raise ValueError("%s must be %d x n" % (key, rows))
+            return (p.value if int(np.prod(shape)) else None), (int(shape[-1]) if len(shape) else 0)
+        r = OlaExecRecords()
+        r.size = C.sizeof(OlaExecRecords)
+        r.flags = ((OLA_RECORDS_REFERENCE_QUIRKS if reference_quirks else 0) | (OLA_RECORDS_ZERO_FILLER if zero_filler else 0) |
+                   (OLA_RECORDS_RESULT_LINE if result_line else 0) | (OLA_RECORDS_EXPLICIT_BETAS if bitwise_beta is not None else 0))
+        r.cpu_log_n, r.prog_log_n, r.range_bits, r.limb_bits = rec["cpu_log_n"], rec["prog_log_n"], range_bits, limb_bits
+        r.steps, r.n_steps = arr("steps", OLA_CPU_STEP_WORDS)
+        r.prog_listing, n = arr("listing", 7)
+        if n != 1 << rec["prog_log_n"]:
+            raise ValueError("listing must be 7 x 2^prog_log_n")
+        r.mem_cells, r.n_mem_cells = arr("cells", OLA_MEM_CELL_WORDS)
+        r.cmp_ops, r.n_cmp_ops = arr("cmp_ops", 2)
+        r.cpu_rc, r.n_cpu_rc = arr("cpu_rc", None)
+        r.bitwise_ops, r.n_bitwise_ops = arr("bitwise_ops", 5)
+        r.accesses, r.n_access = arr("accesses", OLA_STORAGE_ACCESS_WORDS)
+        if siblings is not None:
+            p, k, shape = _words(siblings)
+            keep.append(k)
+            r.siblings = p.value
+        r.psdn_inputs, r.psdn_stride = arr("psdn_inputs", 12)
+        r.psdn_filters, n = arr("psdn_filters", 4)
+        if n != r.psdn_stride:
+            raise ValueError("psdn_inputs and psdn_filters differ in stride")
+        r.psdn_rows = rec.get("psdn_rows", r.psdn_stride)
+        r.tape_cells, r.n_tape_cells = arr("tape_cells", OLA_TAPE_CELL_WORDS)
+        r.psdn_calls, r.n_psdn_calls = arr("psdn_calls", OLA_POSEIDON_CALL_WORDS)
+        r.listing_words, r.n_listing_words = arr("words", None)
+        r.code_addr = (C.c_uint64 * 4)(*[int(x) for x in rec["code_addr"]])
+        r.bitwise_beta, r.program_beta = (int(bitwise_beta) % (1 << 64), int(program_beta) % (1 << 64)) if bitwise_beta is not None else (0, 0)
+        return r, keep
+
+    def tables_from_records(self, rec, **kw):
+        """ola_tables_from_records: all twelve tables resident, from the executor's records (exec_records' arguments).  -> TableSet"""
+        r, keep = self.exec_records(rec, **kw)
+        handle = C.c_void_p()
+        self._chk(self.lib.ola_tables_from_records(self.ctx, C.byref(r), C.byref(handle)))
+        return TableSet(self, handle)
+
+    def prove_from_records(self, airset_blob, rec, cap=8 << 20, **kw):
+        """ola_prove_from_records: AllProof bytes from the executor's records; no table crosses the link."""
+        blob = np.ascontiguousarray(airset_blob, dtype=np.uint64)
+        r, keep = self.exec_records(rec, **kw)
+        need = C.c_size_t(0)
+        buf = C.create_string_buffer(cap)
+        rc = self.lib.ola_prove_from_records(self.ctx, _p(blob), blob.size, C.byref(r), buf, cap, C.byref(need))
+        if rc != 0 and need.value > cap:            # the proof is kept in the context: fetch it, do not prove again
+            buf = C.create_string_buffer(need.value)
+            rc = self.lib.ola_take_pending_proof(self.ctx, buf, need.value, C.byref(need))
+        self._chk(rc)
+        return bytes(buf.raw[:need.value])
 
     def trim(self):
         """Return the context's cached device buffers to the driver (ola_gpu_trim)."""

@@ -812,6 +812,23 @@ void poseidon_chunk_table(const std::vector<PsdnCall>& calls, Table& t, std::vec
     }
 }
 
+// OLA_TRACEGEN_RECORDS_ONLY: the POSEIDON calls as include/ola_gpu.h OLA_POSEIDON_CALL_WORDS records (clk, src, len, dst, psdn_row),
+// column-major in execution order, instead of the table; `first_row` is where the calls' blocks start in the Poseidon table (behind the
+// program-chunk rows, back to back in execution order: the numbering prog_chunk_and_poseidon gives `prow`)
+void poseidon_chunk_records(const std::vector<PsdnCall>& calls, size_t first_row, Table& shape, std::vector<u64>& rec,
+                            std::vector<std::vector<u64>>& prow) {
+    const size_t nc = calls.size();
+    rec.assign(5 * nc, 0);
+    size_t rows = 0;
+    for (size_t c = 0; c < nc; c++) {
+        rec[c] = calls[c].clk; rec[nc + c] = calls[c].src; rec[2 * nc + c] = calls[c].len; rec[3 * nc + c] = calls[c].dst;
+        rec[4 * nc + c] = first_row + prow.size();
+        rows += 1 + calls[c].chunks.size();
+        for (const PsdnChunk& ch : calls[c].chunks) prow.push_back(ch.row);
+    }
+    shape.ncols = NUM_POSEIDON_CHUNK_COLS; shape.n = next_pow2(std::max<size_t>(rows, 8));
+}
+
 // generation/storage.rs:7-123: 256 rows per proof, the CPU's accesses in execution order, then the program-hash reads
 void storage_table(const std::vector<std::vector<StorageRow>>& accesses, const std::vector<std::vector<StorageRow>>& prog_reads, Table& t) {
     size_t total = 0;
@@ -1002,6 +1019,9 @@ struct OlaTraceSet {
     std::vector<u64> cells, cmp_ops, cpu_rc;       // ... and these stand for them
     bool hashes_only = false;                      // OLA_TRACEGEN_HASHES_ONLY: so have STORAGE_ACCESS and POSEIDON ...
     std::vector<u64> accesses, psdn[3];            // ... and the access records, the Poseidon inputs and filters (and the accesses' rows) stand for them
+    bool records_only = false;                     // OLA_TRACEGEN_RECORDS_ONLY: no table has data ...
+    std::vector<u64> bw_ops, tape_cells, psdn_calls, words;   // ... and the bitwise operations, tape cells, POSEIDON calls and padded listing stand for the rest
+    uint64_t code_addr[4] = {0, 0, 0, 0};
 };
 
 extern "C" {
@@ -1019,7 +1039,8 @@ int32_t ola_tracegen_run(const OlaInstr* program, size_t n_instr, const uint64_t
         const bool explicit_betas = flags & OLA_TRACEGEN_EXPLICIT_BETAS;
         const bool quirks = flags & OLA_TRACEGEN_REFERENCE_QUIRKS;
         Run R;
-        R.hashes_only = set->hashes_only = flags & OLA_TRACEGEN_HASHES_ONLY;
+        set->records_only = flags & OLA_TRACEGEN_RECORDS_ONLY;
+        R.hashes_only = set->hashes_only = (flags & OLA_TRACEGEN_HASHES_ONLY) || set->records_only;
         StorageTree tree;
         const Hash4 code_key{code_addr[0], code_addr[1], code_addr[2], code_addr[3]};
         if (prove_program_hash) {
@@ -1057,7 +1078,8 @@ int32_t ola_tracegen_run(const OlaInstr* program, size_t n_instr, const uint64_t
             program_table(R, code_addr, program_beta, T[PROGRAM], words);
         }
         std::vector<std::vector<u64>> builtin_rows;
-        poseidon_chunk_table(R.psdn, T[POSEIDON_CHUNK], builtin_rows);
+        if (set->records_only) poseidon_chunk_records(R.psdn, words.size() / 8, T[POSEIDON_CHUNK], set->psdn_calls, builtin_rows);
+        else poseidon_chunk_table(R.psdn, T[POSEIDON_CHUNK], builtin_rows);
         std::vector<std::vector<StorageRow>> prog_reads;
         if (prove_program_hash && R.hashes_only) {
             R.lean_access(code_key, nullptr, 2);                                    // OLA_STORAGE_FOR_PROG
@@ -1095,10 +1117,34 @@ int32_t ola_tracegen_run(const OlaInstr* program, size_t n_instr, const uint64_t
             for (u64 v : mem_cond) rc.push_back({v, {0, 0, 1, 0}});
             rc_table(rc, range_bits, T[RANGECHECK]);
         }
-        set->bitwise_beta = bitwise_table(bitwise_beta, !explicit_betas, limb_bits, R.bitwise, T[BITWISE], quirks);
-        if (!R.hashes_only) storage_table(R.storage, prog_reads, T[STORAGE_ACCESS]);
-        tape_table(R.tape, T[TAPE]);
-        flag_padding(T[SCCALL], NUM_COL_SCCALL, 8, COL_SCCALL_IS_PADDING);
+        if (set->records_only) {
+            // the remaining tables keep their shape; what the device makes them from, column-major in execution order
+            T[PROG_CHUNK].d = std::vector<u64>();                 // its hashes stay in the Poseidon inputs' capacity words
+            set->words = words;
+            for (int k = 0; k < 4; k++) set->code_addr[k] = code_addr[k];
+            const size_t nb = R.bitwise.size(), nt = R.tape.size(), size = (size_t)1 << limb_bits;
+            set->bw_ops.assign(5 * nb, 0);
+            for (size_t r = 0; r < nb; r++) {
+                const u64 x = R.bitwise[r].a, y = R.bitwise[r].b;
+                need(limb_bits >= 16 || (x < ((u64)1 << (4 * limb_bits)) && y < ((u64)1 << (4 * limb_bits))), "bitwise operand does not fit four limbs");
+                set->bw_ops[r] = 1; set->bw_ops[nb + r] = 1ULL << R.bitwise[r].op; set->bw_ops[2 * nb + r] = x; set->bw_ops[3 * nb + r] = y;
+                set->bw_ops[4 * nb + r] = R.bitwise[r].op == OP_AND ? (x & y) : R.bitwise[r].op == OP_OR ? (x | y) : (x ^ y);
+            }
+            T[BITWISE].ncols = COL_NUM_BITWISE; T[BITWISE].n = next_pow2(std::max(std::max(size, 3 * size * size), nb));
+            // the bitwise table's challenge observes the limb columns, which only the device has: the caller's to draw, like the program table's
+            set->bitwise_beta = explicit_betas ? bitwise_beta % P : ~0ull;
+            set->tape_cells.assign(3 * nt, 0);
+            for (size_t i = 0; i < nt; i++) {
+                set->tape_cells[i] = R.tape[i].addr; set->tape_cells[nt + i] = 1ULL << R.tape[i].op; set->tape_cells[2 * nt + i] = R.tape[i].word;
+            }
+            T[TAPE].ncols = NUM_COL_TAPE; T[TAPE].n = next_pow2(std::max<size_t>(nt, 8));
+            T[SCCALL].ncols = NUM_COL_SCCALL; T[SCCALL].n = 8;
+        } else {
+            set->bitwise_beta = bitwise_table(bitwise_beta, !explicit_betas, limb_bits, R.bitwise, T[BITWISE], quirks);
+            if (!R.hashes_only) storage_table(R.storage, prog_reads, T[STORAGE_ACCESS]);
+            tape_table(R.tape, T[TAPE]);
+            flag_padding(T[SCCALL], NUM_COL_SCCALL, 8, COL_SCCALL_IS_PADDING);
+        }
         *out = set.release();
         return 0;
     } catch (const std::exception& e) {
@@ -1162,6 +1208,28 @@ int32_t ola_tracegen_poseidon_inputs(const OlaTraceSet* set, uint32_t* log_n, co
     while (((size_t)1 << l) < set->tables[POSEIDON].n) l++;
     *log_n = l; *inputs = set->psdn[0].data(); *filters = set->psdn[1].data();
     return 0;
+}
+static int32_t records_only_list(const OlaTraceSet* set, std::vector<u64> OlaTraceSet::*member, size_t words, uint64_t* count, const uint64_t** data) {
+    if (!set || !count || !data) { g_err = "invalid argument"; return -1; }
+    if (!set->records_only) { g_err = "the set was not generated with OLA_TRACEGEN_RECORDS_ONLY"; return -1; }
+    const std::vector<u64>& list = set->*member;
+    *count = list.size() / words; *data = list.data();
+    return 0;
+}
+int32_t ola_tracegen_bitwise_ops(const OlaTraceSet* set, uint64_t* n_ops, const uint64_t** data) {
+    return records_only_list(set, &OlaTraceSet::bw_ops, 5, n_ops, data);
+}
+int32_t ola_tracegen_tape_cells(const OlaTraceSet* set, uint64_t* n_cells, const uint64_t** data) {
+    return records_only_list(set, &OlaTraceSet::tape_cells, 3, n_cells, data);
+}
+int32_t ola_tracegen_poseidon_calls(const OlaTraceSet* set, uint64_t* n_calls, const uint64_t** data) {
+    return records_only_list(set, &OlaTraceSet::psdn_calls, 5, n_calls, data);
+}
+int32_t ola_tracegen_listing_words(const OlaTraceSet* set, uint64_t* n_words, const uint64_t** data, uint64_t code_addr[4]) {
+    if (!code_addr) { g_err = "invalid argument"; return -1; }
+    const int32_t rc = records_only_list(set, &OlaTraceSet::words, 1, n_words, data);
+    if (rc == 0) for (int k = 0; k < 4; k++) code_addr[k] = set->code_addr[k];
+    return rc;
 }
 int32_t ola_tracegen_program_beta(const uint64_t roots[8], uint64_t* beta) {
     if (!roots || !beta) { g_err = "invalid argument"; return -1; }

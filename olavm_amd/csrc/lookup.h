@@ -61,4 +61,17 @@ u32 cmp_trace_log_n(u64 n_ops);
 void generate_memory_trace_dev(DeviceCtx* ctx, const u64* cells, size_t n_cells, bool reference_quirks, u64* out, u64* rc_out, u64 counts[2]);
 void generate_cmp_trace_dev(DeviceCtx* ctx, const u64* ops, size_t n_ops, u64* out, u64* abs_diff_out);
 
+// The tape table (6 columns) from cells in execution order, the Poseidon-chunk table (53) from POSEIDON call records and the program-chunk
+// table (40) from the zero-padded listing (ola_generate_tape_trace / _poseidon_chunk_trace / _prog_chunk_trace): all pointers but code_addr
+// are device memory, every table is 2^small_trace_log_n(rows) high with rows = n_cells, the sum of 1 + len / 8 over the calls (the
+// caller's validation pass computed it, and checked every psdn_row + len / 8 against the Poseidon table's height), n_chunks.  psdn is the
+// resident Poseidon table, 134 x 2^psdn_log_n; n_chunks <= 2^psdn_log_n.  The tape table waits for the stream once (the address bits
+// that size the sort) and once more, like the Poseidon-chunk table with calls, before its work space goes back to the pool (Scratch's
+// destructor); the program-chunk table only enqueues.
+u32 small_trace_log_n(u64 rows);
+void generate_tape_trace_dev(DeviceCtx* ctx, const u64* cells, size_t n_cells, u64* out);
+void generate_poseidon_chunk_trace_dev(DeviceCtx* ctx, const u64* calls, size_t n_calls, u64 rows, const u64* psdn, u32 psdn_log_n, u64* out);
+void generate_prog_chunk_trace_dev(DeviceCtx* ctx, const u64* words, size_t n_chunks, const u64 code_addr[4], bool result_line, const u64* psdn,
+                                   u32 psdn_log_n, u64* out);
+
 }  // namespace ola

@@ -32,6 +32,7 @@
 #include "tablegen_columns.h"
 #include "tablegen_cpu_columns.h"
 #include "tablegen_mem_columns.h"
+#include "tablegen_small_columns.h"
 
 namespace ola {
 
@@ -410,6 +411,7 @@ namespace {
 namespace tg = olatg;
 namespace tc = olatgc;
 namespace tm = olatgm;
+namespace tx = olatgx;
 
 __global__ __launch_bounds__(256) void rc_fill_kernel(const u64* __restrict__ vals, const u64* __restrict__ filters, u32 n_rows, u32 range_bits,
                                                       u32 n, u64* __restrict__ out) {
@@ -788,6 +790,142 @@ __global__ __launch_bounds__(256) void cmp_fill_kernel(const u64* __restrict__ o
     if (live && abs_diff_out) abs_diff_out[i] = d;
 }
 
+// ---- the tape, Poseidon-chunk and program-chunk tables (ola_generate_tape_trace / _poseidon_chunk_trace / _prog_chunk_trace;
+// olavm_amd/air/miniexec.py tape_trace, poseidon_chunk_trace, prog_chunk_and_poseidon).  Narrow tables whose hashes are all output words
+// of rows of the resident Poseidon table, so a row is a gather: thread = row, every column stored along rows.
+
+// canonical tape addresses as sort keys, the identity index, and the OR of the keys (the bits the sort has to cover)
+__global__ __launch_bounds__(256) void tape_key_kernel(const u64* __restrict__ cells, u32 n_cells, u64* __restrict__ keys, u32* __restrict__ idx,
+                                                       unsigned long long* __restrict__ stats) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    unsigned long long r = 0;
+    if (i < n_cells) {
+        r = gl_canon(cells[i]);
+        keys[i] = r;
+        idx[i] = i;
+    }
+    for (int off = warpSize / 2; off > 0; off >>= 1) r |= __shfl_xor(r, off);
+    if ((threadIdx.x & (warpSize - 1)) == 0 && r) atomicOr(stats, r);
+}
+
+// idx: the cells in row order (null: they are in it already).  Rows n_cells .. n repeat the last sorted cell as an unfiltered TLOAD;
+// without cells every row is tracegen.tape_padding_trace's.
+__global__ __launch_bounds__(256) void tape_fill_kernel(const u64* __restrict__ cells, const u32* __restrict__ idx, u32 n_cells, u32 n,
+                                                        u64* __restrict__ out) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const bool live = i < n_cells;
+    u64 addr = 0, op = tx::OP_MASK_TLOAD, value = 0;
+    if (n_cells) {
+        const u32 at = live ? i : n_cells - 1;
+        const u32 c = idx ? idx[at] : at;
+        addr = gl_canon(cells[c]);
+        if (live) op = gl_canon(cells[(size_t)n_cells + c]);
+        value = gl_canon(cells[2 * (size_t)n_cells + c]);
+    }
+    out[(size_t)tx::COL_TAPE_TX_IDX * n + i] = 0;
+    out[(size_t)tx::COL_TAPE_IS_INIT_SEG * n + i] = 0;
+    out[(size_t)tx::COL_TAPE_OPCODE * n + i] = op;
+    out[(size_t)tx::COL_TAPE_ADDR * n + i] = addr;
+    out[(size_t)tx::COL_TAPE_VALUE * n + i] = value;
+    out[(size_t)tx::COL_TAPE_FILTER_LOOKED * n + i] = live ? 1 : 0;
+}
+static_assert(tx::NUM_COL_TAPE == 6, "tape_fill_kernel writes six columns");
+
+// a POSEIDON call record, column-major over the calls
+enum : u32 { PCALL_CLK = 0, PCALL_SRC = 1, PCALL_LEN = 2, PCALL_DST = 3, PCALL_PSDN_ROW = 4 };
+
+// rows per call (1 + len / 8) for the exclusive scan; entry n_calls is 0 so that the scan's last word is the total
+__global__ __launch_bounds__(256) void pchunk_count_kernel(const u64* __restrict__ calls, u32 n_calls, u32* __restrict__ counts) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i > n_calls) return;
+    counts[i] = i < n_calls ? 1u + (u32)(gl_canon(calls[(size_t)PCALL_LEN * n_calls + i]) >> 3) : 0u;
+}
+
+// the last c < n with a[c] <= v (a ascending, a[0] = 0)
+__device__ __forceinline__ u32 last_at_or_below(const u32* __restrict__ a, u32 n, u32 v) {
+    u32 lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const u32 mid = lo + (hi - lo) / 2;
+        if (a[mid] <= v) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// at[c]: the header row of call c (the scan), rows = at[n_calls].  The host has checked every psdn_row + len / 8 against n_psdn; the
+// row index is clamped all the same, so that records changed behind the host's back cannot read outside the table.
+__global__ __launch_bounds__(256) void pchunk_fill_kernel(const u64* __restrict__ calls, u32 n_calls, const u32* __restrict__ at, u32 rows,
+                                                          const u64* __restrict__ psdn, u32 n_psdn, u32 n, u64* __restrict__ out) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    u64 v[tx::NUM_POSEIDON_CHUNK_COLS];
+#pragma unroll
+    for (u32 c = 0; c < tx::NUM_POSEIDON_CHUNK_COLS; c++) v[c] = 0;
+    if (i >= rows) {
+        v[tx::COL_POSEIDON_CHUNK_IS_PADDING_LINE] = 1;
+    } else {
+        const u32 c = last_at_or_below(at, n_calls, i), j = i - at[c];
+        const u64 src = gl_canon(calls[(size_t)PCALL_SRC * n_calls + c]), len = gl_canon(calls[(size_t)PCALL_LEN * n_calls + c]);
+        v[tx::COL_POSEIDON_CHUNK_CLK] = gl_canon(calls[(size_t)PCALL_CLK * n_calls + c]);
+        v[tx::COL_POSEIDON_CHUNK_OPCODE] = tx::OP_MASK_POSEIDON;
+        v[tx::COL_POSEIDON_CHUNK_OP1] = len;
+        v[tx::COL_POSEIDON_CHUNK_DST] = gl_canon(calls[(size_t)PCALL_DST * n_calls + c]);
+        if (j == 0) {
+            v[tx::COL_POSEIDON_CHUNK_OP0] = src;
+            v[tx::COL_POSEIDON_CHUNK_FILTER_LOOKED_CPU] = 1;
+        } else {
+            const u64 first = gl_canon(calls[(size_t)PCALL_PSDN_ROW * n_calls + c]) + (j - 1);
+            const size_t pr = first < n_psdn ? (size_t)first : n_psdn - 1;
+            v[tx::COL_POSEIDON_CHUNK_OP0] = gl_add(src, 8ull * (j - 1));
+            v[tx::COL_POSEIDON_CHUNK_ACC_CNT] = 8ull * j;
+#pragma unroll
+            for (u32 k = 0; k < 8; k++) v[tx::COL_POSEIDON_CHUNK_VALUE_RANGE_START + k] = gl_canon(psdn[(size_t)(tx::COL_POSEIDON_INPUT_RANGE_START + k) * n_psdn + pr]);
+#pragma unroll
+            for (u32 k = 0; k < 4; k++) v[tx::COL_POSEIDON_CHUNK_CAP_RANGE_START + k] = gl_canon(psdn[(size_t)(tx::COL_POSEIDON_INPUT_RANGE_START + 8 + k) * n_psdn + pr]);
+#pragma unroll
+            for (u32 k = 0; k < 12; k++) v[tx::COL_POSEIDON_CHUNK_HASH_RANGE_START + k] = gl_canon(psdn[(size_t)(tx::COL_POSEIDON_OUTPUT_RANGE_START + k) * n_psdn + pr]);
+            v[tx::COL_POSEIDON_CHUNK_IS_EXT_LINE] = 1;
+            v[tx::COL_POSEIDON_CHUNK_IS_RESULT_LINE] = 8ull * j == len ? 1 : 0;
+#pragma unroll
+            for (u32 k = 0; k < 8; k++) v[tx::COL_POSEIDON_CHUNK_FILTER_LOOKING_MEM_RANGE_START + k] = 1;
+            v[tx::COL_POSEIDON_CHUNK_FILTER_LOOKING_POSEIDON] = 1;
+        }
+    }
+#pragma unroll
+    for (u32 c = 0; c < tx::NUM_POSEIDON_CHUNK_COLS; c++) out[(size_t)c * n + i] = v[c];
+}
+
+struct CodeAddr { u64 w[4]; };     // canonical, by value
+
+// row i < n_chunks: listing words 8 i .. 8 i + 7 with row i of the Poseidon table, which hashed them
+__global__ __launch_bounds__(256) void prog_chunk_fill_kernel(const u64* __restrict__ words, u32 n_chunks, CodeAddr code_addr, u32 result_line,
+                                                              const u64* __restrict__ psdn, u32 n_psdn, u32 n, u64* __restrict__ out) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    u64 v[tx::NUM_PROG_CHUNK_COLS];
+#pragma unroll
+    for (u32 c = 0; c < tx::NUM_PROG_CHUNK_COLS; c++) v[c] = 0;
+    if (i >= n_chunks) {
+        v[tx::COL_PROG_CHUNK_IS_PADDING_LINE] = 1;
+    } else {
+#pragma unroll
+        for (u32 k = 0; k < 4; k++) v[tx::COL_PROG_CHUNK_CODE_ADDR_RANGE_START + k] = code_addr.w[k];
+        v[tx::COL_PROG_CHUNK_START_PC] = 8ull * i;
+#pragma unroll
+        for (u32 k = 0; k < 8; k++) v[tx::COL_PROG_CHUNK_INST_RANGE_START + k] = gl_canon(words[8 * (size_t)i + k]);
+#pragma unroll
+        for (u32 k = 0; k < 4; k++) v[tx::COL_PROG_CHUNK_CAP_RANGE_START + k] = gl_canon(psdn[(size_t)(tx::COL_POSEIDON_INPUT_RANGE_START + 8 + k) * n_psdn + i]);
+#pragma unroll
+        for (u32 k = 0; k < 12; k++) v[tx::COL_PROG_CHUNK_HASH_RANGE_START + k] = gl_canon(psdn[(size_t)(tx::COL_POSEIDON_OUTPUT_RANGE_START + k) * n_psdn + i]);
+        v[tx::COL_PROG_CHUNK_IS_FIRST_LINE] = i == 0 ? 1 : 0;
+        v[tx::COL_PROG_CHUNK_IS_RESULT_LINE] = (result_line && i == n_chunks - 1) ? 1 : 0;
+#pragma unroll
+        for (u32 k = 0; k < 8; k++) v[tx::COL_PROG_CHUNK_FILTER_LOOKING_PROG_RANGE_START + k] = 1;
+    }
+#pragma unroll
+    for (u32 c = 0; c < tx::NUM_PROG_CHUNK_COLS; c++) out[(size_t)c * n + i] = v[c];
+}
+
 u32 log2_rows(u64 rows) {            // next power of two, at least 2 (the reference's ext_trace_len)
     u32 log_n = 1;
     while (((u64)1 << log_n) < rows) log_n++;
@@ -926,6 +1064,70 @@ void generate_memory_trace_dev(DeviceCtx* ctx, const u64* cells, size_t n_cells_
 void generate_cmp_trace_dev(DeviceCtx* ctx, const u64* ops, size_t n_ops, u64* out, u64* abs_diff_out) {
     const u32 n = 1u << cmp_trace_log_n(n_ops);
     hipLaunchKernelGGL(cmp_fill_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, ops, (u32)n_ops, n, out, abs_diff_out);
+    HIP_CHECK(hipGetLastError());
+}
+
+u32 small_trace_log_n(u64 rows) { return log2_rows(std::max<u64>(rows, 8)); }
+
+// One host wait: the OR of the canonical addresses sizes the sort's bit range (no pass at all when every address is 0).  rocPRIM's radix
+// sort is stable and the index goes in ascending, so cells of one address keep execution order.
+void generate_tape_trace_dev(DeviceCtx* ctx, const u64* cells, size_t n_cells_, u64* out) {
+    const u32 n = 1u << small_trace_log_n(n_cells_), n_cells = (u32)n_cells_;
+    hipStream_t stream = ctx->stream;
+    if (n_cells == 0) {
+        hipLaunchKernelGGL(tape_fill_kernel, dim3(blocks(n)), dim3(256), 0, stream, nullptr, nullptr, 0u, n, out);
+        HIP_CHECK(hipGetLastError());
+        return;
+    }
+    Scratch mem(ctx);
+    u64* keys = mem.alloc<u64>(2 * (size_t)n_cells);
+    u32* idx = mem.alloc<u32>(2 * (size_t)n_cells);
+    unsigned long long* stats = mem.alloc<unsigned long long>(1);
+    HIP_CHECK(hipMemsetAsync(stats, 0, sizeof(unsigned long long), stream));
+    hipLaunchKernelGGL(tape_key_kernel, dim3(blocks(n_cells)), dim3(256), 0, stream, cells, n_cells, keys, idx, stats);
+    HIP_CHECK(hipGetLastError());
+    unsigned long long host_stats = 0;
+    HIP_CHECK(hipMemcpyAsync(&host_stats, stats, sizeof(host_stats), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    const u32 bits = bit_length(host_stats);
+    const u32* order = nullptr;
+    if (bits) {
+        size_t bytes = 0;
+        HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, keys, keys + n_cells, idx, idx + n_cells, n_cells, 0, bits, stream));
+        void* tmp = mem.alloc<unsigned char>(std::max<size_t>(bytes, 8));
+        HIP_CHECK(rocprim::radix_sort_pairs(tmp, bytes, keys, keys + n_cells, idx, idx + n_cells, n_cells, 0, bits, stream));
+        order = idx + n_cells;
+    }
+    hipLaunchKernelGGL(tape_fill_kernel, dim3(blocks(n)), dim3(256), 0, stream, cells, order, n_cells, n, out);
+    HIP_CHECK(hipGetLastError());
+}
+
+// The caller's validation pass read the lengths and gave `rows`: count, exclusive scan, fill; one host wait, before the scan's work
+// space goes back to the pool.
+void generate_poseidon_chunk_trace_dev(DeviceCtx* ctx, const u64* calls, size_t n_calls_, u64 rows, const u64* psdn, u32 psdn_log_n, u64* out) {
+    const u32 n = 1u << small_trace_log_n(rows), n_calls = (u32)n_calls_;
+    hipStream_t stream = ctx->stream;
+    Scratch mem(ctx);
+    u32* at = nullptr;
+    if (n_calls) {
+        u32* counts = mem.alloc<u32>((size_t)n_calls + 1);
+        at = mem.alloc<u32>((size_t)n_calls + 1);
+        hipLaunchKernelGGL(pchunk_count_kernel, dim3(blocks((size_t)n_calls + 1)), dim3(256), 0, stream, calls, n_calls, counts);
+        HIP_CHECK(hipGetLastError());
+        scan_exclusive(mem, stream, counts, at, 0u, (size_t)n_calls + 1, rocprim::plus<u32>());
+    }
+    hipLaunchKernelGGL(pchunk_fill_kernel, dim3(blocks(n)), dim3(256), 0, stream, calls, n_calls, at, (u32)rows, psdn, 1u << psdn_log_n, n, out);
+    HIP_CHECK(hipGetLastError());
+}
+
+// One launch, no host wait.
+void generate_prog_chunk_trace_dev(DeviceCtx* ctx, const u64* words, size_t n_chunks, const u64 code_addr[4], bool result_line, const u64* psdn,
+                                   u32 psdn_log_n, u64* out) {
+    const u32 n = 1u << small_trace_log_n(n_chunks);
+    CodeAddr ca;
+    for (int k = 0; k < 4; k++) ca.w[k] = gl_canon(code_addr[k]);
+    hipLaunchKernelGGL(prog_chunk_fill_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, words, (u32)n_chunks, ca, result_line ? 1u : 0u, psdn,
+                       1u << psdn_log_n, n, out);
     HIP_CHECK(hipGetLastError());
 }
 

@@ -22,6 +22,7 @@
 #include "tablegen_cpu_columns.h"
 #include "tablegen_mem_columns.h"
 #include "tablegen_storage_columns.h"
+#include "tablegen_small_columns.h"
 #include "peer_group.h"
 #include "rccl_carrier.h"
 
@@ -1523,6 +1524,281 @@ int32_t ola_generate_poseidon_table(OlaCtx* ctx, const uint64_t* inputs, const u
     TableOutput t(ctx, mem, out, (size_t)olatgs::NUM_POSEIDON_COLS << log_n);
     generate_poseidon_table_dev(&ctx->dev, d_in, d_f, n_rows, stride, (size_t)1 << log_n, t.dev);
     t.finish();
+    OLA_CATCH
+}
+
+static_assert(OLA_TAPE_CELL_WORDS == olatgx::TAPE_CELL_WORDS && OLA_POSEIDON_CALL_WORDS == olatgx::POSEIDON_CALL_WORDS,
+              "include/ola_gpu.h and tablegen_small_columns.h disagree on the tape cell or the POSEIDON call record");
+int32_t ola_generate_tape_trace(OlaCtx* ctx, const uint64_t* cells, size_t n_cells, uint64_t* out, uint32_t* log_n_out) {
+    OLA_TRY
+    require(log_n_out, "null pointer");
+    require(n_cells < ((size_t)1 << 31), "2^31 cells or more");
+    *log_n_out = small_trace_log_n(n_cells);
+    if (!out) return OLA_OK;       // the sizing call
+    require(cells || n_cells == 0, "null pointer");
+    require_context(ctx);
+    OLA_ON_DEVICE(ctx);
+    DevBuf mem(&ctx->dev);
+    const u64* d_cells = table_input(ctx, mem, cells, (size_t)OLA_TAPE_CELL_WORDS * n_cells);
+    TableOutput t(ctx, mem, out, (size_t)olatgx::NUM_COL_TAPE << *log_n_out);
+    generate_tape_trace_dev(&ctx->dev, d_cells, n_cells, t.dev);
+    t.finish();
+    OLA_CATCH
+}
+
+int32_t ola_generate_poseidon_chunk_trace(OlaCtx* ctx, const uint64_t* calls, size_t n_calls, const uint64_t* poseidon_table,
+                                          uint32_t psdn_log_n, uint64_t* out, uint32_t* log_n_out) {
+    OLA_TRY
+    require(log_n_out && (calls || n_calls == 0), "null pointer");
+    require(n_calls < ((size_t)1 << 26), "2^26 calls or more");
+    require(psdn_log_n >= 3 && psdn_log_n <= 26, "psdn_log_n out of range (3 .. 26)");
+    require(poseidon_table || !out, "null pointer");
+    OLA_ON_DEVICE(ctx);
+    // the validation pass: len and psdn_row of every call, read on the host before any work
+    const size_t n = n_calls;
+    std::vector<u64> len(n), row(n);
+    fetch_words(ctx, len.data(), calls + 2 * n, n);
+    if (poseidon_table) fetch_words(ctx, row.data(), calls + 4 * n, n);
+    u64 rows = 0;
+    for (size_t c = 0; c < n; c++) {
+        const u64 l = gl_canon(len[c]);
+        require(l != 0, "a POSEIDON call of length 0");
+        require(l % 8 == 0, "a POSEIDON call whose length is no multiple of 8");
+        require(l / 8 <= ((u64)1 << 26), "a POSEIDON call of more than 2^26 blocks");
+        if (poseidon_table) {
+            const u64 r = gl_canon(row[c]);
+            require(r <= ((u64)1 << psdn_log_n) && l / 8 <= ((u64)1 << psdn_log_n) - r, "psdn_row + len / 8 is beyond the Poseidon table");
+        }
+        rows += 1 + l / 8;
+        require(rows <= ((u64)1 << 26), "more than 2^26 rows");
+    }
+    *log_n_out = small_trace_log_n(rows);
+    if (!out) return OLA_OK;       // the sizing call
+    require_context(ctx);
+    DevBuf mem(&ctx->dev);
+    const u64* d_calls = table_input(ctx, mem, calls, (size_t)OLA_POSEIDON_CALL_WORDS * n);
+    const u64* d_psdn = table_input(ctx, mem, poseidon_table, (size_t)olatgx::NUM_POSEIDON_COLS << psdn_log_n);
+    TableOutput t(ctx, mem, out, (size_t)olatgx::NUM_POSEIDON_CHUNK_COLS << *log_n_out);
+    generate_poseidon_chunk_trace_dev(&ctx->dev, d_calls, n, rows, d_psdn, psdn_log_n, t.dev);
+    t.finish();
+    OLA_CATCH
+}
+
+int32_t ola_generate_prog_chunk_trace(OlaCtx* ctx, const uint64_t* words, size_t n_words, const uint64_t* code_addr, uint32_t flags,
+                                      const uint64_t* poseidon_table, uint32_t psdn_log_n, uint64_t* out, uint32_t* log_n_out) {
+    OLA_TRY
+    require(log_n_out, "null pointer");
+    require((flags & ~(uint32_t)OLA_PROG_CHUNK_RESULT_LINE) == 0, "unknown flag");
+    require(psdn_log_n >= 3 && psdn_log_n <= 26, "psdn_log_n out of range (3 .. 26)");
+    require(n_words <= ((size_t)1 << 29), "more than 2^29 listing words");
+    require(n_words % 8 == 0, "the listing is not padded to whole 8-word chunks");
+    require(n_words / 8 <= ((size_t)1 << psdn_log_n), "more chunks than the Poseidon table has rows");
+    *log_n_out = small_trace_log_n(n_words / 8);
+    if (!out) return OLA_OK;       // the sizing call
+    require(poseidon_table && code_addr && (words || n_words == 0), "null pointer");
+    require_context(ctx);
+    OLA_ON_DEVICE(ctx);
+    u64 ca[4];
+    fetch_words(ctx, ca, code_addr, 4);
+    DevBuf mem(&ctx->dev);
+    const u64* d_words = table_input(ctx, mem, words, n_words);
+    const u64* d_psdn = table_input(ctx, mem, poseidon_table, (size_t)olatgx::NUM_POSEIDON_COLS << psdn_log_n);
+    TableOutput t(ctx, mem, out, (size_t)olatgx::NUM_PROG_CHUNK_COLS << *log_n_out);
+    generate_prog_chunk_trace_dev(&ctx->dev, d_words, n_words / 8, ca, (flags & OLA_PROG_CHUNK_RESULT_LINE) != 0, d_psdn, psdn_log_n, t.dev);
+    t.finish();
+    OLA_CATCH
+}
+
+// ---- from the executor's records to the twelve tables (include/ola_gpu.h, the last block of the table generators)
+struct OlaTableSet {
+    OlaCtx* ctx = nullptr;
+    uint64_t* table[12] = {};
+    uint32_t log_n[12] = {};
+    uint64_t params[2] = {0, 0};
+    std::vector<void*> scratch;          // the Poseidon inputs' copies and the range-check value buffer: freed before the set is handed out
+    uint64_t* take(size_t words) { return (uint64_t*)ctx->dev.alloc((words ? words : 1) * 8); }
+    void drop_scratch() { for (void* p : scratch) ctx->dev.free(p); scratch.clear(); }
+    ~OlaTableSet() {
+        if (!ctx) return;
+        DeviceGuard guard(ctx);
+        drop_scratch();
+        for (uint64_t* t : table) if (t) ctx->dev.free(t);
+    }
+};
+enum { TBL_CPU, TBL_MEMORY, TBL_BITWISE, TBL_CMP, TBL_RANGECHECK, TBL_POSEIDON, TBL_POSEIDON_CHUNK, TBL_STORAGE, TBL_TAPE, TBL_SCCALL, TBL_PROGRAM,
+       TBL_PROG_CHUNK };
+
+// a generator's answer: its code and message behind the name of the step
+static void records_step(int32_t rc, const char* step) {
+    if (rc != OLA_OK) throw OlaError(rc, std::string(step) + ": " + g_last_error);
+}
+// generation/builtin.rs:120-131 as backend.bitwise_beta restates it: a fresh Poseidon challenger observes the twelve limb columns (op0,
+// op1, res limbs 0..3) at the table's full height and draws one challenge
+static u64 draw_bitwise_beta(OlaCtx* ctx, const uint64_t* ops, size_t n_ops, uint32_t limb_bits, uint32_t log_n, bool quirks) {
+    std::vector<u64> host(5 * n_ops);
+    fetch_words(ctx, host.data(), ops, 5 * n_ops);
+    const size_t n = (size_t)1 << log_n;
+    const u64 mask = ((u64)1 << limb_bits) - 1;
+    OlaChallenger ch;
+    challenger_init(ch, OLA_HASH_POSEIDON);
+    std::vector<u64> col(n, 0);
+    for (size_t k = 2; k < 5; k++)
+        for (uint32_t i = 0; i < 4; i++) {
+            for (size_t r = 0; r < n_ops; r++) col[r] = (quirks && i == 3) ? 0 : (gl_canon(host[k * n_ops + r]) >> (limb_bits * i)) & mask;
+            challenger_observe(ch, col.data(), n);
+        }
+    return challenger_get(ch);
+}
+
+static void tables_from_records(OlaCtx* ctx, const OlaExecRecords* r, OlaTableSet& s) {
+    s.ctx = ctx;
+    hipStream_t st = ctx->dev.stream;
+    const bool quirks = r->flags & OLA_RECORDS_REFERENCE_QUIRKS, explicit_betas = r->flags & OLA_RECORDS_EXPLICIT_BETAS;
+    const uint32_t tq = quirks ? OLA_TABLEGEN_REFERENCE_QUIRKS : 0u;
+    uint32_t* L = s.log_n;
+    // the storage tree hashed, with the accesses' rows of the Poseidon inputs; the inputs are copies, the caller's are not written
+    const size_t stride = r->psdn_stride;
+    uint64_t* pin = s.take(12 * stride); s.scratch.push_back(pin);
+    uint64_t* pf = s.take(4 * stride); s.scratch.push_back(pf);
+    if (stride) {
+        HIP_CHECK(hipMemcpyAsync(pin, r->psdn_inputs, 12 * stride * 8, hipMemcpyDefault, st));
+        HIP_CHECK(hipMemcpyAsync(pf, r->psdn_filters, 4 * stride * 8, hipMemcpyDefault, st));
+        HIP_CHECK(hipStreamSynchronize(st));     // the caller's host buffers are read before the call goes on
+    }
+    uint64_t roots[8];
+    records_step(ola_generate_storage_trace(ctx, r->accesses, r->n_access, r->siblings, nullptr, &L[TBL_STORAGE], stride ? pin : nullptr,
+                                            stride ? pf : nullptr, stride, nullptr), "storage-access table");
+    s.table[TBL_STORAGE] = s.take((size_t)olatgs::NUM_COL_ST << L[TBL_STORAGE]);
+    records_step(ola_generate_storage_trace(ctx, r->accesses, r->n_access, r->siblings, s.table[TBL_STORAGE], &L[TBL_STORAGE], stride ? pin : nullptr,
+                                            stride ? pf : nullptr, stride, roots), "storage-access table");
+    records_step(ola_generate_poseidon_table(ctx, nullptr, nullptr, r->psdn_rows, stride, nullptr, &L[TBL_POSEIDON]), "Poseidon table");
+    s.table[TBL_POSEIDON] = s.take((size_t)olatgs::NUM_POSEIDON_COLS << L[TBL_POSEIDON]);
+    records_step(ola_generate_poseidon_table(ctx, pin, pf, r->psdn_rows, stride, s.table[TBL_POSEIDON], &L[TBL_POSEIDON]), "Poseidon table");
+    // the two chunk tables gather from it
+    records_step(ola_generate_poseidon_chunk_trace(ctx, r->psdn_calls, r->n_psdn_calls, s.table[TBL_POSEIDON], L[TBL_POSEIDON], nullptr,
+                                                   &L[TBL_POSEIDON_CHUNK]), "Poseidon-chunk table");
+    s.table[TBL_POSEIDON_CHUNK] = s.take((size_t)olatgx::NUM_POSEIDON_CHUNK_COLS << L[TBL_POSEIDON_CHUNK]);
+    records_step(ola_generate_poseidon_chunk_trace(ctx, r->psdn_calls, r->n_psdn_calls, s.table[TBL_POSEIDON], L[TBL_POSEIDON],
+                                                   s.table[TBL_POSEIDON_CHUNK], &L[TBL_POSEIDON_CHUNK]), "Poseidon-chunk table");
+    const uint32_t cflags = (r->flags & OLA_RECORDS_RESULT_LINE) ? OLA_PROG_CHUNK_RESULT_LINE : 0u;
+    records_step(ola_generate_prog_chunk_trace(ctx, nullptr, r->n_listing_words, nullptr, cflags, nullptr, L[TBL_POSEIDON], nullptr, &L[TBL_PROG_CHUNK]),
+                 "program-chunk table");
+    s.table[TBL_PROG_CHUNK] = s.take((size_t)olatgx::NUM_PROG_CHUNK_COLS << L[TBL_PROG_CHUNK]);
+    records_step(ola_generate_prog_chunk_trace(ctx, r->listing_words, r->n_listing_words, r->code_addr, cflags, s.table[TBL_POSEIDON], L[TBL_POSEIDON],
+                                               s.table[TBL_PROG_CHUNK], &L[TBL_PROG_CHUNK]), "program-chunk table");
+    // the comparison and memory tables, their value lists behind the CPU's in one buffer
+    const size_t n_cpu = r->n_cpu_rc, n_cmp = r->n_cmp_ops, n_cells = r->n_mem_cells;
+    uint64_t* vals = s.take(n_cpu + n_cmp + 2 * n_cells); s.scratch.push_back(vals);
+    if (n_cpu) { HIP_CHECK(hipMemcpyAsync(vals, r->cpu_rc, n_cpu * 8, hipMemcpyDefault, st)); HIP_CHECK(hipStreamSynchronize(st)); }
+    records_step(ola_generate_cmp_trace(ctx, nullptr, n_cmp, nullptr, &L[TBL_CMP], nullptr), "comparison table");
+    s.table[TBL_CMP] = s.take((size_t)olatgm::COL_NUM_CMP << L[TBL_CMP]);
+    records_step(ola_generate_cmp_trace(ctx, r->cmp_ops, n_cmp, s.table[TBL_CMP], &L[TBL_CMP], n_cmp ? vals + n_cpu : nullptr), "comparison table");
+    uint64_t counts[2] = {0, 0};
+    records_step(ola_generate_memory_trace(ctx, nullptr, n_cells, tq, nullptr, &L[TBL_MEMORY], nullptr, counts), "memory table");
+    s.table[TBL_MEMORY] = s.take((size_t)olatgm::NUM_MEM_COLS << L[TBL_MEMORY]);
+    records_step(ola_generate_memory_trace(ctx, r->mem_cells, n_cells, tq, s.table[TBL_MEMORY], &L[TBL_MEMORY], n_cells ? vals + n_cpu + n_cmp : nullptr, counts),
+                 "memory table");
+    // the range-check table from that buffer and four filter columns filled from the segment lengths
+    const size_t n_rows = n_cpu + n_cmp + counts[0] + counts[1];
+    records_step(ola_generate_rc_trace(ctx, nullptr, nullptr, n_rows, r->range_bits, nullptr, &L[TBL_RANGECHECK]), "range-check table");
+    uint64_t* filters = s.take(4 * n_rows); s.scratch.push_back(filters);
+    rc_filters_dev(&ctx->dev, n_cpu, n_cmp, counts[0], n_rows, (u64*)filters);
+    s.table[TBL_RANGECHECK] = s.take((size_t)olatg::COL_NUM_RC << L[TBL_RANGECHECK]);
+    records_step(ola_generate_rc_trace(ctx, n_rows ? vals : nullptr, n_rows ? filters : nullptr, n_rows, r->range_bits, s.table[TBL_RANGECHECK],
+                                       &L[TBL_RANGECHECK]), "range-check table");
+    // CPU, tape, SCCALL, bitwise
+    require(r->cpu_log_n >= 1 && r->cpu_log_n <= 26, "CPU table: log_n out of range (1 .. 26)");
+    L[TBL_CPU] = r->cpu_log_n;
+    require(r->n_steps <= ((uint64_t)1 << r->cpu_log_n), "CPU table: more steps than 2^log_n rows");
+    s.table[TBL_CPU] = s.take((size_t)olatgc::NUM_CPU_COLS << L[TBL_CPU]);
+    records_step(ola_generate_cpu_trace(ctx, r->steps, r->n_steps, L[TBL_CPU], s.table[TBL_CPU]), "CPU table");
+    records_step(ola_generate_tape_trace(ctx, nullptr, r->n_tape_cells, nullptr, &L[TBL_TAPE]), "tape table");
+    s.table[TBL_TAPE] = s.take((size_t)olatgx::NUM_COL_TAPE << L[TBL_TAPE]);
+    records_step(ola_generate_tape_trace(ctx, r->tape_cells, r->n_tape_cells, s.table[TBL_TAPE], &L[TBL_TAPE]), "tape table");
+    L[TBL_SCCALL] = 3;
+    s.table[TBL_SCCALL] = s.take((size_t)olatgx::NUM_COL_SCCALL << 3);
+    sccall_padding_dev(&ctx->dev, 8, (u64*)s.table[TBL_SCCALL]);
+    records_step(ola_generate_bitwise_trace(ctx, nullptr, r->n_bitwise_ops, r->limb_bits, 0, tq, nullptr, &L[TBL_BITWISE]), "bitwise table");
+    s.params[0] = explicit_betas ? gl_canon(r->bitwise_beta) : draw_bitwise_beta(ctx, r->bitwise_ops, r->n_bitwise_ops, r->limb_bits, L[TBL_BITWISE], quirks);
+    s.table[TBL_BITWISE] = s.take((size_t)olatg::COL_NUM_BITWISE << L[TBL_BITWISE]);
+    records_step(ola_generate_bitwise_trace(ctx, r->bitwise_ops, r->n_bitwise_ops, r->limb_bits, s.params[0], tq, s.table[TBL_BITWISE], &L[TBL_BITWISE]),
+                 "bitwise table");
+    // the program table, its challenge from the two state roots (generation/prog.rs:23-29)
+    if (explicit_betas) {
+        s.params[1] = gl_canon(r->program_beta);
+    } else {
+        OlaChallenger ch;
+        challenger_init(ch, OLA_HASH_POSEIDON);
+        for (int i = 0; i < 4; i++) { const u64 pair[2] = {gl_canon(roots[i]), gl_canon(roots[4 + i])}; challenger_observe(ch, pair, 2); }
+        s.params[1] = challenger_get(ch);
+    }
+    require(r->prog_log_n >= 1 && r->prog_log_n <= 26, "program table: log_n out of range (1 .. 26)");
+    L[TBL_PROGRAM] = r->prog_log_n;
+    s.table[TBL_PROGRAM] = s.take((size_t)olatg::NUM_PROG_COLS << L[TBL_PROGRAM]);
+    uint64_t exec_rows = 0;
+    records_step(ola_generate_prog_trace_steps(ctx, r->steps, r->n_steps, r->prog_listing, L[TBL_PROGRAM], s.params[1],
+                                               (r->flags & OLA_RECORDS_ZERO_FILLER) ? OLA_TABLEGEN_ZERO_FILLER : 0u, s.table[TBL_PROGRAM], &exec_rows),
+                 "program table");
+    HIP_CHECK(hipStreamSynchronize(st));          // the two fills
+    s.drop_scratch();
+}
+
+static void require_records(OlaCtx* ctx, const OlaExecRecords* rec) {
+    require(rec != nullptr, "null pointer");
+    require(rec->size >= sizeof(OlaExecRecords), "OlaExecRecords.size is smaller than this library's struct");
+    require((rec->flags & ~(uint32_t)(OLA_RECORDS_REFERENCE_QUIRKS | OLA_RECORDS_ZERO_FILLER | OLA_RECORDS_RESULT_LINE | OLA_RECORDS_EXPLICIT_BETAS)) == 0,
+            "unknown flag");
+    require(rec->psdn_stride <= ((uint64_t)1 << 26) && rec->psdn_rows <= rec->psdn_stride, "psdn_rows / psdn_stride out of range");
+    require((rec->psdn_inputs && rec->psdn_filters) || rec->psdn_stride == 0, "null pointer");
+    require(rec->n_cpu_rc < ((uint64_t)1 << 31) && rec->n_bitwise_ops <= ((uint64_t)1 << 26), "too many range-check values or bitwise operations");
+    require((rec->cpu_rc || !rec->n_cpu_rc) && (rec->bitwise_ops || !rec->n_bitwise_ops), "null pointer");
+    require_context(ctx);
+}
+
+int32_t ola_tables_from_records(OlaCtx* ctx, const OlaExecRecords* rec, OlaTableSet** out) {
+    OLA_TRY
+    require(out != nullptr, "null pointer");
+    *out = nullptr;
+    require_records(ctx, rec);
+    OLA_ON_DEVICE(ctx);
+    std::unique_ptr<OlaTableSet> set(new OlaTableSet());
+    tables_from_records(ctx, rec, *set);
+    *out = set.release();
+    OLA_CATCH
+}
+
+int32_t ola_tables_get(const OlaTableSet* set, const uint64_t* ptrs[12], uint32_t log_n[12], uint64_t params[2], uint64_t compress[12]) {
+    OLA_TRY
+    require(set != nullptr, "null pointer");
+    for (int t = 0; t < 12; t++) {
+        if (ptrs) ptrs[t] = set->table[t];
+        if (log_n) log_n[t] = set->log_n[t];
+        if (compress) compress[t] = t == TBL_BITWISE ? set->params[0] : t == TBL_PROGRAM ? set->params[1] : 0;
+    }
+    if (params) { params[0] = set->params[0]; params[1] = set->params[1]; }
+    OLA_CATCH
+}
+
+int32_t ola_tables_free(OlaTableSet* set) {
+    OLA_TRY
+    delete set;
+    OLA_CATCH
+}
+
+int32_t ola_prove_from_records(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, const OlaExecRecords* rec, uint8_t* out, size_t cap,
+                               size_t* out_len) {
+    OLA_TRY
+    require(airset && out_len, "null pointer");
+    require_records(ctx, rec);
+    OLA_ON_DEVICE(ctx);
+    require(airset_widths((const u64*)airset, airset_words).size() == 12, "the AIR set does not have the twelve tables of the records");
+    std::unique_ptr<OlaTableSet> set(new OlaTableSet());
+    tables_from_records(ctx, rec, *set);
+    const uint64_t* ptrs[12];
+    uint64_t compress[12];
+    for (int t = 0; t < 12; t++) { ptrs[t] = set->table[t]; compress[t] = t == TBL_BITWISE ? set->params[0] : t == TBL_PROGRAM ? set->params[1] : 0; }
+    const int32_t rc = ola_prove_with_traces(ctx, airset, airset_words, ptrs, set->log_n, set->params, compress, out, cap, out_len);
+    if (rc != OLA_OK) throw OlaError(rc, g_last_error);
     OLA_CATCH
 }
 

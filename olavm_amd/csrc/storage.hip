@@ -244,4 +244,27 @@ void generate_poseidon_table_dev(DeviceCtx* ctx, const u64* inputs, const u64* f
     hipLaunchKernelGGL(poseidon_trace_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, ctx->stream, inputs, filters, n_rows, stride, n_out, out);
 }
 
+// ---- the small fills of ola_tables_from_records
+// the four filter columns of the range-check table's input (cpu, memory sort, memory region, cmp; 4 x n_rows column-major) from the four
+// segment lengths: the values lie as CPU, comparison, memory sort, memory region
+__global__ __launch_bounds__(256) void rc_filters_kernel(u32 n_cpu, u32 n_cmp, u32 n_sort, u32 n_rows, u64* __restrict__ filters) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows) return;
+    const u32 seg = i < n_cpu ? 0u : i < n_cpu + n_cmp ? 3u : i < n_cpu + n_cmp + n_sort ? 1u : 2u;
+#pragma unroll
+    for (u32 k = 0; k < 4; k++) filters[(size_t)k * n_rows + i] = k == seg ? 1 : 0;
+}
+// the SCCALL table of a run without cross-contract calls: IS_PADDING = 1, the rest 0
+__global__ __launch_bounds__(256) void sccall_padding_kernel(u32 n, u64* __restrict__ out) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= olatgx::NUM_COL_SCCALL * n) return;
+    out[i] = i / n == olatgx::COL_SCCALL_IS_PADDING ? 1 : 0;
+}
+void rc_filters_dev(DeviceCtx* ctx, size_t n_cpu, size_t n_cmp, size_t n_sort, size_t n_rows, u64* filters) {
+    if (n_rows) hipLaunchKernelGGL(rc_filters_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, ctx->stream, (u32)n_cpu, (u32)n_cmp, (u32)n_sort, (u32)n_rows, filters);
+}
+void sccall_padding_dev(DeviceCtx* ctx, u32 n, u64* out) {
+    hipLaunchKernelGGL(sccall_padding_kernel, dim3((olatgx::NUM_COL_SCCALL * n + 255) / 256), dim3(256), 0, ctx->stream, n, out);
+}
+
 }  // namespace ola

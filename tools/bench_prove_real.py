@@ -7,7 +7,7 @@ count = 70000 gives 980 k executed CPU rows (2^20), 280 k memory cells, a 2^21-r
 immediate word) and 280 k range-checked sort values.  The proof is checked with the oracle's verifier; with OLA_TIMING=1 the
 library prints its per-phase times (named after the reference's `timed!` scopes) to stderr.
 
-    python tools/bench_prove_real.py [count] [reps] [--json out.json] [--phases] [--oracle] [--python] [--storage-slots N] [--hasher blake3] [--steps | --cells | --hashes] [--shape readme]
+    python tools/bench_prove_real.py [count] [reps] [--json out.json] [--phases] [--oracle] [--python] [--storage-slots N] [--hasher blake3] [--steps | --cells | --hashes | --records] [--shape readme]
 
 --steps compares the two ways from an execution to proof bytes, taken in alternation `reps` times in this process: the table path
 (the native generator fills all twelve tables, they are uploaded and proven) and the step path (the generator runs with
@@ -21,7 +21,10 @@ leave there.  --hashes adds a fourth way, the hashes path: the generator runs wi
 state tree and records no Poseidon row for it -- and on top of the cell path's five tables ola_generate_storage_trace hashes the tree on the
 device, writes the storage-access table and fills the accesses' rows of the Poseidon table's inputs, ola_generate_poseidon_table makes
 the Poseidon table from them, and the program table's challenge is drawn from the two roots the storage call returns; usable with
---storage-slots.  Identical proof bytes on every path are asserted in every round.  --shape readme runs the README's Fibonacci shape
+--storage-slots.  --records takes three ways in alternation: the table path, the hashes path and the records path -- the generator runs
+with OLA_TRACEGEN_RECORDS_ONLY, builds no table, and one call, ola_prove_from_records, makes all twelve tables in HBM and proves them (so
+its device_table_generation_s is part of prove_s); every path also reports link_bytes, the bytes that crossed the link: the tables'
+(ola_gpu_upload_stats) plus the records handed to the device.  Identical proof bytes on every path are asserted in every round.  --shape readme runs the README's Fibonacci shape
 (miniexec.fibonacci_loop(47, 3000): 864 002 CPU rows, every other table small) instead of the memory program.
 """
 import json
@@ -54,10 +57,11 @@ def main():
         prog, kw = M.fibonacci_loop(47, 3000), {}
     else:
         prog, kw = M.memory_program(count), {}
-    if "--steps" in sys.argv or "--cells" in sys.argv or "--hashes" in sys.argv:
-        return steps_against_tables(prog, kw, blob, reps, hasher, out, "--cells" in sys.argv or "--hashes" in sys.argv,
+    if "--steps" in sys.argv or "--cells" in sys.argv or "--hashes" in sys.argv or "--records" in sys.argv:
+        return steps_against_tables(prog, kw, blob, reps, hasher, out, "--cells" in sys.argv or "--hashes" in sys.argv or "--records" in sys.argv,
                                     "storage_heavy_program(%d, %d)" % (slots, count) if slots else
-                                    "fibonacci_loop(47, 3000)" if shape == "readme" else "memory_program(%d)" % count, "--hashes" in sys.argv)
+                                    "fibonacci_loop(47, 3000)" if shape == "readme" else "memory_program(%d)" % count, "--hashes" in sys.argv or "--records" in sys.argv,
+                                    "--records" in sys.argv)
     traces, params, compress = gen.instance(prog, range_bits=16, limb_bits=8, max_steps=1 << 24, **kw)
     gen_s = time.time() - t0
     heights = [int(t.shape[1]).bit_length() - 1 for t in traces]
@@ -102,18 +106,27 @@ def main():
         raise SystemExit(1)
 
 
-def steps_against_tables(prog, kw, blob, reps, hasher, out, cells, workload, hashes=False):
+def steps_against_tables(prog, kw, blob, reps, hasher, out, cells, workload, hashes=False, records=False):
     import numpy as np
     import torch
     from olavm_amd.air import fastexec, ola_tables as T
     from olavm_amd.backend import Backend
     be = Backend(device=0, hasher=hasher)
-    runs = {"table_path": [], "step_path": []}
-    if cells:
+    runs = {"table_path": []}
+    if not records:                    # --records: the table, hashes and records path alone
+        runs["step_path"] = []
+    if cells and not records:
         runs["cell_path"] = []
     if hashes:
         runs["hashes_path"] = []
+    if records:
+        runs["records_path"] = []
     proofs = {}
+    nbytes = lambda rec, keys: int(sum(np.asarray(rec[k]).nbytes for k in keys))
+    STEP_KEYS = ("steps", "listing")
+    CELL_KEYS = STEP_KEYS + ("cells", "cmp_ops", "cpu_rc")
+    HASH_KEYS = CELL_KEYS + ("accesses", "psdn_inputs", "psdn_filters")
+    RECORD_KEYS = HASH_KEYS + ("bitwise_ops", "tape_cells", "psdn_calls", "words")
 
     def five_tables(rec, beta):
         """the CPU, program, comparison, memory and range-check tables in HBM from the records of a cells-only (or hashes-only) run"""
@@ -145,26 +158,28 @@ def steps_against_tables(prog, kw, blob, reps, hasher, out, cells, workload, has
         proofs["table_path"] = bytes(be.prove_with_traces(blob, traces, params, compress))
         t2 = time.perf_counter()
         a = {"native_trace_generation_s": tm["native_s"], "binding_copies_s": tm["copy_s"], "device_table_generation_s": 0.0, "prove_s": t2 - t1,
-             "total_s": t2 - t0, "total_without_binding_copies_s": t2 - t0 - tm["copy_s"]}
+             "total_s": t2 - t0, "total_without_binding_copies_s": t2 - t0 - tm["copy_s"], "link_bytes": be.upload_stats()["link_bytes"]}
         del traces
-        t0 = time.perf_counter()
-        lean, params, compress, rec = fastexec.instance(prog, range_bits=16, limb_bits=8, max_steps=1 << 24, steps_only=True, timings=tm, **kw)
-        t1 = time.perf_counter()
-        d_cpu = torch.empty((T.NUM_CPU_COLS, 1 << rec["cpu_log_n"]), dtype=torch.int64, device="cuda")
-        d_pg = torch.empty((T.NUM_PROG_COLS, 1 << rec["prog_log_n"]), dtype=torch.int64, device="cuda")
-        d_steps = torch.from_numpy(rec["steps"].view(np.int64)).cuda()
-        torch.cuda.synchronize()                                 # complete before the library's stream reads and writes them
-        be.generate_cpu_trace(d_steps, rec["cpu_log_n"], out=d_cpu)
-        be.generate_prog_trace_steps(d_steps, rec["listing"], params[1], out=d_pg)
-        t2 = time.perf_counter()
-        lean[T.CPU], lean[T.PROGRAM] = d_cpu, d_pg
-        proofs["step_path"] = bytes(be.prove_with_traces(blob, lean, params, compress))
-        t3 = time.perf_counter()
-        b = {"native_trace_generation_s": tm["native_s"], "binding_copies_s": tm["copy_s"], "device_table_generation_s": t2 - t1, "prove_s": t3 - t2,
-             "total_s": t3 - t0, "total_without_binding_copies_s": t3 - t0 - tm["copy_s"]}
-        del lean, d_cpu, d_pg, d_steps
-        assert proofs["step_path"] == proofs["table_path"], "the two paths give different proof bytes"
-        if cells:
+        if not records:
+            t0 = time.perf_counter()
+            lean, params, compress, rec = fastexec.instance(prog, range_bits=16, limb_bits=8, max_steps=1 << 24, steps_only=True, timings=tm, **kw)
+            t1 = time.perf_counter()
+            d_cpu = torch.empty((T.NUM_CPU_COLS, 1 << rec["cpu_log_n"]), dtype=torch.int64, device="cuda")
+            d_pg = torch.empty((T.NUM_PROG_COLS, 1 << rec["prog_log_n"]), dtype=torch.int64, device="cuda")
+            d_steps = torch.from_numpy(rec["steps"].view(np.int64)).cuda()
+            torch.cuda.synchronize()                                 # complete before the library's stream reads and writes them
+            be.generate_cpu_trace(d_steps, rec["cpu_log_n"], out=d_cpu)
+            be.generate_prog_trace_steps(d_steps, rec["listing"], params[1], out=d_pg)
+            t2 = time.perf_counter()
+            lean[T.CPU], lean[T.PROGRAM] = d_cpu, d_pg
+            proofs["step_path"] = bytes(be.prove_with_traces(blob, lean, params, compress))
+            t3 = time.perf_counter()
+            b = {"native_trace_generation_s": tm["native_s"], "binding_copies_s": tm["copy_s"], "device_table_generation_s": t2 - t1, "prove_s": t3 - t2,
+                 "total_s": t3 - t0, "total_without_binding_copies_s": t3 - t0 - tm["copy_s"],
+                 "link_bytes": be.upload_stats()["link_bytes"] + nbytes(rec, STEP_KEYS)}
+            del lean, d_cpu, d_pg, d_steps
+            assert proofs["step_path"] == proofs["table_path"], "the two paths give different proof bytes"
+        if cells and not records:
             t0 = time.perf_counter()
             lean, params, compress, rec = fastexec.instance(prog, range_bits=16, limb_bits=8, max_steps=1 << 24, cells_only=True, timings=tm, **kw)
             t1 = time.perf_counter()
@@ -175,7 +190,8 @@ def steps_against_tables(prog, kw, blob, reps, hasher, out, cells, workload, has
             proofs["cell_path"] = bytes(be.prove_with_traces(blob, lean, params, compress))
             t3 = time.perf_counter()
             c = {"native_trace_generation_s": tm["native_s"], "binding_copies_s": tm["copy_s"], "device_table_generation_s": t2 - t1, "prove_s": t3 - t2,
-                 "total_s": t3 - t0, "total_without_binding_copies_s": t3 - t0 - tm["copy_s"]}
+                 "total_s": t3 - t0, "total_without_binding_copies_s": t3 - t0 - tm["copy_s"],
+                 "link_bytes": be.upload_stats()["link_bytes"] + nbytes(rec, CELL_KEYS)}
             del lean, d
             assert proofs["cell_path"] == proofs["table_path"], "the cell path gives different proof bytes"
         if hashes:
@@ -197,30 +213,50 @@ def steps_against_tables(prog, kw, blob, reps, hasher, out, cells, workload, has
             proofs["hashes_path"] = bytes(be.prove_with_traces(blob, lean, params, compress))
             t3 = time.perf_counter()
             h = {"native_trace_generation_s": tm["native_s"], "binding_copies_s": tm["copy_s"], "device_table_generation_s": t2 - t1, "prove_s": t3 - t2,
-                 "total_s": t3 - t0, "total_without_binding_copies_s": t3 - t0 - tm["copy_s"]}
+                 "total_s": t3 - t0, "total_without_binding_copies_s": t3 - t0 - tm["copy_s"],
+                 "link_bytes": be.upload_stats()["link_bytes"] + nbytes(rec, HASH_KEYS)}
             del lean, d, d_st, d_ps, d_in, d_f
             assert proofs["hashes_path"] == proofs["table_path"], "the hashes path gives different proof bytes"
+        if records:
+            t0 = time.perf_counter()
+            _, _, _, rec = fastexec.instance(prog, range_bits=16, limb_bits=8, max_steps=1 << 24, records_only=True, timings=tm, **kw)
+            t1 = time.perf_counter()
+            proofs["records_path"] = bytes(be.prove_from_records(blob, rec, range_bits=16, limb_bits=8, result_line=bool(kw.get("prove_program_hash"))))
+            t3 = time.perf_counter()
+            r = {"native_trace_generation_s": tm["native_s"], "binding_copies_s": tm["copy_s"], "device_table_generation_s": 0.0, "prove_s": t3 - t1,
+                 "total_s": t3 - t0, "total_without_binding_copies_s": t3 - t0 - tm["copy_s"],
+                 "link_bytes": be.upload_stats()["link_bytes"] + nbytes(rec, RECORD_KEYS)}
+            del rec
+            assert proofs["records_path"] == proofs["table_path"], "the records path gives different proof bytes"
         if rep:
             runs["table_path"].append(a)
-            runs["step_path"].append(b)
-            if cells:
+            if not records:
+                runs["step_path"].append(b)
+            if cells and not records:
                 runs["cell_path"].append(c)
             if hashes:
                 runs["hashes_path"].append(h)
+            if records:
+                runs["records_path"].append(r)
         print(("warm-up " if not rep else "") + "table path %s" % {k: round(v, 3) for k, v in a.items()}, flush=True)
-        print(("warm-up " if not rep else "") + "step path  %s" % {k: round(v, 3) for k, v in b.items()}, flush=True)
-        if cells:
+        if not records:
+            print(("warm-up " if not rep else "") + "step path  %s" % {k: round(v, 3) for k, v in b.items()}, flush=True)
+        if records:
+            print(("warm-up " if not rep else "") + "records path %s" % {k: round(v, 3) for k, v in r.items()}, flush=True)
+        if cells and not records:
             print(("warm-up " if not rep else "") + "cell path  %s" % {k: round(v, 3) for k, v in c.items()}, flush=True)
         if hashes:
             print(("warm-up " if not rep else "") + "hashes path %s" % {k: round(v, 3) for k, v in h.items()}, flush=True)
     be.close()
     med = lambda path, key: sorted(r[key] for r in runs[path])[len(runs[path]) // 2]
     summary = {path: {key: round(med(path, key), 3) for key in runs[path][0]} for path in runs}
+    spans = {path: [round(min(r["total_s"] for r in runs[path]), 3), round(max(r["total_s"] for r in runs[path]), 3)] for path in runs}
     print(json.dumps(summary), flush=True)
+    print(json.dumps({"total_s_span": spans}), flush=True)
     if out:
         os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
         json.dump({"workload": workload + ", ola_stark(range_bits=16, limb_bits=8)", "hasher": hasher, "reps": reps,
-                   "proof_bytes_identical": True, "median": summary, "runs": runs}, open(out, "w"), indent=1)
+                   "proof_bytes_identical": True, "median": summary, "total_s_span": spans, "runs": runs}, open(out, "w"), indent=1)
 
 
 if __name__ == "__main__":

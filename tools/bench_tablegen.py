@@ -1,8 +1,9 @@
 """Times ola_generate_rc_trace / ola_generate_bitwise_trace / ola_generate_prog_trace -- and ola_generate_cpu_trace /
 ola_generate_prog_trace_steps, the cases cpu:20 cpu:22 progsteps:21 progsteps:23, and ola_generate_memory_trace / ola_generate_cmp_trace,
 the cases mem:19 mem:21 cmp:16, and ola_generate_storage_trace / ola_generate_poseidon_table, the cases storage:141 storage:8170
-storagesib:141 storagesib:8170 (the number is the number of accesses; `sib` = with the caller's siblings) poseidon:22 -- with resident
-inputs and outputs, next to
+storagesib:141 storagesib:8170 (the number is the number of accesses; `sib` = with the caller's siblings) poseidon:22, and
+ola_generate_tape_trace / ola_generate_poseidon_chunk_trace / ola_generate_prog_chunk_trace, the cases tape:N pchunk:N progchunk:N (the
+number is the number of tape cells, of POSEIDON calls, of 8-word listing chunks) -- with resident inputs and outputs, next to
 the same derived columns obtained without them: one ola_permuted_cols_dev call per pair (device) plus numpy for the other columns
 (host), and next to the oracle's sequential permuted_cols on one host core (as tools/bench_lookup.py measures it).
 
@@ -33,6 +34,7 @@ CASES = ["bitwise:18", "rc:16", "rc:21", "prog:20", "prog:23"]
 STEP_CASES = ["cpu:20", "cpu:22", "progsteps:21", "progsteps:23"]       # named on the command line
 CELL_CASES = ["mem:19", "mem:21", "cmp:16"]                              # named on the command line
 HASH_CASES = ["storage:141", "storage:8170", "storagesib:141", "storagesib:8170", "poseidon:22"]     # named on the command line
+SMALL_CASES = ["tape:100000", "pchunk:30000", "progchunk:100000"]          # named on the command line
 FN = (lambda x, y: x & y, lambda x, y: x | y, lambda x, y: x ^ y)
 
 
@@ -53,6 +55,21 @@ def inputs(kind, log_n, rng):
         recs[13] = 512 * np.arange(k)
         sib = (rng.integers(0, P, (1024, k), dtype=np.uint64),) if kind == "storagesib" else ()
         return (recs,) + sib, {"stride": 512 * k}
+    if kind in SMALL_KINDS:
+        # log_n is a count here as well.  tape: a quarter as many addresses as cells, written once and read three times on average;
+        # pchunk: call i hashes 1 + i % 4 blocks, the blocks back to back in the Poseidon table; progchunk: one table row per chunk.
+        # The Poseidon table is random words: the gathers do not depend on them
+        k = log_n
+        if kind == "tape":
+            return (np.stack([rng.integers(0, max(k // 4, 1), k, dtype=np.uint64), np.full(k, T.op_mask("TLOAD"), dtype=np.uint64),
+                              rng.integers(0, P, k, dtype=np.uint64)]),), {}
+        blocks = 1 + np.arange(k, dtype=np.uint64) % np.uint64(4) if kind == "pchunk" else np.ones(k, dtype=np.uint64)
+        psdn = rng.integers(0, P, (T.NUM_POSEIDON_COLS, 1 << max(3, (int(blocks.sum()) - 1).bit_length())), dtype=np.uint64)
+        if kind == "progchunk":
+            return (rng.integers(0, P, 8 * k, dtype=np.uint64), rng.integers(0, P, 4, dtype=np.uint64), psdn), {}
+        first = np.concatenate([[0], np.cumsum(blocks)[:-1]]).astype(np.uint64)
+        return (np.stack([10 + np.arange(k, dtype=np.uint64), rng.integers(0, 1 << 32, k, dtype=np.uint64), 8 * blocks,
+                          rng.integers(0, 1 << 32, k, dtype=np.uint64), first]), psdn), {}
     n = 1 << log_n
     if kind == "poseidon":
         return (rng.integers(0, P, (12, n), dtype=np.uint64), rng.integers(0, 2, (4, n), dtype=np.uint64)), {}
@@ -136,17 +153,29 @@ def call(be, kind, dev, kw, out):
                                          psdn_filters=kw["psdn"][1], roots_out=False)[0]
     if kind == "poseidon":
         return be.generate_poseidon_table(dev[0], dev[1], out=out)
+    if kind == "tape":
+        return be.generate_tape_trace(dev[0], out=out)
+    if kind == "pchunk":
+        return be.generate_poseidon_chunk_trace(dev[0], dev[1], out=out)
+    if kind == "progchunk":
+        return be.generate_prog_chunk_trace(dev[0], dev[1], dev[2], result_line=True, out=out)
     if kind == "progsteps":
         return be.generate_prog_trace_steps(dev[0], dev[1], kw["beta"], out=out)[0]
     return be.generate_prog_trace(dev[0], dev[1], kw["beta"], out=out)
 
 
 NCOLS = {"rc": T.COL_NUM_RC, "bitwise": T.COL_NUM_BITWISE, "prog": T.NUM_PROG_COLS, "cpu": T.NUM_CPU_COLS, "progsteps": T.NUM_PROG_COLS,
-         "mem": T.NUM_MEM_COLS, "cmp": T.COL_NUM_CMP, "storage": T.NUM_COL_ST, "storagesib": T.NUM_COL_ST, "poseidon": T.NUM_POSEIDON_COLS}
+         "mem": T.NUM_MEM_COLS, "cmp": T.COL_NUM_CMP, "storage": T.NUM_COL_ST, "storagesib": T.NUM_COL_ST, "poseidon": T.NUM_POSEIDON_COLS,
+         "tape": T.NUM_COL_TAPE, "pchunk": T.NUM_POSEIDON_CHUNK_COLS, "progchunk": T.NUM_PROG_CHUNK_COLS}
+SMALL_KINDS = ("tape", "pchunk", "progchunk")
 
 
 def table_log_n(kind, arg):
-    """log2 of the table's height: the case's number, but for the storage cases, whose number counts accesses"""
+    """log2 of the table's height: the case's number, but for the storage cases, whose number counts accesses, and the tape and chunk
+    cases, whose number counts cells, calls (call i: a header row and 1 + i % 4 extension rows) and chunks"""
+    if kind in SMALL_KINDS:
+        rows = arg if kind != "pchunk" else sum(2 + i % 4 for i in range(arg))
+        return max(3, (rows - 1).bit_length())
     return max(3, (256 * arg - 1).bit_length()) if kind in ("storage", "storagesib") else arg
 
 
@@ -155,7 +184,7 @@ def pairs_of(kind):
     if kind == "rc":
         return [(T.RC_LIMB_LO, T.RC_FIX_RANGE_CHECK_U16, T.RC_LIMB_LO_PERMUTED, T.RC_FIX_RANGE_CHECK_U16_PERMUTED_LO),
                 (T.RC_LIMB_HI, T.RC_FIX_RANGE_CHECK_U16, T.RC_LIMB_HI_PERMUTED, T.RC_FIX_RANGE_CHECK_U16_PERMUTED_HI)]
-    if kind in ("cpu", "mem", "cmp", "storage", "storagesib", "poseidon"):
+    if kind in ("cpu", "mem", "cmp", "storage", "storagesib", "poseidon") + SMALL_KINDS:
         return []
     if kind in ("prog", "progsteps"):
         return [(T.COL_PROG_EXEC_COMP_PROG, T.COL_PROG_COMP_PROG, T.COL_PROG_EXEC_COMP_PROG_PERM, T.COL_PROG_COMP_PROG_PERM)]
@@ -239,6 +268,11 @@ def measure(kind, log_n, runs):
         rec["table_words"] = NCOLS[kind] * n
         be.close()
         return rec
+    if kind in SMALL_KINDS:                # no permuted pairs; the host-side counterpart is tape_table() / poseidon_chunk_table() / prog_chunk_and_poseidon()
+        rec["records"] = arg
+        rec["table_words"] = NCOLS[kind] * n
+        be.close()
+        return rec
     if kind in ("mem", "cmp"):             # no permuted pairs; the host-side counterpart is memory_table() / cmp_table() of the native generator (docs/EXPERIMENTS.md, the last section)
         rec["cells" if kind == "mem" else "operand_pairs"] = int(host[0].shape[1])
         rec["table_words"] = NCOLS[kind] * n
@@ -319,14 +353,14 @@ def traced_kernels(kind, log_n, calls, pair_by_pair):
 def launches(kind, log_n):
     rec = {}
     for label, pbp in (("call", False), ("pair_by_pair", True)):
-        if pbp and kind in ("storage", "storagesib", "poseidon"):      # no lookup pairs: nothing to compare with
+        if pbp and kind in ("storage", "storagesib", "poseidon") + SMALL_KINDS:      # no lookup pairs: nothing to compare with
             continue
         one, two = traced_kernels(kind, log_n, 1, pbp), traced_kernels(kind, log_n, 2, pbp)
         per = {k: two.get(k, 0) - one.get(k, 0) for k in two}
         rec[label + "_launches"] = sum(per.values())
         sorts = {k: v for k, v in per.items() if "radix" in k.lower() or "onesweep" in k.lower() or "sort" in k.lower()}
         rec[label + "_sort_kernel_launches"] = sum(sorts.values())
-        rec[label + "_kernels"] = {k[:96]: v for k, v in sorted(per.items()) if v}
+        rec[label + "_kernels"] = {k: v for k, v in sorted(per.items()) if v}      # the whole name: rocPRIM's kernels differ only far into it
     return rec
 
 

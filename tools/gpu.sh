@@ -273,6 +273,12 @@ PY
                    timeout -k 10 600 python -m pytest tests/test_gpu_storage_tablegen.py tests/test_storage_tablegen_abi.py -x -q 2>&1 | tail -15 | tee $O/pytest.log && \
                    timeout -k 10 900 python tools/bench_tablegen.py --json $O/tablegen_hashes.json storage:141 storage:8170 storagesib:141 storagesib:8170 poseidon:22 2>&1 | grep -v amdgpu | tee $O/tablegen_hashes.txt && \
                    timeout -k 10 900 python tools/bench_prove_real.py 29600 2 --hashes --storage-slots 408 --json $O/hashes_vs_cells_slots408.json 2>&1 | grep -v amdgpu | tee $O/hashes_vs_cells_slots408.txt ) ;;
+    records)     # from the executor's records to proof bytes: the three narrow generators' and the one call's tests, the generators' timings and launch counts, then table, hashes and records path in alternation
+                 ( set -o pipefail
+                   timeout -k 10 900 python -m pytest tests/test_gpu_small_tablegen.py tests/test_small_tablegen_abi.py tests/test_gpu_prove_from_records.py tests/test_records_abi.py -x -q 2>&1 | tail -15 | tee $O/pytest.log && \
+                   timeout -k 10 600 python tools/bench_tablegen.py --json $O/tablegen_small.json tape:100000 pchunk:30000 progchunk:100000 2>&1 | grep -v amdgpu | tee $O/tablegen_small.txt && \
+                   timeout -k 10 900 python tools/bench_prove_real.py 29600 3 --records --storage-slots 408 --json $O/records_vs_hashes_slots408.json 2>&1 | grep -v amdgpu | tee $O/records_vs_hashes_slots408.txt && \
+                   timeout -k 10 600 python tools/bench_prove_real.py 0 3 --records --shape readme --json $O/records_vs_hashes_readme.json 2>&1 | grep -v amdgpu | tee $O/records_vs_hashes_readme.txt ) ;;
     check_lookup) # ola_check_lookup: its tests, then the CPU -> memory and CPU -> program lookups of a 2^22-row executed instance, valid and with one looked row dropped
                  ( set -o pipefail
                    timeout -k 10 600 python -m pytest tests/test_gpu_check_lookup.py -x -q 2>&1 | tail -15 | tee $O/pytest.log && \
