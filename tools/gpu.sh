@@ -286,6 +286,9 @@ PY
     zcolumns)    # the Z-column kernels word for word against the integer reference, at caller-chosen challenges
                  ( set -o pipefail
                    timeout -k 10 600 python -m pytest tests/test_gpu_zcolumns.py -q --durations=12 2>&1 | tail -30 | tee $O/pytest.log ) ;;
+    quotient)    # the quotient kernels (generated and interpreter) word for word against the integer reference, at caller-chosen challenges
+                 ( set -o pipefail
+                   timeout -k 10 600 python -m pytest tests/test_gpu_quotient.py -q --durations=12 2>&1 | tail -30 | tee $O/pytest.log ) ;;
     *)           echo "unknown step $step" ;;
   esac
 done
