@@ -54,7 +54,9 @@ extern "C" {
  * inputs, and the Poseidon table at its padded height, resident); so were ola_generate_tape_trace, ola_generate_poseidon_chunk_trace
  * and ola_generate_prog_chunk_trace (the tape table sorted on the device, and the two chunk tables gathered from the resident Poseidon
  * table); so were OlaExecRecords, ola_tables_from_records, ola_tables_get, ola_tables_free and ola_prove_from_records (the twelve
- * generators composed in one call, from the executor's records to resident tables and to proof bytes). */
+ * generators composed in one call, from the executor's records to resident tables and to proof bytes); so were OlaVerifyReport, the
+ * OLA_VERIFY_* reasons and the entry points ola_verify_all_proof and ola_verify_opening (proof bytes to a verdict with the place and
+ * the reason of a refusal). */
 #define OLA_GPU_ABI_VERSION 7
 #define OLA_OK 0
 #define OLA_E_INVALID_ARG (-1)
@@ -894,6 +896,81 @@ int32_t ola_tables_get(const OlaTableSet* set, const uint64_t* ptrs[12], uint32_
 int32_t ola_tables_free(OlaTableSet* set);
 int32_t ola_prove_from_records(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, const OlaExecRecords* rec, uint8_t* out,
                                size_t cap, size_t* out_len);
+
+/* ---- verification: proof bytes to a verdict ------------------------------------------------------------------------------------
+ * ola_verify_all_proof is the reference's `verify_proof` (circuits/src/stark/verifier.rs:35) for the context's configuration: the
+ * hasher of the Merkle trees and the transcript is the context's (all four OLA_HASH_*, the proof-of-work hasher as in ola_pow), the
+ * FRI parameters are the context's OlaGpuConfig.  In the reference's order: get_challenges, CtlCheckVars::from_proofs, then per
+ * table validate_proof_shape, eval_vanishing_poly over the extension field at zeta, the quotient identity and plonky2's
+ * verify_fri_proof, and verify_cross_table_lookups last.
+ * The sequential part -- reading the bytes, the transcript, the constraints at zeta, the proof of work, the lookup products -- runs
+ * on the host; every Merkle path (one per table, query and oracle, one per table, query and FRI layer) and the FRI algebra of
+ * every (table, query) run on the device: one upload, two kernel launches and one read-back of flags per call, whatever the
+ * number of tables, queries and layers (olavm_amd/csrc/verify_host.h, verify.hip).
+ * airset: as for ola_prove_with_traces.  params: the concatenated per-table constraint parameters as for ola_prove_with_traces, or
+ *   NULL: every parameter of table t is then the proof's compress_challenges[t], as the reference's verifier takes them.
+ * proof: AllProof in the reference wire format (serialization.rs read_all_proof), what ola_prove_with_traces* and
+ *   ola_prove_from_records write.
+ * Returns OLA_OK when verification RAN: the verdict is in *report, a rejected proof is not an error.  OLA_E_INVALID_ARG: a NULL
+ * argument, a malformed AIR-set blob, or a multi-device context (as the per-phase entry points refuse one); OLA_E_NO_DEVICE without
+ * a HIP device (no context can exist then; there is no CPU fallback).
+ * When several checks fail, the report names the one the reference reaches first: tables in order; within a table its shape, the
+ * quotient identity, the proof of work, then the queries in order; within a query the initial trees in oracle order (trace, Zs,
+ * quotient), then per FRI layer the consistency check before that layer's Merkle path, then the final polynomial; the lookup
+ * products last.
+ * A field word >= p anywhere in the proof is refused as OLA_VERIFY_MALFORMED: an honest serializer never writes one
+ * (serialization.rs:50-52), what the reference does with such a word is not defined by its wire format, and the kernels may then
+ * assume canonical input.  The words of a Blake3 digest are bytes, not field elements, and may take any value.
+ * Leaves are hashed by the rule of this library's commitments: hash_no_pad of the row for every width, rows of four words or fewer
+ * included, as MerkleTree::new_v2 (hash/merkle_tree/mod.rs:180-266) and verify_merkle_proof_to_cap (hash/merkle_proofs.rs:51-80) hash them in
+ * the reference; Blake3_256 of the canonical little-endian words under OLA_HASH_BLAKE3. */
+#define OLA_VERIFY_OK 0u
+#define OLA_VERIFY_MALFORMED 1u                 /* truncated, trailing bytes, a word >= p, wrong number of table proofs        */
+#define OLA_VERIFY_EMPTY_FRI 2u                 /* no query round or no initial tree to take the degree from                   */
+#define OLA_VERIFY_SHAPE_OPENING_WIDTH 3u       /* validate_proof_shape: local_values / next_values                            */
+#define OLA_VERIFY_SHAPE_ZS_WIDTH 4u            /*   permutation_ctl_zs / permutation_ctl_zs_next                              */
+#define OLA_VERIFY_SHAPE_CTL_ZS_LAST_WIDTH 5u   /*   ctl_zs_last                                                               */
+#define OLA_VERIFY_SHAPE_QUOTIENT_WIDTH 6u      /*   quotient_polys                                                            */
+#define OLA_VERIFY_QUOTIENT_IDENTITY 7u         /* verifier.rs:295 "Mismatch between evaluation and opening of quotient polynomial" */
+#define OLA_VERIFY_SHAPE_CAP_HEIGHT 8u          /* validate_fri_proof_shape (fri/validate_shape.rs:11-67): a commit-phase cap  */
+#define OLA_VERIFY_SHAPE_QUERY_ROUNDS 9u        /*   number of query rounds                                                    */
+#define OLA_VERIFY_SHAPE_INITIAL_PROOFS 10u     /*   number of initial trees of a query                                        */
+#define OLA_VERIFY_SHAPE_LEAF_LEN 11u           /*   width of an opened row                                                    */
+#define OLA_VERIFY_SHAPE_INITIAL_PATH_LEN 12u   /*   length of an initial tree's Merkle path                                   */
+#define OLA_VERIFY_SHAPE_STEPS 13u              /*   number of FRI layers of a query (or of commit-phase caps)                 */
+#define OLA_VERIFY_SHAPE_EVALS_LEN 14u          /*   a layer's coset                                                           */
+#define OLA_VERIFY_SHAPE_STEP_PATH_LEN 15u      /*   length of a layer's Merkle path                                           */
+#define OLA_VERIFY_SHAPE_FINAL_POLY_LEN 16u     /*   the final polynomial                                                      */
+#define OLA_VERIFY_POW 17u                      /* fri/verifier.rs:59-73 "Invalid proof of work witness."                      */
+#define OLA_VERIFY_MERKLE_INITIAL 18u           /* merkle_proofs.rs:71 for an initial tree; oracle_or_layer = 0 trace, 1 Zs, 2 quotient */
+#define OLA_VERIFY_FRI_CONSISTENCY 19u          /* fri/verifier.rs:218: a layer's evals[x_index within coset] is not the folded value; oracle_or_layer = layer */
+#define OLA_VERIFY_MERKLE_COMMIT 20u            /* merkle_proofs.rs:71 for a commit-phase tree; oracle_or_layer = layer        */
+#define OLA_VERIFY_FINAL_POLY 21u               /* "Final polynomial evaluation is invalid."                                   */
+#define OLA_VERIFY_CTL 22u                      /* cross_table_lookup.rs:551-584 "Cross-table lookup verification failed."      */
+typedef struct OlaVerifyReport {
+    uint32_t accepted;          /* 1 / 0                                                                                      */
+    uint32_t reason;            /* OLA_VERIFY_*                                                                               */
+    int32_t table;              /* where the reference stops; -1 where it does not apply                                      */
+    int32_t query;
+    int32_t oracle_or_layer;
+    uint32_t merkle_jobs;       /* Merkle paths checked on the device                                                         */
+    uint32_t query_jobs;        /* (table, query) pairs whose FRI algebra ran on the device                                   */
+    uint32_t kernel_launches;   /* 2, or 0 when the host stage refused the proof before any table reached the device          */
+    double host_ms;             /* the host stage: reading, transcript, constraints at zeta, image                            */
+    double device_ms;           /* upload, the two kernels, read-back (wall clock around the stream)                          */
+    char message[96];           /* starts with the reason in words, NUL-terminated                                            */
+} OlaVerifyReport;
+int32_t ola_verify_all_proof(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, const uint64_t* params, const uint8_t* proof,
+                             size_t proof_len, OlaVerifyReport* report);
+/* The counterpart of ola_open_and_prove: verifies an opening set and its FRI proof (write_opening_set || write_fri_proof, the bytes
+ * ola_open_and_prove returns) against the three commitments' caps, continuing the caller's transcript.  caps: 3 x 2^cap_height x 4
+ * words (trace, Zs, quotient); num_polys: the three commitments' widths; degree_bits: log2 of the trace length.  *challenger must
+ * stand where the prover's stood when it called ola_open_and_prove; when the proof is accepted it is left where the prover's
+ * stands afterwards, otherwise it is unchanged.  table is -1 in the report.  Everything else as above; an opening set whose widths
+ * are not the instance's is refused with the OLA_VERIFY_SHAPE_* reason of its vector. */
+int32_t ola_verify_opening(OlaCtx* ctx, const uint64_t* caps, const uint32_t num_polys[3], uint32_t degree_bits,
+                           uint32_t num_permutation_zs, const uint8_t* proof, size_t proof_len, OlaChallenger* challenger,
+                           OlaVerifyReport* report);
 
 /* ---- coset-partitioned proving over several GPUs ---------------------------------------------------------
  * One process per GPU; every process calls ola_prove_with_traces with the SAME traces.  Because the transcript is a

@@ -12,6 +12,8 @@
 //   plonky2/plonky2/src/fri/prover.rs:126        fri_proof_of_work        ola_host::fri_proof_of_work
 //   circuits/src/stark/prover.rs:79              prove_with_traces        ola_host::prove_with_traces
 //   circuits/src/stark/prover.rs:330             prove_single_table       ola_host::prove_single_table
+//   circuits/src/stark/verifier.rs:35            verify_proof             ola_host::verify_proof
+//   circuits/src/stark/verifier.rs:220 (FRI part) verify_stark_proof...   ola_host::verify_stark_proof_opening
 //   circuits/src/stark/lookup.rs:68              permuted_cols            ola_host::permuted_cols
 //   circuits/src/generation/poseidon.rs:5        generate_poseidon_trace  ola_host::generate_poseidon_trace
 //   circuits/src/generation/cpu.rs:11            generate_cpu_trace       ola_host::generate_cpu_trace
@@ -347,6 +349,34 @@ inline std::vector<uint8_t> prove_with_traces(const Gpu& g, const std::vector<F>
     check(rc);
     out.resize(len);
     return out;
+}
+
+// ---- circuits/src/stark/verifier.rs:35-206 ------------------------------------------------------------------------------------------
+// verify_proof(ola_stark, all_proof, config): the reference returns Ok(()) or the first failing `ensure!` as an anyhow::Error.  Here the
+// report is returned: `accepted`, and for a refusal the OLA_VERIFY_* reason, the table, query and oracle-or-layer where the reference
+// stops, and its words.  params empty: the per-table parameters are the proof's compress challenges, as in the reference.  A rejected
+// proof is a report, not an exception; only a call that could not run throws.
+inline OlaVerifyReport verify_proof(const Gpu& g, const std::vector<F>& airset, const std::vector<uint8_t>& all_proof, const std::vector<F>& params = {}) {
+    OlaVerifyReport rep{};
+    check(ola_verify_all_proof(g.ctx(), airset.data(), airset.size(), params.empty() ? nullptr : params.data(), all_proof.data(), all_proof.size(), &rep));
+    return rep;
+}
+// The verifier's side of open_and_prove: the FRI half of verify_stark_proof_with_challenges (verifier.rs:298-323, plonky2's verify_fri_proof)
+// for one table's opening set and FRI proof, continuing the caller's transcript; `challenger` advances as the prover's did when the proof
+// is accepted.  caps: the trace, Zs and quotient commitments' caps; num_polys: their widths.
+inline OlaVerifyReport verify_stark_proof_opening(const Gpu& g, const std::array<MerkleCap, 3>& caps, const std::array<uint32_t, 3>& num_polys,
+                                                  uint32_t degree_bits, uint32_t num_permutation_zs, const std::vector<uint8_t>& openings,
+                                                  const std::vector<uint8_t>& fri_proof, Challenger& challenger) {
+    std::vector<F> cap_words;
+    for (const MerkleCap& cap : caps) {
+        if (cap.size() != (size_t)1 << g.config.cap_height) throw Error(OLA_E_INVALID_ARG, "a cap of 2^cap_height digests per commitment");
+        for (const HashOut& h : cap) cap_words.insert(cap_words.end(), h.begin(), h.end());
+    }
+    std::vector<uint8_t> bytes(openings);
+    bytes.insert(bytes.end(), fri_proof.begin(), fri_proof.end());
+    OlaVerifyReport rep{};
+    check(ola_verify_opening(g.ctx(), cap_words.data(), num_polys.data(), degree_bits, num_permutation_zs, bytes.data(), bytes.size(), &challenger.raw(), &rep));
+    return rep;
 }
 
 // From the executor's records (OlaExecRecords: set `size` to sizeof, pointers host or device memory) to the AllProof wire bytes: the

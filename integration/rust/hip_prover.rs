@@ -254,6 +254,28 @@ where
     Ok(proof)
 }
 
+/// `verify_proof` (circuits/src/stark/verifier.rs:35) on the device: the `AllProof` goes over in the reference's own wire format
+/// (`Buffer::write_all_proof`, serialization.rs:377-393), the per-table parameters are taken from its compress challenges as the
+/// reference's verifier takes them, and a refusal comes back as the reference's error would: the first failing check, in words, with
+/// its table, query and oracle or layer.  The Merkle paths and the FRI algebra run on the GPU (`ola_verify_all_proof`).
+pub fn verify_proof_hip<F, C, const D: usize>(config: &StarkConfig, all_proof: &AllProof<F, C, D>) -> Result<()>
+where
+    F: RichField + Extendable<D>,
+    C: GenericConfig<D, F = F>,
+{
+    ensure!(D == 2, "the backend verifies over the quadratic extension");
+    let mut buffer = Buffer::new(Vec::new());
+    buffer.write_all_proof(all_proof)?;
+    let bytes = buffer.bytes();
+    let words = airset();
+    with_ctx(hasher_of::<F, C, D>()?, config, |c| {
+        let mut report: OlaVerifyReport = unsafe { std::mem::zeroed() };
+        check(unsafe { ola_verify_all_proof(c, words.as_ptr(), words.len(), std::ptr::null(), bytes.as_ptr(), bytes.len(), &mut report) })?;
+        ensure!(report.accepted == 1, "{}", unsafe { CStr::from_ptr(report.message.as_ptr()) }.to_string_lossy());
+        Ok(())
+    })
+}
+
 pub fn prove_with_traces_hip<F, C, const D: usize>(
     ola_stark: &OlaStark<F, D>,
     config: &StarkConfig,

@@ -208,6 +208,47 @@ pub struct OlaLookupMismatch {
     pub looked_row: u64,
     pub values: [u64; OLA_LOOKUP_MAX_VALUES],
 }
+/// `OlaVerifyReport.reason` (`OLA_VERIFY_*` of ola_gpu.h): where the reference's `verify_proof` stops
+pub const OLA_VERIFY_OK: u32 = 0;
+pub const OLA_VERIFY_MALFORMED: u32 = 1;
+pub const OLA_VERIFY_EMPTY_FRI: u32 = 2;
+pub const OLA_VERIFY_SHAPE_OPENING_WIDTH: u32 = 3;
+pub const OLA_VERIFY_SHAPE_ZS_WIDTH: u32 = 4;
+pub const OLA_VERIFY_SHAPE_CTL_ZS_LAST_WIDTH: u32 = 5;
+pub const OLA_VERIFY_SHAPE_QUOTIENT_WIDTH: u32 = 6;
+pub const OLA_VERIFY_QUOTIENT_IDENTITY: u32 = 7;
+pub const OLA_VERIFY_SHAPE_CAP_HEIGHT: u32 = 8;
+pub const OLA_VERIFY_SHAPE_QUERY_ROUNDS: u32 = 9;
+pub const OLA_VERIFY_SHAPE_INITIAL_PROOFS: u32 = 10;
+pub const OLA_VERIFY_SHAPE_LEAF_LEN: u32 = 11;
+pub const OLA_VERIFY_SHAPE_INITIAL_PATH_LEN: u32 = 12;
+pub const OLA_VERIFY_SHAPE_STEPS: u32 = 13;
+pub const OLA_VERIFY_SHAPE_EVALS_LEN: u32 = 14;
+pub const OLA_VERIFY_SHAPE_STEP_PATH_LEN: u32 = 15;
+pub const OLA_VERIFY_SHAPE_FINAL_POLY_LEN: u32 = 16;
+pub const OLA_VERIFY_POW: u32 = 17;
+pub const OLA_VERIFY_MERKLE_INITIAL: u32 = 18;
+pub const OLA_VERIFY_FRI_CONSISTENCY: u32 = 19;
+pub const OLA_VERIFY_MERKLE_COMMIT: u32 = 20;
+pub const OLA_VERIFY_FINAL_POLY: u32 = 21;
+pub const OLA_VERIFY_CTL: u32 = 22;
+/// The verdict of `ola_verify_all_proof` / `ola_verify_opening`: `accepted`, and for a refusal the reason and the table, query and
+/// oracle-or-layer (-1 where they do not apply) at which the reference's verifier stops; `message` starts with the reason in words.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct OlaVerifyReport {
+    pub accepted: u32,
+    pub reason: u32,
+    pub table: i32,
+    pub query: i32,
+    pub oracle_or_layer: i32,
+    pub merkle_jobs: u32,
+    pub query_jobs: u32,
+    pub kernel_launches: u32,
+    pub host_ms: f64,
+    pub device_ms: f64,
+    pub message: [c_char; 96],
+}
 /// `ola_all_gather_fn`: gather `bytes` bytes of device memory from every rank into `recv_dev` (rank order), 0 = done
 pub type OlaAllGatherFn = Option<unsafe extern "C" fn(user: *mut c_void, send_dev: *const c_void, recv_dev: *mut c_void, bytes: usize) -> i32>;
 
@@ -300,6 +341,10 @@ extern "C" {
     pub fn ola_check_lookup(ctx: *mut OlaCtx, airset: *const u64, airset_words: usize, cols: *const *const *const u64,
         log_n: *const u32, lookup: u32, out: *mut OlaLookupMismatch, cap: u32, n_out: *mut u32, totals: *mut u64,
         width: *mut u32) -> i32;
+    pub fn ola_verify_all_proof(ctx: *mut OlaCtx, airset: *const u64, airset_words: usize, params: *const u64, proof: *const u8,
+        proof_len: usize, report: *mut OlaVerifyReport) -> i32;
+    pub fn ola_verify_opening(ctx: *mut OlaCtx, caps: *const u64, num_polys: *const u32, degree_bits: u32, num_permutation_zs: u32,
+        proof: *const u8, proof_len: usize, challenger: *mut OlaChallenger, report: *mut OlaVerifyReport) -> i32;
     pub fn ola_take_pending_proof(ctx: *mut OlaCtx, out: *mut u8, cap: usize, out_len: *mut usize) -> i32;
     pub fn ola_prove_single_table(ctx: *mut OlaCtx, airset: *const u64, airset_words: usize, table: u32,
         trace_cols: *const *const u64, trace_commitment: *const OlaBatch, trace_cap: *const u64,

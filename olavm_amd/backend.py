@@ -109,6 +109,40 @@ class OlaLookupMismatch(C.Structure):
                 ("looking_row", C.c_uint64), ("looked_row", C.c_uint64), ("values", C.c_uint64 * OLA_LOOKUP_MAX_VALUES)]
 
 
+class OlaVerifyReport(C.Structure):
+    """include/ola_gpu.h OlaVerifyReport: the verdict of ola_verify_all_proof / ola_verify_opening and where a refusal stops."""
+    _fields_ = [("accepted", C.c_uint32), ("reason", C.c_uint32), ("table", C.c_int32), ("query", C.c_int32), ("oracle_or_layer", C.c_int32),
+                ("merkle_jobs", C.c_uint32), ("query_jobs", C.c_uint32), ("kernel_launches", C.c_uint32), ("host_ms", C.c_double),
+                ("device_ms", C.c_double), ("message", C.c_char * 96)]
+
+
+# OLA_VERIFY_* (include/ola_gpu.h), by value
+VERIFY_REASONS = ("OK", "MALFORMED", "EMPTY_FRI", "SHAPE_OPENING_WIDTH", "SHAPE_ZS_WIDTH", "SHAPE_CTL_ZS_LAST_WIDTH", "SHAPE_QUOTIENT_WIDTH",
+                  "QUOTIENT_IDENTITY", "SHAPE_CAP_HEIGHT", "SHAPE_QUERY_ROUNDS", "SHAPE_INITIAL_PROOFS", "SHAPE_LEAF_LEN", "SHAPE_INITIAL_PATH_LEN",
+                  "SHAPE_STEPS", "SHAPE_EVALS_LEN", "SHAPE_STEP_PATH_LEN", "SHAPE_FINAL_POLY_LEN", "POW", "MERKLE_INITIAL", "FRI_CONSISTENCY",
+                  "MERKLE_COMMIT", "FINAL_POLY", "CTL")
+
+
+class VerifyResult:
+    """What a verification says: truthy when the proof is accepted; otherwise `reason` (a name of VERIFY_REASONS; `code` its OLA_VERIFY_*
+    value), `table`, `query`, `oracle_or_layer` (None where they do not apply) and `message` say where the reference's verifier stops."""
+
+    def __init__(self, rep):
+        opt = lambda v: None if v < 0 else int(v)
+        self.accepted, self.code = bool(rep.accepted), int(rep.reason)
+        self.reason = VERIFY_REASONS[self.code] if self.code < len(VERIFY_REASONS) else str(self.code)
+        self.table, self.query, self.oracle_or_layer = opt(rep.table), opt(rep.query), opt(rep.oracle_or_layer)
+        self.merkle_jobs, self.query_jobs, self.kernel_launches = int(rep.merkle_jobs), int(rep.query_jobs), int(rep.kernel_launches)
+        self.host_ms, self.device_ms = float(rep.host_ms), float(rep.device_ms)
+        self.message = rep.message.decode()
+
+    def __bool__(self):
+        return self.accepted
+
+    def __repr__(self):
+        return "VerifyResult(%s)" % self.message
+
+
 CHECK_SECTIONS = ("AIR", "PERMUTATION", "LOOKUP")
 CONSTRAINT_KINDS = ("constraint", "constraint_transition", "constraint_first_row", "constraint_last_row")
 
@@ -262,6 +296,11 @@ def load_library():
     L.ola_check_lookup.argtypes = [C.c_void_p, U64P, C.c_size_t, C.POINTER(C.POINTER(U64P)), C.POINTER(C.c_uint32), C.c_uint32,
                                    C.POINTER(OlaLookupMismatch), C.c_uint32, C.POINTER(C.c_uint32), U64P, C.POINTER(C.c_uint32)]
     L.ola_check_lookup.restype = C.c_int32
+    L.ola_verify_all_proof.argtypes = [C.c_void_p, U64P, C.c_size_t, U64P, C.c_char_p, C.c_size_t, C.POINTER(OlaVerifyReport)]
+    L.ola_verify_all_proof.restype = C.c_int32
+    L.ola_verify_opening.argtypes = [C.c_void_p, U64P, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t,
+                                     C.POINTER(OlaChallenger), C.POINTER(OlaVerifyReport)]
+    L.ola_verify_opening.restype = C.c_int32
     _lib = L
     return L
 
@@ -284,6 +323,7 @@ EXPORTS = [
     "ola_generate_tape_trace", "ola_generate_poseidon_chunk_trace", "ola_generate_prog_chunk_trace",
     "ola_tables_from_records", "ola_tables_get", "ola_tables_free", "ola_prove_from_records",
     "ola_open", "ola_fri_plan", "ola_fri_commit_begin", "ola_fri_commit_next_layer", "ola_fri_commit_finish", "ola_fri_query", "ola_fri_free",
+    "ola_verify_all_proof", "ola_verify_opening",
 ]
 
 
@@ -1377,6 +1417,30 @@ class Backend:
                                       "looking_table_name": names[table] if names and table is not None else None, "looking_row": lrow,
                                       "looked_row": drow})
         return rep
+
+    def verify_all_proof(self, airset_blob, proof, params=None):
+        """ola_verify_all_proof: the reference's `verify_proof` of AllProof bytes under this context's configuration -> VerifyResult.
+        params: the per-table constraint parameters as for prove_with_traces; None takes them from the proof's compress challenges,
+        as the reference's verifier does.  A rejected proof is a result, not an error."""
+        blob = np.ascontiguousarray(airset_blob, dtype=np.uint64)
+        pr = None if params is None or len(params) == 0 else np.ascontiguousarray(params, dtype=np.uint64)
+        proof = bytes(proof)
+        rep = OlaVerifyReport()
+        self._chk(self.lib.ola_verify_all_proof(self.ctx, _p(blob), blob.size, None if pr is None else _p(pr), proof, len(proof), C.byref(rep)))
+        return VerifyResult(rep)
+
+    def verify_opening(self, caps, num_polys, degree_bits, num_permutation_zs, proof, challenger):
+        """ola_verify_opening, the counterpart of open_and_prove: caps = the three commitments' caps (3 x 2^cap_height x 4), num_polys
+        their widths, proof = opening-set bytes + FRI-proof bytes, challenger = the transcript where the prover's stood before
+        open_and_prove (a Challenger; advanced to where the prover's stands afterwards when the proof is accepted) -> VerifyResult"""
+        cp = np.ascontiguousarray(caps, dtype=np.uint64).reshape(-1)
+        if cp.size != 3 * 4 << self.cap_height:
+            raise OlaGpuError(-1, "invalid argument: caps must be 3 x 2^cap_height digests")
+        proof = bytes(proof)
+        rep = OlaVerifyReport()
+        self._chk(self.lib.ola_verify_opening(self.ctx, _p(cp), (C.c_uint32 * 3)(*[int(x) for x in num_polys]), int(degree_bits),
+                                              int(num_permutation_zs), proof, len(proof), C.byref(challenger.c), C.byref(rep)))
+        return VerifyResult(rep)
 
     def prove_single_table(self, airset_blob, table, trace, batch, ctl_challenges, params, challenger):
         """StarkProof bytes of one table (ola_prove_single_table): `batch` is the table's trace commitment, `challenger` the

@@ -18,13 +18,19 @@
 // blocks -- about 10 k instructions against 216 k for the Poseidon sponge -- so leaf hashing turns from VALU-bound into a pass
 // over the LDE at HBM speed (8 B per element read, column-major, consecutive lanes on consecutive addresses).
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#endif
 
 #include "gl.cuh"
 
 namespace ola {
 
+#if defined(__HIPCC__)
 #define B3_HD __host__ __device__ __forceinline__
+#else
+#define B3_HD inline
+#endif
 
 enum : u32 { B3_CHUNK_START = 1, B3_CHUNK_END = 2, B3_PARENT = 4, B3_ROOT = 8 };
 enum : int { B3_CHUNK_WORDS = 128 };   // u64 words per 1024-byte chunk
@@ -40,7 +46,11 @@ B3_HD constexpr int b3_sched(int r, int i) {
     for (int t = 0; t < r; t++) k = P[k];
     return k;
 }
+#if defined(__clang__)
 B3_HD u32 b3_rotr(u32 x, int n) { return __builtin_rotateright32(x, (u32)n); }
+#else
+B3_HD u32 b3_rotr(u32 x, int n) { return (x >> n) | (x << (32 - n)); }   // n is 7, 8, 12 or 16
+#endif
 
 #define B3_G(a, b, c, d, x, y)                                   \
     s[a] = s[a] + s[b] + (x); s[d] = b3_rotr(s[d] ^ s[a], 16);   \

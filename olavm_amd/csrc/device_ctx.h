@@ -18,12 +18,9 @@
 #include <unordered_map>
 #include <vector>
 
-namespace ola {
+#include "ola_error.h"
 
-struct OlaError : public std::runtime_error {
-    int code;
-    OlaError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
+namespace ola {
 
 #define HIP_CHECK(expr)                                                                                   \
     do {                                                                                                  \

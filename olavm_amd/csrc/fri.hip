@@ -29,64 +29,9 @@
 #include "poseidon_host.h"
 #include "poseidon2_host.h"
 #include "blake3.cuh"
+#include "challenger_host.h"
 
 namespace ola {
-
-// ------------------------------------------------------------------------------------------------ challenger
-static void challenger_duplex(OlaChallenger& ch) {
-    for (uint32_t i = 0; i < ch.input_len; i++) ch.sponge_state[i] = ch.input_buffer[i];
-    ch.input_len = 0;
-    u64 s[12];
-    for (int i = 0; i < 12; i++) s[i] = ch.sponge_state[i];
-    switch (ch.hasher) {                                         // H::Permutation of Challenger<F, H> (challenger.rs:134-153)
-        case OLA_HASH_POSEIDON: poseidon_permute_host(s); break;
-        case OLA_HASH_BLAKE3: b3_permutation_host(s); break;
-        case OLA_HASH_POSEIDON2:
-        case OLA_HASH_POSEIDON2_POW_POSEIDON: poseidon2_permute_host(s); break;
-        default: throw OlaError(OLA_E_INTERNAL, "challenger of an unknown hasher");
-    }
-    for (int i = 0; i < 12; i++) ch.sponge_state[i] = s[i];
-    for (int i = 0; i < 8; i++) ch.output_buffer[i] = s[i];
-    ch.output_len = 8;
-}
-void challenger_observe(OlaChallenger& ch, const u64* e, size_t n) {
-    for (size_t i = 0; i < n; i++) {
-        ch.output_len = 0;
-        ch.input_buffer[ch.input_len++] = gl_canon(e[i]);
-        if (ch.input_len == 8) challenger_duplex(ch);
-    }
-}
-// observe_cap (challenger.rs:75-84): GenericHashOut::to_vec of every digest
-void challenger_observe_cap(OlaChallenger& ch, const u64* digests, size_t n) {
-    // HashOut (Poseidon, Poseidon2): its four elements; Blake3's 32 bytes: five elements of 7 bytes (b3_digest_elements)
-    if (ch.hasher != OLA_HASH_BLAKE3) { challenger_observe(ch, digests, 4 * n); return; }
-    for (size_t i = 0; i < n; i++) {
-        u64 e[5];
-        b3_digest_elements(digests + 4 * i, e);
-        challenger_observe(ch, e, 5);
-    }
-}
-void challenger_init(OlaChallenger& ch, uint32_t hasher) {
-    memset(&ch, 0, sizeof(ch));
-    ch.hasher = hasher;
-}
-u64 challenger_get(OlaChallenger& ch) {
-    if (ch.input_len != 0 || ch.output_len == 0) challenger_duplex(ch);
-    return ch.output_buffer[--ch.output_len];
-}
-void challenger_compact(OlaChallenger& ch) {
-    if (ch.input_len != 0) challenger_duplex(ch);
-    ch.output_len = 0;
-}
-static Ext2 challenger_get_ext(OlaChallenger& ch) {
-    const u64 a = challenger_get(ch);
-    const u64 b = challenger_get(ch);
-    return ext_make(a, b);
-}
-static void challenger_observe_ext(OlaChallenger& ch, Ext2 e) {
-    u64 v[2] = {e.a, e.b};
-    challenger_observe(ch, v, 2);
-}
 
 // ------------------------------------------------------------------------------------------------ kernels
 // two-level extension power table: z^k = lo[k & mask] * hi[k >> h]; stored as 4 planes [lo.a | lo.b | hi.a | hi.b]

@@ -34,6 +34,7 @@
 #include "fri.hip"
 #include "stark.hip"
 #include "check.hip"
+#include "verify.hip"
 #include "storage.hip"
 #include "selftest.hip"
 
@@ -1131,6 +1132,52 @@ int32_t ola_check_lookup(OlaCtx* ctx, const uint64_t* airset, size_t airset_word
     *width = rep.width;
     for (int k = 0; k < 4; k++) totals[k] = rep.totals[k];
     for (size_t i = 0; i < rep.entries.size() && i < cap; i++) out[i] = rep.entries[i];
+    OLA_CATCH
+}
+
+// ------------------------------------------------------------------------------------------------ verification
+// the verifier runs where the per-phase entry points run: on a single-device context
+static void require_context(OlaCtx* ctx);
+static void require_verifier_context(OlaCtx* ctx) {
+    require_context(ctx);
+    require(ctx->peers.empty() && ctx->dev.shard.world <= 1, "the verifier runs on single-device contexts");
+}
+static double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int32_t ola_verify_all_proof(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, const uint64_t* params, const uint8_t* proof,
+                             size_t proof_len, OlaVerifyReport* report) {
+    OLA_TRY
+    require(airset && proof && report, "null pointer");
+    require_verifier_context(ctx);
+    OLA_ON_DEVICE(ctx);
+    const auto t0 = std::chrono::steady_clock::now();
+    const vfy::Stage st = vfy::all_proof_stage(vfy::config_of(ctx->cfg), (const u64*)airset, airset_words, (const u64*)params, proof, proof_len);
+    OlaVerifyReport rep;
+    memset(&rep, 0, sizeof(rep));
+    rep.host_ms = ms_since(t0);
+    verify_on_device(&ctx->dev, st, &rep);
+    *report = rep;
+    OLA_CATCH
+}
+
+int32_t ola_verify_opening(OlaCtx* ctx, const uint64_t* caps, const uint32_t num_polys[3], uint32_t degree_bits, uint32_t num_permutation_zs,
+                           const uint8_t* proof, size_t proof_len, OlaChallenger* challenger, OlaVerifyReport* report) {
+    OLA_TRY
+    require(caps && num_polys && proof && challenger && report, "null pointer");
+    require_verifier_context(ctx);
+    OLA_ON_DEVICE(ctx);
+    require(challenger->hasher == ctx->cfg.hasher, "the challenger was not initialised for this context's hasher (ola_challenger_init_hasher)");
+    require(challenger->input_len <= 8 && challenger->output_len <= 8, "challenger");
+    const auto t0 = std::chrono::steady_clock::now();
+    const vfy::Stage st = vfy::opening_stage(vfy::config_of(ctx->cfg), (const u64*)caps, num_polys, degree_bits, num_permutation_zs, proof, proof_len, *challenger);
+    OlaVerifyReport rep;
+    memset(&rep, 0, sizeof(rep));
+    rep.host_ms = ms_since(t0);
+    verify_on_device(&ctx->dev, st, &rep);
+    if (rep.accepted) *challenger = st.transcript;       // where the prover's stands after ola_open_and_prove
+    *report = rep;
     OLA_CATCH
 }
 

@@ -289,6 +289,11 @@ PY
     quotient)    # the quotient kernels (generated and interpreter) word for word against the integer reference, at caller-chosen challenges
                  ( set -o pipefail
                    timeout -k 10 600 python -m pytest tests/test_gpu_quotient.py -q --durations=12 2>&1 | tail -30 | tee $O/pytest.log ) ;;
+    verify)      # ola_verify_all_proof / ola_verify_opening: their tests, then the host and the device stage on 2^22-row proofs against the oracle's verifier on the same bytes
+                 ( set -o pipefail
+                   timeout -k 10 900 python -m pytest tests/test_gpu_verify.py tests/test_gpu_host_verify_api.py -q --durations=12 2>&1 | tail -30 | tee $O/pytest.log && \
+                   OLA_HASHER=blake3 timeout -k 10 600 python tools/bench_verify.py 22 5 --json $O/verify_blake3.json 2>&1 | grep -v amdgpu | tee $O/verify_blake3.txt && \
+                   OLA_HASHER=poseidon timeout -k 10 600 python tools/bench_verify.py 22 5 --json $O/verify_poseidon.json 2>&1 | grep -v amdgpu | tee $O/verify_poseidon.txt ) ;;
     *)           echo "unknown step $step" ;;
   esac
 done
