@@ -51,7 +51,7 @@ TABLEGEN_COLUMNS_H = "olavm_amd/csrc/tablegen_columns.h"
 
 def tablegen_columns_header():
     """The checked header olavm_amd/csrc/tablegen_columns.h: column indices of the range-check, bitwise and program tables and the three
-    bitwise opcode masks, for the device-side table generators in olavm_amd/csrc/lookup.hip.  The file is committed (lookup.hip is compiled
+    bitwise opcode masks, for the device-side table generators in olavm_amd/csrc/tablegen.hip.  The file is committed (tablegen.hip is compiled
     before anything is generated); tests/test_tablegen_abi.py compares it with this text.  Regenerate:
         python -c "from olavm_amd.air import dump; print(dump.tablegen_columns_header(), end='')" > olavm_amd/csrc/tablegen_columns.h"""
     from . import ola_tables as T
@@ -79,7 +79,7 @@ CPU_STEP_WORDS = 66      # include/ola_gpu.h OLA_CPU_STEP_WORDS; olavm_amd/air/c
 
 def tablegen_cpu_columns_header():
     """The checked header olavm_amd/csrc/tablegen_cpu_columns.h: every column index of the CPU table, the bit position of every opcode
-    mask and the layout of a step record, for ola_generate_cpu_trace / ola_generate_prog_trace_steps in olavm_amd/csrc/lookup.hip (the
+    mask and the layout of a step record, for ola_generate_cpu_trace / ola_generate_prog_trace_steps in olavm_amd/csrc/tablegen.hip (the
     program table's indices are in tablegen_columns.h).  Committed like its sibling; tests/test_cpu_tablegen_abi.py compares it with
     this text.  Regenerate:
         python -c "from olavm_amd.air import dump; print(dump.tablegen_cpu_columns_header(), end='')" > olavm_amd/csrc/tablegen_cpu_columns.h"""
@@ -116,7 +116,7 @@ MEM_OPS = ("CALL", "MLOAD", "MSTORE", "POSEIDON", "RET", "SLOAD", "SSTORE", "TLO
 def tablegen_mem_columns_header():
     """The checked header olavm_amd/csrc/tablegen_mem_columns.h: the column indices of the memory and comparison tables, the start of the
     heap region and the nine op masks of a memory cell with their ranks, for ola_generate_memory_trace / ola_generate_cmp_trace in
-    olavm_amd/csrc/lookup.hip.  Committed like its siblings; tests/test_mem_tablegen_abi.py compares it with this text.  Regenerate:
+    olavm_amd/csrc/tablegen.hip.  Committed like its siblings; tests/test_mem_tablegen_abi.py compares it with this text.  Regenerate:
         python -c "from olavm_amd.air import dump; print(dump.tablegen_mem_columns_header(), end='')" > olavm_amd/csrc/tablegen_mem_columns.h"""
     from . import ola_tables as T
     assert list(MEM_OPS) == sorted(MEM_OPS)
@@ -166,7 +166,7 @@ POSEIDON_CALL_WORDS = 5      # include/ola_gpu.h OLA_POSEIDON_CALL_WORDS: clk, s
 def tablegen_small_columns_header():
     """The checked header olavm_amd/csrc/tablegen_small_columns.h: the column indices of the tape, Poseidon-chunk, program-chunk and SCCALL
     tables, where the Poseidon table keeps a permutation's inputs and outputs, the two opcode masks and the layout of a tape cell and of
-    a POSEIDON call record, for ola_generate_tape_trace / _poseidon_chunk_trace / _prog_chunk_trace in olavm_amd/csrc/lookup.hip.
+    a POSEIDON call record, for ola_generate_tape_trace / _poseidon_chunk_trace / _prog_chunk_trace in olavm_amd/csrc/tablegen.hip.
     Committed like its siblings; tests/test_small_tablegen_abi.py compares it with this text.  Regenerate:
         python -c "from olavm_amd.air import dump; print(dump.tablegen_small_columns_header(), end='')" > olavm_amd/csrc/tablegen_small_columns.h"""
     from . import ola_tables as T

@@ -69,7 +69,7 @@ def test_column_header_of_the_kernels_is_the_table_description():
     for lo, hi in re.findall(r"constexpr uint32_t COL_\w+_START = (\d+)u, COL_\w+_END = (\d+)u;", text):
         covered += range(int(lo), int(hi))
     assert sorted(covered) == list(range(T.NUM_CPU_COLS))                # every column of the CPU table, once
-    src = open(os.path.join(ROOT, "olavm_amd", "csrc", "lookup.hip")).read()
+    src = open(os.path.join(ROOT, "olavm_amd", "csrc", "tablegen.hip")).read()
     assert '#include "tablegen_cpu_columns.h"' in src
     gen = src[src.index("cpu_fill_kernel"):]
     assert not re.search(r"\bout \+ \(size_t\)\d+ \* n|\bout\[\(size_t\)\d+ \* n", gen), "a column index was typed in"

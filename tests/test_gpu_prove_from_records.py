@@ -130,3 +130,50 @@ def test_a_cpu_table_too_small_for_the_steps_is_refused_by_name(backends, stark,
         be.prove_from_records(stark.blob(), unknown, **kw)
     assert "Poseidon-chunk table" in str(e.value)
     assert be.prove_from_records(stark.blob(), rec, **kw) == bytes(be.prove_with_traces(stark.blob(), traces, params, compress))
+
+
+def refused_then_builds(be, instance, bad, message, table):
+    """`bad` is refused with exactly `message` behind the name of its step; the untouched records then give miniexec's `table` on the
+    same context"""
+    from olavm_amd.backend import OlaGpuError
+    (traces, params, compress), rec, kw = instance
+    with pytest.raises(OlaGpuError) as e:
+        be.tables_from_records(bad, **kw)
+    assert e.value.code == OLA_E_INVALID_ARG and str(e.value) == "ola_gpu error -1: " + message
+    ts = be.tables_from_records(rec, **kw)
+    try:
+        assert np.array_equal(ts.tables[table].to_host(), traces[table])
+    finally:
+        ts.free()
+
+
+def test_an_unknown_flag_in_an_access_record_is_refused_by_the_storage_step(backends, instances):
+    rec = instances["storage"][1]
+    bad = dict(rec)
+    bad["accesses"] = rec["accesses"].copy()
+    assert bad["accesses"].shape[1] > 1
+    bad["accesses"][12, 1] |= np.uint64(8)                                              # bit 3 of the flags word: not a flag
+    refused_then_builds(backends["poseidon"], instances["storage"], bad,
+                        "storage-access table: invalid argument: unknown flag in an access record", T.STORAGE_ACCESS)
+
+
+def test_a_poseidon_call_of_length_0_is_refused_by_the_chunk_step(backends, instances):
+    rec = instances["hash"][1]
+    bad = dict(rec)
+    bad["psdn_calls"] = rec["psdn_calls"].copy()
+    assert bad["psdn_calls"].shape[1] > 0
+    bad["psdn_calls"][2, 0] = 0                                                         # len
+    refused_then_builds(backends["poseidon"], instances["hash"], bad,
+                        "Poseidon-chunk table: invalid argument: a POSEIDON call of length 0", T.POSEIDON_CHUNK)
+
+
+def test_a_program_table_too_small_for_the_executed_rows_is_refused_by_the_program_step(backends, instances):
+    (traces, _, _), rec, _ = instances["mixed"]
+    exec_rows = int(traces[T.PROGRAM][T.COL_PROG_FILTER_EXEC].sum())
+    bad = dict(rec)
+    bad["prog_log_n"] = (exec_rows - 1).bit_length() - 1                                # one below what the executed rows need
+    assert 1 <= bad["prog_log_n"] < rec["prog_log_n"] and exec_rows > 1 << bad["prog_log_n"]
+    bad["listing"] = np.ascontiguousarray(rec["listing"][:, :1 << bad["prog_log_n"]])
+    refused_then_builds(backends["poseidon"], instances["mixed"], bad,
+                        "program table: invalid argument: the steps give more executed rows than 2^log_n (the count is in *exec_rows_out)",
+                        T.PROGRAM)

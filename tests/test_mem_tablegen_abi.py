@@ -82,7 +82,7 @@ def test_column_header_of_the_kernels_is_the_table_description():
     mem = sorted(int(v) for v in re.findall(r"constexpr uint32_t COL_MEM_\w+ = (\d+)u;", text))
     cmp_ = sorted(int(v) for v in re.findall(r"constexpr uint32_t COL_CMP_\w+ = (\d+)u;", text))
     assert mem == list(range(T.NUM_MEM_COLS)) and cmp_ == list(range(T.COL_NUM_CMP))          # every column of both tables, once
-    src = open(os.path.join(ROOT, "olavm_amd", "csrc", "lookup.hip")).read()
+    src = open(os.path.join(ROOT, "olavm_amd", "csrc", "tablegen.hip")).read()
     assert '#include "tablegen_mem_columns.h"' in src
     gen = src[src.index("mem_op_key"):src.index("u32 log2_rows")]
     assert not re.search(r"\bout \+ \(size_t\)\d+ \* n|\bout\[\(size_t\)\d+ \* n|put\(\d", gen), "a column index was typed in"

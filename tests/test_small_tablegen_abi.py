@@ -99,7 +99,7 @@ def test_column_header_of_the_kernels_is_the_table_description():
     assert "NUM_COL_TAPE = 6u, NUM_POSEIDON_CHUNK_COLS = 53u, NUM_PROG_CHUNK_COLS = 40u, NUM_COL_SCCALL = 26u;" in text
     assert "NUM_POSEIDON_COLS = %du;" % T.NUM_POSEIDON_COLS in text
     assert "OP_MASK_TLOAD = %dull;" % T.op_mask("TLOAD") in text and "OP_MASK_POSEIDON = %dull;" % T.op_mask("POSEIDON") in text
-    src = open(os.path.join(ROOT, "olavm_amd", "csrc", "lookup.hip")).read()
+    src = open(os.path.join(ROOT, "olavm_amd", "csrc", "tablegen.hip")).read()
     assert '#include "tablegen_small_columns.h"' in src
     new = src[src.index("// ---- the tape, Poseidon-chunk and program-chunk tables"):src.index("u32 log2_rows(")]
     assert "tx::COL_TAPE_ADDR" in new and not re.search(r"\bout\[\(size_t\)\d+ \* n|\bv\[\d", new), "a column index was typed in"

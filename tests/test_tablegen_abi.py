@@ -58,18 +58,17 @@ def test_symbols_are_exported_and_declared_with_equal_arity(lib):
 
 
 def test_column_header_of_the_kernels_is_the_table_description():
-    """olavm_amd/csrc/tablegen_columns.h is committed (lookup.hip is compiled before anything is generated): it must be what
-    olavm_amd/air/dump.py prints from ola_tables.py today, and lookup.hip must take its indices from there."""
+    """olavm_amd/csrc/tablegen_columns.h is committed (tablegen.hip is compiled before anything is generated): it must be what
+    olavm_amd/air/dump.py prints from ola_tables.py today, and tablegen.hip must take its indices from there."""
     from olavm_amd.air import dump, ola_tables as T
     text = open(os.path.join(ROOT, dump.TABLEGEN_COLUMNS_H)).read()
     assert text == dump.tablegen_columns_header()
     assert "constexpr uint32_t RC_LIMB_HI_PERMUTED = %du;" % T.RC_LIMB_HI_PERMUTED in text
     assert "constexpr uint32_t BW_FIX_COMPRESS_PERMUTED_START = %du" % T.BW_FIX_COMPRESS_PERMUTED.start in text
     assert "constexpr uint64_t OP_MASK_XOR = %dull;" % T.op_mask("XOR") in text
-    src = open(os.path.join(ROOT, "olavm_amd", "csrc", "lookup.hip")).read()
+    src = open(os.path.join(ROOT, "olavm_amd", "csrc", "tablegen.hip")).read()
     assert '#include "tablegen_columns.h"' in src
-    gen = src[src.index("table generators"):]
-    assert not re.search(r"\bout \+ \(size_t\)\d+ \* n|\bout\[\(size_t\)\d+ \* n", gen), "a column index was typed in"
+    assert not re.search(r"\bout \+ \(size_t\)\d+ \* n|\bout\[\(size_t\)\d+ \* n", src), "a column index was typed in"
 
 
 def test_sizing_call_needs_no_context(lib):
