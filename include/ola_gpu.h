@@ -56,7 +56,8 @@ extern "C" {
  * table); so were OlaExecRecords, ola_tables_from_records, ola_tables_get, ola_tables_free and ola_prove_from_records (the twelve
  * generators composed in one call, from the executor's records to resident tables and to proof bytes); so were OlaVerifyReport, the
  * OLA_VERIFY_* reasons and the entry points ola_verify_all_proof and ola_verify_opening (proof bytes to a verdict with the place and
- * the reason of a refusal). */
+ * the reason of a refusal); so were the hasher OLA_HASH_KECCAK (KeccakGoldilocksConfig: Keccak-256 trees and challenger, 25-byte
+ * digests) and the host entry points ola_keccak_hash_elements and ola_challenger_init_keccak. */
 #define OLA_GPU_ABI_VERSION 7
 #define OLA_OK 0
 #define OLA_E_INVALID_ARG (-1)
@@ -88,14 +89,21 @@ typedef struct OlaGpuConfig {
                                  * and proof of work all Poseidon2 (hash/poseidon2.rs:50); OLA_HASH_POSEIDON2_POW_POSEIDON =
                                  * Poseidon2GoldilocksConfig2 (plonk/config.rs:135): Poseidon2 trees and challenger, Poseidon
                                  * proof of work.
+                                 * OLA_HASH_KECCAK = KeccakGoldilocksConfig (plonk/config.rs:145): Merkle trees and challenger on
+                                 * Keccak-256 truncated to 25 bytes (hash/keccak.rs, KeccakHash<25>), Poseidon proof of work.  A
+                                 * digest keeps 4 words in memory (word 3 = byte 24, upper 56 bits zero) and is 25 bytes in a proof.
+                                 * The value 4 is unassigned and refused.
                                  * The field takes the place of the struct's tail padding: sizeof is unchanged.             */
 } OlaGpuConfig;
 #define OLA_HASH_POSEIDON 0u
 #define OLA_HASH_BLAKE3 1u
 #define OLA_HASH_POSEIDON2 2u
 #define OLA_HASH_POSEIDON2_POW_POSEIDON 3u
+#define OLA_HASH_KECCAK 5u /* 4 is not a hasher */
 
 /* ---- lifetime (replaces gpu_init / gpu_free, cfft/ntt/mod.rs:89-121 and core/src/storage/db.rs:248) ---- */
+/* The configuration is validated before a device is looked for: OLA_E_INVALID_ARG for a value out of range (an unassigned hasher
+ * among them) with or without a device, OLA_E_NO_DEVICE for a valid configuration on a machine without one. */
 int32_t ola_gpu_init(const OlaGpuConfig* cfg, OlaCtx** out_ctx);
 /* OLA_GPU_ABI_VERSION of the library that was loaded; *challenger_size / *config_size (may be NULL) receive its sizeof(OlaChallenger)
  * and sizeof(OlaGpuConfig). */
@@ -309,6 +317,7 @@ int32_t ola_ntt_batch_dev(OlaCtx* ctx, int32_t op, const uint64_t* in_dev, uint6
 /* ---- Poseidon / Merkle: replaces hash/poseidon.rs:593-603, hashing.rs:84-111, merkle_tree/mod.rs:180-337 --
  * ola_hash_rows, ola_merkle_cap and every commitment hash with the context's Hasher: the Poseidon sponge, the Poseidon2 sponge
  * under OLA_HASH_POSEIDON2 / OLA_HASH_POSEIDON2_POW_POSEIDON (the same sponge and tree, hash/poseidon2.rs:500-512), or under
+ * OLA_HASH_KECCAK KeccakHash<25> (hash/keccak.rs; word 3 of a digest is byte 24 alone), or under
  * OLA_HASH_BLAKE3 Blake3_256 (hash/blake3.rs:203-233) of the canonical little-endian words; a digest is 4 words (32 bytes)
  * either way, and a Blake3 digest is bytes -- its words may be >= p and are never reduced. */
 /* n states of 12 elements each, permuted in place (host memory). */
@@ -363,18 +372,25 @@ typedef struct OlaChallenger {
     uint64_t output_buffer[8];
     uint32_t input_len;
     uint32_t output_len;
-    uint32_t hasher;            /* OLA_HASH_*: the permutation (Poseidon, Poseidon2, or Blake3Permutation, hash/blake3.rs:166-201) and */
+    uint32_t hasher;            /* OLA_HASH_*: the permutation (Poseidon, Poseidon2, Blake3Permutation or KeccakPermutation) and       */
     uint32_t reserved;          /* how a digest is observed; set by the init calls, do not change afterwards                 */
 } OlaChallenger;
 
 int32_t ola_challenger_init(OlaChallenger* ch);                          /* Challenger::<F, PoseidonHash>::new()          */
-int32_t ola_challenger_init_hasher(OlaChallenger* ch, uint32_t hasher);  /* Challenger::<F, C::Hasher>::new()             */
+int32_t ola_challenger_init_hasher(OlaChallenger* ch, uint32_t hasher);  /* Challenger::<F, C::Hasher>::new(), hashers 0..3 */
+/* Challenger::<F, KeccakHash<25>>::new(): the transcript of OLA_HASH_KECCAK.  Its own entry point: ola_challenger_init_hasher keeps
+ * the range of values it was published with (0..3) and refuses every other, 5 included. */
+int32_t ola_challenger_init_keccak(OlaChallenger* ch);
 /* observe_cap (iop/challenger.rs:75-84) of n digests of 4 words: a Poseidon digest is 4 elements, a Blake3 digest is observed
- * as the 5 elements BytesHash::to_vec cuts it into (7 bytes each, hash/hash_types.rs:142-152). */
+ * as the 5 elements BytesHash::to_vec cuts it into (7 bytes each, hash/hash_types.rs:142-152), a Keccak digest (25 bytes: words
+ * 0..2 and the low byte of word 3) as 4 elements of 7, 7, 7 and 4 bytes. */
 int32_t ola_challenger_observe_cap(OlaChallenger* ch, const uint64_t* digests, size_t n);
 /* Blake3_256::hash_no_pad of n field elements as this backend computes it on the device (canonical little-endian words,
  * hash/blake3.rs:203-213), on the host: for digests the integrator needs outside a proof, and the CPU-side test of the kernel code. */
 int32_t ola_blake3_hash_elements(const uint64_t* elems, size_t n, uint64_t out[4]);
+/* KeccakHash<25>::hash_no_pad of n field elements (1..4096) the same way (hash/keccak.rs: the first 25 bytes of Keccak-256 -- original
+ * padding, not SHA3-256 -- of the canonical little-endian words), on the host: out[0..2] are bytes 0..23, out[3] is byte 24. */
+int32_t ola_keccak_hash_elements(const uint64_t* elems, size_t n, uint64_t out[4]);
 int32_t ola_challenger_observe(OlaChallenger* ch, const uint64_t* elems, size_t n);
 int32_t ola_challenger_get(OlaChallenger* ch, uint64_t* out, size_t n);
 int32_t ola_challenger_compact(OlaChallenger* ch);
@@ -899,7 +915,7 @@ int32_t ola_prove_from_records(OlaCtx* ctx, const uint64_t* airset, size_t airse
 
 /* ---- verification: proof bytes to a verdict ------------------------------------------------------------------------------------
  * ola_verify_all_proof is the reference's `verify_proof` (circuits/src/stark/verifier.rs:35) for the context's configuration: the
- * hasher of the Merkle trees and the transcript is the context's (all four OLA_HASH_*, the proof-of-work hasher as in ola_pow), the
+ * hasher of the Merkle trees and the transcript is the context's (every OLA_HASH_*, the proof-of-work hasher as in ola_pow), the
  * FRI parameters are the context's OlaGpuConfig.  In the reference's order: get_challenges, CtlCheckVars::from_proofs, then per
  * table validate_proof_shape, eval_vanishing_poly over the extension field at zeta, the quotient identity and plonky2's
  * verify_fri_proof, and verify_cross_table_lookups last.
@@ -923,7 +939,7 @@ int32_t ola_prove_from_records(OlaCtx* ctx, const uint64_t* airset, size_t airse
  * assume canonical input.  The words of a Blake3 digest are bytes, not field elements, and may take any value.
  * Leaves are hashed by the rule of this library's commitments: hash_no_pad of the row for every width, rows of four words or fewer
  * included, as MerkleTree::new_v2 (hash/merkle_tree/mod.rs:180-266) and verify_merkle_proof_to_cap (hash/merkle_proofs.rs:51-80) hash them in
- * the reference; Blake3_256 of the canonical little-endian words under OLA_HASH_BLAKE3. */
+ * the reference; Blake3_256 / KeccakHash<25> of the canonical little-endian words under OLA_HASH_BLAKE3 / OLA_HASH_KECCAK. */
 #define OLA_VERIFY_OK 0u
 #define OLA_VERIFY_MALFORMED 1u                 /* truncated, trailing bytes, a word >= p, wrong number of table proofs        */
 #define OLA_VERIFY_EMPTY_FRI 2u                 /* no query round or no initial tree to take the degree from                   */

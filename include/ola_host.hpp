@@ -64,7 +64,7 @@ inline uint32_t log2_strict(size_t n) {   // util/src/lib.rs log2_strict: panics
 struct StarkConfig {
     uint32_t rate_bits = 3, cap_height = 4, proof_of_work_bits = 16, fri_arity_bits = 4, fri_final_poly_bits = 5, num_query_rounds = 28,
              num_challenges = 2;
-    // GenericConfig::Hasher (plonk/config.rs:112-161): OLA_HASH_POSEIDON = PoseidonGoldilocksConfig, OLA_HASH_BLAKE3 = Blake3GoldilocksConfig
+    // GenericConfig::Hasher (plonk/config.rs:112-161): OLA_HASH_POSEIDON = PoseidonGoldilocksConfig, OLA_HASH_BLAKE3 = Blake3GoldilocksConfig, OLA_HASH_KECCAK = KeccakGoldilocksConfig
     // OLA_HASH_POSEIDON2 = Poseidon2GoldilocksConfig, OLA_HASH_POSEIDON2_POW_POSEIDON = Poseidon2GoldilocksConfig2
     uint32_t hasher = OLA_HASH_POSEIDON;
     static StarkConfig standard_fast_config() { return StarkConfig{}; }
@@ -235,7 +235,9 @@ public:
 class Challenger {
 public:
     Challenger() { check(ola_challenger_init(&ch_)); }                                                        // :37
-    explicit Challenger(const Gpu& g) { check(ola_challenger_init_hasher(&ch_, g.config.hasher)); }           // Challenger::<F, C::Hasher>::new()
+    explicit Challenger(const Gpu& g) {                                                                       // Challenger::<F, C::Hasher>::new()
+        check(g.config.hasher == OLA_HASH_KECCAK ? ola_challenger_init_keccak(&ch_) : ola_challenger_init_hasher(&ch_, g.config.hasher));
+    }
     void observe_element(F e) { check(ola_challenger_observe(&ch_, &e, 1)); }                                  // :46
     void observe_elements(const std::vector<F>& es) { check(ola_challenger_observe(&ch_, es.data(), es.size())); }   // :64
     void observe_hash(const HashOut& h) { check(ola_challenger_observe_cap(&ch_, h.data(), 1)); }              // :79

@@ -46,10 +46,10 @@ def write_traces(path, traces, compress):
         f.write(struct.pack("<I", len(compress)) + b"".join(struct.pack("<Q", int(c)) for c in compress))
 
 
-def parse_all_proof(raw, blob=None):
+def parse_all_proof(raw, blob=None, digest_bytes=32):
     """The spans of an AllProof in the reference wire format (circuits/src/stark/serialization.rs:349-393 write_proof /
     write_all_proof), in the order the prover produces them: [(name, start, end)], tiling `raw` exactly.  Digests are 32 bytes
-    under either hash configuration.  Used to say WHICH phase of WHICH table differs first."""
+    under the Poseidon, Poseidon2 and Blake3 configurations, digest_bytes = 25 under KeccakGoldilocksConfig.  Used to say WHICH phase of WHICH table differs first."""
     import struct as st
     spans, off = [], 0
 
@@ -68,7 +68,7 @@ def parse_all_proof(raw, blob=None):
 
     def cap(name):
         n = u32()
-        span(name, 32 * n)
+        span(name, digest_bytes * n)
 
     def ext_vec(name):
         n = u32()
@@ -82,7 +82,7 @@ def parse_all_proof(raw, blob=None):
         nonlocal off
         depth = raw[off]
         off += 1
-        span(name, 32 * depth)
+        span(name, digest_bytes * depth)
 
     nt = u32()
     for t in range(nt):

@@ -8,7 +8,7 @@
 //! and is decoded with `Buffer::read_all_proof` (:394-412).  The `timed!` scopes of the CPU prover come back with the GPU's
 //! times and are replayed into the caller's `TimingTree`.  The executor / client path above (`client/src/main.rs:174-214`,
 //! `circuits/benches/fibo_loop.rs:72-91`) does not change.  The hash configuration is the caller's `C`:
-//! `PoseidonGoldilocksConfig` or `Blake3GoldilocksConfig`.
+//! `PoseidonGoldilocksConfig`, `Blake3GoldilocksConfig` or `KeccakGoldilocksConfig`.
 use std::any::type_name;
 use std::ffi::CStr;
 use std::sync::{Mutex, OnceLock};
@@ -78,7 +78,9 @@ struct CtxKey {
 /// that many devices and the partition and its exchanges happen inside the library (`OLA_COLLECTIVE` = peer | rccl selects who
 /// moves the bytes).  The guard is held for the whole proof.
 fn with_ctx<R>(hasher: u32, config: &StarkConfig, body: impl FnOnce(*mut OlaCtx) -> Result<R>) -> Result<R> {
-    static CTX: [OnceLock<Mutex<Option<(SendPtr, CtxKey)>>>; 4] = [OnceLock::new(), OnceLock::new(), OnceLock::new(), OnceLock::new()];
+    // one slot per OLA_HASH_* value, 0..=OLA_HASH_KECCAK (4 is unassigned and stays empty)
+    static CTX: [OnceLock<Mutex<Option<(SendPtr, CtxKey)>>>; 6] =
+        [OnceLock::new(), OnceLock::new(), OnceLock::new(), OnceLock::new(), OnceLock::new(), OnceLock::new()];
     let mut slot = CTX[hasher as usize].get_or_init(|| Mutex::new(None)).lock().unwrap_or_else(|e| e.into_inner());
     let fri = &config.fri_config;
     // the library folds with one arity; StarkConfig::standard_fast_config is ConstantArityBits(4, 5) (config.rs:18-30)
@@ -171,6 +173,9 @@ fn hasher_of<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, const D: 
         Ok(OLA_HASH_POSEIDON)
     } else if name.contains("Blake3") {
         Ok(OLA_HASH_BLAKE3)
+    } else if name.contains("KeccakHash<25>") {
+        // KeccakGoldilocksConfig (plonk/config.rs:145-151); another truncation is another wire format the backend does not write
+        Ok(OLA_HASH_KECCAK)
     } else {
         Err(anyhow::anyhow!("the hip backend has no Merkle hasher for {name}"))
     }

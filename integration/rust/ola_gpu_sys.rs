@@ -30,6 +30,8 @@ pub const OLA_HASH_BLAKE3: u32 = 1;
 pub const OLA_HASH_POSEIDON2: u32 = 2;
 /// Poseidon2GoldilocksConfig2 (plonk/config.rs:133-141): Poseidon2 trees and transcript, Poseidon proof of work
 pub const OLA_HASH_POSEIDON2_POW_POSEIDON: u32 = 3;
+/// KeccakGoldilocksConfig (plonk/config.rs:145-151): Keccak-256 trees and transcript (25-byte digests), Poseidon proof of work; 4 is unassigned
+pub const OLA_HASH_KECCAK: u32 = 5;
 pub const OLA_NTT_EVALUATE: i32 = 0;
 pub const OLA_NTT_INTERPOLATE: i32 = 1;
 pub const OLA_NTT_COSET_LDE: i32 = 2;
@@ -312,8 +314,10 @@ extern "C" {
     pub fn ola_batch_get_lde_row(ctx: *mut OlaCtx, batch: *const OlaBatch, index: usize, step: usize, row_out: *mut u64) -> i32;
     pub fn ola_challenger_init(ch: *mut OlaChallenger) -> i32;
     pub fn ola_challenger_init_hasher(ch: *mut OlaChallenger, hasher: u32) -> i32;
+    pub fn ola_challenger_init_keccak(ch: *mut OlaChallenger) -> i32;
     pub fn ola_challenger_observe_cap(ch: *mut OlaChallenger, digests: *const u64, n: usize) -> i32;
     pub fn ola_blake3_hash_elements(elems: *const u64, n: usize, out: *mut u64) -> i32;
+    pub fn ola_keccak_hash_elements(elems: *const u64, n: usize, out: *mut u64) -> i32;
     pub fn ola_challenger_observe(ch: *mut OlaChallenger, elems: *const u64, n: usize) -> i32;
     pub fn ola_challenger_get(ch: *mut OlaChallenger, out: *mut u64, n: usize) -> i32;
     pub fn ola_challenger_compact(ch: *mut OlaChallenger) -> i32;

@@ -155,9 +155,11 @@ class OlaChallenger(C.Structure):
 # GenericConfig::Hasher (plonk/config.rs:112-161): PoseidonGoldilocksConfig / Blake3GoldilocksConfig / Poseidon2GoldilocksConfig /
 # Poseidon2GoldilocksConfig2 (Poseidon2 trees and transcript, Poseidon proof of work)
 OLA_HASH_POSEIDON, OLA_HASH_BLAKE3, OLA_HASH_POSEIDON2, OLA_HASH_POSEIDON2_POW_POSEIDON = 0, 1, 2, 3
+OLA_HASH_KECCAK = 5   # 4 is unassigned
 HASHERS = {"poseidon": OLA_HASH_POSEIDON, "blake3": OLA_HASH_BLAKE3, "poseidon2": OLA_HASH_POSEIDON2,
            "poseidon2_pow_poseidon": OLA_HASH_POSEIDON2_POW_POSEIDON, OLA_HASH_POSEIDON: OLA_HASH_POSEIDON, OLA_HASH_BLAKE3: OLA_HASH_BLAKE3,
-           OLA_HASH_POSEIDON2: OLA_HASH_POSEIDON2, OLA_HASH_POSEIDON2_POW_POSEIDON: OLA_HASH_POSEIDON2_POW_POSEIDON}
+           OLA_HASH_POSEIDON2: OLA_HASH_POSEIDON2, OLA_HASH_POSEIDON2_POW_POSEIDON: OLA_HASH_POSEIDON2_POW_POSEIDON,
+           "keccak": OLA_HASH_KECCAK, OLA_HASH_KECCAK: OLA_HASH_KECCAK}
 
 
 def lib_path():
@@ -216,8 +218,10 @@ def load_library():
     L.ola_batch_get_lde_row.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, U64P]
     L.ola_challenger_init.argtypes = [C.POINTER(OlaChallenger)]
     L.ola_challenger_init_hasher.argtypes = [C.POINTER(OlaChallenger), C.c_uint32]
+    L.ola_challenger_init_keccak.argtypes = [C.POINTER(OlaChallenger)]
     L.ola_challenger_observe_cap.argtypes = [C.POINTER(OlaChallenger), U64P, C.c_size_t]
     L.ola_blake3_hash_elements.argtypes = [U64P, C.c_size_t, U64P]
+    L.ola_keccak_hash_elements.argtypes = [U64P, C.c_size_t, U64P]
     L.ola_challenger_observe.argtypes = [C.POINTER(OlaChallenger), U64P, C.c_size_t]
     L.ola_challenger_get.argtypes = [C.POINTER(OlaChallenger), U64P, C.c_size_t]
     L.ola_challenger_compact.argtypes = [C.POINTER(OlaChallenger)]
@@ -310,7 +314,7 @@ EXPORTS = [
     "ola_poseidon_permute", "ola_poseidon2_permute", "ola_hash_rows", "ola_merkle_cap", "ola_commit_values", "ola_commit_coeffs",
     "ola_commit_values_dev", "ola_commit_coeffs_dev", "ola_batch_free", "ola_batch_shape", "ola_batch_get_coeffs",
     "ola_batch_get_leaf", "ola_batch_get_lde_row", "ola_challenger_init", "ola_challenger_observe",
-    "ola_challenger_get", "ola_challenger_compact", "ola_challenger_init_hasher", "ola_challenger_observe_cap", "ola_blake3_hash_elements", "ola_open_and_prove", "ola_pow", "ola_prove_with_traces",
+    "ola_challenger_get", "ola_challenger_compact", "ola_challenger_init_hasher", "ola_challenger_init_keccak", "ola_challenger_observe_cap", "ola_blake3_hash_elements", "ola_keccak_hash_elements", "ola_open_and_prove", "ola_pow", "ola_prove_with_traces",
     "ola_air_kernels_available", "ola_commit_values_shard", "ola_commit_values_shard_dev", "ola_set_shard", "ola_gpu_trim", "ola_generate_poseidon_trace",
     "ola_permuted_cols", "ola_permuted_cols_dev", "ola_prove_single_table", "ola_take_pending_proof", "ola_gpu_memory_stats", "ola_gpu_selftest", "ola_gpu_reserve",
     "ola_table_shape", "ola_perm_z", "ola_ctl_z", "ola_quotient", "ola_set_shard_options", "ola_gpu_get_stream",
@@ -445,12 +449,15 @@ class Challenger:
     def __init__(self, lib=None, hasher="poseidon"):
         self.lib = lib or load_library()
         self.c = OlaChallenger()
-        rc = self.lib.ola_challenger_init_hasher(C.byref(self.c), HASHERS[hasher])
+        if HASHERS[hasher] == OLA_HASH_KECCAK:          # its own entry point: ola_challenger_init_hasher takes 0..3 only
+            rc = self.lib.ola_challenger_init_keccak(C.byref(self.c))
+        else:
+            rc = self.lib.ola_challenger_init_hasher(C.byref(self.c), HASHERS[hasher])
         if rc != 0:
             raise OlaGpuError(rc, self.lib.ola_gpu_last_error().decode())
 
     def observe_cap(self, digests):
-        """observe_cap: 4 elements per Poseidon digest, 5 (7 bytes each) per Blake3 digest."""
+        """observe_cap: 4 elements per Poseidon digest, 5 (7 bytes each) per Blake3 digest, 4 (7, 7, 7 and 4 bytes) per Keccak digest."""
         d = np.ascontiguousarray(digests, dtype=np.uint64).reshape(-1, 4)
         self.lib.ola_challenger_observe_cap(C.byref(self.c), _p(d), d.shape[0])
 

@@ -7,11 +7,16 @@
 #include "../../include/ola_gpu.h"
 #include "blake3.cuh"
 #include "gl.cuh"
+#include "keccak.cuh"
 #include "ola_error.h"
 #include "poseidon2_host.h"
 #include "poseidon_host.h"
 
 namespace ola {
+
+// bytes of a digest on the wire where the Hasher's digest is bytes (BytesHash<N>::to_bytes, util/serialization.rs:89-97: Blake3_256<32>,
+// KeccakHash<25>), written as they are and never reduced; 0 for a HashOut, which is four canonical field words
+inline int digest_wire_bytes(uint32_t hasher) { return hasher == OLA_HASH_BLAKE3 ? 32 : hasher == OLA_HASH_KECCAK ? KECCAK_DIGEST_BYTES : 0; }
 
 // ------------------------------------------------------------------------------------------------ challenger
 inline void challenger_duplex(OlaChallenger& ch) {
@@ -22,6 +27,7 @@ inline void challenger_duplex(OlaChallenger& ch) {
     switch (ch.hasher) {                                         // H::Permutation of Challenger<F, H> (challenger.rs:134-153)
         case OLA_HASH_POSEIDON: poseidon_permute_host(s); break;
         case OLA_HASH_BLAKE3: b3_permutation_host(s); break;
+        case OLA_HASH_KECCAK: keccak_permutation_host(s); break;
         case OLA_HASH_POSEIDON2:
         case OLA_HASH_POSEIDON2_POW_POSEIDON: poseidon2_permute_host(s); break;
         default: throw OlaError(OLA_E_INTERNAL, "challenger of an unknown hasher");
@@ -39,7 +45,16 @@ inline void challenger_observe(OlaChallenger& ch, const u64* e, size_t n) {
 }
 // observe_cap (challenger.rs:75-84): GenericHashOut::to_vec of every digest
 inline void challenger_observe_cap(OlaChallenger& ch, const u64* digests, size_t n) {
-    // HashOut (Poseidon, Poseidon2): its four elements; Blake3's 32 bytes: five elements of 7 bytes (b3_digest_elements)
+    // HashOut (Poseidon, Poseidon2): its four elements; Blake3's 32 bytes: five elements of 7 bytes (b3_digest_elements); Keccak's 25
+    // bytes: four elements of 7, 7, 7 and 4 bytes (keccak_digest_elements)
+    if (ch.hasher == OLA_HASH_KECCAK) {
+        for (size_t i = 0; i < n; i++) {
+            u64 e[4];
+            keccak_digest_elements(digests + 4 * i, e);
+            challenger_observe(ch, e, 4);
+        }
+        return;
+    }
     if (ch.hasher != OLA_HASH_BLAKE3) { challenger_observe(ch, digests, 4 * n); return; }
     for (size_t i = 0; i < n; i++) {
         u64 e[5];

@@ -694,7 +694,7 @@ static void scan_plane(DevBuf& mem, u64* plane, size_t n, u64* tot) {
 
 struct ByteWriter {
     std::vector<uint8_t>& b;
-    bool bytes_hash = false;   // Blake3 digests are 32 bytes (BytesHash::to_bytes), written as they are; a HashOut is 4 canonical words
+    int bytes_hash = 0;        // digest_wire_bytes: Blake3 digests are 32 bytes, Keccak digests 25 (BytesHash::to_bytes), written as they are; 0: a HashOut is 4 canonical words
     void u8(uint8_t x) { b.push_back(x); }
     void u32(uint32_t x) { for (int i = 0; i < 4; i++) b.push_back((uint8_t)(x >> (8 * i))); }
     void field(u64 x) { x = gl_canon(x); for (int i = 0; i < 8; i++) b.push_back((uint8_t)(x >> (8 * i))); }
@@ -702,10 +702,8 @@ struct ByteWriter {
     void ext_vec(const std::vector<Ext2>& v) { u32((uint32_t)v.size()); for (auto& e : v) ext(e); }
     void field_vec(const u64* v, size_t n) { u32((uint32_t)n); for (size_t i = 0; i < n; i++) field(v[i]); }
     void hash(const u64* h) {
-        for (int i = 0; i < 4; i++) {
-            if (bytes_hash) { for (int k = 0; k < 8; k++) b.push_back((uint8_t)(h[i] >> (8 * k))); }
-            else field(h[i]);
-        }
+        if (bytes_hash) { for (int k = 0; k < bytes_hash; k++) b.push_back((uint8_t)(h[k >> 3] >> (8 * (k & 7)))); return; }
+        for (int i = 0; i < 4; i++) field(h[i]);
     }
     void cap(const u64* c, size_t len) { u32((uint32_t)len); for (size_t i = 0; i < len; i++) hash(c + 4 * i); }
     void merkle_proof(const u64* sib, int depth) { u8((uint8_t)depth); for (int i = 0; i < depth; i++) hash(sib + 4 * i); }
@@ -1117,7 +1115,7 @@ void open_and_prove(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, 
     const Ext2 zeta = challenger_get_ext(ch);
     const OpenPoints pts = open_points(mem, zeta, degree_bits);
     const OpeningSet set = open_set(mem, oracles, pts);
-    ByteWriter w{bytes, ctx->hasher == (int)OLA_HASH_BLAKE3};
+    ByteWriter w{bytes, digest_wire_bytes((uint32_t)ctx->hasher)};
     set.write(w);
     openings_len = bytes.size();
 
@@ -1248,7 +1246,7 @@ static Ext2 ext_arg(const u64 v[2]) { return ext_make(gl_canon(v[0]), gl_canon(v
 void fri_steps_open(OlaFri& f, const u64 zeta[2], std::vector<uint8_t>& bytes) {
     f.pts = open_points(f.mem, ext_arg(zeta), f.degree_bits);
     DevBuf tmp(f.ctx);
-    ByteWriter w{bytes, f.ctx->hasher == (int)OLA_HASH_BLAKE3};
+    ByteWriter w{bytes, digest_wire_bytes((uint32_t)f.ctx->hasher)};
     open_set(tmp, f.oracles, f.pts).write(w);
 }
 
@@ -1303,7 +1301,7 @@ void fri_steps_query(OlaFri& f, const u64* x_index, uint32_t nq, std::vector<uin
         query_layers(tmp, f.commit.layers, 0, f.cfg.cap_height, xs, q);
         tmp.sync_collect();
     }
-    ByteWriter w{bytes, f.ctx->hasher == (int)OLA_HASH_BLAKE3};
+    ByteWriter w{bytes, digest_wire_bytes((uint32_t)f.ctx->hasher)};
     write_query_rounds(w, f.oracles, q);
 }
 

@@ -1,4 +1,5 @@
-// Poseidon-Goldilocks sponge + Merkle tree kernels for gfx950 (and the Blake3 leaves / nodes of Blake3GoldilocksConfig, blake3.cuh).
+// Poseidon-Goldilocks sponge + Merkle tree kernels for gfx950 (and the byte-hash leaves / nodes of Blake3GoldilocksConfig, blake3.cuh,
+// and KeccakGoldilocksConfig, keccak.cuh).
 // The sponge kernels are templates over the permutation: Poseidon (poseidon.cuh) or Poseidon2 (poseidon2.cuh, the Hasher of
 // Poseidon2GoldilocksConfig / Poseidon2GoldilocksConfig2 -- the same sponge and tree, hash/poseidon2.rs:500-512).
 //
@@ -22,6 +23,7 @@
 #include "poseidon.cuh"
 #include "poseidon2.cuh"
 #include "blake3.cuh"
+#include "keccak.cuh"
 
 namespace ola {
 
@@ -308,50 +310,67 @@ __global__ __launch_bounds__(256) void pow_kernel(u64 h0, u64 h1, u64 h2, u64 h3
     if ((s[0] >> (64 - bits)) == 0) atomicMin(best, (unsigned long long)nonce);
 }
 
-// ---- Blake3GoldilocksConfig (blake3.cuh): the same three leaf shapes and the same heap, one thread per leaf / node ----
-// MULTI = leaves of more than one 1024-byte chunk (more than 128 elements: the 134-column Poseidon table); the single-chunk
-// kernels need no stack of chaining values and therefore no scratch memory.
+// ---- Blake3GoldilocksConfig (blake3.cuh) and KeccakGoldilocksConfig (keccak.cuh): the byte hashes.  The same three leaf shapes and
+// the same heap, one thread per leaf / node; one body per kernel, instantiated for either hash (BH).
+// MULTI = Blake3 leaves of more than one 1024-byte chunk (more than 128 elements: the 134-column Poseidon table); the single-chunk
+// kernels need no stack of chaining values and therefore no scratch memory.  Keccak's sponge has no such case (MULTI = false).
+enum : int { BH_BLAKE3 = 0, BH_KECCAK = 1 };
 template <bool MULTI, class WordFn>
 __device__ __forceinline__ void b3_leaf(WordFn word, u32 nwords, u32 (&d)[8]) {
     if (MULTI) b3_hash_words(word, nwords, d);
     else b3_chunk_cv(word, 0, nwords, 0, true, d);
 }
-template <bool MULTI>
-__global__ __launch_bounds__(256) void leaf_b3_colmajor_kernel(const u64* __restrict__ base, size_t col_stride, int ncols,
-                                                               size_t num_leaves, u64* __restrict__ out) {
+// digest of the `nwords` canonical words `word(i)` to out4
+template <int BH, bool MULTI, class WordFn>
+__device__ __forceinline__ void bytes_leaf(WordFn word, u32 nwords, u64* __restrict__ out4) {
+    if constexpr (BH == BH_KECCAK) {
+        u64 d[4];
+        keccak_hash_words(word, nwords, d);
+        ulonglong2* o = reinterpret_cast<ulonglong2*>(out4);
+        o[0] = make_ulonglong2(d[0], d[1]);
+        o[1] = make_ulonglong2(d[2], d[3]);
+    } else {
+        u32 d[8];
+        b3_leaf<MULTI>(word, nwords, d);
+        b3_store_digest(out4, d);
+    }
+}
+template <int BH>
+__device__ __forceinline__ void bytes_node(const u64* __restrict__ children8, u64* __restrict__ out4) {
+    if constexpr (BH == BH_KECCAK) keccak_node(children8, out4);
+    else b3_node(children8, out4);
+}
+template <int BH, bool MULTI>
+__global__ __launch_bounds__(256) void leaf_bytes_colmajor_kernel(const u64* __restrict__ base, size_t col_stride, int ncols,
+                                                                  size_t num_leaves, u64* __restrict__ out) {
     const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= num_leaves) return;
-    u32 d[8];
-    b3_leaf<MULTI>([&](u32 i) { return gl_canon(base[(size_t)i * col_stride + j]); }, (u32)ncols, d);
-    b3_store_digest(out + j * 4, d);
+    bytes_leaf<BH, MULTI>([&](u32 i) { return gl_canon(base[(size_t)i * col_stride + j]); }, (u32)ncols, out + j * 4);
 }
-template <bool MULTI>
-__global__ __launch_bounds__(256) void leaf_b3_rowmajor_kernel(const u64* __restrict__ rows, size_t row_len, size_t num_leaves,
-                                                               u64* __restrict__ out) {
+template <int BH, bool MULTI>
+__global__ __launch_bounds__(256) void leaf_bytes_rowmajor_kernel(const u64* __restrict__ rows, size_t row_len, size_t num_leaves,
+                                                                  u64* __restrict__ out) {
     const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= num_leaves) return;
     const u64* r = rows + j * row_len;
-    u32 d[8];
-    b3_leaf<MULTI>([&](u32 i) { return gl_canon(r[i]); }, (u32)row_len, d);
-    b3_store_digest(out + j * 4, d);
+    bytes_leaf<BH, MULTI>([&](u32 i) { return gl_canon(r[i]); }, (u32)row_len, out + j * 4);
 }
-template <bool MULTI>
-__global__ __launch_bounds__(256) void leaf_b3_ext_kernel(const u64* __restrict__ plane_a, const u64* __restrict__ plane_b, int arity,
-                                                          size_t num_leaves, u64* __restrict__ out) {
+template <int BH, bool MULTI>
+__global__ __launch_bounds__(256) void leaf_bytes_ext_kernel(const u64* __restrict__ plane_a, const u64* __restrict__ plane_b, int arity,
+                                                             size_t num_leaves, u64* __restrict__ out) {
     const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= num_leaves) return;
-    u32 d[8];
-    b3_leaf<MULTI>([&](u32 i) { return gl_canon(((i & 1) ? plane_b : plane_a)[j * arity + (i >> 1)]); }, (u32)(2 * arity), d);
-    b3_store_digest(out + j * 4, d);
+    bytes_leaf<BH, MULTI>([&](u32 i) { return gl_canon(((i & 1) ? plane_b : plane_a)[j * arity + (i >> 1)]); }, (u32)(2 * arity), out + j * 4);
 }
-// The same leaves for arity 16, through LDS (round 6).  A thread of leaf_b3_ext_kernel reads 16 + 16 words 128 bytes apart from its
+// The same leaves for arity 16, through LDS (round 6).  A thread of leaf_bytes_ext_kernel reads 16 + 16 words 128 bytes apart from its
 // neighbour's: a wave touches 64 lines per load and the lines are gone from the vector cache before their other words are asked
 // for -- 17.1 GB fetched per 2^22-row proof for 1.2 GB of values (profiles/r05_proof_pmc_blake3.txt).  Here a workgroup copies
 // its 128 leaves x 16 values of both planes with 16-byte loads on consecutive addresses and every thread hashes its leaf out of
 // LDS (rows padded to 17 words: conflict-free for 8-byte reads).
 #define B3X_LEAVES 128
-__global__ __launch_bounds__(B3X_LEAVES) void leaf_b3_ext16_kernel(const u64* __restrict__ plane_a, const u64* __restrict__ plane_b, size_t num_leaves,
-                                                                   u64* __restrict__ out) {
+template <int BH>
+__global__ __launch_bounds__(B3X_LEAVES) void leaf_bytes_ext16_kernel(const u64* __restrict__ plane_a, const u64* __restrict__ plane_b, size_t num_leaves,
+                                                                      u64* __restrict__ out) {
     __shared__ u64 tile[2][B3X_LEAVES * 17];
     const size_t j0 = (size_t)blockIdx.x * B3X_LEAVES;
     const size_t base = j0 * 16;
@@ -370,14 +389,13 @@ __global__ __launch_bounds__(B3X_LEAVES) void leaf_b3_ext16_kernel(const u64* __
     __syncthreads();
     const size_t j = j0 + threadIdx.x;
     if (j >= num_leaves) return;
-    u32 d[8];
-    b3_leaf<false>([&](u32 i) { return gl_canon(tile[i & 1][threadIdx.x * 17 + (i >> 1)]); }, 32u, d);
-    b3_store_digest(out + j * 4, d);
+    bytes_leaf<BH, false>([&](u32 i) { return gl_canon(tile[i & 1][threadIdx.x * 17 + (i >> 1)]); }, 32u, out + j * 4);
 }
-__global__ __launch_bounds__(256) void merkle_level_b3_kernel(u64* __restrict__ heap, size_t first, size_t count) {
+template <int BH>
+__global__ __launch_bounds__(256) void merkle_level_bytes_kernel(u64* __restrict__ heap, size_t first, size_t count) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count) return;
-    b3_node(heap + 8 * (first + t), heap + 4 * (first + t));
+    bytes_node<BH>(heap + 8 * (first + t), heap + 4 * (first + t));
 }
 // `nlev` (<= 8) consecutive levels in one launch (round 6): a workgroup computes 256 nodes of the level of `first` nodes from their
 // children in the heap, then the 128, 64, ... nodes above them out of LDS -- every level is still written to the heap (sibling paths
@@ -385,13 +403,14 @@ __global__ __launch_bounds__(256) void merkle_level_b3_kernel(u64* __restrict__ 
 // 314 level launches and 20.6 GB per proof before): eight levels per launch are SLOWER (6.3 -> 8.4 ms: the upper levels run on 128, 64,
 // ... 1 lanes of a workgroup that keeps its slot for eight compressions in a row), two or three are a little faster (5.8 ms), four 6.0;
 // the default is two (OLA_MERKLE_FUSED_LEVELS, 0 = one launch per level).
-__global__ __launch_bounds__(256) void merkle_levels_b3_kernel(u64* __restrict__ heap, size_t first, int nlev) {
+template <int BH>
+__global__ __launch_bounds__(256) void merkle_levels_bytes_kernel(u64* __restrict__ heap, size_t first, int nlev) {
     __shared__ u64 sh[2][256 * 4];
     const int t = threadIdx.x;
     u64 d[4];
     {
         const size_t node = first + (size_t)blockIdx.x * 256 + t;
-        b3_node(heap + 8 * node, d);
+        bytes_node<BH>(heap + 8 * node, d);
 #pragma unroll
         for (int k = 0; k < 4; k++) { heap[4 * node + k] = d[k]; sh[0][4 * t + k] = d[k]; }
     }
@@ -400,21 +419,31 @@ __global__ __launch_bounds__(256) void merkle_levels_b3_kernel(u64* __restrict__
         const int count = 256 >> l;
         if (t < count) {
             const size_t node = (first >> l) + (size_t)blockIdx.x * count + t;
-            b3_node(&sh[(l - 1) & 1][8 * t], d);
+            bytes_node<BH>(&sh[(l - 1) & 1][8 * t], d);
 #pragma unroll
             for (int k = 0; k < 4; k++) { heap[4 * node + k] = d[k]; sh[l & 1][4 * t + k] = d[k]; }
         }
     }
 }
 // levels of `first` nodes and fewer (first <= blockDim.x) down to the level of `last` nodes in one workgroup
-__global__ __launch_bounds__(256) void merkle_top_b3_kernel(u64* __restrict__ heap, size_t first, size_t last) {
+template <int BH>
+__global__ __launch_bounds__(256) void merkle_top_bytes_kernel(u64* __restrict__ heap, size_t first, size_t last) {
     for (size_t level = first; level >= last && level >= 1; level >>= 1) {
-        if (threadIdx.x < level) b3_node(heap + 8 * (level + threadIdx.x), heap + 4 * (level + threadIdx.x));
+        if (threadIdx.x < level) bytes_node<BH>(heap + 8 * (level + threadIdx.x), heap + 4 * (level + threadIdx.x));
         __threadfence_block();
         __syncthreads();
     }
 }
-static inline bool is_b3(const DeviceCtx* ctx) { return ctx->hasher == (int)OLA_HASH_BLAKE3; }
+static inline bool is_keccak(const DeviceCtx* ctx) { return ctx->hasher == (int)OLA_HASH_KECCAK; }
+// the byte hashes: digests that are bytes, one thread per leaf / node
+static inline bool is_bytes_hash(const DeviceCtx* ctx) { return ctx->hasher == (int)OLA_HASH_BLAKE3 || is_keccak(ctx); }
+// f(std::integral_constant<int, BH>, std::integral_constant<bool, MULTI>) for the context's byte hash and a leaf of `words` words
+template <class F>
+static void with_bytes_hash(const DeviceCtx* ctx, size_t words, F&& f) {
+    if (is_keccak(ctx)) f(std::integral_constant<int, BH_KECCAK>(), std::false_type());
+    else if (words > (size_t)B3_CHUNK_WORDS) f(std::integral_constant<int, BH_BLAKE3>(), std::true_type());
+    else f(std::integral_constant<int, BH_BLAKE3>(), std::false_type());
+}
 // f(std::integral_constant<int, PERM>) with the sponge permutation of `hasher`: the context's Hasher (trees) or InnerHasher (proof of
 // work).  Every hasher the context accepts is named here: a new one is an error until it is, never a silent Poseidon.
 template <class F>
@@ -431,7 +460,7 @@ static inline uint32_t inner_hasher(const DeviceCtx* ctx) {
     return ctx->hasher == (int)OLA_HASH_POSEIDON2 ? OLA_HASH_POSEIDON2 : OLA_HASH_POSEIDON;
 }
 static void require_leaf_width(size_t words) {
-    if (words == 0 || words > 4096) throw OlaError(-1, "Blake3 leaves hold 1..4096 field elements");
+    if (words == 0 || words > 4096) throw OlaError(-1, "Blake3 and Keccak leaves hold 1..4096 field elements");
 }
 
 // ---- host launchers ----
@@ -440,21 +469,23 @@ void poseidon_init(DeviceCtx*) {   // both permutations' constants on the callin
     poseidon2_upload_constants();
 }
 
-// hash invocations per leaf of `words` field elements: sponge permutations (rate 8), or Blake3 compressions (64-byte blocks,
-// plus the parent compressions of a multi-chunk leaf)
+// hash invocations per leaf of `words` field elements: sponge permutations (rate 8), Blake3 compressions (64-byte blocks,
+// plus the parent compressions of a multi-chunk leaf), or Keccak-f permutations (rate 17 words, the padding always in the count)
 static double leaf_hash_calls(const DeviceCtx* ctx, size_t words) {
-    if (is_b3(ctx)) { const size_t blocks = (words * 8 + 63) / 64, chunks = (words * 8 + 1023) / 1024; return (double)(blocks + chunks - 1); }
+    if (is_keccak(ctx)) return (double)(words / KECCAK_RATE_WORDS + 1);
+    if (ctx->hasher == (int)OLA_HASH_BLAKE3) { const size_t blocks = (words * 8 + 63) / 64, chunks = (words * 8 + 1023) / 1024; return (double)(blocks + chunks - 1); }
     return (double)((words + 7) / 8);
 }
 void launch_leaf_hash_colmajor(DeviceCtx* ctx, const u64* base, size_t col_stride, int ncols, size_t num_leaves,
                                u64* out) {
     PhaseScope ph(ctx, PH_LEAF_HASH, (double)num_leaves * leaf_hash_calls(ctx, (size_t)ncols), (double)num_leaves * ((size_t)ncols * 8 + 32));
-    if (is_b3(ctx)) {
+    if (is_bytes_hash(ctx)) {
         require_leaf_width((size_t)ncols);
         if (num_leaves) {
             const dim3 grid((unsigned)((num_leaves + 255) / 256));
-            if ((size_t)ncols > (size_t)B3_CHUNK_WORDS) hipLaunchKernelGGL(leaf_b3_colmajor_kernel<true>, grid, dim3(256), 0, ctx->stream, base, col_stride, ncols, num_leaves, out);
-            else hipLaunchKernelGGL(leaf_b3_colmajor_kernel<false>, grid, dim3(256), 0, ctx->stream, base, col_stride, ncols, num_leaves, out);
+            with_bytes_hash(ctx, (size_t)ncols, [&](auto bh, auto multi) {
+                hipLaunchKernelGGL((leaf_bytes_colmajor_kernel<decltype(bh)::value, decltype(multi)::value>), grid, dim3(256), 0, ctx->stream, base, col_stride, ncols, num_leaves, out);
+            });
         }
         return;
     }
@@ -471,12 +502,13 @@ void launch_leaf_hash_colmajor(DeviceCtx* ctx, const u64* base, size_t col_strid
     });
 }
 void launch_leaf_hash_rowmajor(DeviceCtx* ctx, const u64* rows, size_t row_len, size_t num_leaves, u64* out) {
-    if (is_b3(ctx)) {
+    if (is_bytes_hash(ctx)) {
         require_leaf_width(row_len);
         if (num_leaves) {
             const dim3 grid((unsigned)((num_leaves + 255) / 256));
-            if (row_len > (size_t)B3_CHUNK_WORDS) hipLaunchKernelGGL(leaf_b3_rowmajor_kernel<true>, grid, dim3(256), 0, ctx->stream, rows, row_len, num_leaves, out);
-            else hipLaunchKernelGGL(leaf_b3_rowmajor_kernel<false>, grid, dim3(256), 0, ctx->stream, rows, row_len, num_leaves, out);
+            with_bytes_hash(ctx, row_len, [&](auto bh, auto multi) {
+                hipLaunchKernelGGL((leaf_bytes_rowmajor_kernel<decltype(bh)::value, decltype(multi)::value>), grid, dim3(256), 0, ctx->stream, rows, row_len, num_leaves, out);
+            });
         }
         return;
     }
@@ -493,18 +525,20 @@ void launch_leaf_hash_rowmajor(DeviceCtx* ctx, const u64* rows, size_t row_len, 
 }
 void launch_leaf_hash_ext(DeviceCtx* ctx, const u64* pa, const u64* pb, int arity, size_t num_leaves, u64* out) {
     PhaseScope ph(ctx, PH_LEAF_HASH, (double)num_leaves * leaf_hash_calls(ctx, (size_t)(2 * arity)), (double)num_leaves * ((size_t)arity * 16 + 32));
-    if (is_b3(ctx)) {
+    if (is_bytes_hash(ctx)) {
         require_leaf_width((size_t)(2 * arity));
         if (num_leaves) {
             const dim3 grid((unsigned)((num_leaves + 255) / 256));
             static const bool staged = !(getenv("OLA_LEAF_EXT_STAGED") && !strcmp(getenv("OLA_LEAF_EXT_STAGED"), "0"));
             if (arity == 16 && staged && num_leaves >= 1024 && (((uintptr_t)pa | (uintptr_t)pb) & 15) == 0) {
-                hipLaunchKernelGGL(leaf_b3_ext16_kernel, dim3((unsigned)((num_leaves + B3X_LEAVES - 1) / B3X_LEAVES)), dim3(B3X_LEAVES), 0, ctx->stream, pa, pb,
-                                   num_leaves, out);
+                const dim3 grid16((unsigned)((num_leaves + B3X_LEAVES - 1) / B3X_LEAVES));
+                if (is_keccak(ctx)) hipLaunchKernelGGL(leaf_bytes_ext16_kernel<BH_KECCAK>, grid16, dim3(B3X_LEAVES), 0, ctx->stream, pa, pb, num_leaves, out);
+                else hipLaunchKernelGGL(leaf_bytes_ext16_kernel<BH_BLAKE3>, grid16, dim3(B3X_LEAVES), 0, ctx->stream, pa, pb, num_leaves, out);
                 return;
             }
-            if ((size_t)(2 * arity) > (size_t)B3_CHUNK_WORDS) hipLaunchKernelGGL(leaf_b3_ext_kernel<true>, grid, dim3(256), 0, ctx->stream, pa, pb, arity, num_leaves, out);
-            else hipLaunchKernelGGL(leaf_b3_ext_kernel<false>, grid, dim3(256), 0, ctx->stream, pa, pb, arity, num_leaves, out);
+            with_bytes_hash(ctx, (size_t)(2 * arity), [&](auto bh, auto multi) {
+                hipLaunchKernelGGL((leaf_bytes_ext_kernel<decltype(bh)::value, decltype(multi)::value>), grid, dim3(256), 0, ctx->stream, pa, pb, arity, num_leaves, out);
+            });
         }
         return;
     }
@@ -525,19 +559,26 @@ void launch_merkle_build(DeviceCtx* ctx, u64* heap, size_t num_leaves, uint32_t 
     const size_t last = (size_t)1 << cap_height, top = 256;   // levels of <= `top` nodes share one launch (1024 threads)
     PhaseScope ph(ctx, PH_MERKLE_LEVELS, num_leaves > last ? (double)(num_leaves - last) : 0.0, num_leaves > last ? (double)(num_leaves - last) * 96 : 0.0);
     size_t level = num_leaves / 2;
-    if (is_b3(ctx)) {
+    if (is_bytes_hash(ctx)) {
         static const int fused = getenv("OLA_MERKLE_FUSED_LEVELS") ? atoi(getenv("OLA_MERKLE_FUSED_LEVELS")) : 2;
         if (fused > 1 && last <= top && (level & (level - 1)) == 0) {
             while (level > top) {          // level is a power of two >= 512: up to `fused` levels per launch, the last of them still above `top`
                 int nlev = 0;
                 while (nlev < fused && nlev < 8 && (level >> nlev) > top) nlev++;
-                hipLaunchKernelGGL(merkle_levels_b3_kernel, dim3((unsigned)(level / 256)), dim3(256), 0, ctx->stream, heap, level, nlev);
+                if (is_keccak(ctx)) hipLaunchKernelGGL(merkle_levels_bytes_kernel<BH_KECCAK>, dim3((unsigned)(level / 256)), dim3(256), 0, ctx->stream, heap, level, nlev);
+                else hipLaunchKernelGGL(merkle_levels_bytes_kernel<BH_BLAKE3>, dim3((unsigned)(level / 256)), dim3(256), 0, ctx->stream, heap, level, nlev);
                 level >>= nlev;
             }
         }
-        for (; level >= last && level > top; level /= 2)
-            hipLaunchKernelGGL(merkle_level_b3_kernel, dim3((unsigned)((level + 255) / 256)), dim3(256), 0, ctx->stream, heap, level, level);
-        if (level >= last && level >= 1) hipLaunchKernelGGL(merkle_top_b3_kernel, dim3(1), dim3(256), 0, ctx->stream, heap, level, last);
+        for (; level >= last && level > top; level /= 2) {
+            const dim3 grid((unsigned)((level + 255) / 256));
+            if (is_keccak(ctx)) hipLaunchKernelGGL(merkle_level_bytes_kernel<BH_KECCAK>, grid, dim3(256), 0, ctx->stream, heap, level, level);
+            else hipLaunchKernelGGL(merkle_level_bytes_kernel<BH_BLAKE3>, grid, dim3(256), 0, ctx->stream, heap, level, level);
+        }
+        if (level >= last && level >= 1) {
+            if (is_keccak(ctx)) hipLaunchKernelGGL(merkle_top_bytes_kernel<BH_KECCAK>, dim3(1), dim3(256), 0, ctx->stream, heap, level, last);
+            else hipLaunchKernelGGL(merkle_top_bytes_kernel<BH_BLAKE3>, dim3(1), dim3(256), 0, ctx->stream, heap, level, last);
+        }
         return;
     }
     with_perm((uint32_t)ctx->hasher, [&](auto perm) {

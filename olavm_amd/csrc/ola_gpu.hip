@@ -114,7 +114,7 @@ static void require_context(OlaCtx* ctx) {
 }
 // the GenericConfig<2> types the library proves under (include/ola_gpu.h OLA_HASH_*)
 static bool known_hasher(uint32_t h) {
-    return h == OLA_HASH_POSEIDON || h == OLA_HASH_BLAKE3 || h == OLA_HASH_POSEIDON2 || h == OLA_HASH_POSEIDON2_POW_POSEIDON;
+    return h == OLA_HASH_POSEIDON || h == OLA_HASH_BLAKE3 || h == OLA_HASH_POSEIDON2 || h == OLA_HASH_POSEIDON2_POW_POSEIDON || h == OLA_HASH_KECCAK;   // 4 is unassigned
 }
 
 // The HIP current device is a property of the calling host thread: every entry point that works on a context makes the
@@ -160,7 +160,7 @@ static OlaGpuConfig resolve_config(const OlaGpuConfig* cfg) {
     require(c.fri_final_poly_bits <= 16, "fri_final_poly_bits must be at most 16");
     require(c.num_query_rounds >= 1 && c.num_query_rounds <= 1024, "num_query_rounds must be in 1..1024");
     require(c.num_challenges == 2, "num_challenges must be 2 (circuits/src/stark/config.rs)");
-    require(known_hasher(c.hasher), "hasher must be OLA_HASH_POSEIDON, OLA_HASH_BLAKE3, OLA_HASH_POSEIDON2 or OLA_HASH_POSEIDON2_POW_POSEIDON");
+    require(known_hasher(c.hasher), "hasher must be OLA_HASH_POSEIDON, OLA_HASH_BLAKE3, OLA_HASH_POSEIDON2, OLA_HASH_POSEIDON2_POW_POSEIDON or OLA_HASH_KECCAK");
     return c;
 }
 
@@ -426,6 +426,7 @@ int32_t ola_gpu_warmup_wait(double* ms_out) {
 int32_t ola_gpu_init(const OlaGpuConfig* cfg, OlaCtx** out_ctx) {
     OLA_TRY
     require(out_ctx != nullptr, "out_ctx is NULL");
+    const OlaGpuConfig c = resolve_config(cfg);   // before the device is looked for: a configuration that is no configuration is OLA_E_INVALID_ARG with or without one
     warmup_join();
     int ndev = 0;
     const auto t_rt = std::chrono::steady_clock::now();
@@ -434,7 +435,6 @@ int32_t ola_gpu_init(const OlaGpuConfig* cfg, OlaCtx** out_ctx) {
     { const char* t = getenv("OLA_TIMING");
       if (t && *t && *t != '0') fprintf(stderr, "[ola-timing] init: %-52s %9.3f ms\n", "hipGetDeviceCount (HIP runtime start-up)",
                                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_rt).count()); }
-    const OlaGpuConfig c = resolve_config(cfg);
     require(c.device < ndev, "device index out of range");
     OlaCtx* warm = take_warm_ctx(c, c.device);
     *out_ctx = warm ? warm : create_device_ctx(c, c.device, c.stream).release();
@@ -869,8 +869,15 @@ int32_t ola_challenger_init(OlaChallenger* ch) {
 int32_t ola_challenger_init_hasher(OlaChallenger* ch, uint32_t hasher) {
     OLA_TRY
     require(ch, "challenger");
-    require(known_hasher(hasher), "hasher must be OLA_HASH_POSEIDON, OLA_HASH_BLAKE3, OLA_HASH_POSEIDON2 or OLA_HASH_POSEIDON2_POW_POSEIDON");
+    // the values this entry point took when it was published, 0..3, and no other: the Keccak transcript has its own (below)
+    require(known_hasher(hasher) && hasher != OLA_HASH_KECCAK, "hasher must be OLA_HASH_POSEIDON, OLA_HASH_BLAKE3, OLA_HASH_POSEIDON2 or OLA_HASH_POSEIDON2_POW_POSEIDON");
     challenger_init(*ch, hasher);
+    OLA_CATCH
+}
+int32_t ola_challenger_init_keccak(OlaChallenger* ch) {
+    OLA_TRY
+    require(ch, "challenger");
+    challenger_init(*ch, OLA_HASH_KECCAK);
     OLA_CATCH
 }
 int32_t ola_challenger_observe_cap(OlaChallenger* ch, const uint64_t* digests, size_t n) {
@@ -885,6 +892,16 @@ int32_t ola_blake3_hash_elements(const uint64_t* elems, size_t n, uint64_t out[4
     std::vector<u64> w(n);
     for (size_t i = 0; i < n; i++) w[i] = gl_canon(elems[i]);
     b3_hash_bytes32_host(w.data(), (u32)n, (u64*)out);
+    OLA_CATCH
+}
+int32_t ola_keccak_hash_elements(const uint64_t* elems, size_t n, uint64_t out[4]) {
+    OLA_TRY
+    require(elems && out && n >= 1 && n <= 4096, "1..4096 elements");
+    std::vector<u64> w(n);
+    for (size_t i = 0; i < n; i++) w[i] = gl_canon(elems[i]);
+    u64 d[4];
+    keccak_hash_words([&](u32 i) { return w[i]; }, (u32)n, d);
+    for (int i = 0; i < 4; i++) out[i] = d[i];
     OLA_CATCH
 }
 int32_t ola_challenger_observe(OlaChallenger* ch, const uint64_t* e, size_t n) {
@@ -915,7 +932,7 @@ int32_t ola_open_and_prove(OlaCtx* ctx, const OlaBatch* trace, const OlaBatch* z
     require_full(trace); require_full(zs); require_full(quotient);
     require(trace->log_n == zs->log_n && trace->log_n == quotient->log_n, "degree mismatch between commitments");
     require(num_permutation_zs <= zs->ncols, "num_permutation_zs");
-    require(challenger->hasher == ctx->cfg.hasher, "the challenger was not initialised for this context's hasher (ola_challenger_init_hasher)");
+    require(challenger->hasher == ctx->cfg.hasher, "the challenger was not initialised for this context's hasher (ola_challenger_init_hasher, ola_challenger_init_keccak)");
     OlaChallenger ch = *challenger;  // only committed on success
     std::vector<uint8_t> bytes;
     size_t olen = 0;
@@ -1179,7 +1196,7 @@ int32_t ola_verify_opening(OlaCtx* ctx, const uint64_t* caps, const uint32_t num
     require(caps && num_polys && proof && challenger && report, "null pointer");
     require_verifier_context(ctx);
     OLA_ON_DEVICE(ctx);
-    require(challenger->hasher == ctx->cfg.hasher, "the challenger was not initialised for this context's hasher (ola_challenger_init_hasher)");
+    require(challenger->hasher == ctx->cfg.hasher, "the challenger was not initialised for this context's hasher (ola_challenger_init_hasher, ola_challenger_init_keccak)");
     require(challenger->input_len <= 8 && challenger->output_len <= 8, "challenger");
     const auto t0 = std::chrono::steady_clock::now();
     const vfy::Stage st = vfy::opening_stage(vfy::config_of(ctx->cfg), (const u64*)caps, num_polys, degree_bits, num_permutation_zs, proof, proof_len, *challenger);
@@ -1212,7 +1229,7 @@ int32_t ola_prove_single_table(OlaCtx* ctx, const uint64_t* airset, size_t airse
     OLA_TRY
     OLA_ON_DEVICE(ctx);
     require(ctx && airset && trace_cols && trace_commitment && trace_cap && ctl_challenges && challenger && out_len, "null pointer");
-    require(challenger->hasher == ctx->cfg.hasher, "the challenger was not initialised for this context's hasher (ola_challenger_init_hasher)");
+    require(challenger->hasher == ctx->cfg.hasher, "the challenger was not initialised for this context's hasher (ola_challenger_init_hasher, ola_challenger_init_keccak)");
     std::vector<uint8_t> bytes;
     OlaChallenger ch = *challenger;          // the caller's transcript only advances when the proof was produced
     prove_single_table_host(&ctx->dev, *ctx->tables, ctx->cfg, (const u64*)airset, airset_words, table, (const u64* const*)trace_cols,

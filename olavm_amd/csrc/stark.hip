@@ -844,7 +844,7 @@ static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuCo
     challenger_observe_cap(ch, q_cap.data(), q_cap.size() / 4);
 
     // ---- write_proof (serialization.rs:349-358): caps, then opening set + FRI proof ----
-    ByteWriter w{bytes, ctx->hasher == (int)OLA_HASH_BLAKE3};
+    ByteWriter w{bytes, digest_wire_bytes((uint32_t)ctx->hasher)};
     write_cap(w, trace_cap);
     write_cap(w, zs_cap);
     write_cap(w, q_cap);
@@ -1177,7 +1177,7 @@ void prove_with_traces(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cf
     std::vector<GpChallenge> ctl_ch;
     for (int c = 0; c < nch; c++) ctl_ch.push_back(get_gp(ch));
     const std::vector<std::vector<CtlJob>> jobs = ctl_jobs(set, ctl_ch);
-    ByteWriter w{bytes, ctx->hasher == (int)OLA_HASH_BLAKE3};
+    ByteWriter w{bytes, digest_wire_bytes((uint32_t)ctx->hasher)};
     w.u32((uint32_t)nt);
     size_t poff = 0;
     std::vector<u64> zero_params(64, 0);

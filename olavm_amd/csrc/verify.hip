@@ -23,17 +23,20 @@
 #include "poseidon.cuh"
 #include "poseidon2.cuh"
 #include "blake3.cuh"
+#include "keccak.cuh"
 #include "verify_host.h"
 
 namespace ola {
 
-enum : int { VH_POSEIDON = 0, VH_POSEIDON2 = 1, VH_BLAKE3 = 2 };
+enum : int { VH_POSEIDON = 0, VH_POSEIDON2 = 1, VH_BLAKE3 = 2, VH_KECCAK = 3 };
 
 // Hasher::hash_no_pad of `len` words at `leaf`, by the rule of the row-major leaf kernels (merkle.hip): the sponge over chunks of
 // eight for every width, Blake3_256 of the canonical little-endian words
 template <int H>
 __device__ __forceinline__ void vfy_hash_leaf(const u64* __restrict__ leaf, u32 len, u64 (&d)[4]) {
-    if constexpr (H == VH_BLAKE3) {
+    if constexpr (H == VH_KECCAK) {
+        keccak_hash_words([&](u32 i) { return leaf[i]; }, len, d);
+    } else if constexpr (H == VH_BLAKE3) {
         u32 cv[8];
         if (len > (u32)B3_CHUNK_WORDS) b3_hash_words([&](u32 i) { return leaf[i]; }, len, cv);
         else b3_chunk_cv([&](u32 i) { return leaf[i]; }, 0, len, 0, true, cv);
@@ -57,7 +60,10 @@ __device__ __forceinline__ void vfy_hash_leaf(const u64* __restrict__ leaf, u32 
 // Hasher::two_to_one(l, r)
 template <int H>
 __device__ __forceinline__ void vfy_two_to_one(const u64 (&l)[4], const u64 (&r)[4], u64 (&d)[4]) {
-    if constexpr (H == VH_BLAKE3) {
+    if constexpr (H == VH_KECCAK) {
+        const u64 c[8] = {l[0], l[1], l[2], l[3], r[0], r[1], r[2], r[3]};
+        keccak_node(c, d);
+    } else if constexpr (H == VH_BLAKE3) {
         const u64 c[8] = {l[0], l[1], l[2], l[3], r[0], r[1], r[2], r[3]};
         b3_node(c, d);
     } else {
@@ -241,6 +247,9 @@ void verify_on_device(DeviceCtx* ctx, const vfy::Stage& st, OlaVerifyReport* rep
                         break;
                     case OLA_HASH_BLAKE3:
                         hipLaunchKernelGGL(merkle_paths_check_kernel<VH_BLAKE3>, grid, block, 0, ctx->stream, d_image, data_words, st.merkle_off, (u32)nm, d_flags);
+                        break;
+                    case OLA_HASH_KECCAK:
+                        hipLaunchKernelGGL(merkle_paths_check_kernel<VH_KECCAK>, grid, block, 0, ctx->stream, d_image, data_words, st.merkle_off, (u32)nm, d_flags);
                         break;
                     case OLA_HASH_POSEIDON2:
                     case OLA_HASH_POSEIDON2_POW_POSEIDON:

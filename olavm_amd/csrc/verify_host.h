@@ -67,8 +67,8 @@ struct WProof { std::vector<Digest> trace_cap, zs_cap, quotient_cap; WOpenings o
 
 // Every length prefix is checked against the bytes that are left BEFORE anything is allocated for it.
 struct Reader {
-    const uint8_t* p; size_t n, off = 0; bool ok = true; bool digest_bytes;   // digest_bytes: Blake3 digests, never reduced
-    Reader(const uint8_t* bytes, size_t len, uint32_t hasher) : p(bytes), n(len), digest_bytes(hasher == OLA_HASH_BLAKE3) {}
+    const uint8_t* p; size_t n, off = 0; bool ok = true; int digest_bytes;   // digest_wire_bytes: 32 (Blake3) or 25 (Keccak) bytes, never reduced; 0: four field words
+    Reader(const uint8_t* bytes, size_t len, uint32_t hasher) : p(bytes), n(len), digest_bytes(digest_wire_bytes(hasher)) {}
     size_t left() const { return n - off; }
     bool need(size_t count, size_t each) {
         if (!ok) return false;
@@ -82,8 +82,13 @@ struct Reader {
     void words(std::vector<u64>& v, size_t count) { if (!need(count, 8)) return; v.reserve(count); for (size_t i = 0; i < count && ok; i++) v.push_back(field()); }
     void field_vec(std::vector<u64>& v) { const uint32_t l = u32(); words(v, l); }
     void ext_vec(std::vector<u64>& v) { const uint32_t l = u32(); if (!need(l, 16)) return; words(v, 2 * (size_t)l); }
-    Digest digest() { Digest h; for (int i = 0; i < 4; i++) h[i] = digest_bytes ? raw64() : field(); return h; }
-    void digests(std::vector<Digest>& v, size_t count) { if (!need(count, 32)) return; v.reserve(count); for (size_t i = 0; i < count && ok; i++) v.push_back(digest()); }
+    Digest digest() {
+        Digest h = {0, 0, 0, 0};
+        if (digest_bytes == KECCAK_DIGEST_BYTES) { for (int i = 0; i < 3; i++) h[i] = raw64(); h[3] = u8(); return h; }   // the in-memory layout: word 3 is byte 24
+        for (int i = 0; i < 4; i++) h[i] = digest_bytes ? raw64() : field();
+        return h;
+    }
+    void digests(std::vector<Digest>& v, size_t count) { if (!need(count, digest_bytes ? (size_t)digest_bytes : 32)) return; v.reserve(count); for (size_t i = 0; i < count && ok; i++) v.push_back(digest()); }
     void cap(std::vector<Digest>& v) { const uint32_t l = u32(); digests(v, l); }
     void merkle_proof(std::vector<Digest>& v) { const uint8_t l = u8(); digests(v, l); }
     void opening_set(WOpenings& o) {
@@ -217,7 +222,7 @@ inline void fri_challenges(OlaChallenger& ch, const Config& cfg, const WFri& fri
     for (int i = 0; i < 4; i++) s[i] = challenger_get(ch);
     s[4] = fri.pow_witness;
     // C::InnerHasher::hash_no_pad of five elements is one permutation: Poseidon2 in Poseidon2GoldilocksConfig, Poseidon in every other
-    if (cfg.hasher == OLA_HASH_POSEIDON2) poseidon2_permute_host(s); else poseidon_permute_host(s);
+    if (cfg.hasher == OLA_HASH_POSEIDON2) poseidon2_permute_host(s); else poseidon_permute_host(s);   // Blake3 and Keccak configurations: Poseidon
     out.pow_response = s[0];
     const u64 lde_size = (u64)1 << (degree_bits + cfg.rate_bits);
     for (int i = 0; i < cfg.num_queries; i++) out.query_indices.push_back(challenger_get(ch) % lde_size);
@@ -668,7 +673,8 @@ inline Stage opening_stage(const Config& cfg, const u64* caps, const uint32_t nu
             Digest d;
             for (int k = 0; k < 4; k++) {
                 d[(size_t)k] = caps[((size_t)o * cap_len + i) * 4 + (size_t)k];
-                if (cfg.hasher != OLA_HASH_BLAKE3 && d[(size_t)k] >= GL_P) throw OlaError(OLA_E_INVALID_ARG, "caps: a digest word is not canonical");
+                if (cfg.hasher == OLA_HASH_KECCAK) { if (k == 3 && d[3] > 0xFF) throw OlaError(OLA_E_INVALID_ARG, "caps: word 3 of a Keccak digest holds byte 24 only"); }
+                else if (cfg.hasher != OLA_HASH_BLAKE3 && d[(size_t)k] >= GL_P) throw OlaError(OLA_E_INVALID_ARG, "caps: a digest word is not canonical");
             }
             cap[o].push_back(d);
         }

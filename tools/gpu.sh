@@ -112,7 +112,7 @@ for _ in range(4):
 print(os.environ["AB_HASHER"], "wall %.1f ms, quotient kernels %.2f ms, opening evaluations %.2f ms, LDE %.2f ms, leaves %.2f ms" % best)
 PY
                  done 2>&1 | grep -v amdgpu | tee $O/quot.txt ;;
-    openings)    # round 6: eval_points_wide_kernel, fold16_kernel, leaf_b3_ext16_kernel against the kernels they replace (environment switches, same box, alternating)
+    openings)    # round 6: eval_points_wide_kernel, fold16_kernel, leaf_bytes_ext16_kernel against the kernels they replace (environment switches, same box, alternating)
                  for h in blake3 poseidon; do for v in 0 1 0 1; do AB_HASHER=$h OLA_EVAL_WIDE=$v OLA_FOLD16=$v OLA_LEAF_EXT_STAGED=$v timeout 300 python - <<'PY'
 import os, sys
 sys.path.insert(0, ".")
@@ -154,7 +154,7 @@ for _ in range(4):
 print(os.environ["AB_NAME"], "wall %.1f ms, quotient kernels %.2f ms" % best, "proof sha256", hashlib.sha256(bytes(proof)).hexdigest()[:16])
 PY
                  done 2>&1 | grep -v amdgpu | tee $O/ab.txt; cp ab_tmp/libola_cur.so olavm_amd/lib/libola_gpu.so ;;
-    merkle_ab)   # round 6: eight Blake3 Merkle levels per launch (merkle_levels_b3_kernel) against one launch per level (OLA_MERKLE_FUSED_LEVELS=0)
+    merkle_ab)   # round 6: eight Blake3 Merkle levels per launch (merkle_levels_bytes_kernel) against one launch per level (OLA_MERKLE_FUSED_LEVELS=0)
                  [ "${AB_SKIP_TESTS:-0}" = 1 ] || timeout 1200 python -m pytest tests/test_gpu_blake3.py tests/test_gpu_fullsize.py -x -q -k "blake3 or b3 or commitment" 2>&1 | tail -3 | tee $O/pytest.log
                  for v in ${AB_LEVELS:-0 2 3 4 0 2 3 4}; do AB_HASHER=blake3 OLA_MERKLE_FUSED_LEVELS=$v timeout 300 python - <<'PY'
 import os, sys, hashlib
@@ -294,6 +294,10 @@ PY
                    timeout -k 10 900 python -m pytest tests/test_gpu_verify.py tests/test_gpu_host_verify_api.py -q --durations=12 2>&1 | tail -30 | tee $O/pytest.log && \
                    OLA_HASHER=blake3 timeout -k 10 600 python tools/bench_verify.py 22 5 --json $O/verify_blake3.json 2>&1 | grep -v amdgpu | tee $O/verify_blake3.txt && \
                    OLA_HASHER=poseidon timeout -k 10 600 python tools/bench_verify.py 22 5 --json $O/verify_poseidon.json 2>&1 | grep -v amdgpu | tee $O/verify_poseidon.txt ) ;;
+    keccak)      # KeccakGoldilocksConfig: its tests, then the 2^22-row padding instance under Keccak, Blake3 and Poseidon taking turns in one process, and ola_verify_all_proof
+                 ( set -o pipefail
+                   timeout -k 10 600 python -m pytest tests/test_gpu_keccak.py -q --durations=12 2>&1 | tail -30 | tee $O/pytest.log && \
+                   timeout -k 10 600 python tools/bench_keccak.py ${KECCAK_LOG_N:-22} ${KECCAK_ROUNDS:-5} --json $O/bench_keccak.json 2>&1 | grep -v amdgpu | tee $O/bench_keccak.txt ) ;;
     *)           echo "unknown step $step" ;;
   esac
 done

@@ -65,6 +65,12 @@ def decode_all_proof(raw, hasher="poseidon"):
 
     def digest():
         nonlocal off
+        if hasher == "keccak":                   # BytesHash<25>: 25 bytes on the wire (util/serialization.rs:89-97)
+            h = bytes_hash(raw[off:off + 25])
+            if len(h[0]) != 25:
+                raise ValueError(f"truncated digest at byte {off}")
+            off += 25
+            return h
         h = bytes_hash(raw[off:off + 32]) if hasher == "blake3" else hash_out(raw, off)      # a HashOut under Poseidon and Poseidon2
         if hasher != "blake3" and any(x.v != w for x, w in zip(h["elements"], struct.unpack_from("<4Q", raw, off))):
             raise ValueError(f"non-canonical digest word at byte {off}")
@@ -273,6 +279,92 @@ def blake3_hooks(it):
     return permute
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# Keccak-256 (`keccak_hash::keccak`, a crate outside the reference tree, is the one function hash/keccak.rs calls): the published
+# algorithm -- Keccak-f[1600], rate 136 bytes, the original padding 0x01 .. 0x80 -- checked against tests/golden/keccak_vectors.json
+# before use.  hash/keccak.rs itself (hash_no_pad, two_to_one, KeccakPermutation::permute) is interpreted from the reference's source.
+M64 = (1 << 64) - 1
+KECCAK_RC = []
+KECCAK_ROT = [0] * 25        # rotation of lane x + 5y
+KECCAK_TO = [0] * 25         # where pi moves it
+
+
+def _keccak_tables():
+    r = 1
+    for _ in range(24):      # the round constants from the degree-8 LFSR of the Keccak reference (section 1.2)
+        rc = 0
+        for j in range(7):
+            if r & 1:
+                rc |= 1 << ((1 << j) - 1)
+            r = ((r << 1) ^ 0x171) if r & 0x80 else (r << 1)
+        KECCAK_RC.append(rc)
+    x, y = 1, 0
+    for t in range(24):
+        KECCAK_ROT[x + 5 * y] = ((t + 1) * (t + 2) // 2) % 64
+        x, y = y, (2 * x + 3 * y) % 5
+    for x in range(5):
+        for y in range(5):
+            KECCAK_TO[x + 5 * y] = y + 5 * ((2 * x + 3 * y) % 5)
+
+
+_keccak_tables()
+
+
+def _keccak_f(a):
+    for rc in KECCAK_RC:
+        c = [a[x] ^ a[x + 5] ^ a[x + 10] ^ a[x + 15] ^ a[x + 20] for x in range(5)]
+        d = [c[x - 1] ^ (((c[(x + 1) % 5] << 1) | (c[(x + 1) % 5] >> 63)) & M64) for x in range(5)]
+        b = [0] * 25
+        for i in range(25):
+            v, n = a[i] ^ d[i % 5], KECCAK_ROT[i]
+            b[KECCAK_TO[i]] = ((v << n) | (v >> (64 - n))) & M64
+        a = [b[i] ^ (~b[i - i % 5 + (i + 1) % 5] & b[i - i % 5 + (i + 2) % 5]) for i in range(25)]
+        a[0] ^= rc
+    return a
+
+
+def keccak256(data):
+    """32-byte Keccak-256 of `data` (not SHA3-256: the domain byte is 0x01)"""
+    data = bytes(data)
+    pad = data + b"\x01" + bytes(-(len(data) + 1) % 136)
+    pad = pad[:-1] + bytes([pad[-1] | 0x80])
+    a = [0] * 25
+    for off in range(0, len(pad), 136):
+        for i, w in enumerate(struct.unpack_from("<17Q", pad, off)):
+            a[i] ^= w
+        a = _keccak_f(a)
+    return struct.pack("<4Q", *a[:4])
+
+
+def check_keccak():
+    import json
+    fx = json.load(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "keccak_vectors.json")))
+    for text, want in fx["keccak256"].items():
+        if keccak256(text.encode()).hex() != want:
+            raise SystemExit("the Keccak-256 restatement fails the published digest of %r" % text)
+    for v in fx["hash_no_pad"]:
+        h = keccak256(b"".join(struct.pack("<Q", x) for x in v["input"]))
+        if list(struct.unpack("<3Q", h[:24])) + [h[24]] != v["digest"]:
+            raise SystemExit("the Keccak-256 restatement fails the vector of %d words" % len(v["input"]))
+
+
+def keccak_hooks(it):
+    """`keccak_hash::keccak(bytes) -> H256`: `.0` and `.to_fixed_bytes()` are its 32 bytes"""
+    def as_bytes(v):
+        return bytes(int(x) for x in (v[0] if isinstance(v, Struct) else v))
+    it.fn_hooks["keccak"] = lambda args: Struct({"__name__": "H256", 0: [R.TInt(x, 8) for x in keccak256(as_bytes(args[0]))]})
+    it.assoc_hooks[("H256", "to_fixed_bytes")] = lambda args: list(args[0][0])
+    # std::mem::size_of::<u64>(): inside hash/keccak.rs only, whose every call has that type argument (checked in its text)
+    text = open(os.path.join(it.plonky2, "hash", "keccak.rs")).read()
+    if set(re.findall(r"size_of::<(\w+)>", text)) != {"u64"} or "size_of(" in text.replace("size_of::<u64>()", ""):
+        raise SystemExit("hash/keccak.rs takes size_of of something other than u64")
+    it.fn_hooks_in[("keccak.rs", "size_of")] = lambda args: 8
+    # `Buffer::new(Vec::new())` (hash/keccak.rs:61): plonky2's Buffer (util/serialization.rs, whose write_field_vec writes no length), not
+    # the one of circuits/src/stark/serialization.rs; the std::io::Cursor under it is the interpreter's own, as in RefVerifier.encode
+    plonky2_buffer = os.path.join(it.plonky2, "util", "serialization.rs")
+    it.assoc_hooks[("Buffer", "new")] = lambda args: Struct({"__name__": "Buffer", "__file__": plonky2_buffer, 0: R.Cursor(args[0])})
+
+
 def verifier_interp(reference, fast_hash=True, hasher="poseidon"):
     it, circ, diag, rc = poseidon_tables(reference)
     base = it.plonky2
@@ -290,7 +382,8 @@ def verifier_interp(reference, fast_hash=True, hasher="poseidon"):
     if re.search(r"const W: Self = Self\((\d+)\);", open(os.path.join(reference, "plonky2", "field", "src", "goldilocks_extensions.rs")).read()).group(1) != str(Fe2.W):
         raise SystemExit("the quadratic extension's W is not 7")
     # Hasher::zero_hash (plonk/config.rs:72-78): HASH_SIZE zero bytes through Hash::from_bytes
-    it.assoc_hooks[("Hasher", "zero_hash")] = (lambda args: bytes_hash(bytes(32))) if hasher == "blake3" else (lambda args: hash_out(bytes(32), 0))
+    it.assoc_hooks[("Hasher", "zero_hash")] = ((lambda args: bytes_hash(bytes(32))) if hasher == "blake3" else (lambda args: bytes_hash(bytes(25))) if hasher == "keccak"
+                                               else (lambda args: hash_out(bytes(32), 0)))
     poseidon = it.permutation_hook
     if fast_hash:
         fp = FastPoseidon(circ, diag, rc)
@@ -306,6 +399,18 @@ def verifier_interp(reference, fast_hash=True, hasher="poseidon"):
                             "Hash": ["BytesHash"]})
         # `H::Permutation::permute` (the challenger's sponge) is the config hasher's; `P::permute` inside hashing.rs is PoseidonHash's own
         it.permutation_hook = lambda st, segs=None: onion(st) if (segs and "Permutation" in segs) else poseidon(st)
+    elif hasher == "keccak":
+        # KeccakGoldilocksConfig (plonk/config.rs:145-151): Hasher = KeccakHash<25>, InnerHasher = PoseidonHash (the proof of work).  The
+        # hasher and its permutation are the reference's own source (hash/keccak.rs); only the crate function under them is hooked.
+        check_keccak()
+        keccak_hooks(it)
+        keccak_rs = os.path.join(base, "hash", "keccak.rs")
+        it.extra_files.append(keccak_rs)
+        it.generics.update({"C": ["KeccakGoldilocksConfig"], "Hasher": ["KeccakHash", "Hasher"], "H": ["KeccakHash", "Hasher"], "OH": ["KeccakHash", "Hasher"],
+                            "Hash": ["BytesHash"]})
+        it.const_generics["N"] = 25              # KeccakHash<25>
+        it.permutation_hook = lambda st, segs=None: (list(it.call_assoc("KeccakPermutation", "permute", [list(st)], keccak_rs))
+                                                     if (segs and "Permutation" in segs) else poseidon(st))
     elif hasher in POSEIDON2_CONFIGS:
         # Poseidon2GoldilocksConfig / Poseidon2GoldilocksConfig2 (plonk/config.rs:123-141): Hasher = Poseidon2Hash; InnerHasher (the proof of
         # work) = Poseidon2Hash / PoseidonHash.  Every permutation the interpreter reaches is Poseidon2's -- the challenger's and the one
@@ -415,8 +520,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("proof")
     ap.add_argument("--reference", default="/root/reference")
-    ap.add_argument("--hasher", default="poseidon", choices=("poseidon", "blake3", "poseidon2", "poseidon2_pow_poseidon"),
-                    help="PoseidonGoldilocksConfig, Blake3GoldilocksConfig, Poseidon2GoldilocksConfig or Poseidon2GoldilocksConfig2")
+    ap.add_argument("--hasher", default="poseidon", choices=("poseidon", "blake3", "poseidon2", "poseidon2_pow_poseidon", "keccak"),
+                    help="PoseidonGoldilocksConfig, Blake3GoldilocksConfig, Poseidon2GoldilocksConfig, Poseidon2GoldilocksConfig2 or KeccakGoldilocksConfig")
     a = ap.parse_args()
     raw = open(a.proof, "rb").read()
     proof = decode_all_proof(raw, a.hasher)
@@ -547,9 +652,9 @@ def clone_values(vs):
     return [Struct({"__name__": "PolynomialValues", "values": list(v["values"])}) for v in vs]
 
 
-def table_span(raw, k):
-    """byte range of table k's StarkProof inside an AllProof"""
+def table_span(raw, k, digest_bytes=32):
+    """byte range of table k's StarkProof inside an AllProof (digest_bytes = 25 under KeccakGoldilocksConfig)"""
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "integration", "pin"))
     import compare_with_dump as CD
-    spans = [(n, a, b) for n, a, b in CD.parse_all_proof(raw) if n.startswith("table %d:" % k)]
+    spans = [(n, a, b) for n, a, b in CD.parse_all_proof(raw, digest_bytes=digest_bytes) if n.startswith("table %d:" % k)]
     return spans[0][1] - 4, spans[-1][2]          # the cap's u32 count precedes its span

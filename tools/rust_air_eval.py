@@ -846,6 +846,8 @@ class Interp:
         self.packing_width = 0              # P::WIDTH where the reference's code is generic over a packing (a driver sets 1)
         self.features = set()               # cargo features `cfg!(feature = "..")` sees: the reference builds with "parallel" (a driver sets it)
         self.num_threads = 8                # what maybe_rayon::current_num_threads() answers (results must not depend on it)
+        self.const_generics = {}            # const generic parameter -> its value in the instantiation at hand (`N` of KeccakHash<N>)
+        self.fn_hooks_in = {}               # (file name, free function name) -> python function: a hook that holds inside one source file only
         self.fn_hooks = {}                  # free function name -> python function of the argument list
         self.assoc_hooks = {}               # (type, fn) -> python function of the argument list: the reference's calls into crates outside its tree
         self.extra_files = []               # files outside the AIR tree whose impl blocks a driver needs (plonky2's fri/, iop/challenger.rs)
@@ -1731,6 +1733,8 @@ class Interp:
                 return None
             if name in ("true", "false"):
                 return name == "true"
+            if name in self.const_generics:
+                return self.const_generics[name]
         if len(segs) >= 2 and name in FIELD_CONSTS and segs[-2] in ("P", "F", "FE", "Scalar", "GoldilocksField", "Self", "Extension"):
             return Fe2(FIELD_CONSTS[name], 0) if segs[-2] == "Extension" else Fe(FIELD_CONSTS[name])
         if len(segs) >= 2 and name in self.field_consts and segs[-2] in ("F", "Self", "GoldilocksField"):
@@ -1779,6 +1783,8 @@ class Interp:
             raise self.err(src, line, "call of a non-function")
         segs = callee[1]
         name = segs[-1]
+        if len(segs) == 1 and (os.path.basename(src.path), name) in self.fn_hooks_in:
+            return self.fn_hooks_in[(os.path.basename(src.path), name)](args)
         if name in self.fn_hooks and (len(segs) == 1 or not re.match(r"^[A-Z]", segs[-2])):
             return self.fn_hooks[name](args)
         if len(segs) == 1 and name in env and isinstance(env[name], Closure):
@@ -1850,6 +1856,12 @@ class Interp:
             return None
         if name == "once" and "iter" in segs:
             return [args[0]]
+        if name == "repeat_with" and "iter" in segs:
+            # iter::repeat_with(f): f(), f(), ... without end (hash/keccak.rs:25: the challenger's hash onion, cut by `.take`)
+            def forever(f=args[0]):
+                while True:
+                    yield self.call_closure(f, [])
+            return LazyIter(forever())
         if name == "repeat" and ("iter" in segs or (len(segs) == 1 and self.find_fn_file(name, src.path) is None)):
             return RepeatForever(args[0])
         if name == "from" and len(segs) >= 2 and segs[-2] in INT_TYPES | {"F", "P", "FE"}:
@@ -2006,13 +2018,24 @@ class Interp:
         if isinstance(r, Cursor):
             if name == "write_all":
                 return r.write_all(args[0])
-            if name == "get_ref":
+            if name in ("get_ref", "into_inner"):
                 return r.data
             raise self.err(src, line, f"Cursor::{name}")
         if name == "to_vec" and isinstance(r, Struct) and "__name__" in r:         # HashOut::to_vec (hash_types.rs:80), not the slice adaptor
             v = self.call_assoc(r["__name__"], name, args, r.get("__file__", src.path), self_val=r, has_self=True)
             if v is not NOT_FOUND:
                 return v
+        if isinstance(r, LazyIter):
+            # an iterator without end: the adaptors stay pending until `.take(n)` cuts it into a list
+            if name == "map":
+                return LazyIter(self.call_closure(args[0], [x]) for x in r.it)
+            if name == "filter":
+                return LazyIter(x for x in r.it if self.truthy(self.call_closure(args[0], [x])))
+            if name in ("flat_map", "flat_map_iter"):
+                return LazyIter(y for x in r.it for y in self.iterate(self.call_closure(args[0], [x]), src, line))
+            if name == "take":
+                return [x for _, x in zip(range(args[0]), r.it)]
+            raise self.err(src, line, f"iter::repeat_with().{name}")
         # ---- adaptors that do nothing here
         if name in ("iter", "into_iter", "iter_mut", "copied", "cloned", "collect", "collect_vec", "to_vec", "try_into", "unwrap", "expect", "by_ref",
                     "as_ref", "as_mut", "borrow", "borrow_mut", "as_mut_slice", "as_ptr", "as_mut_ptr", "into", "to_owned", "as_slice_of_cells", "peekable", "into_par_iter", "par_iter", "par_iter_mut", "unwrap_or_else", "unwrap_or_default"):
@@ -2368,6 +2391,13 @@ class Interp:
             if params and params[0] == ("pid", "self"):
                 return self.call_fn(target, name, args, r)
         raise self.err(src, line, f"method `.{name}()` on {type(r).__name__}")
+
+
+class LazyIter:
+    """an endless iterator (iter::repeat_with and what `.map` / `.filter` / `.flat_map` make of it), kept as a Python generator"""
+
+    def __init__(self, it):
+        self.it = it
 
 
 class RepeatForever:
