@@ -184,8 +184,8 @@ struct DeviceCtx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool owns_stream = false;
-    int hasher = 0;                            // OLA_HASH_POSEIDON / _BLAKE3 / _POSEIDON2 / _POSEIDON2_POW_POSEIDON: GenericConfig::Hasher of the Merkle
-                                               // trees and the challenger (and InnerHasher of the proof of work: merkle.hip inner_hasher)
+    int hasher = 0;                            // the configuration (a row of hasher_host.h): GenericConfig::Hasher of the Merkle trees and the
+                                               // challenger, and through the row's `inner` the InnerHasher of the proof of work
     bool timing = false;                       // OLA_TIMING=1: per-phase wall-clock on stderr (synchronises at phase edges)
     bool priming = false;                      // ola_gpu_warmup's throw-away proof of an all-zero instance: the divisibility check is off
     std::vector<void*> persistent;

@@ -1,7 +1,7 @@
-// Poseidon-Goldilocks sponge + Merkle tree kernels for gfx950 (and the byte-hash leaves / nodes of Blake3GoldilocksConfig, blake3.cuh,
-// and KeccakGoldilocksConfig, keccak.cuh).
-// The sponge kernels are templates over the permutation: Poseidon (poseidon.cuh) or Poseidon2 (poseidon2.cuh, the Hasher of
-// Poseidon2GoldilocksConfig / Poseidon2GoldilocksConfig2 -- the same sponge and tree, hash/poseidon2.rs:500-512).
+// Merkle tree kernels for gfx950, one body per leaf shape and thread mapping, instantiated for the hash policies of hasher.cuh: the
+// Poseidon and Poseidon2 sponges (poseidon.cuh, poseidon2.cuh: PoseidonGoldilocksConfig, Poseidon2GoldilocksConfig /
+// Poseidon2GoldilocksConfig2 -- the same sponge and tree, hash/poseidon2.rs:500-512) and the byte hashes of Blake3GoldilocksConfig
+// (blake3.cuh) and KeccakGoldilocksConfig (keccak.cuh).
 //
 // Replaces (reference, relative to plonky2/plonky2/src/hash):
 //   hashing.rs:84-107            hash_n_to_m_no_pad  -- overwrite-mode sponge, rate 8, 4-element digest
@@ -20,96 +20,52 @@
 #include "../../include/ola_gpu.h"
 #include "device_ctx.h"
 #include "gl.cuh"
-#include "poseidon.cuh"
-#include "poseidon2.cuh"
-#include "blake3.cuh"
-#include "keccak.cuh"
+#include "hasher.cuh"
+#include "hasher_host.h"
 
 namespace ola {
 
 // batches up to this many states / nodes / leaves use the quad-cooperative (latency-oriented) kernels
 static const size_t QUAD_MAX = 8192;
 
-// the algebraic permutation of a sponge kernel
-enum : int { PERM_POSEIDON = 0, PERM_POSEIDON2 = 1 };
-template <int PERM>
-__device__ __forceinline__ void permute12(u64 (&s)[12]) {
-    if constexpr (PERM == PERM_POSEIDON2) poseidon2_permute(s);
-    else poseidon_permute(s);
-}
-template <int PERM>
-__device__ __forceinline__ void permute_quad(u64 (&x)[3], int q) {
-    if constexpr (PERM == PERM_POSEIDON2) poseidon2_permute_quad(x, q);
-    else poseidon_permute_quad(x, q);
-}
-
+// ---- the three leaf shapes: words(j) delivers word i of leaf j.  Trace values are canonicalised as they are read; the extension
+// planes only for the byte hashes (CANON), whose digest depends on the representative -- the sponge reduces whatever it absorbs.
 // leaf j = (cols[0][j], cols[1][j], ...), column c at base + c*col_stride
-template <int PERM>
-__global__ __launch_bounds__(256) void leaf_hash_colmajor_kernel(const u64* __restrict__ base, size_t col_stride,
-                                                                  int ncols, size_t num_leaves, u64* __restrict__ out) {
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= num_leaves) return;
-    u64 s[12];
-#pragma unroll
-    for (int i = 0; i < 12; i++) s[i] = 0;
-    for (int c0 = 0; c0 < ncols; c0 += 8) {
-        const int len = min(8, ncols - c0);
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-            if (i < len) s[i] = gl_canon(base[(size_t)(c0 + i) * col_stride + j]);
-        permute12<PERM>(s);
+struct ColMajorSrc {
+    const u64* base; size_t col_stride; u32 ncols;
+    __device__ __forceinline__ u32 nwords() const { return ncols; }
+    __device__ __forceinline__ auto words(size_t j) const {
+        return [b = base, stride = col_stride, j](u32 i) { return gl_canon(b[(size_t)i * stride + j]); };
     }
-    ulonglong2* o = reinterpret_cast<ulonglong2*>(out + j * 4);
-    o[0] = make_ulonglong2(s[0], s[1]);
-    o[1] = make_ulonglong2(s[2], s[3]);
-}
-
+};
 // leaf j = row j of a row-major matrix (rows of row_len elements)
-template <int PERM>
-__global__ __launch_bounds__(256) void leaf_hash_rowmajor_kernel(const u64* __restrict__ rows, size_t row_len,
-                                                                  size_t num_leaves, u64* __restrict__ out) {
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= num_leaves) return;
-    const u64* r = rows + j * row_len;
-    u64 s[12];
-#pragma unroll
-    for (int i = 0; i < 12; i++) s[i] = 0;
-    for (size_t c0 = 0; c0 < row_len; c0 += 8) {
-        const int len = (int)min((size_t)8, row_len - c0);
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-            if (i < len) s[i] = gl_canon(r[c0 + i]);
-        permute12<PERM>(s);
+struct RowMajorSrc {
+    const u64* rows; size_t row_len;
+    __device__ __forceinline__ u32 nwords() const { return (u32)row_len; }
+    __device__ __forceinline__ auto words(size_t j) const {
+        return [r = rows, at = j * row_len](u32 i) { return gl_canon(r[at + i]); };
     }
-    ulonglong2* o = reinterpret_cast<ulonglong2*>(out + j * 4);
-    o[0] = make_ulonglong2(s[0], s[1]);
-    o[1] = make_ulonglong2(s[2], s[3]);
-}
+};
+// FRI commit-phase leaves (fri/prover.rs:90-96): leaf j = flatten(`arity` consecutive bit-reversed extension values) =
+// (a[arity j], b[arity j], a[arity j + 1], b[arity j + 1], ...) with the extension field stored as two planes.
+template <bool CANON>
+struct ExtSrc {
+    const u64* plane_a; const u64* plane_b; u32 arity;
+    __device__ __forceinline__ u32 nwords() const { return 2 * arity; }
+    __device__ __forceinline__ auto words(size_t j) const {
+        return [pa = plane_a, pb = plane_b, at = j * arity](u32 i) {
+            const u64 v = ((i & 1) ? pb : pa)[at + (i >> 1)];
+            return CANON ? gl_canon(v) : v;
+        };
+    }
+};
 
-// FRI commit-phase leaves (fri/prover.rs:90-96): leaf j = flatten(16 consecutive bit-reversed extension values) =
-// (a[16j], b[16j], a[16j+1], b[16j+1], ...) with the extension field stored as two planes.
-template <int PERM>
-__global__ __launch_bounds__(256) void leaf_hash_ext_kernel(const u64* __restrict__ plane_a,
-                                                            const u64* __restrict__ plane_b, int arity,
-                                                            size_t num_leaves, u64* __restrict__ out) {
+// one lane per leaf
+template <class H, class Src>
+__global__ __launch_bounds__(256) void leaf_hash_kernel(Src src, size_t num_leaves, u64* __restrict__ out) {
     const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= num_leaves) return;
-    u64 s[12];
-#pragma unroll
-    for (int i = 0; i < 12; i++) s[i] = 0;
-    for (int k0 = 0; k0 < arity; k0 += 4) {  // 4 extension elements = 8 sponge lanes per permutation
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (k0 + k < arity) {
-                s[2 * k] = plane_a[j * arity + k0 + k];
-                s[2 * k + 1] = plane_b[j * arity + k0 + k];
-            }
-        }
-        permute12<PERM>(s);
-    }
-    ulonglong2* o = reinterpret_cast<ulonglong2*>(out + j * 4);
-    o[0] = make_ulonglong2(s[0], s[1]);
-    o[1] = make_ulonglong2(s[2], s[3]);
+    H::leaf(src.words(j), src.nwords(), out + j * 4);
 }
 
 // ---- quad-cooperative variants (4 threads per leaf / node, poseidon.cuh): same digests, used when the batch is too small
@@ -126,52 +82,11 @@ __device__ __forceinline__ void quad_store_digest(u64* __restrict__ out4, const 
     if (q == 1) out4[3] = x[0];
 }
 
-template <int PERM>
-__global__ __launch_bounds__(256) void leaf_hash_colmajor_quad_kernel(const u64* __restrict__ base, size_t col_stride, int ncols,
-                                                                       size_t num_leaves, u64* __restrict__ out) {
+template <int PERM, class Src>
+__global__ __launch_bounds__(256) void leaf_hash_quad_kernel(Src src, size_t num_leaves, u64* __restrict__ out) {
     QUAD_PROLOGUE(num_leaves)
-    u64 x[3] = {0, 0, 0};
-    for (int c0 = 0; c0 < ncols; c0 += 8) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const int e = 3 * q + k;   // sponge lane
-            if (e < 8 && c0 + e < ncols) x[k] = gl_canon(base[(size_t)(c0 + e) * col_stride + j]);
-        }
-        permute_quad<PERM>(x, q);
-    }
-    quad_store_digest(out + j * 4, x, q, live);
-}
-
-template <int PERM>
-__global__ __launch_bounds__(256) void leaf_hash_rowmajor_quad_kernel(const u64* __restrict__ rows, size_t row_len, size_t num_leaves,
-                                                                       u64* __restrict__ out) {
-    QUAD_PROLOGUE(num_leaves)
-    const u64* r = rows + j * row_len;
-    u64 x[3] = {0, 0, 0};
-    for (size_t c0 = 0; c0 < row_len; c0 += 8) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const size_t e = 3 * q + k;
-            if (e < 8 && c0 + e < row_len) x[k] = gl_canon(r[c0 + e]);
-        }
-        permute_quad<PERM>(x, q);
-    }
-    quad_store_digest(out + j * 4, x, q, live);
-}
-
-template <int PERM>
-__global__ __launch_bounds__(256) void leaf_hash_ext_quad_kernel(const u64* __restrict__ plane_a, const u64* __restrict__ plane_b, int arity,
-                                                                  size_t num_leaves, u64* __restrict__ out) {
-    QUAD_PROLOGUE(num_leaves)
-    u64 x[3] = {0, 0, 0};
-    for (int k0 = 0; k0 < arity; k0 += 4) {   // sponge lane e = 2*kk (+1): extension element k0 + e/2, plane e & 1
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const int e = 3 * q + k;
-            if (e < 8 && k0 + e / 2 < arity) x[k] = ((e & 1) ? plane_b : plane_a)[j * arity + k0 + e / 2];
-        }
-        permute_quad<PERM>(x, q);
-    }
+    u64 x[3];
+    sponge_quad_leaf<PERM>(src.words(j), src.nwords(), x, q);
     quad_store_digest(out + j * 4, x, q, live);
 }
 
@@ -193,19 +108,12 @@ __global__ __launch_bounds__(256) void merkle_level_quad_kernel(u64* __restrict_
     quad_hash_node<PERM>(heap, first + j, q, live);
 }
 
-// parents [first, first+count) of a heap-ordered digest array
-template <int PERM>
+// parents [first, first+count) of a heap-ordered digest array, one lane per node (children 2i, 2i+1 are adjacent)
+template <class H>
 __global__ __launch_bounds__(256) void merkle_level_kernel(u64* __restrict__ heap, size_t first, size_t count) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count) return;
-    const size_t i = first + t;
-    const ulonglong2* ch = reinterpret_cast<const ulonglong2*>(heap + 8 * i);  // children 2i, 2i+1 are adjacent
-    const ulonglong2 c0 = ch[0], c1 = ch[1], c2 = ch[2], c3 = ch[3];
-    u64 s[12] = {c0.x, c0.y, c1.x, c1.y, c2.x, c2.y, c3.x, c3.y, 0, 0, 0, 0};
-    permute12<PERM>(s);
-    ulonglong2* o = reinterpret_cast<ulonglong2*>(heap + 4 * i);
-    o[0] = make_ulonglong2(s[0], s[1]);
-    o[1] = make_ulonglong2(s[2], s[3]);
+    H::node(heap + 8 * (first + t), heap + 4 * (first + t));
 }
 
 // The top of a tree in one launch: levels of `first` nodes and fewer (4 * first <= blockDim.x), down to the level of `last`
@@ -310,65 +218,14 @@ __global__ __launch_bounds__(256) void pow_kernel(u64 h0, u64 h1, u64 h2, u64 h3
     if ((s[0] >> (64 - bits)) == 0) atomicMin(best, (unsigned long long)nonce);
 }
 
-// ---- Blake3GoldilocksConfig (blake3.cuh) and KeccakGoldilocksConfig (keccak.cuh): the byte hashes.  The same three leaf shapes and
-// the same heap, one thread per leaf / node; one body per kernel, instantiated for either hash (BH).
-// MULTI = Blake3 leaves of more than one 1024-byte chunk (more than 128 elements: the 134-column Poseidon table); the single-chunk
-// kernels need no stack of chaining values and therefore no scratch memory.  Keccak's sponge has no such case (MULTI = false).
-enum : int { BH_BLAKE3 = 0, BH_KECCAK = 1 };
-template <bool MULTI, class WordFn>
-__device__ __forceinline__ void b3_leaf(WordFn word, u32 nwords, u32 (&d)[8]) {
-    if (MULTI) b3_hash_words(word, nwords, d);
-    else b3_chunk_cv(word, 0, nwords, 0, true, d);
-}
-// digest of the `nwords` canonical words `word(i)` to out4
-template <int BH, bool MULTI, class WordFn>
-__device__ __forceinline__ void bytes_leaf(WordFn word, u32 nwords, u64* __restrict__ out4) {
-    if constexpr (BH == BH_KECCAK) {
-        u64 d[4];
-        keccak_hash_words(word, nwords, d);
-        ulonglong2* o = reinterpret_cast<ulonglong2*>(out4);
-        o[0] = make_ulonglong2(d[0], d[1]);
-        o[1] = make_ulonglong2(d[2], d[3]);
-    } else {
-        u32 d[8];
-        b3_leaf<MULTI>(word, nwords, d);
-        b3_store_digest(out4, d);
-    }
-}
-template <int BH>
-__device__ __forceinline__ void bytes_node(const u64* __restrict__ children8, u64* __restrict__ out4) {
-    if constexpr (BH == BH_KECCAK) keccak_node(children8, out4);
-    else b3_node(children8, out4);
-}
-template <int BH, bool MULTI>
-__global__ __launch_bounds__(256) void leaf_bytes_colmajor_kernel(const u64* __restrict__ base, size_t col_stride, int ncols,
-                                                                  size_t num_leaves, u64* __restrict__ out) {
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= num_leaves) return;
-    bytes_leaf<BH, MULTI>([&](u32 i) { return gl_canon(base[(size_t)i * col_stride + j]); }, (u32)ncols, out + j * 4);
-}
-template <int BH, bool MULTI>
-__global__ __launch_bounds__(256) void leaf_bytes_rowmajor_kernel(const u64* __restrict__ rows, size_t row_len, size_t num_leaves,
-                                                                  u64* __restrict__ out) {
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= num_leaves) return;
-    const u64* r = rows + j * row_len;
-    bytes_leaf<BH, MULTI>([&](u32 i) { return gl_canon(r[i]); }, (u32)row_len, out + j * 4);
-}
-template <int BH, bool MULTI>
-__global__ __launch_bounds__(256) void leaf_bytes_ext_kernel(const u64* __restrict__ plane_a, const u64* __restrict__ plane_b, int arity,
-                                                             size_t num_leaves, u64* __restrict__ out) {
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= num_leaves) return;
-    bytes_leaf<BH, MULTI>([&](u32 i) { return gl_canon(((i & 1) ? plane_b : plane_a)[j * arity + (i >> 1)]); }, (u32)(2 * arity), out + j * 4);
-}
-// The same leaves for arity 16, through LDS (round 6).  A thread of leaf_bytes_ext_kernel reads 16 + 16 words 128 bytes apart from its
-// neighbour's: a wave touches 64 lines per load and the lines are gone from the vector cache before their other words are asked
+// ---- kernels of the byte hashes alone (H::BYTES: one thread per leaf / node throughout, no quad forms)
+// The extension leaves for arity 16, through LDS (round 6).  A thread of leaf_hash_kernel<H, ExtSrc> reads 16 + 16 words 128 bytes apart
+// from its neighbour's: a wave touches 64 lines per load and the lines are gone from the vector cache before their other words are asked
 // for -- 17.1 GB fetched per 2^22-row proof for 1.2 GB of values (profiles/r05_proof_pmc_blake3.txt).  Here a workgroup copies
 // its 128 leaves x 16 values of both planes with 16-byte loads on consecutive addresses and every thread hashes its leaf out of
 // LDS (rows padded to 17 words: conflict-free for 8-byte reads).
 #define B3X_LEAVES 128
-template <int BH>
+template <class H>
 __global__ __launch_bounds__(B3X_LEAVES) void leaf_bytes_ext16_kernel(const u64* __restrict__ plane_a, const u64* __restrict__ plane_b, size_t num_leaves,
                                                                       u64* __restrict__ out) {
     __shared__ u64 tile[2][B3X_LEAVES * 17];
@@ -389,13 +246,7 @@ __global__ __launch_bounds__(B3X_LEAVES) void leaf_bytes_ext16_kernel(const u64*
     __syncthreads();
     const size_t j = j0 + threadIdx.x;
     if (j >= num_leaves) return;
-    bytes_leaf<BH, false>([&](u32 i) { return gl_canon(tile[i & 1][threadIdx.x * 17 + (i >> 1)]); }, 32u, out + j * 4);
-}
-template <int BH>
-__global__ __launch_bounds__(256) void merkle_level_bytes_kernel(u64* __restrict__ heap, size_t first, size_t count) {
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    bytes_node<BH>(heap + 8 * (first + t), heap + 4 * (first + t));
+    H::leaf([&](u32 i) { return gl_canon(tile[i & 1][threadIdx.x * 17 + (i >> 1)]); }, 32u, out + j * 4);
 }
 // `nlev` (<= 8) consecutive levels in one launch (round 6): a workgroup computes 256 nodes of the level of `first` nodes from their
 // children in the heap, then the 128, 64, ... nodes above them out of LDS -- every level is still written to the heap (sibling paths
@@ -403,14 +254,14 @@ __global__ __launch_bounds__(256) void merkle_level_bytes_kernel(u64* __restrict
 // 314 level launches and 20.6 GB per proof before): eight levels per launch are SLOWER (6.3 -> 8.4 ms: the upper levels run on 128, 64,
 // ... 1 lanes of a workgroup that keeps its slot for eight compressions in a row), two or three are a little faster (5.8 ms), four 6.0;
 // the default is two (OLA_MERKLE_FUSED_LEVELS, 0 = one launch per level).
-template <int BH>
+template <class H>
 __global__ __launch_bounds__(256) void merkle_levels_bytes_kernel(u64* __restrict__ heap, size_t first, int nlev) {
     __shared__ u64 sh[2][256 * 4];
     const int t = threadIdx.x;
-    u64 d[4];
+    alignas(16) u64 d[4];
     {
         const size_t node = first + (size_t)blockIdx.x * 256 + t;
-        bytes_node<BH>(heap + 8 * node, d);
+        H::node(heap + 8 * node, d);
 #pragma unroll
         for (int k = 0; k < 4; k++) { heap[4 * node + k] = d[k]; sh[0][4 * t + k] = d[k]; }
     }
@@ -419,48 +270,20 @@ __global__ __launch_bounds__(256) void merkle_levels_bytes_kernel(u64* __restric
         const int count = 256 >> l;
         if (t < count) {
             const size_t node = (first >> l) + (size_t)blockIdx.x * count + t;
-            bytes_node<BH>(&sh[(l - 1) & 1][8 * t], d);
+            H::node(&sh[(l - 1) & 1][8 * t], d);
 #pragma unroll
             for (int k = 0; k < 4; k++) { heap[4 * node + k] = d[k]; sh[l & 1][4 * t + k] = d[k]; }
         }
     }
 }
 // levels of `first` nodes and fewer (first <= blockDim.x) down to the level of `last` nodes in one workgroup
-template <int BH>
+template <class H>
 __global__ __launch_bounds__(256) void merkle_top_bytes_kernel(u64* __restrict__ heap, size_t first, size_t last) {
     for (size_t level = first; level >= last && level >= 1; level >>= 1) {
-        if (threadIdx.x < level) bytes_node<BH>(heap + 8 * (level + threadIdx.x), heap + 4 * (level + threadIdx.x));
+        if (threadIdx.x < level) H::node(heap + 8 * (level + threadIdx.x), heap + 4 * (level + threadIdx.x));
         __threadfence_block();
         __syncthreads();
     }
-}
-static inline bool is_keccak(const DeviceCtx* ctx) { return ctx->hasher == (int)OLA_HASH_KECCAK; }
-// the byte hashes: digests that are bytes, one thread per leaf / node
-static inline bool is_bytes_hash(const DeviceCtx* ctx) { return ctx->hasher == (int)OLA_HASH_BLAKE3 || is_keccak(ctx); }
-// f(std::integral_constant<int, BH>, std::integral_constant<bool, MULTI>) for the context's byte hash and a leaf of `words` words
-template <class F>
-static void with_bytes_hash(const DeviceCtx* ctx, size_t words, F&& f) {
-    if (is_keccak(ctx)) f(std::integral_constant<int, BH_KECCAK>(), std::false_type());
-    else if (words > (size_t)B3_CHUNK_WORDS) f(std::integral_constant<int, BH_BLAKE3>(), std::true_type());
-    else f(std::integral_constant<int, BH_BLAKE3>(), std::false_type());
-}
-// f(std::integral_constant<int, PERM>) with the sponge permutation of `hasher`: the context's Hasher (trees) or InnerHasher (proof of
-// work).  Every hasher the context accepts is named here: a new one is an error until it is, never a silent Poseidon.
-template <class F>
-static void with_perm(uint32_t hasher, F&& f) {
-    switch (hasher) {
-        case OLA_HASH_POSEIDON: f(std::integral_constant<int, PERM_POSEIDON>()); return;
-        case OLA_HASH_POSEIDON2:
-        case OLA_HASH_POSEIDON2_POW_POSEIDON: f(std::integral_constant<int, PERM_POSEIDON2>()); return;
-        default: throw OlaError(OLA_E_INTERNAL, "no sponge permutation for this hasher");
-    }
-}
-// plonk/config.rs:117-161: InnerHasher is Poseidon2 in Poseidon2GoldilocksConfig only, Poseidon in every other configuration
-static inline uint32_t inner_hasher(const DeviceCtx* ctx) {
-    return ctx->hasher == (int)OLA_HASH_POSEIDON2 ? OLA_HASH_POSEIDON2 : OLA_HASH_POSEIDON;
-}
-static void require_leaf_width(size_t words) {
-    if (words == 0 || words > 4096) throw OlaError(-1, "Blake3 and Keccak leaves hold 1..4096 field elements");
 }
 
 // ---- host launchers ----
@@ -469,128 +292,83 @@ void poseidon_init(DeviceCtx*) {   // both permutations' constants on the callin
     poseidon2_upload_constants();
 }
 
-// hash invocations per leaf of `words` field elements: sponge permutations (rate 8), Blake3 compressions (64-byte blocks,
-// plus the parent compressions of a multi-chunk leaf), or Keccak-f permutations (rate 17 words, the padding always in the count)
-static double leaf_hash_calls(const DeviceCtx* ctx, size_t words) {
-    if (is_keccak(ctx)) return (double)(words / KECCAK_RATE_WORDS + 1);
-    if (ctx->hasher == (int)OLA_HASH_BLAKE3) { const size_t blocks = (words * 8 + 63) / 64, chunks = (words * 8 + 1023) / 1024; return (double)(blocks + chunks - 1); }
-    return (double)((words + 7) / 8);
+// hash invocations per leaf of `words` field elements, for the phase accounting
+static double leaf_hash_calls(const DeviceCtx* ctx, size_t words) { return hasher_row((uint32_t)ctx->hasher).leaf_calls(words); }
+
+// the leaves of `src` under H: a quad per leaf for a small batch of sponge leaves, else a lane per leaf
+template <class H, class Src>
+static void launch_leaves(DeviceCtx* ctx, const Src& src, size_t words, size_t num_leaves, u64* out) {
+    if (H::BYTES && (words == 0 || words > 4096)) throw OlaError(-1, "Blake3 and Keccak leaves hold 1..4096 field elements");
+    if (num_leaves == 0) return;
+    if constexpr (!H::BYTES) {
+        if (num_leaves <= QUAD_MAX) {
+            hipLaunchKernelGGL((leaf_hash_quad_kernel<H::perm, Src>), dim3((unsigned)((4 * num_leaves + 255) / 256)), dim3(256), 0, ctx->stream, src, num_leaves, out);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((leaf_hash_kernel<H, Src>), dim3((unsigned)((num_leaves + 255) / 256)), dim3(256), 0, ctx->stream, src, num_leaves, out);
 }
 void launch_leaf_hash_colmajor(DeviceCtx* ctx, const u64* base, size_t col_stride, int ncols, size_t num_leaves,
                                u64* out) {
     PhaseScope ph(ctx, PH_LEAF_HASH, (double)num_leaves * leaf_hash_calls(ctx, (size_t)ncols), (double)num_leaves * ((size_t)ncols * 8 + 32));
-    if (is_bytes_hash(ctx)) {
-        require_leaf_width((size_t)ncols);
-        if (num_leaves) {
-            const dim3 grid((unsigned)((num_leaves + 255) / 256));
-            with_bytes_hash(ctx, (size_t)ncols, [&](auto bh, auto multi) {
-                hipLaunchKernelGGL((leaf_bytes_colmajor_kernel<decltype(bh)::value, decltype(multi)::value>), grid, dim3(256), 0, ctx->stream, base, col_stride, ncols, num_leaves, out);
-            });
-        }
-        return;
-    }
-    with_perm((uint32_t)ctx->hasher, [&](auto perm) {
-        constexpr int PERM = decltype(perm)::value;
-        if (num_leaves <= QUAD_MAX) {
-            hipLaunchKernelGGL(leaf_hash_colmajor_quad_kernel<PERM>, dim3((unsigned)((4 * num_leaves + 255) / 256)), dim3(256), 0, ctx->stream, base,
-                               col_stride, ncols, num_leaves, out);
-            return;
-        }
-        const unsigned blocks = (unsigned)((num_leaves + 255) / 256);
-        hipLaunchKernelGGL(leaf_hash_colmajor_kernel<PERM>, dim3(blocks), dim3(256), 0, ctx->stream, base, col_stride, ncols,
-                           num_leaves, out);
+    with_hash((uint32_t)ctx->hasher, (size_t)ncols, [&](auto tag) {
+        using H = typename decltype(tag)::type;
+        launch_leaves<H>(ctx, ColMajorSrc{base, col_stride, (u32)ncols}, (size_t)ncols, num_leaves, out);
     });
 }
 void launch_leaf_hash_rowmajor(DeviceCtx* ctx, const u64* rows, size_t row_len, size_t num_leaves, u64* out) {
-    if (is_bytes_hash(ctx)) {
-        require_leaf_width(row_len);
-        if (num_leaves) {
-            const dim3 grid((unsigned)((num_leaves + 255) / 256));
-            with_bytes_hash(ctx, row_len, [&](auto bh, auto multi) {
-                hipLaunchKernelGGL((leaf_bytes_rowmajor_kernel<decltype(bh)::value, decltype(multi)::value>), grid, dim3(256), 0, ctx->stream, rows, row_len, num_leaves, out);
-            });
-        }
-        return;
-    }
-    with_perm((uint32_t)ctx->hasher, [&](auto perm) {
-        constexpr int PERM = decltype(perm)::value;
-        if (num_leaves <= QUAD_MAX) {
-            hipLaunchKernelGGL(leaf_hash_rowmajor_quad_kernel<PERM>, dim3((unsigned)((4 * num_leaves + 255) / 256)), dim3(256), 0, ctx->stream, rows,
-                               row_len, num_leaves, out);
-            return;
-        }
-        const unsigned blocks = (unsigned)((num_leaves + 255) / 256);
-        hipLaunchKernelGGL(leaf_hash_rowmajor_kernel<PERM>, dim3(blocks), dim3(256), 0, ctx->stream, rows, row_len, num_leaves, out);
+    with_hash((uint32_t)ctx->hasher, row_len, [&](auto tag) {
+        using H = typename decltype(tag)::type;
+        launch_leaves<H>(ctx, RowMajorSrc{rows, row_len}, row_len, num_leaves, out);
     });
 }
 void launch_leaf_hash_ext(DeviceCtx* ctx, const u64* pa, const u64* pb, int arity, size_t num_leaves, u64* out) {
-    PhaseScope ph(ctx, PH_LEAF_HASH, (double)num_leaves * leaf_hash_calls(ctx, (size_t)(2 * arity)), (double)num_leaves * ((size_t)arity * 16 + 32));
-    if (is_bytes_hash(ctx)) {
-        require_leaf_width((size_t)(2 * arity));
-        if (num_leaves) {
-            const dim3 grid((unsigned)((num_leaves + 255) / 256));
-            static const bool staged = !(getenv("OLA_LEAF_EXT_STAGED") && !strcmp(getenv("OLA_LEAF_EXT_STAGED"), "0"));
+    const size_t words = (size_t)(2 * arity);
+    PhaseScope ph(ctx, PH_LEAF_HASH, (double)num_leaves * leaf_hash_calls(ctx, words), (double)num_leaves * ((size_t)arity * 16 + 32));
+    static const bool staged = !(getenv("OLA_LEAF_EXT_STAGED") && !strcmp(getenv("OLA_LEAF_EXT_STAGED"), "0"));
+    with_hash((uint32_t)ctx->hasher, words, [&](auto tag) {
+        using H = typename decltype(tag)::type;
+        if constexpr (H::BYTES) {
             if (arity == 16 && staged && num_leaves >= 1024 && (((uintptr_t)pa | (uintptr_t)pb) & 15) == 0) {
-                const dim3 grid16((unsigned)((num_leaves + B3X_LEAVES - 1) / B3X_LEAVES));
-                if (is_keccak(ctx)) hipLaunchKernelGGL(leaf_bytes_ext16_kernel<BH_KECCAK>, grid16, dim3(B3X_LEAVES), 0, ctx->stream, pa, pb, num_leaves, out);
-                else hipLaunchKernelGGL(leaf_bytes_ext16_kernel<BH_BLAKE3>, grid16, dim3(B3X_LEAVES), 0, ctx->stream, pa, pb, num_leaves, out);
+                hipLaunchKernelGGL(leaf_bytes_ext16_kernel<typename H::Small>, dim3((unsigned)((num_leaves + B3X_LEAVES - 1) / B3X_LEAVES)), dim3(B3X_LEAVES), 0, ctx->stream, pa, pb, num_leaves, out);
                 return;
             }
-            with_bytes_hash(ctx, (size_t)(2 * arity), [&](auto bh, auto multi) {
-                hipLaunchKernelGGL((leaf_bytes_ext_kernel<decltype(bh)::value, decltype(multi)::value>), grid, dim3(256), 0, ctx->stream, pa, pb, arity, num_leaves, out);
-            });
         }
-        return;
-    }
-    with_perm((uint32_t)ctx->hasher, [&](auto perm) {
-        constexpr int PERM = decltype(perm)::value;
-        if (num_leaves <= QUAD_MAX) {
-            hipLaunchKernelGGL(leaf_hash_ext_quad_kernel<PERM>, dim3((unsigned)((4 * num_leaves + 255) / 256)), dim3(256), 0, ctx->stream, pa, pb, arity,
-                               num_leaves, out);
-            return;
-        }
-        const unsigned blocks = (unsigned)((num_leaves + 255) / 256);
-        hipLaunchKernelGGL(leaf_hash_ext_kernel<PERM>, dim3(blocks), dim3(256), 0, ctx->stream, pa, pb, arity, num_leaves, out);
+        launch_leaves<H>(ctx, ExtSrc<H::BYTES>{pa, pb, (u32)arity}, words, num_leaves, out);
     });
 }
 // heap[N..2N) must hold the leaf digests; fills heap[2^cap_height .. N): like the reference (merkle_tree/mod.rs:228-233)
 // nothing above the cap is ever hashed
 void launch_merkle_build(DeviceCtx* ctx, u64* heap, size_t num_leaves, uint32_t cap_height) {
-    const size_t last = (size_t)1 << cap_height, top = 256;   // levels of <= `top` nodes share one launch (1024 threads)
+    const size_t last = (size_t)1 << cap_height, top = 256;   // levels of <= `top` nodes share one launch
     PhaseScope ph(ctx, PH_MERKLE_LEVELS, num_leaves > last ? (double)(num_leaves - last) : 0.0, num_leaves > last ? (double)(num_leaves - last) * 96 : 0.0);
-    size_t level = num_leaves / 2;
-    if (is_bytes_hash(ctx)) {
-        static const int fused = getenv("OLA_MERKLE_FUSED_LEVELS") ? atoi(getenv("OLA_MERKLE_FUSED_LEVELS")) : 2;
-        if (fused > 1 && last <= top && (level & (level - 1)) == 0) {
-            while (level > top) {          // level is a power of two >= 512: up to `fused` levels per launch, the last of them still above `top`
-                int nlev = 0;
-                while (nlev < fused && nlev < 8 && (level >> nlev) > top) nlev++;
-                if (is_keccak(ctx)) hipLaunchKernelGGL(merkle_levels_bytes_kernel<BH_KECCAK>, dim3((unsigned)(level / 256)), dim3(256), 0, ctx->stream, heap, level, nlev);
-                else hipLaunchKernelGGL(merkle_levels_bytes_kernel<BH_BLAKE3>, dim3((unsigned)(level / 256)), dim3(256), 0, ctx->stream, heap, level, nlev);
-                level >>= nlev;
+    static const int fused = getenv("OLA_MERKLE_FUSED_LEVELS") ? atoi(getenv("OLA_MERKLE_FUSED_LEVELS")) : 2;
+    with_hash((uint32_t)ctx->hasher, 0, [&](auto tag) {
+        using H = typename decltype(tag)::type::Small;
+        size_t level = num_leaves / 2;
+        if constexpr (H::BYTES) {
+            if (fused > 1 && last <= top && (level & (level - 1)) == 0) {
+                while (level > top) {          // level is a power of two >= 512: up to `fused` levels per launch, the last of them still above `top`
+                    int nlev = 0;
+                    while (nlev < fused && nlev < 8 && (level >> nlev) > top) nlev++;
+                    hipLaunchKernelGGL(merkle_levels_bytes_kernel<H>, dim3((unsigned)(level / 256)), dim3(256), 0, ctx->stream, heap, level, nlev);
+                    level >>= nlev;
+                }
             }
         }
         for (; level >= last && level > top; level /= 2) {
-            const dim3 grid((unsigned)((level + 255) / 256));
-            if (is_keccak(ctx)) hipLaunchKernelGGL(merkle_level_bytes_kernel<BH_KECCAK>, grid, dim3(256), 0, ctx->stream, heap, level, level);
-            else hipLaunchKernelGGL(merkle_level_bytes_kernel<BH_BLAKE3>, grid, dim3(256), 0, ctx->stream, heap, level, level);
-        }
-        if (level >= last && level >= 1) {
-            if (is_keccak(ctx)) hipLaunchKernelGGL(merkle_top_bytes_kernel<BH_KECCAK>, dim3(1), dim3(256), 0, ctx->stream, heap, level, last);
-            else hipLaunchKernelGGL(merkle_top_bytes_kernel<BH_BLAKE3>, dim3(1), dim3(256), 0, ctx->stream, heap, level, last);
-        }
-        return;
-    }
-    with_perm((uint32_t)ctx->hasher, [&](auto perm) {
-        constexpr int PERM = decltype(perm)::value;
-        for (; level >= last && level > top; level /= 2) {
-            if (level <= QUAD_MAX) {
-                hipLaunchKernelGGL(merkle_level_quad_kernel<PERM>, dim3((unsigned)((4 * level + 255) / 256)), dim3(256), 0, ctx->stream, heap, level, level);
-            } else {
-                hipLaunchKernelGGL(merkle_level_kernel<PERM>, dim3((unsigned)((level + 255) / 256)), dim3(256), 0, ctx->stream, heap, level, level);
+            if constexpr (!H::BYTES) {
+                if (level <= QUAD_MAX) {
+                    hipLaunchKernelGGL(merkle_level_quad_kernel<H::perm>, dim3((unsigned)((4 * level + 255) / 256)), dim3(256), 0, ctx->stream, heap, level, level);
+                    continue;
+                }
             }
+            hipLaunchKernelGGL(merkle_level_kernel<H>, dim3((unsigned)((level + 255) / 256)), dim3(256), 0, ctx->stream, heap, level, level);
         }
-        if (level >= last && level >= 1) hipLaunchKernelGGL(merkle_top_kernel<PERM>, dim3(1), dim3(1024), 0, ctx->stream, heap, level, last);
+        if (level >= last && level >= 1) {   // the byte hashes with a lane per node (256 threads), the sponges with a quad per node (1024)
+            if constexpr (H::BYTES) hipLaunchKernelGGL(merkle_top_bytes_kernel<H>, dim3(1), dim3(256), 0, ctx->stream, heap, level, last);
+            else hipLaunchKernelGGL(merkle_top_kernel<H::perm>, dim3(1), dim3(1024), 0, ctx->stream, heap, level, last);
+        }
     });
 }
 // `hasher` names the permutation (OLA_HASH_POSEIDON or OLA_HASH_POSEIDON2), not the context's configuration
@@ -608,7 +386,7 @@ void launch_poseidon_states(DeviceCtx* ctx, u64* states, size_t n, uint32_t hash
 }
 // one batch of the proof-of-work search with the context's InnerHasher (fri/prover.rs:133 C::InnerHasher::hash_no_pad)
 static void launch_pow_batch(DeviceCtx* ctx, hipStream_t stream, const u64 h[4], u64 start, u64 count, u32 bits, unsigned long long* best) {
-    with_perm(inner_hasher(ctx), [&](auto perm) {
+    with_perm(hasher_row((uint32_t)ctx->hasher).inner, [&](auto perm) {
         constexpr int PERM = decltype(perm)::value;
         hipLaunchKernelGGL(pow_kernel<PERM>, dim3((unsigned)(count / 256)), dim3(256), 0, stream, h[0], h[1], h[2], h[3], start, bits, best);
     });

@@ -17,7 +17,7 @@
 #include "../../include/ola_gpu.h"
 #include "device_ctx.h"
 #include "gl.cuh"
-#include "poseidon_host.h"
+#include "hasher_host.h"
 #include "lookup.h"
 #include "tablegen.h"
 #include "tablegen_columns.h"
@@ -112,10 +112,8 @@ static void require_context(OlaCtx* ctx) {
     }
     require(false, "ctx is NULL");
 }
-// the GenericConfig<2> types the library proves under (include/ola_gpu.h OLA_HASH_*)
-static bool known_hasher(uint32_t h) {
-    return h == OLA_HASH_POSEIDON || h == OLA_HASH_BLAKE3 || h == OLA_HASH_POSEIDON2 || h == OLA_HASH_POSEIDON2_POW_POSEIDON || h == OLA_HASH_KECCAK;   // 4 is unassigned
-}
+// the GenericConfig<2> types the library proves under (include/ola_gpu.h OLA_HASH_*): the rows of hasher_host.h
+static bool known_hasher(uint32_t h) { return hasher_info(h) != nullptr; }
 
 // The HIP current device is a property of the calling host thread: every entry point that works on a context makes the
 // context's device current for its duration (and puts the caller's back), so that hipMalloc and constant uploads land on the

@@ -13,6 +13,7 @@
 // leaf length and depth.  Every offset a job carries is checked against the size of the image before it is used.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <vector>
@@ -20,63 +21,15 @@
 #include "../../include/ola_gpu.h"
 #include "device_ctx.h"
 #include "gl.cuh"
-#include "poseidon.cuh"
-#include "poseidon2.cuh"
-#include "blake3.cuh"
-#include "keccak.cuh"
+#include "hasher.cuh"
 #include "verify_host.h"
 
 namespace ola {
 
-enum : int { VH_POSEIDON = 0, VH_POSEIDON2 = 1, VH_BLAKE3 = 2, VH_KECCAK = 3 };
-
-// Hasher::hash_no_pad of `len` words at `leaf`, by the rule of the row-major leaf kernels (merkle.hip): the sponge over chunks of
-// eight for every width, Blake3_256 of the canonical little-endian words
-template <int H>
-__device__ __forceinline__ void vfy_hash_leaf(const u64* __restrict__ leaf, u32 len, u64 (&d)[4]) {
-    if constexpr (H == VH_KECCAK) {
-        keccak_hash_words([&](u32 i) { return leaf[i]; }, len, d);
-    } else if constexpr (H == VH_BLAKE3) {
-        u32 cv[8];
-        if (len > (u32)B3_CHUNK_WORDS) b3_hash_words([&](u32 i) { return leaf[i]; }, len, cv);
-        else b3_chunk_cv([&](u32 i) { return leaf[i]; }, 0, len, 0, true, cv);
-#pragma unroll
-        for (int k = 0; k < 4; k++) d[k] = (u64)cv[2 * k] | ((u64)cv[2 * k + 1] << 32);
-    } else {
-        u64 s[12];
-#pragma unroll
-        for (int i = 0; i < 12; i++) s[i] = 0;
-        for (u32 c0 = 0; c0 < len; c0 += 8) {
-            const u32 n = len - c0 < 8u ? len - c0 : 8u;
-#pragma unroll
-            for (int i = 0; i < 8; i++)
-                if ((u32)i < n) s[i] = leaf[c0 + i];
-            permute12<H == VH_POSEIDON2 ? PERM_POSEIDON2 : PERM_POSEIDON>(s);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) d[k] = s[k];
-    }
-}
-// Hasher::two_to_one(l, r)
-template <int H>
-__device__ __forceinline__ void vfy_two_to_one(const u64 (&l)[4], const u64 (&r)[4], u64 (&d)[4]) {
-    if constexpr (H == VH_KECCAK) {
-        const u64 c[8] = {l[0], l[1], l[2], l[3], r[0], r[1], r[2], r[3]};
-        keccak_node(c, d);
-    } else if constexpr (H == VH_BLAKE3) {
-        const u64 c[8] = {l[0], l[1], l[2], l[3], r[0], r[1], r[2], r[3]};
-        b3_node(c, d);
-    } else {
-        u64 s[12] = {l[0], l[1], l[2], l[3], r[0], r[1], r[2], r[3], 0, 0, 0, 0};
-        permute12<H == VH_POSEIDON2 ? PERM_POSEIDON2 : PERM_POSEIDON>(s);
-#pragma unroll
-        for (int k = 0; k < 4; k++) d[k] = s[k];
-    }
-}
-
 // verify_merkle_proof_to_cap: hash the leaf, walk the siblings by the index bits, compare with cap[index >> depth].
 // data_words: the part of the image the jobs may point into (the job lists lie behind it).
-template <int H>
+// H: the hash policy (hasher.cuh); the leaf's words are hashed as they lie in the image (the host stage read them as canonical words).
+template <class H>
 __global__ __launch_bounds__(64) void merkle_paths_check_kernel(const u64* __restrict__ image, size_t data_words, size_t jobs_off, u32 n_jobs,
                                                                 u32* __restrict__ flags) {
     const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -92,18 +45,16 @@ __global__ __launch_bounds__(64) void merkle_paths_check_kernel(const u64* __res
         flags[j] = vfy::MF_BOUNDS;
         return;
     }
-    u64 cur[4];
-    vfy_hash_leaf<H>(image + leaf_off, len, cur);
+    alignas(16) u64 cur[4];
+    const u64* leaf = image + leaf_off;
+    H::leaf([&](u32 i) { return leaf[i]; }, len, cur);
     for (u32 d = 0; d < depth; d++) {
         const u64* s = image + sib_off + 4 * (size_t)d;
-        const u64 sib[4] = {s[0], s[1], s[2], s[3]};
         const bool right = index & 1;      // this node is the right child: the sibling goes first
-        u64 l[4], r[4], o[4];
+        alignas(16) u64 pair[8];
 #pragma unroll
-        for (int k = 0; k < 4; k++) { l[k] = right ? sib[k] : cur[k]; r[k] = right ? cur[k] : sib[k]; }
-        vfy_two_to_one<H>(l, r, o);
-#pragma unroll
-        for (int k = 0; k < 4; k++) cur[k] = o[k];
+        for (int k = 0; k < 4; k++) { pair[k] = right ? s[k] : cur[k]; pair[4 + k] = right ? cur[k] : s[k]; }
+        H::node(pair, cur);
         index >>= 1;
     }
     bool ok = index < cap_len;
@@ -241,22 +192,12 @@ void verify_on_device(DeviceCtx* ctx, const vfy::Stage& st, OlaVerifyReport* rep
             const size_t data_words = st.merkle_off;      // the job lists lie behind the data
             if (nm) {
                 const dim3 grid((unsigned)((nm + 63) / 64)), block(64);
-                switch (ctx->hasher) {
-                    case OLA_HASH_POSEIDON:
-                        hipLaunchKernelGGL(merkle_paths_check_kernel<VH_POSEIDON>, grid, block, 0, ctx->stream, d_image, data_words, st.merkle_off, (u32)nm, d_flags);
-                        break;
-                    case OLA_HASH_BLAKE3:
-                        hipLaunchKernelGGL(merkle_paths_check_kernel<VH_BLAKE3>, grid, block, 0, ctx->stream, d_image, data_words, st.merkle_off, (u32)nm, d_flags);
-                        break;
-                    case OLA_HASH_KECCAK:
-                        hipLaunchKernelGGL(merkle_paths_check_kernel<VH_KECCAK>, grid, block, 0, ctx->stream, d_image, data_words, st.merkle_off, (u32)nm, d_flags);
-                        break;
-                    case OLA_HASH_POSEIDON2:
-                    case OLA_HASH_POSEIDON2_POW_POSEIDON:
-                        hipLaunchKernelGGL(merkle_paths_check_kernel<VH_POSEIDON2>, grid, block, 0, ctx->stream, d_image, data_words, st.merkle_off, (u32)nm, d_flags);
-                        break;
-                    default: throw OlaError(OLA_E_INTERNAL, "no Merkle path kernel for this hasher");
-                }
+                size_t leaf_words = 0;      // the widest leaf: Blake3's single-chunk form serves while none exceeds a chunk
+                for (const vfy::MerkleJob& m : st.merkle) leaf_words = std::max(leaf_words, (size_t)m.leaf_len);
+                with_hash((uint32_t)ctx->hasher, leaf_words, [&](auto tag) {
+                    using H = typename decltype(tag)::type;
+                    hipLaunchKernelGGL(merkle_paths_check_kernel<H>, grid, block, 0, ctx->stream, d_image, data_words, st.merkle_off, (u32)nm, d_flags);
+                });
                 rep->kernel_launches++;
             }
             if (nq) {

@@ -221,8 +221,8 @@ inline void fri_challenges(OlaChallenger& ch, const Config& cfg, const WFri& fri
     u64 s[12] = {0};
     for (int i = 0; i < 4; i++) s[i] = challenger_get(ch);
     s[4] = fri.pow_witness;
-    // C::InnerHasher::hash_no_pad of five elements is one permutation: Poseidon2 in Poseidon2GoldilocksConfig, Poseidon in every other
-    if (cfg.hasher == OLA_HASH_POSEIDON2) poseidon2_permute_host(s); else poseidon_permute_host(s);   // Blake3 and Keccak configurations: Poseidon
+    // C::InnerHasher::hash_no_pad of five elements is one permutation of the InnerHasher (a sponge in every configuration)
+    hasher_row(hasher_row(cfg.hasher).inner).permute(s);
     out.pow_response = s[0];
     const u64 lde_size = (u64)1 << (degree_bits + cfg.rate_bits);
     for (int i = 0; i < cfg.num_queries; i++) out.query_indices.push_back(challenger_get(ch) % lde_size);
@@ -667,14 +667,15 @@ inline Stage opening_stage(const Config& cfg, const u64* caps, const uint32_t nu
     if ((int)op.ctl_last.size() != num_ctl) return fail(OLA_VERIFY_SHAPE_CTL_ZS_LAST_WIDTH);
     if ((int)op.quotient.size() != 2 * num_polys[2]) return fail(OLA_VERIFY_SHAPE_QUOTIENT_WIDTH);
     const size_t cap_len = (size_t)1 << cfg.cap_height;
+    const HasherInfo& hasher = hasher_row(cfg.hasher);
     std::vector<Digest> cap[3];
     for (int o = 0; o < 3; o++)
         for (size_t i = 0; i < cap_len; i++) {
             Digest d;
             for (int k = 0; k < 4; k++) {
                 d[(size_t)k] = caps[((size_t)o * cap_len + i) * 4 + (size_t)k];
-                if (cfg.hasher == OLA_HASH_KECCAK) { if (k == 3 && d[3] > 0xFF) throw OlaError(OLA_E_INVALID_ARG, "caps: word 3 of a Keccak digest holds byte 24 only"); }
-                else if (cfg.hasher != OLA_HASH_BLAKE3 && d[(size_t)k] >= GL_P) throw OlaError(OLA_E_INVALID_ARG, "caps: a digest word is not canonical");
+                if (k == 3 && d[3] > hasher.cap_word3_max) throw OlaError(OLA_E_INVALID_ARG, "caps: word 3 of a Keccak digest holds byte 24 only");
+                if (hasher.cap_canonical && d[(size_t)k] >= GL_P) throw OlaError(OLA_E_INVALID_ARG, "caps: a digest word is not canonical");
             }
             cap[o].push_back(d);
         }

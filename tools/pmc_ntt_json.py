@@ -97,7 +97,7 @@ def main():
         },
         "calibration": {
             "leaf_hash_colmajor_kernel": {"algorithmic_read_kib": 94 * (1 << 22) * 8 / 1024,
-                                          "FETCH_SIZE_kib": next((v for k, v in kernels.items() if k.startswith(("ola::leaf_hash_colmajor_kernel", "void ola::leaf_hash_colmajor_kernel<0>"))), {}).get("FETCH_SIZE", {}).get("per_dispatch")},
+                                          "FETCH_SIZE_kib": next((v for k, v in kernels.items() if k.startswith(("ola::leaf_hash_colmajor_kernel", "void ola::leaf_hash_colmajor_kernel<0>", "void ola::leaf_hash_kernel<ola::SpongeHash<0>, ola::ColMajorSrc>"))), {}).get("FETCH_SIZE", {}).get("per_dispatch")},
         },
         "kernels": kernels,
     }
