@@ -57,7 +57,9 @@ extern "C" {
  * generators composed in one call, from the executor's records to resident tables and to proof bytes); so were OlaVerifyReport, the
  * OLA_VERIFY_* reasons and the entry points ola_verify_all_proof and ola_verify_opening (proof bytes to a verdict with the place and
  * the reason of a refusal); so were the hasher OLA_HASH_KECCAK (KeccakGoldilocksConfig: Keccak-256 trees and challenger, 25-byte
- * digests) and the host entry points ola_keccak_hash_elements and ola_challenger_init_keccak. */
+ * digests) and the host entry points ola_keccak_hash_elements and ola_challenger_init_keccak; so were the OLA_FRI_* strategies and
+ * the entry points ola_gpu_set_fri_reduction and ola_fri_reduction_arity_bits (FriReductionStrategy::Fixed and MinSize: an arity
+ * per FRI layer, in the prover and in the verifier). */
 #define OLA_GPU_ABI_VERSION 7
 #define OLA_OK 0
 #define OLA_E_INVALID_ARG (-1)
@@ -108,6 +110,32 @@ int32_t ola_gpu_init(const OlaGpuConfig* cfg, OlaCtx** out_ctx);
 /* OLA_GPU_ABI_VERSION of the library that was loaded; *challenger_size / *config_size (may be NULL) receive its sizeof(OlaChallenger)
  * and sizeof(OlaGpuConfig). */
 int32_t ola_gpu_abi_version(size_t* challenger_size, size_t* config_size);
+
+/* ---- FriReductionStrategy (plonky2/plonky2/src/fri/reduction_strategies.rs:7-25): the arity of every FRI layer ----
+ * A context starts with ConstantArityBits(cfg.fri_arity_bits, cfg.fri_final_poly_bits).  ola_gpu_set_fri_reduction replaces the
+ * strategy for every call that BEGINS after it: ola_prove_with_traces*, ola_prove_single_table, ola_prove_from_records,
+ * ola_open_and_prove, ola_open / ola_fri_* (an OlaFri keeps the plan it was opened with), ola_verify_all_proof and
+ * ola_verify_opening.  Like the reference, one strategy serves all tables of a proof; the transcript does not see the plan.
+ *   OLA_FRI_FIXED      args[0..n) are the layers' arity bits, each in 1..4 (the verifier keeps one coset of a layer in registers),
+ *                      n = 0..32; n = 0 is no reduction at all.  A plan whose total exceeds degree_bits + rate_bits - cap_height of
+ *                      a table, or its degree_bits, fails the call that proves or verifies that table with OLA_E_INVALID_ARG
+ *                      ("FRI total reduction arity is too large.", plonk/circuit_builder.rs:922-925); the context goes on working.
+ *   OLA_FRI_MIN_SIZE   n = 0: MinSize(None), n = 1: MinSize(Some(args[0])), args[0] in 1..4: the search of
+ *                      fri/reduction_strategies.rs:60-164 for the smallest estimated proof.  Final polynomials grow to 2^9
+ *                      coefficients at the default rate and query count.
+ * A bad argument is OLA_E_INVALID_ARG and leaves the previous strategy in place.  Multi-device contexts (ola_gpu_init_multi with more
+ * than one device) are refused with OLA_E_INVALID_ARG: the coset partition's first layer is measured and tested for arity 16 only.
+ * ctx == NULL: OLA_E_NO_DEVICE on a machine without a HIP device, OLA_E_INVALID_ARG otherwise; the other arguments are validated first.
+ *
+ * ola_fri_reduction_arity_bits is the plan itself, host only (no device, no context): strategy.reduction_arity_bits(degree_bits,
+ * cfg.rate_bits, cfg.cap_height, cfg.num_query_rounds) with cfg == NULL meaning the defaults.  out receives min(*n_out, cap) entries,
+ * *n_out the plan's length; OLA_E_INVALID_ARG when cap is too small (*n_out is set), for a bad strategy or degree_bits > 32. */
+#define OLA_FRI_CONSTANT_ARITY_BITS 0u  /* cfg.fri_arity_bits / cfg.fri_final_poly_bits: the default                          */
+#define OLA_FRI_FIXED 1u                /* args[0..n): the layers' arity bits, n = 0 .. 32; n = 0: no reduction               */
+#define OLA_FRI_MIN_SIZE 2u             /* n = 0: MinSize(None); n = 1: MinSize(Some(args[0]))                                 */
+int32_t ola_gpu_set_fri_reduction(OlaCtx* ctx, uint32_t strategy, const uint32_t* args, uint32_t n);
+int32_t ola_fri_reduction_arity_bits(const OlaGpuConfig* cfg, uint32_t strategy, const uint32_t* args, uint32_t n,
+                                     uint32_t degree_bits, uint32_t* out, uint32_t cap, uint32_t* n_out);
 /* One context that spans n_devices GPUs of the node (1, 2, 4 or 8; devices = HIP ordinals, NULL = 0..n-1): the caller stays the
  * single process the reference's prover is (client/src/main.rs:174-214, one `prove` per process; the reference's own GPU state is
  * process-wide, cfft/ntt/mod.rs:14-17,48-50) and calls ola_prove_with_traces ONCE; inside, rank r is a worker thread on

@@ -60,6 +60,23 @@ inline uint32_t log2_strict(size_t n) {   // util/src/lib.rs log2_strict: panics
     return k;
 }
 
+// FriReductionStrategy (plonky2/plonky2/src/fri/reduction_strategies.rs:7-25).  The default, ConstantArityBits, takes its two numbers
+// from StarkConfig::fri_arity_bits / fri_final_poly_bits.
+struct FriReductionStrategy {
+    uint32_t kind = OLA_FRI_CONSTANT_ARITY_BITS;
+    std::vector<uint32_t> args;
+    static FriReductionStrategy ConstantArityBits() { return FriReductionStrategy{}; }
+    static FriReductionStrategy Fixed(std::vector<uint32_t> arity_bits) { FriReductionStrategy s; s.kind = OLA_FRI_FIXED; s.args = std::move(arity_bits); return s; }
+    static FriReductionStrategy MinSize() { FriReductionStrategy s; s.kind = OLA_FRI_MIN_SIZE; return s; }                       // MinSize(None)
+    static FriReductionStrategy MinSize(uint32_t max_arity_bits) { FriReductionStrategy s = MinSize(); s.args.push_back(max_arity_bits); return s; }
+    // strategy.reduction_arity_bits(degree_bits, rate_bits, cap_height, num_queries) (ola_fri_reduction_arity_bits: host only)
+    std::vector<uint32_t> reduction_arity_bits(const OlaGpuConfig* cfg, uint32_t degree_bits) const {
+        uint32_t out[64], n = 0;
+        check(ola_fri_reduction_arity_bits(cfg, kind, args.data(), (uint32_t)args.size(), degree_bits, out, 64, &n));
+        return std::vector<uint32_t>(out, out + n);
+    }
+};
+
 // FriConfig / StarkConfig::standard_fast_config (circuits/src/stark/config.rs:20-35) with the fields the backend reads.
 struct StarkConfig {
     uint32_t rate_bits = 3, cap_height = 4, proof_of_work_bits = 16, fri_arity_bits = 4, fri_final_poly_bits = 5, num_query_rounds = 28,
@@ -67,6 +84,7 @@ struct StarkConfig {
     // GenericConfig::Hasher (plonk/config.rs:112-161): OLA_HASH_POSEIDON = PoseidonGoldilocksConfig, OLA_HASH_BLAKE3 = Blake3GoldilocksConfig, OLA_HASH_KECCAK = KeccakGoldilocksConfig
     // OLA_HASH_POSEIDON2 = Poseidon2GoldilocksConfig, OLA_HASH_POSEIDON2_POW_POSEIDON = Poseidon2GoldilocksConfig2
     uint32_t hasher = OLA_HASH_POSEIDON;
+    FriReductionStrategy reduction_strategy;      // single-device contexts take all three variants, multi-device ones the default
     static StarkConfig standard_fast_config() { return StarkConfig{}; }
 };
 
@@ -79,6 +97,7 @@ public:
         g.proof_of_work_bits = c.proof_of_work_bits; g.fri_arity_bits = c.fri_arity_bits; g.fri_final_poly_bits = c.fri_final_poly_bits;
         g.num_query_rounds = c.num_query_rounds; g.num_challenges = c.num_challenges; g.hasher = c.hasher;
         check(ola_gpu_init(&g, &ctx_));
+        set_reduction_strategy(c.reduction_strategy);
     }
     // One context spanning several GPUs of the node (ola_gpu_init_multi): prove_with_traces then runs on all of them in one call.
     explicit Gpu(const std::vector<int32_t>& devices, const StarkConfig& c = StarkConfig::standard_fast_config()) : config(c) {
@@ -87,6 +106,7 @@ public:
         g.proof_of_work_bits = c.proof_of_work_bits; g.fri_arity_bits = c.fri_arity_bits; g.fri_final_poly_bits = c.fri_final_poly_bits;
         g.num_query_rounds = c.num_query_rounds; g.num_challenges = c.num_challenges; g.hasher = c.hasher;
         check(ola_gpu_init_multi(&g, devices.data(), (uint32_t)devices.size(), &ctx_));
+        set_reduction_strategy(c.reduction_strategy);
     }
     uint32_t device_count() const { uint32_t n = 0; check(ola_gpu_device_count(ctx_, &n)); return n; }
     ~Gpu() { if (ctx_) ola_gpu_free(ctx_); }
@@ -98,6 +118,12 @@ public:
     const StarkConfig config;
 
 private:
+    // (from the constructors: a refused strategy frees the context, whose destructor will not run)
+    void set_reduction_strategy(const FriReductionStrategy& s) {
+        if (s.kind == OLA_FRI_CONSTANT_ARITY_BITS && s.args.empty()) return;
+        const int32_t rc = ola_gpu_set_fri_reduction(ctx_, s.kind, s.args.data(), (uint32_t)s.args.size());
+        if (rc != OLA_OK) { const Error e(rc, ola_gpu_last_error()); ola_gpu_free(ctx_); ctx_ = nullptr; throw e; }
+    }
     OlaCtx* ctx_ = nullptr;
 };
 

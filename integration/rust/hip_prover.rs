@@ -69,6 +69,10 @@ struct CtxKey {
     num_query_rounds: u32,
     num_challenges: u32,
     gpus: u32,
+    /// `FriReductionStrategy` as `ola_gpu_set_fri_reduction` takes it: OLA_FRI_*, then its arguments
+    strategy: u32,
+    plan_n: u32,
+    plan_args: [u32; 32],
 }
 
 /// One context per hash configuration for the life of the process, and ONE proof at a time on the GPU: a context is
@@ -83,11 +87,33 @@ fn with_ctx<R>(hasher: u32, config: &StarkConfig, body: impl FnOnce(*mut OlaCtx)
         [OnceLock::new(), OnceLock::new(), OnceLock::new(), OnceLock::new(), OnceLock::new(), OnceLock::new()];
     let mut slot = CTX[hasher as usize].get_or_init(|| Mutex::new(None)).lock().unwrap_or_else(|e| e.into_inner());
     let fri = &config.fri_config;
-    // the library folds with one arity; StarkConfig::standard_fast_config is ConstantArityBits(4, 5) (config.rs:18-30)
-    let (arity_bits, final_poly_bits) = match fri.reduction_strategy {
-        FriReductionStrategy::ConstantArityBits(a, f) => (a as u32, f as u32),
-        ref other => bail!("the hip backend folds with FriReductionStrategy::ConstantArityBits only, the config asks for {other:?}"),
-    };
+    // all three variants (fri/reduction_strategies.rs:7-25); StarkConfig::standard_fast_config is ConstantArityBits(4, 5)
+    // (config.rs:18-30), whose two numbers travel in OlaGpuConfig, the other two go through ola_gpu_set_fri_reduction
+    let (mut arity_bits, mut final_poly_bits) = (4u32, 5u32);
+    let (mut strategy, mut plan_n, mut plan_args) = (OLA_FRI_CONSTANT_ARITY_BITS, 0u32, [0u32; 32]);
+    match fri.reduction_strategy {
+        FriReductionStrategy::ConstantArityBits(a, f) => {
+            arity_bits = a as u32;
+            final_poly_bits = f as u32;
+        }
+        FriReductionStrategy::Fixed(ref layers) => {
+            if layers.len() > plan_args.len() {
+                bail!("the hip backend takes FriReductionStrategy::Fixed plans of at most 32 layers, the config has {}", layers.len());
+            }
+            strategy = OLA_FRI_FIXED;
+            plan_n = layers.len() as u32;
+            for (dst, &a) in plan_args.iter_mut().zip(layers.iter()) {
+                *dst = a as u32;
+            }
+        }
+        FriReductionStrategy::MinSize(max_arity_bits) => {
+            strategy = OLA_FRI_MIN_SIZE;
+            if let Some(m) = max_arity_bits {
+                plan_n = 1;
+                plan_args[0] = m as u32;
+            }
+        }
+    }
     let key = CtxKey {
         rate_bits: fri.rate_bits as u32,
         cap_height: fri.cap_height as u32,
@@ -97,6 +123,9 @@ fn with_ctx<R>(hasher: u32, config: &StarkConfig, body: impl FnOnce(*mut OlaCtx)
         num_query_rounds: fri.num_query_rounds as u32,
         num_challenges: config.num_challenges as u32,
         gpus: std::env::var("OLA_GPUS").ok().and_then(|v| v.parse().ok()).unwrap_or(1),
+        strategy,
+        plan_n,
+        plan_args,
     };
     if let Some((old, old_key)) = slot.as_ref() {
         if *old_key != key {
@@ -120,6 +149,13 @@ fn with_ctx<R>(hasher: u32, config: &StarkConfig, body: impl FnOnce(*mut OlaCtx)
         cfg.hasher = hasher;
         let mut c = std::ptr::null_mut();
         check(unsafe { ola_gpu_init_multi(&cfg, std::ptr::null(), key.gpus, &mut c) })?;
+        if key.strategy != OLA_FRI_CONSTANT_ARITY_BITS {
+            // (a multi-device context refuses Fixed and MinSize: the error says so)
+            if let Err(e) = check(unsafe { ola_gpu_set_fri_reduction(c, key.strategy, key.plan_args.as_ptr(), key.plan_n) }) {
+                let _ = unsafe { ola_gpu_free(c) };
+                return Err(e);
+            }
+        }
         *slot = Some((SendPtr(c), key));
     }
     body(slot.as_ref().unwrap().0 .0)

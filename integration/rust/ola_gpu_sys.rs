@@ -32,6 +32,12 @@ pub const OLA_HASH_POSEIDON2: u32 = 2;
 pub const OLA_HASH_POSEIDON2_POW_POSEIDON: u32 = 3;
 /// KeccakGoldilocksConfig (plonk/config.rs:145-151): Keccak-256 trees and transcript (25-byte digests), Poseidon proof of work; 4 is unassigned
 pub const OLA_HASH_KECCAK: u32 = 5;
+/// FriReductionStrategy::ConstantArityBits (fri/reduction_strategies.rs:18): the numbers of OlaGpuConfig, the default
+pub const OLA_FRI_CONSTANT_ARITY_BITS: u32 = 0;
+/// FriReductionStrategy::Fixed (fri/reduction_strategies.rs:9): the layers' arity bits
+pub const OLA_FRI_FIXED: u32 = 1;
+/// FriReductionStrategy::MinSize (fri/reduction_strategies.rs:24): no argument = None, one = Some(max_arity_bits)
+pub const OLA_FRI_MIN_SIZE: u32 = 2;
 pub const OLA_NTT_EVALUATE: i32 = 0;
 pub const OLA_NTT_INTERPOLATE: i32 = 1;
 pub const OLA_NTT_COSET_LDE: i32 = 2;
@@ -327,6 +333,8 @@ extern "C" {
     pub fn ola_pow(ctx: *mut OlaCtx, h: *const u64, bits: u32, witness: *mut u64) -> i32;
     pub fn ola_open(ctx: *mut OlaCtx, trace: *const OlaBatch, zs: *const OlaBatch, quotient: *const OlaBatch, num_permutation_zs: u32,
         zeta: *const u64, out: *mut u8, cap: usize, out_len: *mut usize, fri_out: *mut *mut OlaFri) -> i32;
+    pub fn ola_gpu_set_fri_reduction(ctx: *mut OlaCtx, strategy: u32, args: *const u32, n: u32) -> i32;
+    pub fn ola_fri_reduction_arity_bits(cfg: *const OlaGpuConfig, strategy: u32, args: *const u32, n: u32, degree_bits: u32, out: *mut u32, cap: u32, n_out: *mut u32) -> i32;
     pub fn ola_fri_plan(fri: *const OlaFri, arity_bits: *mut u32, cap: u32, n_layers: *mut u32, final_poly_len: *mut u32) -> i32;
     pub fn ola_fri_commit_begin(fri: *mut OlaFri, alpha: *const u64) -> i32;
     pub fn ola_fri_commit_next_layer(fri: *mut OlaFri, beta: *const u64, cap_out: *mut u64) -> i32;

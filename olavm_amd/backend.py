@@ -305,6 +305,11 @@ def load_library():
     L.ola_verify_opening.argtypes = [C.c_void_p, U64P, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t,
                                      C.POINTER(OlaChallenger), C.POINTER(OlaVerifyReport)]
     L.ola_verify_opening.restype = C.c_int32
+    L.ola_gpu_set_fri_reduction.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]
+    L.ola_gpu_set_fri_reduction.restype = C.c_int32
+    L.ola_fri_reduction_arity_bits.argtypes = [C.POINTER(OlaGpuConfig), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
+                                               C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.ola_fri_reduction_arity_bits.restype = C.c_int32
     _lib = L
     return L
 
@@ -328,7 +333,48 @@ EXPORTS = [
     "ola_tables_from_records", "ola_tables_get", "ola_tables_free", "ola_prove_from_records",
     "ola_open", "ola_fri_plan", "ola_fri_commit_begin", "ola_fri_commit_next_layer", "ola_fri_commit_finish", "ola_fri_query", "ola_fri_free",
     "ola_verify_all_proof", "ola_verify_opening",
+    "ola_gpu_set_fri_reduction", "ola_fri_reduction_arity_bits",
 ]
+
+# FriReductionStrategy (include/ola_gpu.h OLA_FRI_*)
+FRI_STRATEGIES = {"constant_arity_bits": 0, "fixed": 1, "min_size": 2}
+
+
+def _fri_reduction_args(reduction):
+    """("fixed", [4, 3, 3]) | ("min_size", None | k) | ("constant_arity_bits",) | None -> (strategy, c_uint32 array or None, n)"""
+    if reduction is None:
+        reduction = ("constant_arity_bits",)
+    if isinstance(reduction, str):
+        reduction = (reduction,)
+    name, arg = reduction[0], (reduction[1] if len(reduction) > 1 else None)
+    if name not in FRI_STRATEGIES:
+        raise ValueError("unknown FRI reduction strategy %r (one of %s)" % (name, ", ".join(FRI_STRATEGIES)))
+    if name == "fixed":
+        vals = [int(a) for a in (arg if arg is not None else [])]
+    elif name == "min_size":
+        vals = [] if arg is None else [int(arg)]
+    else:
+        vals = []
+    if any(v < 0 or v > 0xFFFFFFFF for v in vals):
+        raise ValueError("FRI reduction arguments are 32-bit unsigned numbers")
+    arr = (C.c_uint32 * len(vals))(*vals) if vals else None
+    return FRI_STRATEGIES[name], arr, len(vals)
+
+
+def fri_reduction_arity_bits(reduction, degree_bits, **cfg):
+    """ola_fri_reduction_arity_bits: the arity bits of every FRI layer of a 2^degree_bits-row table under `reduction` (as for
+    Backend(fri_reduction=...)) and the configuration's rate_bits, cap_height, num_query_rounds, fri_arity_bits and
+    fri_final_poly_bits.  Host only: needs no device."""
+    L = load_library()
+    c = OlaGpuConfig(-1, None, cfg.get("rate_bits", 3), cfg.get("cap_height", 4), cfg.get("proof_of_work_bits", 16),
+                     cfg.get("fri_arity_bits", 4), cfg.get("fri_final_poly_bits", 5), cfg.get("num_query_rounds", 28),
+                     cfg.get("num_challenges", 2), HASHERS[cfg.get("hasher", "poseidon")])
+    strategy, arr, n = _fri_reduction_args(reduction)
+    out, n_out = (C.c_uint32 * 64)(), C.c_uint32()
+    code = L.ola_fri_reduction_arity_bits(C.byref(c), strategy, arr, n, int(degree_bits), out, 64, C.byref(n_out))
+    if code != 0:
+        raise OlaGpuError(code, L.ola_gpu_last_error().decode())
+    return [int(out[i]) for i in range(n_out.value)]
 
 
 def describe_column(col):
@@ -602,6 +648,18 @@ class Backend:
                         os.environ["OLA_COLLECTIVE"] = old
         else:
             self._chk(self.lib.ola_gpu_init(C.byref(c), C.byref(self.ctx)))
+        if cfg.get("fri_reduction") is not None:
+            try:
+                self.set_fri_reduction(cfg["fri_reduction"])
+            except Exception:
+                self.close()            # (the constructor fails: nobody else can free the context)
+                raise
+
+    def set_fri_reduction(self, reduction):
+        """ola_gpu_set_fri_reduction: ("fixed", [4, 3, 3]) | ("min_size", None | k) | ("constant_arity_bits",) for every call that
+        begins from now on (proving and verifying); a refused argument leaves the previous strategy in place."""
+        strategy, arr, n = _fri_reduction_args(reduction)
+        self._chk(self.lib.ola_gpu_set_fri_reduction(self.ctx, strategy, arr, n))
 
     PHASES = ("leaf_hash", "merkle_levels", "fri_fold", "lde", "intt", "quotient", "open_eval")
 

@@ -18,6 +18,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "fri_plan.h"
 #include "ola_error.h"
 
 namespace ola {
@@ -186,6 +187,7 @@ struct DeviceCtx {
     bool owns_stream = false;
     int hasher = 0;                            // the configuration (a row of hasher_host.h): GenericConfig::Hasher of the Merkle trees and the
                                                // challenger, and through the row's `inner` the InnerHasher of the proof of work
+    FriPlanSpec fri_plan;                      // FriReductionStrategy of the calls that begin from now on (ola_gpu_set_fri_reduction)
     bool timing = false;                       // OLA_TIMING=1: per-phase wall-clock on stderr (synchronises at phase edges)
     bool priming = false;                      // ola_gpu_warmup's throw-away proof of an all-zero instance: the divisibility check is off
     std::vector<void*> persistent;

@@ -392,6 +392,40 @@ __global__ __launch_bounds__(256) void fold16_kernel(const u64* __restrict__ ca,
     }
 }
 
+// The same arrangement as a template on the arity bits (FriReductionStrategy::Fixed and MinSize plan layers of arity 8, 4 and 2):
+// a thread loads two neighbouring coefficients of both planes with 16-byte loads, 2^(AB-1) neighbouring lanes hold one output and
+// AB - 1 exchanges join them by beta^2, beta^4, .. (pw.p[r] = beta^(2^(r+1)), computed by the host).  A group is 1, 2, 4 or 8
+// aligned lanes and a workgroup a multiple of 64 pairs, so no group straddles a wave.  Launched for arities 8 and 4.  AB = 4 is
+// fold16_kernel's arithmetic step for step; arity 16 keeps its own kernel, whose time at 2^22 rows is on record.  AB = 1 would
+// exchange nothing, and is not launched: fold_kernel's lanes already read 16 bytes apart there, and at 2^22 rows the pair form
+// was not faster.
+struct FoldPowers { Ext2 p[3]; };
+template <int AB>
+__global__ __launch_bounds__(256) void fold_pairs_kernel(const u64* __restrict__ ca, const u64* __restrict__ cb, size_t nz_out, Ext2 b1, FoldPowers pw,
+                                                         u64* __restrict__ oa, u64* __restrict__ ob) {
+    static_assert(AB >= 1 && AB <= 4, "a group of 2^(AB-1) lanes inside one wave");
+    constexpr int G = 1 << (AB - 1);                                     // lanes per output
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;      // pair index: coefficients 2t, 2t + 1
+    const size_t last = nz_out * G - 1;
+    const size_t tt = t < last ? t : last;                               // surplus lanes redo the last pair: the wave stays whole
+    const ulonglong2 va = *reinterpret_cast<const ulonglong2*>(ca + 2 * tt);
+    const ulonglong2 vb = *reinterpret_cast<const ulonglong2*>(cb + 2 * tt);
+    Ext2 s = ext_add(ext_make(va.x, vb.x), ext_mul(ext_make(va.y, vb.y), b1));
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int r = 0; r < AB - 1; r++) {
+        const int m = 1 << r;
+        const Ext2 o = ext_shfl_xor(s, m);
+        const bool up = (lane & m) != 0;
+        const Ext2 lo = up ? o : s, hi = up ? s : o;
+        s = ext_add(lo, ext_mul(hi, pw.p[r]));
+    }
+    if ((t & (G - 1)) == 0 && t <= last) {
+        oa[t >> (AB - 1)] = s.a;
+        ob[t >> (AB - 1)] = s.b;
+    }
+}
+
 // out[q][2k], out[q][2k+1] = (a, b)[idx[q]*arity + k]
 __global__ void gather_ext_leaves_kernel(const u64* __restrict__ pa, const u64* __restrict__ pb, int arity,
                                          const unsigned long long* __restrict__ idx, u64* __restrict__ out) {
@@ -709,15 +743,10 @@ struct ByteWriter {
     void merkle_proof(const u64* sib, int depth) { u8((uint8_t)depth); for (int i = 0; i < depth; i++) hash(sib + 4 * i); }
 };
 
-static std::vector<int> fri_arities(const OlaGpuConfig& cfg, int degree_bits) {
-    // fri/reduction_strategies.rs:40-52  ConstantArityBits(arity_bits, final_poly_bits)
-    std::vector<int> v;
-    int d = degree_bits;
-    while (d > (int)cfg.fri_final_poly_bits && d + (int)cfg.rate_bits - (int)cfg.fri_arity_bits >= (int)cfg.cap_height) {
-        v.push_back((int)cfg.fri_arity_bits);
-        d -= (int)cfg.fri_arity_bits;
-    }
-    return v;
+// fri/reduction_strategies.rs:30-57 under the context's strategy (fri_plan.h)
+static std::vector<int> fri_arities(const DeviceCtx* ctx, const OlaGpuConfig& cfg, int degree_bits) {
+    return fri_plan_arity_bits(ctx->fri_plan, (int)cfg.fri_arity_bits, (int)cfg.fri_final_poly_bits, degree_bits, (int)cfg.rate_bits, (int)cfg.cap_height,
+                               (size_t)cfg.num_query_rounds);
 }
 
 struct FriLayer {
@@ -791,9 +820,7 @@ struct FriOracles {
 };
 
 static void fri_check_arities(const std::vector<int>& arities, const OlaGpuConfig& cfg, int degree_bits) {
-    int tot = 0;
-    for (int a : arities) tot += a;
-    if (tot > degree_bits + (int)cfg.rate_bits - (int)cfg.cap_height) throw OlaError(OLA_E_INVALID_ARG, "FRI total reduction arity is too large.");
+    if (!fri_plan_fits(arities, degree_bits, (int)cfg.rate_bits, (int)cfg.cap_height)) throw OlaError(OLA_E_INVALID_ARG, "FRI total reduction arity is too large.");
 }
 
 // the opening points zeta, g zeta, g^-1 (prover.rs:499-503): power tables of the points (the first three with limbs) and of
@@ -946,16 +973,24 @@ static void fri_fold(DevBuf& mem, FriCommit& c, int ab, Ext2 beta) {
     const size_t len = c.len, out_len = len >> ab;
     u64* folded = mem.alloc(2 * out_len);
     static const bool fold16_off = getenv("OLA_FOLD16") && !strcmp(getenv("OLA_FOLD16"), "0");
-    if (arity == 16 && !fold16_off && c.nz % 16 == 0 && c.nz >= 4096) {
-        const size_t nz_out = c.nz / 16;
+    // the loads on consecutive addresses for arities 4, 8 and 16 (OLA_FOLD16=0: the plain kernel, for every arity): the non-zero
+    // prefix is whole outputs and at least 4096 coefficients
+    if (ab >= 2 && ab <= 4 && !fold16_off && c.nz % (size_t)arity == 0 && c.nz >= 4096) {
+        const size_t nz_out = c.nz >> ab, pairs = c.nz / 2;
         PhaseScope ph(ctx, PH_FRI_FOLD, (double)(c.nz + nz_out) * 16, (double)c.nz);
         if (nz_out < out_len) {
             HIP_CHECK(hipMemsetAsync(folded + nz_out, 0, (out_len - nz_out) * 8, ctx->stream));
             HIP_CHECK(hipMemsetAsync(folded + out_len + nz_out, 0, (out_len - nz_out) * 8, ctx->stream));
         }
         const Ext2 b2 = ext_mul(beta, beta), b4 = ext_mul(b2, b2), b8 = ext_mul(b4, b4);
-        hipLaunchKernelGGL(fold16_kernel, dim3((unsigned)((nz_out * 8 + 255) / 256)), dim3(256), 0, ctx->stream, c.coef, c.coef + len, nz_out, beta,
-                           b2, b4, b8, folded, folded + out_len);
+        const FoldPowers pw = {{b2, b4, b8}};
+        const dim3 grid((unsigned)((pairs + 255) / 256)), block(256);
+        u64* ca = c.coef; u64* cb = c.coef + len; u64* oa = folded; u64* ob = folded + out_len;
+        switch (ab) {
+            case 2: hipLaunchKernelGGL(fold_pairs_kernel<2>, grid, block, 0, ctx->stream, ca, cb, nz_out, beta, pw, oa, ob); break;
+            case 3: hipLaunchKernelGGL(fold_pairs_kernel<3>, grid, block, 0, ctx->stream, ca, cb, nz_out, beta, pw, oa, ob); break;
+            default: hipLaunchKernelGGL(fold16_kernel, grid, block, 0, ctx->stream, ca, cb, nz_out, beta, b2, b4, b8, oa, ob); break;
+        }
         c.nz = nz_out;
     } else {
         PhaseScope ph(ctx, PH_FRI_FOLD, (double)(len + out_len) * 16, (double)len);
@@ -1108,7 +1143,7 @@ void open_and_prove(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, 
     const int rate_bits = (int)cfg.rate_bits;
     const size_t N = n << rate_bits;
     const size_t len_cap = (size_t)1 << cfg.cap_height;
-    const std::vector<int> arities = fri_arities(cfg, degree_bits);
+    const std::vector<int> arities = fri_arities(ctx, cfg, degree_bits);
     fri_check_arities(arities, cfg, degree_bits);
 
     // ---- zeta and the opening set (prover.rs:499-524) ----
@@ -1234,7 +1269,7 @@ struct OlaFri {      // (global, like OlaBatch: the C header names it)
     void* owner = nullptr;            // the OlaCtx the batches belong to (the C wrappers make its device current)
     OlaFri(ola::DeviceCtx* c, ola::NttTables* t, const OlaGpuConfig& g, const OlaBatch* tr, const OlaBatch* z, const OlaBatch* q, uint32_t np)
         : ctx(c), tables(t), cfg(g), oracles{tr, z, q, np}, mem(c, /*pinned=*/false), degree_bits((int)tr->log_n), rate_bits((int)g.rate_bits),
-          N(tr->n() << g.rate_bits), arities(ola::fri_arities(g, (int)tr->log_n)), commit(nullptr, N, tr->n()) {
+          N(tr->n() << g.rate_bits), arities(ola::fri_arities(c, g, (int)tr->log_n)), commit(nullptr, N, tr->n()) {
         ola::fri_check_arities(arities, cfg, degree_bits);
     }
 };

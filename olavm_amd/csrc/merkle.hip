@@ -248,6 +248,45 @@ __global__ __launch_bounds__(B3X_LEAVES) void leaf_bytes_ext16_kernel(const u64*
     if (j >= num_leaves) return;
     H::leaf([&](u32 i) { return gl_canon(tile[i & 1][threadIdx.x * 17 + (i >> 1)]); }, 32u, out + j * 4);
 }
+// The same staging for arities 8 and 4 (AB = 3, 2: layers that FriReductionStrategy::Fixed and MinSize plan).  Rows of 2^AB + 1 words:
+// ds_read_b64 banks by (byte address / 4) mod 64 within each 32-lane half, lane l reads word l S + k, i.e. dwords 2 (l S + k) and the
+// next -- the 32 lanes cover all 64 banks exactly once when l S mod 32 takes 32 values, that is for every odd S: 9 and 5 as for 17.
+template <class H, int AB>
+__global__ __launch_bounds__(B3X_LEAVES) void leaf_bytes_ext_tile_kernel(const u64* __restrict__ plane_a, const u64* __restrict__ plane_b, size_t num_leaves,
+                                                                         u64* __restrict__ out) {
+    static_assert(AB == 2 || AB == 3, "arity 16 has leaf_bytes_ext16_kernel, arity 2 needs no tile");
+    constexpr int A = 1 << AB, S = A + 1;
+    __shared__ u64 tile[2][B3X_LEAVES * S];
+    const size_t j0 = (size_t)blockIdx.x * B3X_LEAVES;
+    const size_t base = j0 * A;
+    const size_t avail = (num_leaves - j0 < (size_t)B3X_LEAVES ? num_leaves - j0 : (size_t)B3X_LEAVES) * A;
+#pragma unroll
+    for (int i = 0; i < A / 2; i++) {
+        const size_t e = 2 * ((size_t)threadIdx.x + B3X_LEAVES * i);
+        if (e < avail) {
+            const ulonglong2 va = *reinterpret_cast<const ulonglong2*>(plane_a + base + e);
+            const ulonglong2 vb = *reinterpret_cast<const ulonglong2*>(plane_b + base + e);
+            const size_t at = (e >> AB) * S + (e & (A - 1));
+            tile[0][at] = va.x; tile[0][at + 1] = va.y;
+            tile[1][at] = vb.x; tile[1][at + 1] = vb.y;
+        }
+    }
+    __syncthreads();
+    const size_t j = j0 + threadIdx.x;
+    if (j >= num_leaves) return;
+    H::leaf([&](u32 i) { return gl_canon(tile[i & 1][threadIdx.x * S + (i >> 1)]); }, (u32)(2 * A), out + j * 4);
+}
+// Arity 2: a thread's own leaf is 16 bytes per plane, and neighbouring lanes' loads are neighbours
+template <class H>
+__global__ __launch_bounds__(256) void leaf_bytes_ext2_kernel(const u64* __restrict__ plane_a, const u64* __restrict__ plane_b, size_t num_leaves,
+                                                              u64* __restrict__ out) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= num_leaves) return;
+    const ulonglong2 va = *reinterpret_cast<const ulonglong2*>(plane_a + 2 * j);
+    const ulonglong2 vb = *reinterpret_cast<const ulonglong2*>(plane_b + 2 * j);
+    // (selects, not an array: a run-time index would put it into scratch memory)
+    H::leaf([&](u32 i) { return gl_canon((i & 2) ? ((i & 1) ? vb.y : va.y) : ((i & 1) ? vb.x : va.x)); }, 4u, out + j * 4);
+}
 // `nlev` (<= 8) consecutive levels in one launch (round 6): a workgroup computes 256 nodes of the level of `first` nodes from their
 // children in the heap, then the 128, 64, ... nodes above them out of LDS -- every level is still written to the heap (sibling paths
 // read it), but only the bottom one is read back.  Measured on the 2^22-row Blake3 proof (profiles/r06_merkle_levels_per_launch.txt,
@@ -329,8 +368,14 @@ void launch_leaf_hash_ext(DeviceCtx* ctx, const u64* pa, const u64* pb, int arit
     with_hash((uint32_t)ctx->hasher, words, [&](auto tag) {
         using H = typename decltype(tag)::type;
         if constexpr (H::BYTES) {
-            if (arity == 16 && staged && num_leaves >= 1024 && (((uintptr_t)pa | (uintptr_t)pb) & 15) == 0) {
-                hipLaunchKernelGGL(leaf_bytes_ext16_kernel<typename H::Small>, dim3((unsigned)((num_leaves + B3X_LEAVES - 1) / B3X_LEAVES)), dim3(B3X_LEAVES), 0, ctx->stream, pa, pb, num_leaves, out);
+            // every global load a 16-byte load on consecutive addresses (OLA_LEAF_EXT_STAGED=0: the plain kernel, for every arity)
+            if (staged && num_leaves >= 1024 && (((uintptr_t)pa | (uintptr_t)pb) & 15) == 0 && (arity == 16 || arity == 8 || arity == 4 || arity == 2)) {
+                using HS = typename H::Small;
+                const dim3 tiles((unsigned)((num_leaves + B3X_LEAVES - 1) / B3X_LEAVES)), tile_block(B3X_LEAVES);
+                if (arity == 16) hipLaunchKernelGGL(leaf_bytes_ext16_kernel<HS>, tiles, tile_block, 0, ctx->stream, pa, pb, num_leaves, out);
+                else if (arity == 8) hipLaunchKernelGGL((leaf_bytes_ext_tile_kernel<HS, 3>), tiles, tile_block, 0, ctx->stream, pa, pb, num_leaves, out);
+                else if (arity == 4) hipLaunchKernelGGL((leaf_bytes_ext_tile_kernel<HS, 2>), tiles, tile_block, 0, ctx->stream, pa, pb, num_leaves, out);
+                else hipLaunchKernelGGL(leaf_bytes_ext2_kernel<HS>, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256), 0, ctx->stream, pa, pb, num_leaves, out);
                 return;
             }
         }

@@ -594,6 +594,35 @@ int32_t ola_gpu_abi_version(size_t* challenger_size, size_t* config_size) {
     return OLA_GPU_ABI_VERSION;
 }
 
+// FriReductionStrategy of a context (fri_plan.h).  The coset partition divides the FIRST FRI layer among the ranks (fri.hip, "FRI
+// commit phase"); that path is measured and tested for arity 16, so a partitioned context keeps ConstantArityBits.
+static const char* const kFriPartitionRefusal =
+    "Fixed and MinSize FRI reduction strategies run on single-device contexts: the coset partition's first FRI layer is tested for ConstantArityBits only";
+int32_t ola_gpu_set_fri_reduction(OlaCtx* ctx, uint32_t strategy, const uint32_t* args, uint32_t n) {
+    OLA_TRY
+    if (const char* bad = fri_plan_spec_check(strategy, args, n)) require(false, bad);
+    require_context(ctx);
+    require(strategy == OLA_FRI_CONSTANT_ARITY_BITS || (ctx->peers.empty() && ctx->dev.shard.world <= 1), kFriPartitionRefusal);
+    const FriPlanSpec spec = fri_plan_spec(strategy, args, n);
+    ctx->dev.fri_plan = spec;
+    for (OlaCtx* p : ctx->peers) p->dev.fri_plan = spec;      // (ConstantArityBits only: back to the default on every rank)
+    OLA_CATCH
+}
+int32_t ola_fri_reduction_arity_bits(const OlaGpuConfig* cfg, uint32_t strategy, const uint32_t* args, uint32_t n, uint32_t degree_bits, uint32_t* out,
+                                     uint32_t cap, uint32_t* n_out) {
+    OLA_TRY
+    require(n_out, "null pointer");
+    const OlaGpuConfig c = resolve_config(cfg);
+    if (const char* bad = fri_plan_spec_check(strategy, args, n)) require(false, bad);
+    require(degree_bits <= 32, "degree_bits must be at most 32");
+    const std::vector<int> plan = fri_plan_arity_bits(fri_plan_spec(strategy, args, n), (int)c.fri_arity_bits, (int)c.fri_final_poly_bits, (int)degree_bits,
+                                                      (int)c.rate_bits, (int)c.cap_height, (size_t)c.num_query_rounds);
+    *n_out = (uint32_t)plan.size();
+    require(plan.size() <= cap && (out || plan.empty()), "out is too small for the plan");
+    for (size_t i = 0; i < plan.size(); i++) out[i] = (uint32_t)plan[i];
+    OLA_CATCH
+}
+
 int32_t ola_gpu_device_count(OlaCtx* ctx, uint32_t* n_devices) {
     OLA_TRY
     require(ctx && n_devices, "null pointer");
@@ -1179,7 +1208,7 @@ int32_t ola_verify_all_proof(OlaCtx* ctx, const uint64_t* airset, size_t airset_
     require_verifier_context(ctx);
     OLA_ON_DEVICE(ctx);
     const auto t0 = std::chrono::steady_clock::now();
-    const vfy::Stage st = vfy::all_proof_stage(vfy::config_of(ctx->cfg), (const u64*)airset, airset_words, (const u64*)params, proof, proof_len);
+    const vfy::Stage st = vfy::all_proof_stage(vfy::config_of(ctx->cfg, ctx->dev.fri_plan), (const u64*)airset, airset_words, (const u64*)params, proof, proof_len);
     OlaVerifyReport rep;
     memset(&rep, 0, sizeof(rep));
     rep.host_ms = ms_since(t0);
@@ -1197,7 +1226,7 @@ int32_t ola_verify_opening(OlaCtx* ctx, const uint64_t* caps, const uint32_t num
     require(challenger->hasher == ctx->cfg.hasher, "the challenger was not initialised for this context's hasher (ola_challenger_init_hasher, ola_challenger_init_keccak)");
     require(challenger->input_len <= 8 && challenger->output_len <= 8, "challenger");
     const auto t0 = std::chrono::steady_clock::now();
-    const vfy::Stage st = vfy::opening_stage(vfy::config_of(ctx->cfg), (const u64*)caps, num_polys, degree_bits, num_permutation_zs, proof, proof_len, *challenger);
+    const vfy::Stage st = vfy::opening_stage(vfy::config_of(ctx->cfg, ctx->dev.fri_plan), (const u64*)caps, num_polys, degree_bits, num_permutation_zs, proof, proof_len, *challenger);
     OlaVerifyReport rep;
     memset(&rep, 0, sizeof(rep));
     rep.host_ms = ms_since(t0);
@@ -1482,6 +1511,7 @@ int32_t ola_set_shard(OlaCtx* ctx, uint32_t rank, uint32_t world, ola_all_gather
     require(world >= 1 && world <= 8 && (world & (world - 1)) == 0 && rank < world, "world must be 1, 2, 4 or 8 and rank < world");
     require(ctx->peers.empty(), "a multi-device context partitions the proof itself; ola_set_shard is for one-device contexts of multi-process hosts");
     require(world == 1 || all_gather, "a sharded context needs an all_gather callback");
+    require(world == 1 || ctx->dev.fri_plan.strategy == OLA_FRI_CONSTANT_ARITY_BITS, kFriPartitionRefusal);
     ShardInfo sh;
     if (world > 1) {
         sh.rank = rank; sh.world = world;

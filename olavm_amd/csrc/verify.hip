@@ -115,18 +115,27 @@ __global__ __launch_bounds__(64) void fri_query_check_kernel(const u64* __restri
     u64 x_index = w[vfy::QJ_X_INDEX * n];
     if (tab_off > data_words || (u64)vfy::TAB_WORDS > data_words - tab_off) { flags[j] = vfy::QF_BOUNDS; return; }
     const u64* tab = image + tab_off;
-    const u64 lde_bits = tab[vfy::TH_LDE_BITS], layers = tab[vfy::TH_LAYERS], ab64 = tab[vfy::TH_ARITY_BITS];
+    const u64 lde_bits = tab[vfy::TH_LDE_BITS], layers = tab[vfy::TH_LAYERS], arities_off = tab[vfy::TH_ARITIES_OFF];
     const u64 final_off = tab[vfy::TH_FINAL_OFF], final_len = tab[vfy::TH_FINAL_LEN], betas_off = tab[vfy::TH_BETAS_OFF];
     const u64 n0 = tab[vfy::TH_N0], n1 = tab[vfy::TH_N1], n2 = tab[vfy::TH_N2], nperm = tab[vfy::TH_NPERM];
     const u64 widths[3] = {n0, n1, n2};
-    bool in_bounds = lde_bits <= (u64)vfy::MAX_LDE_BITS && ab64 >= 1 && ab64 <= (u64)vfy::MAX_ARITY_BITS && layers <= 32 && nperm <= n1 &&
+    bool in_bounds = lde_bits <= (u64)vfy::MAX_LDE_BITS && layers <= 32 && nperm <= n1 &&
                      (x_index >> lde_bits) == 0;
     for (int o = 0; o < 3; o++) in_bounds = in_bounds && row_off[o] <= data_words && widths[o] <= data_words - row_off[o];
-    in_bounds = in_bounds && steps_off <= data_words && layers * (2ull << ab64) <= data_words - steps_off;
+    // each layer's arity bits (a per-table list next to the betas): 1 .. MAX_ARITY_BITS, and the evaluations at their own widths
+    in_bounds = in_bounds && arities_off <= data_words && layers <= data_words - arities_off;
+    u64 steps_words = 0;
+    if (in_bounds)
+        for (u64 i = 0; i < layers; i++) {
+            const u64 a = image[arities_off + i];
+            if (a < 1 || a > (u64)vfy::MAX_ARITY_BITS) { in_bounds = false; break; }
+            steps_words += 2ull << a;
+        }
+    in_bounds = in_bounds && steps_off <= data_words && steps_words <= data_words - steps_off;
     in_bounds = in_bounds && betas_off <= data_words && 2 * layers <= data_words - betas_off;
     in_bounds = in_bounds && final_off <= data_words && final_len <= (data_words - final_off) / 2;
     if (!in_bounds) { flags[j] = vfy::QF_BOUNDS; return; }
-    const int log_n = (int)lde_bits, ab = (int)ab64;
+    const int log_n = (int)lde_bits;
     const Ext2 alpha = vfy_ext(tab + vfy::TH_ALPHA);
     const u64* r0 = image + row_off[0];
     const u64* r1 = image + row_off[1];
@@ -150,13 +159,15 @@ __global__ __launch_bounds__(64) void fri_query_check_kernel(const u64* __restri
     Ext2 old_eval = ext_scalar_mul(sum, x);       // the prover's final polynomial was multiplied by X (fri/oracle.rs:218)
 
     u32 verdict = vfy::QF_OK;
+    const u64* evals = image + steps_off;
     for (u32 i = 0; i < (u32)layers; i++) {
+        const int ab = (int)image[arities_off + i];
         const u32 within = (u32)x_index & ((1u << ab) - 1);
-        const u64* evals = image + steps_off + (size_t)i * (2u << ab);
         if (!ext_eq(vfy_ext(evals + 2 * (size_t)within), old_eval)) { verdict = vfy::QF_CONSISTENCY | (i << 8); break; }
         old_eval = vfy_compute_evaluation(x, within, ab, evals, vfy_ext(image + betas_off + 2 * (size_t)i));
         for (int k = 0; k < ab; k++) x = gl_mul(x, x);
         x_index >>= ab;
+        evals += 2u << ab;
     }
     if (verdict == vfy::QF_OK) {
         Ext2 fe = zero;

@@ -36,6 +36,7 @@
 #include "../../include/ola_gpu.h"
 #include "airset_host.h"
 #include "challenger_host.h"
+#include "fri_plan.h"
 #include "gl.cuh"
 #include "ola_error.h"
 
@@ -45,9 +46,11 @@ namespace vfy {
 struct Config {
     int rate_bits = 3, cap_height = 4, pow_bits = 16, arity_bits = 4, final_poly_bits = 5, num_queries = 28, num_challenges = 2;
     uint32_t hasher = OLA_HASH_POSEIDON;
+    FriPlanSpec plan;      // FriReductionStrategy; the default is ConstantArityBits(arity_bits, final_poly_bits)
 };
-inline Config config_of(const OlaGpuConfig& c) {
+inline Config config_of(const OlaGpuConfig& c, const FriPlanSpec& plan = FriPlanSpec()) {
     Config v;
+    v.plan = plan;
     v.rate_bits = (int)c.rate_bits; v.cap_height = (int)c.cap_height; v.pow_bits = (int)c.proof_of_work_bits; v.arity_bits = (int)c.fri_arity_bits;
     v.final_poly_bits = (int)c.fri_final_poly_bits; v.num_queries = (int)c.num_query_rounds; v.num_challenges = (int)c.num_challenges;
     v.hasher = c.hasher;
@@ -160,7 +163,7 @@ inline const char* reason_text(uint32_t r) {
 // ------------------------------------------------------------------------------------------------ the image and the job lists
 // Table header, TAB_WORDS words at tab_off (all offsets are word offsets into the image):
 enum {
-    TH_LDE_BITS = 0, TH_LAYERS, TH_ARITY_BITS, TH_FINAL_OFF, TH_FINAL_LEN, TH_ALPHA /* 2 */, TH_BETAS_OFF = 7, TH_N0, TH_N1, TH_N2, TH_NPERM,
+    TH_LDE_BITS = 0, TH_LAYERS, TH_ARITIES_OFF /* `layers` words: each layer's arity bits */, TH_FINAL_OFF, TH_FINAL_LEN, TH_ALPHA /* 2 */, TH_BETAS_OFF = 7, TH_N0, TH_N1, TH_N2, TH_NPERM,
     TH_ZETA /* 2 */, TH_ZETA_NEXT = 14 /* 2 */, TH_G_INV = 16, TH_REDUCED = 17 /* 3 x 2: reduced openings per batch */,
     TH_ALPHA_POW = 23 /* 3 x 2: alpha^(batch length) */, TAB_WORDS = 32
 };
@@ -203,11 +206,9 @@ struct Stage {
 inline Ext2 ext_from(u64 x) { return ext_make(x, 0); }
 inline Ext2 ext_at(const std::vector<u64>& v, size_t i) { return ext_make(v[2 * i], v[2 * i + 1]); }
 
-// fri/reduction_strategies.rs:40-52 ConstantArityBits
-inline int fri_layers(const Config& c, int degree_bits) {
-    int layers = 0, d = degree_bits;
-    while (d > c.final_poly_bits && d + c.rate_bits - c.arity_bits >= c.cap_height) { layers++; d -= c.arity_bits; }
-    return layers;
+// fri/reduction_strategies.rs:30-57 under the configuration's strategy: the arity bits of every layer (fri_plan.h)
+inline std::vector<int> fri_layers(const Config& c, int degree_bits) {
+    return fri_plan_arity_bits(c.plan, c.arity_bits, c.final_poly_bits, degree_bits, c.rate_bits, c.cap_height, (size_t)c.num_queries);
 }
 
 // fri/challenges.rs:25-73
@@ -246,8 +247,15 @@ inline Verdict fri_stage(Stage& st, const Config& cfg, int table, const std::vec
     Verdict v;
     v.table = table;
     auto fail = [&](uint32_t reason, int query = -1, int which = -1) { v.reason = reason; v.query = query; v.oracle_or_layer = which; return v; };
-    const int lde_bits = degree_bits + cfg.rate_bits, layers = fri_layers(cfg, degree_bits), ab = cfg.arity_bits;
-    const size_t arity = (size_t)1 << ab, cap_len = (size_t)1 << cfg.cap_height;
+    const std::vector<int> arities = fri_layers(cfg, degree_bits);
+    const int lde_bits = degree_bits + cfg.rate_bits, layers = (int)arities.size();
+    if (layers > 64) throw OlaError(OLA_E_INVALID_ARG, "the verifier supports FRI plans of at most 64 layers");
+    int total_bits = 0;
+    for (int a : arities) {
+        if (a < 1 || a > MAX_ARITY_BITS) throw OlaError(OLA_E_INVALID_ARG, "the verifier supports FRI arities of 2 to 16");
+        total_bits += a;
+    }
+    const size_t cap_len = (size_t)1 << cfg.cap_height;
     // validate_fri_proof_shape
     for (size_t i = 0; i < fri.commit_caps.size(); i++)
         if (fri.commit_caps[i].size() != cap_len) return fail(OLA_VERIFY_SHAPE_CAP_HEIGHT, -1, (int)i);
@@ -262,13 +270,14 @@ inline Verdict fri_stage(Stage& st, const Config& cfg, int table, const std::vec
         if ((int)q.steps.size() != layers) return fail(OLA_VERIFY_SHAPE_STEPS, (int)r);
         int bits = lde_bits;
         for (int i = 0; i < layers; i++) {
-            bits -= ab;
-            if (q.steps[i].evals.size() != 2 * arity) return fail(OLA_VERIFY_SHAPE_EVALS_LEN, (int)r, i);
+            bits -= arities[(size_t)i];
+            if (q.steps[i].evals.size() != ((size_t)2 << arities[(size_t)i])) return fail(OLA_VERIFY_SHAPE_EVALS_LEN, (int)r, i);
             if ((int)q.steps[i].path.size() + cfg.cap_height != bits) return fail(OLA_VERIFY_SHAPE_STEP_PATH_LEN, (int)r, i);
         }
     }
-    if (degree_bits < layers * ab) throw OlaError(OLA_E_INVALID_ARG, "the FRI plan folds below degree one: final_poly_bits is too small for arity_bits");
-    if (fri.final_poly.size() != 2 * ((size_t)1 << (degree_bits - layers * ab))) return fail(OLA_VERIFY_SHAPE_FINAL_POLY_LEN);
+    // a plan that does not fit the table is the caller's configuration, not the proof's fault (as in the prover)
+    if (!fri_plan_fits(arities, degree_bits, cfg.rate_bits, cfg.cap_height)) throw OlaError(OLA_E_INVALID_ARG, "FRI total reduction arity is too large.");
+    if (fri.final_poly.size() != 2 * ((size_t)1 << (degree_bits - total_bits))) return fail(OLA_VERIFY_SHAPE_FINAL_POLY_LEN);
     if (cfg.pow_bits > 0 && (fc.pow_response >> (64 - cfg.pow_bits)) != 0) return fail(OLA_VERIFY_POW);
     // one beta was drawn per commit cap, one is used per layer: with caps to spare the transcript is not the prover's (the proof of
     // work has just caught that, up to 2^-pow_bits), with too few there is no beta to fold by
@@ -297,7 +306,7 @@ inline Verdict fri_stage(Stage& st, const Config& cfg, int table, const std::vec
                                (size_t)(num_polys[1] - num_permutation_zs)};
     {
         u64* h = im.data() + tab_off;
-        h[TH_LDE_BITS] = (u64)lde_bits; h[TH_LAYERS] = (u64)layers; h[TH_ARITY_BITS] = (u64)ab;
+        h[TH_LDE_BITS] = (u64)lde_bits; h[TH_LAYERS] = (u64)layers;
         h[TH_FINAL_LEN] = fri.final_poly.size() / 2;
         h[TH_ALPHA] = fc.fri_alpha.a; h[TH_ALPHA + 1] = fc.fri_alpha.b;
         h[TH_N0] = (u64)num_polys[0]; h[TH_N1] = (u64)num_polys[1]; h[TH_N2] = (u64)num_polys[2]; h[TH_NPERM] = (u64)num_permutation_zs;
@@ -312,13 +321,15 @@ inline Verdict fri_stage(Stage& st, const Config& cfg, int table, const std::vec
     {
         const size_t betas_off = im.size();
         for (const Ext2& b : fc.fri_betas) { im.push_back(b.a); im.push_back(b.b); }
+        const size_t arities_off = im.size();
+        for (int a : arities) im.push_back((u64)a);
         const size_t final_off = push_words(im, fri.final_poly.data(), fri.final_poly.size());
-        im[tab_off + TH_BETAS_OFF] = betas_off; im[tab_off + TH_FINAL_OFF] = final_off;
+        im[tab_off + TH_BETAS_OFF] = betas_off; im[tab_off + TH_ARITIES_OFF] = arities_off; im[tab_off + TH_FINAL_OFF] = final_off;
     }
     size_t cap_off[3], commit_cap_off[64];
     for (int o = 0; o < 3; o++) cap_off[o] = push_digests(im, *caps[o]);
     for (int i = 0; i < layers; i++) commit_cap_off[i] = push_digests(im, fri.commit_caps[i]);
-    // ---- the queries: rows, layer evaluations (contiguous, layer i at steps_off + 2 * arity * i), sibling lists
+    // ---- the queries: rows, layer evaluations (contiguous, each layer at its own width 2 * 2^arity_bits), sibling lists
     for (size_t r = 0; r < fri.queries.size(); r++) {
         const WQuery& q = fri.queries[r];
         QueryJob qj;
@@ -334,10 +345,13 @@ inline Verdict fri_stage(Stage& st, const Config& cfg, int table, const std::vec
             m.table = table; m.query = (int)r; m.kind = 0; m.which = o;
             st.merkle.push_back(m);
         }
+        size_t step_off = qj.steps_off;
         for (int i = 0; i < layers; i++) {
-            x_index >>= ab;
+            const size_t width = (size_t)2 << arities[(size_t)i];
+            x_index >>= arities[(size_t)i];
             MerkleJob m;
-            m.leaf_off = qj.steps_off + 2 * arity * (size_t)i; m.leaf_len = (uint32_t)(2 * arity); m.sib_off = push_digests(im, q.steps[i].path);
+            m.leaf_off = step_off; m.leaf_len = (uint32_t)width;
+            step_off += width; m.sib_off = push_digests(im, q.steps[i].path);
             m.depth = (uint32_t)q.steps[i].path.size(); m.cap_off = commit_cap_off[i]; m.cap_len = (uint32_t)cap_len; m.index = x_index;
             m.table = table; m.query = (int)r; m.kind = 1; m.which = i;
             st.merkle.push_back(m);
@@ -519,7 +533,9 @@ inline void observe_openings(OlaChallenger& ch, const WOpenings& op) {
 }
 
 inline void require_config(const Config& cfg) {
-    if (cfg.arity_bits < 1 || cfg.arity_bits > MAX_ARITY_BITS) throw OlaError(OLA_E_INVALID_ARG, "the verifier supports FRI arities of 2 to 16");
+    if (cfg.plan.strategy == OLA_FRI_CONSTANT_ARITY_BITS && (cfg.arity_bits < 1 || cfg.arity_bits > MAX_ARITY_BITS))
+        throw OlaError(OLA_E_INVALID_ARG, "the verifier supports FRI arities of 2 to 16");
+    if (fri_plan_spec_check(cfg.plan.strategy, cfg.plan.args, cfg.plan.n)) throw OlaError(OLA_E_INVALID_ARG, "the FRI reduction strategy is malformed");
     if (cfg.rate_bits < 1 || cfg.rate_bits > 8 || cfg.cap_height < 0 || cfg.cap_height > 16 || cfg.pow_bits < 0 || cfg.pow_bits > 40 ||
         cfg.num_queries < 1 || cfg.num_queries > 1024 || cfg.num_challenges < 1 || cfg.num_challenges > 8 || cfg.final_poly_bits < 0)
         throw OlaError(OLA_E_INVALID_ARG, "configuration out of range for the verifier");

@@ -298,6 +298,15 @@ PY
                  ( set -o pipefail
                    timeout -k 10 600 python -m pytest tests/test_gpu_keccak.py -q --durations=12 2>&1 | tail -30 | tee $O/pytest.log && \
                    timeout -k 10 600 python tools/bench_keccak.py ${KECCAK_LOG_N:-22} ${KECCAK_ROUNDS:-5} --json $O/bench_keccak.json 2>&1 | grep -v amdgpu | tee $O/bench_keccak.txt ) ;;
+    fri_plans)   # FriReductionStrategy Fixed / MinSize: their tests, then at 2^22 rows the pair-fold and staged-leaf kernels against the plain ones (one process per
+                 # setting of the two switches, alternating), the default proof's bytes, and MinSize against the default strategy under Blake3 and Keccak
+                 ( set -o pipefail
+                   timeout -k 10 900 python -m pytest tests/test_gpu_fri_plans.py -x -q --durations=12 2>&1 | tail -30 | tee $O/pytest.log && \
+                   for s in min_size:3 constant:2 constant:1 min_size; do for v in 1 0 1 0; do [ $s = min_size ] && [ $v = 0 ] && continue
+                     OLA_FOLD16=$v OLA_LEAF_EXT_STAGED=$v timeout -k 10 300 python tools/bench_fri_plans.py ab $s ${FRI_LOG_N:-22} 4 --hasher blake3 2>&1 | grep -v amdgpu || exit 1
+                   done; done | tee $O/ab.txt && \
+                   timeout -k 10 300 python tools/bench_fri_plans.py ab default ${FRI_LOG_N:-22} 4 --hasher blake3 2>&1 | grep -v amdgpu | tee $O/default.txt && \
+                   timeout -k 10 600 python tools/bench_fri_plans.py sizes ${FRI_LOG_N:-22} 5 --json $O/sizes.json 2>&1 | grep -v amdgpu | tee $O/sizes.txt ) ;;
     *)           echo "unknown step $step" ;;
   esac
 done

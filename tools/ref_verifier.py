@@ -452,13 +452,17 @@ STARK_FIELDS = ["cpu_stark", "memory_stark", "bitwise_stark", "cmp_stark", "rang
 class RefVerifier:
     """The reference's verifier over one reference tree.  `verify(raw)` -> (True, None) or (False, "file.rs:line" of the `ensure!` that failed)."""
 
-    def __init__(self, reference="/root/reference", fast_hash=True, hasher="poseidon"):
+    def __init__(self, reference="/root/reference", fast_hash=True, hasher="poseidon", reduction_strategy=None):
+        """reduction_strategy: None keeps standard_fast_config's ConstantArityBits(4, 5); ("MinSize", [None]), ("MinSize", [3]) or
+        ("Fixed", [[4, 3, 3]]) is `config.fri_config.reduction_strategy = FriReductionStrategy::<variant>(<payload>)`"""
         sys.setrecursionlimit(max(sys.getrecursionlimit(), 20000))
         self.reference = reference
         self.hasher = hasher
         self.it = verifier_interp(reference, fast_hash, hasher)
         self.stark_dir = os.path.join(reference, "circuits", "src", "stark")
         self.config = self.it.call_assoc("StarkConfig", "standard_fast_config", [], os.path.join(self.stark_dir, "config.rs"))
+        if reduction_strategy is not None:
+            self.config["fri_config"]["reduction_strategy"] = Enum("FriReductionStrategy", reduction_strategy[0], list(reduction_strategy[1]))
 
     def ola_stark(self):
         """what `OlaStark::default()` (ola_stark.rs:45-64) builds, minus its init_gpu() call: twelve default table structs (compress challenges unset,
@@ -522,11 +526,14 @@ def main():
     ap.add_argument("--reference", default="/root/reference")
     ap.add_argument("--hasher", default="poseidon", choices=("poseidon", "blake3", "poseidon2", "poseidon2_pow_poseidon", "keccak"),
                     help="PoseidonGoldilocksConfig, Blake3GoldilocksConfig, Poseidon2GoldilocksConfig, Poseidon2GoldilocksConfig2 or KeccakGoldilocksConfig")
+    ap.add_argument("--min-size", nargs="?", const="none", default=None, metavar="MAX_ARITY_BITS",
+                    help="verify under FriReductionStrategy::MinSize(None), or MinSize(Some(MAX_ARITY_BITS)), instead of ConstantArityBits(4, 5)")
     a = ap.parse_args()
     raw = open(a.proof, "rb").read()
     proof = decode_all_proof(raw, a.hasher)
     print("decoded: %d tables, %d bytes" % (len(proof["stark_proofs"]), len(raw)))
-    rv = RefVerifier(a.reference, hasher=a.hasher)
+    strategy = None if a.min_size is None else ("MinSize", [None if a.min_size == "none" else int(a.min_size)])
+    rv = RefVerifier(a.reference, hasher=a.hasher, reduction_strategy=strategy)
     if rv.encode(proof) != raw:
         raise SystemExit("write_all_proof of the decoded proof does not give back the bytes")
     print("write_all_proof (serialization.rs:377), interpreted, reproduces the %d bytes" % len(raw))

@@ -482,6 +482,14 @@ class Parser:
             if self.eat("="):
                 init = self.expr()
             return ("let", pat, init, ln), False, True
+        if t == "const" and re.match(r"^[A-Z_][A-Z0-9_]*$", self.peek(1)) and self.peek(2) == ":":
+            # a constant local to a function (fri/reduction_strategies.rs:142 `const D: usize = 4;`): a binding of the block
+            self.next()
+            name = self.next()
+            self.expect(":")
+            self.skip_type(("=", ";"))
+            self.expect("=")
+            return ("let", ("pid", name), self.expr(), ln), False, True
         if t == "for" and self.peek(1) != "<":
             self.next()
             pat = self.pattern()
@@ -1854,6 +1862,8 @@ class Interp:
             return [self.call_closure(args[0], [i]) for i in range(n_)]
         if name == "init_gpu":
             return None
+        if name == "now" and len(segs) >= 2 and segs[-2] == "Instant" and not args:
+            return None                             # fri/reduction_strategies.rs:71: `start` is read inside `debug!` only, which has no value here
         if name == "once" and "iter" in segs:
             return [args[0]]
         if name == "repeat_with" and "iter" in segs:
@@ -2036,6 +2046,8 @@ class Interp:
             if name == "take":
                 return [x for _, x in zip(range(args[0]), r.it)]
             raise self.err(src, line, f"iter::repeat_with().{name}")
+        if name == "unwrap_or" and len(args) == 1 and isinstance(r, int) and not isinstance(r, bool):
+            return r                # `Some(x)` stays x (class Opt): `prefix.last().copied().unwrap_or(..)` of a non-empty vector
         # ---- adaptors that do nothing here
         if name in ("iter", "into_iter", "iter_mut", "copied", "cloned", "collect", "collect_vec", "to_vec", "try_into", "unwrap", "expect", "by_ref",
                     "as_ref", "as_mut", "borrow", "borrow_mut", "as_mut_slice", "as_ptr", "as_mut_ptr", "into", "to_owned", "as_slice_of_cells", "peekable", "into_par_iter", "par_iter", "par_iter_mut", "unwrap_or_else", "unwrap_or_default"):
@@ -2808,6 +2820,51 @@ def primitives(reference):
     return out
 
 
+FRI_PLANS_FIXTURE = os.path.join(ROOT, "tests", "golden", "ref_fri_plans.json")
+FRI_PLAN_DEGREE_BITS = tuple(range(0, 27))
+FRI_PLAN_RATE_BITS = (1, 2, 3, 4)
+FRI_PLAN_QUERIES = (10, 28, 84)
+FRI_PLAN_CAP_HEIGHT = 4
+# [variant, payload]: MinSize(None | Some(k)), ConstantArityBits(arity_bits, final_poly_bits), Fixed(list); Fixed([1, 1]) is the reference's
+# own test value (plonk/proof.rs:467)
+FRI_PLAN_STRATEGIES = ([["MinSize", [None]]] + [["MinSize", [k]] for k in (1, 2, 3, 4)] +
+                       [["ConstantArityBits", [4, 5]], ["ConstantArityBits", [3, 5]], ["ConstantArityBits", [2, 5]], ["ConstantArityBits", [1, 5]],
+                        ["ConstantArityBits", [4, 2]]] +
+                       [["Fixed", [v]] for v in ([], [1, 1], [4, 3, 3], [1, 4, 2, 3])])
+
+
+def fri_plan_call(it, strategy, degree_bits, rate_bits, cap_height, num_queries):
+    """FriReductionStrategy::reduction_arity_bits (fri/reduction_strategies.rs:30) interpreted, or None where the reference panics (its
+    `assert!(degree_bits >= arity_bits)`, :46)"""
+    f = os.path.join(it.plonky2, "fri", "reduction_strategies.rs")
+    variant, payload = strategy
+    try:
+        return [int(x) for x in it.call_assoc("FriReductionStrategy", "reduction_arity_bits",
+                                              [Enum("FriReductionStrategy", variant, clone(list(payload))), degree_bits, rate_bits, cap_height, num_queries], f)]
+    except RustError as e:
+        if "assert" in str(e) or "overflow" in str(e) or "underflow" in str(e):
+            return None
+        raise
+
+
+def fri_plans(reference, keep=lambda strategy, degree_bits, rate_bits, num_queries: True):
+    """The reference's own reduction plans for all three variants of FriReductionStrategy: entries [strategy, rate_bits, num_queries,
+    [plan per degree_bits]] at cap_height 4 (tests/test_fri_plan.py).  `keep` selects what is derived (the test re-derives a part)."""
+    it = plonky2_interp(reference)
+    out = {"generated_by": "tools/rust_air_eval.py --fri-plans",
+           "source": "plonky2/plonky2/src/fri/reduction_strategies.rs: FriReductionStrategy::reduction_arity_bits",
+           "cap_height": FRI_PLAN_CAP_HEIGHT, "degree_bits": list(FRI_PLAN_DEGREE_BITS), "plans": []}
+    for strategy in FRI_PLAN_STRATEGIES:
+        for rb in FRI_PLAN_RATE_BITS:
+            for nq in FRI_PLAN_QUERIES:
+                if strategy[0] == "Fixed" and (rb, nq) != (FRI_PLAN_RATE_BITS[0], FRI_PLAN_QUERIES[0]):
+                    continue            # a Fixed plan is its list whatever the table: one entry
+                plans = [fri_plan_call(it, strategy, db, rb, FRI_PLAN_CAP_HEIGHT, nq) if keep(strategy, db, rb, nq) else "skipped"
+                         for db in FRI_PLAN_DEGREE_BITS]
+                out["plans"].append({"strategy": strategy, "rate_bits": rb, "num_queries": nq, "reduction_arity_bits": plans})
+    return out
+
+
 NTT_FIXTURE = os.path.join(ROOT, "tests", "golden", "ref_ntt_vectors.json")
 NTT_OPS = ("evaluate_poly", "interpolate_poly", "evaluate_poly_with_offset", "interpolate_poly_with_offset")
 
@@ -3111,6 +3168,7 @@ def main():
     ap.add_argument("--out", default=FIXTURE)
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--primitives", action="store_true", help="the hashing / transcript / FRI-parameter vectors instead of the AIR vectors")
+    ap.add_argument("--fri-plans", action="store_true", help="FriReductionStrategy::reduction_arity_bits for Fixed, ConstantArityBits and MinSize (ref_fri_plans.json)")
     ap.add_argument("--ntt", action="store_true", help="the transform vectors (cfft) instead of the AIR vectors")
     ap.add_argument("--tracegen", nargs="?", const="all", choices=("all", "vectors", "cpu_steps", "storage"),
                     help="the trace generators' outputs (generation/*.rs) instead of the AIR vectors: `vectors` (ref_tracegen_vectors.json), "
@@ -3147,6 +3205,19 @@ def main():
         data = ntt_vectors(a.reference)
         text = json.dumps(data, indent=0) + "\n"
         print("%d transforms" % len(data["vectors"]))
+        if a.check:
+            if open(out).read() != text:
+                raise SystemExit(out + " is stale")
+            print("fixture is up to date")
+            return
+        open(out, "w").write(text)
+        print("wrote", out, "(%d bytes)" % len(text))
+        return
+    if a.fri_plans:
+        out = FRI_PLANS_FIXTURE if a.out == FIXTURE else a.out
+        data = fri_plans(a.reference)
+        text = json.dumps(data, separators=(",", ":")) + "\n"
+        print("%d plan lists of %d tables each" % (len(data["plans"]), len(data["degree_bits"])))
         if a.check:
             if open(out).read() != text:
                 raise SystemExit(out + " is stale")
