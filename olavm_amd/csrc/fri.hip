@@ -357,53 +357,28 @@ __global__ __launch_bounds__(256) void fold_kernel(const u64* __restrict__ ca, c
     ob[j] = s.b;
 }
 
-// The same fold for arity 16 with loads on consecutive addresses (round 6): thread j of fold_kernel reads sixteen words 128 bytes
-// apart from thread j + 1's -- 16.4 GB fetched per 2^22-row proof for 1.1 GB of coefficients (profiles/r05_proof_pmc_blake3.txt).
-// Here a thread loads TWO neighbouring coefficients of both planes with 16-byte loads, eight neighbouring lanes hold one output's
-// sixteen, and three exchanges join them: s = c_even + beta c_odd, then pairs by beta^2, beta^4, beta^8.  `nz_out` outputs are
-// computed (the caller zero-fills the rest: the first layer's planes are zero beyond the n coefficients, 7/8 of their length).
+// lane ^ m's value, both halves of both words
 __device__ __forceinline__ Ext2 ext_shfl_xor(Ext2 v, int m) {
     Ext2 r;
     r.a = ((u64)(u32)__shfl_xor((int)(u32)(v.a >> 32), m, 64) << 32) | (u32)__shfl_xor((int)(u32)v.a, m, 64);
     r.b = ((u64)(u32)__shfl_xor((int)(u32)(v.b >> 32), m, 64) << 32) | (u32)__shfl_xor((int)(u32)v.b, m, 64);
     return r;
 }
-__global__ __launch_bounds__(256) void fold16_kernel(const u64* __restrict__ ca, const u64* __restrict__ cb, size_t nz_out, Ext2 b1, Ext2 b2, Ext2 b4,
-                                                     Ext2 b8, u64* __restrict__ oa, u64* __restrict__ ob) {
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;      // pair index: coefficients 2t, 2t + 1
-    const size_t last = nz_out * 8 - 1;
-    const size_t tt = t < last ? t : last;                               // surplus lanes redo the last pair: the wave stays whole
-    const ulonglong2 va = *reinterpret_cast<const ulonglong2*>(ca + 2 * tt);
-    const ulonglong2 vb = *reinterpret_cast<const ulonglong2*>(cb + 2 * tt);
-    Ext2 s = ext_add(ext_make(va.x, vb.x), ext_mul(ext_make(va.y, vb.y), b1));
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        const int m = 1 << r;
-        const Ext2 pw = r == 0 ? b2 : (r == 1 ? b4 : b8);
-        const Ext2 o = ext_shfl_xor(s, m);
-        const bool up = (lane & m) != 0;
-        const Ext2 lo = up ? o : s, hi = up ? s : o;
-        s = ext_add(lo, ext_mul(hi, pw));
-    }
-    if ((t & 7) == 0 && t <= last) {
-        oa[t >> 3] = s.a;
-        ob[t >> 3] = s.b;
-    }
-}
 
-// The same arrangement as a template on the arity bits (FriReductionStrategy::Fixed and MinSize plan layers of arity 8, 4 and 2):
-// a thread loads two neighbouring coefficients of both planes with 16-byte loads, 2^(AB-1) neighbouring lanes hold one output and
-// AB - 1 exchanges join them by beta^2, beta^4, .. (pw.p[r] = beta^(2^(r+1)), computed by the host).  A group is 1, 2, 4 or 8
-// aligned lanes and a workgroup a multiple of 64 pairs, so no group straddles a wave.  Launched for arities 8 and 4.  AB = 4 is
-// fold16_kernel's arithmetic step for step; arity 16 keeps its own kernel, whose time at 2^22 rows is on record.  AB = 1 would
-// exchange nothing, and is not launched: fold_kernel's lanes already read 16 bytes apart there, and at 2^22 rows the pair form
-// was not faster.
+// The same fold for arities 4, 8 and 16 with loads on consecutive addresses (round 6): thread j of fold_kernel at arity 16 reads
+// sixteen words 128 bytes apart from thread j + 1's -- 16.4 GB fetched per 2^22-row proof for 1.1 GB of coefficients
+// (profiles/r05_proof_pmc_blake3.txt).  Here a thread loads TWO neighbouring coefficients of both planes with 16-byte loads,
+// 2^(AB-1) neighbouring lanes hold one output (AB the arity bits: FriReductionStrategy::Fixed and MinSize plan layers of arity 8
+// and 4 beside the default 16) and AB - 1 exchanges join them: s = c_even + beta c_odd, then pairs by beta^2, beta^4, ..
+// (pw.p[r] = beta^(2^(r+1)), computed by the host).  A group is 2, 4 or 8 aligned lanes and a workgroup a multiple of 64 pairs, so
+// no group straddles a wave.  `nz_out` outputs are computed (the caller zero-fills the rest: the first layer's planes are zero
+// beyond the n coefficients, 7/8 of their length).  AB = 1 would exchange nothing, and is not launched: fold_kernel's lanes
+// already read 16 bytes apart there, and at 2^22 rows the pair form was not faster.
 struct FoldPowers { Ext2 p[3]; };
 template <int AB>
 __global__ __launch_bounds__(256) void fold_pairs_kernel(const u64* __restrict__ ca, const u64* __restrict__ cb, size_t nz_out, Ext2 b1, FoldPowers pw,
                                                          u64* __restrict__ oa, u64* __restrict__ ob) {
-    static_assert(AB >= 1 && AB <= 4, "a group of 2^(AB-1) lanes inside one wave");
+    static_assert(AB >= 2 && AB <= 4, "the arities launched: a group of 2, 4 or 8 lanes inside one wave");
     constexpr int G = 1 << (AB - 1);                                     // lanes per output
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;      // pair index: coefficients 2t, 2t + 1
     const size_t last = nz_out * G - 1;
@@ -989,7 +964,7 @@ static void fri_fold(DevBuf& mem, FriCommit& c, int ab, Ext2 beta) {
         switch (ab) {
             case 2: hipLaunchKernelGGL(fold_pairs_kernel<2>, grid, block, 0, ctx->stream, ca, cb, nz_out, beta, pw, oa, ob); break;
             case 3: hipLaunchKernelGGL(fold_pairs_kernel<3>, grid, block, 0, ctx->stream, ca, cb, nz_out, beta, pw, oa, ob); break;
-            default: hipLaunchKernelGGL(fold16_kernel, grid, block, 0, ctx->stream, ca, cb, nz_out, beta, b2, b4, b8, oa, ob); break;
+            default: hipLaunchKernelGGL(fold_pairs_kernel<4>, grid, block, 0, ctx->stream, ca, cb, nz_out, beta, pw, oa, ob); break;
         }
         c.nz = nz_out;
     } else {

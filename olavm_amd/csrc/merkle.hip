@@ -219,42 +219,19 @@ __global__ __launch_bounds__(256) void pow_kernel(u64 h0, u64 h1, u64 h2, u64 h3
 }
 
 // ---- kernels of the byte hashes alone (H::BYTES: one thread per leaf / node throughout, no quad forms)
-// The extension leaves for arity 16, through LDS (round 6).  A thread of leaf_hash_kernel<H, ExtSrc> reads 16 + 16 words 128 bytes apart
-// from its neighbour's: a wave touches 64 lines per load and the lines are gone from the vector cache before their other words are asked
-// for -- 17.1 GB fetched per 2^22-row proof for 1.2 GB of values (profiles/r05_proof_pmc_blake3.txt).  Here a workgroup copies
-// its 128 leaves x 16 values of both planes with 16-byte loads on consecutive addresses and every thread hashes its leaf out of
-// LDS (rows padded to 17 words: conflict-free for 8-byte reads).
+// The extension leaves of arity 16, 8 and 4 (AB = 4, 3, 2: the default, and layers that FriReductionStrategy::Fixed and MinSize plan),
+// through LDS (round 6).  A thread of leaf_hash_kernel<H, ExtSrc> at arity 16 reads 16 + 16 words 128 bytes apart from its neighbour's: a
+// wave touches 64 lines per load and the lines are gone from the vector cache before their other words are asked for -- 17.1 GB
+// fetched per 2^22-row proof for 1.2 GB of values (profiles/r05_proof_pmc_blake3.txt).  Here a workgroup copies its 128 leaves x
+// 2^AB values of both planes with 16-byte loads on consecutive addresses and every thread hashes its leaf out of LDS.  Rows of
+// S = 2^AB + 1 words: ds_read_b64 banks by (byte address / 4) mod 64 within each 32-lane half, lane l reads word l S + k, i.e. dwords
+// 2 (l S + k) and the next -- the 32 lanes cover all 64 banks exactly once when l S mod 32 takes 32 values, that is for every odd S:
+// 17, 9 and 5.
 #define B3X_LEAVES 128
-template <class H>
-__global__ __launch_bounds__(B3X_LEAVES) void leaf_bytes_ext16_kernel(const u64* __restrict__ plane_a, const u64* __restrict__ plane_b, size_t num_leaves,
-                                                                      u64* __restrict__ out) {
-    __shared__ u64 tile[2][B3X_LEAVES * 17];
-    const size_t j0 = (size_t)blockIdx.x * B3X_LEAVES;
-    const size_t base = j0 * 16;
-    const size_t avail = (num_leaves - j0 < (size_t)B3X_LEAVES ? num_leaves - j0 : (size_t)B3X_LEAVES) * 16;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const size_t e = 2 * ((size_t)threadIdx.x + B3X_LEAVES * i);
-        if (e < avail) {
-            const ulonglong2 va = *reinterpret_cast<const ulonglong2*>(plane_a + base + e);
-            const ulonglong2 vb = *reinterpret_cast<const ulonglong2*>(plane_b + base + e);
-            const size_t at = (e >> 4) * 17 + (e & 15);
-            tile[0][at] = va.x; tile[0][at + 1] = va.y;
-            tile[1][at] = vb.x; tile[1][at + 1] = vb.y;
-        }
-    }
-    __syncthreads();
-    const size_t j = j0 + threadIdx.x;
-    if (j >= num_leaves) return;
-    H::leaf([&](u32 i) { return gl_canon(tile[i & 1][threadIdx.x * 17 + (i >> 1)]); }, 32u, out + j * 4);
-}
-// The same staging for arities 8 and 4 (AB = 3, 2: layers that FriReductionStrategy::Fixed and MinSize plan).  Rows of 2^AB + 1 words:
-// ds_read_b64 banks by (byte address / 4) mod 64 within each 32-lane half, lane l reads word l S + k, i.e. dwords 2 (l S + k) and the
-// next -- the 32 lanes cover all 64 banks exactly once when l S mod 32 takes 32 values, that is for every odd S: 9 and 5 as for 17.
 template <class H, int AB>
 __global__ __launch_bounds__(B3X_LEAVES) void leaf_bytes_ext_tile_kernel(const u64* __restrict__ plane_a, const u64* __restrict__ plane_b, size_t num_leaves,
                                                                          u64* __restrict__ out) {
-    static_assert(AB == 2 || AB == 3, "arity 16 has leaf_bytes_ext16_kernel, arity 2 needs no tile");
+    static_assert(AB >= 2 && AB <= 4, "arity 2 needs no tile: leaf_bytes_ext2_kernel");
     constexpr int A = 1 << AB, S = A + 1;
     __shared__ u64 tile[2][B3X_LEAVES * S];
     const size_t j0 = (size_t)blockIdx.x * B3X_LEAVES;
@@ -372,10 +349,12 @@ void launch_leaf_hash_ext(DeviceCtx* ctx, const u64* pa, const u64* pb, int arit
             if (staged && num_leaves >= 1024 && (((uintptr_t)pa | (uintptr_t)pb) & 15) == 0 && (arity == 16 || arity == 8 || arity == 4 || arity == 2)) {
                 using HS = typename H::Small;
                 const dim3 tiles((unsigned)((num_leaves + B3X_LEAVES - 1) / B3X_LEAVES)), tile_block(B3X_LEAVES);
-                if (arity == 16) hipLaunchKernelGGL(leaf_bytes_ext16_kernel<HS>, tiles, tile_block, 0, ctx->stream, pa, pb, num_leaves, out);
-                else if (arity == 8) hipLaunchKernelGGL((leaf_bytes_ext_tile_kernel<HS, 3>), tiles, tile_block, 0, ctx->stream, pa, pb, num_leaves, out);
-                else if (arity == 4) hipLaunchKernelGGL((leaf_bytes_ext_tile_kernel<HS, 2>), tiles, tile_block, 0, ctx->stream, pa, pb, num_leaves, out);
-                else hipLaunchKernelGGL(leaf_bytes_ext2_kernel<HS>, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256), 0, ctx->stream, pa, pb, num_leaves, out);
+                switch (arity) {
+                    case 16: hipLaunchKernelGGL((leaf_bytes_ext_tile_kernel<HS, 4>), tiles, tile_block, 0, ctx->stream, pa, pb, num_leaves, out); break;
+                    case 8: hipLaunchKernelGGL((leaf_bytes_ext_tile_kernel<HS, 3>), tiles, tile_block, 0, ctx->stream, pa, pb, num_leaves, out); break;
+                    case 4: hipLaunchKernelGGL((leaf_bytes_ext_tile_kernel<HS, 2>), tiles, tile_block, 0, ctx->stream, pa, pb, num_leaves, out); break;
+                    default: hipLaunchKernelGGL(leaf_bytes_ext2_kernel<HS>, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256), 0, ctx->stream, pa, pb, num_leaves, out); break;
+                }
                 return;
             }
         }

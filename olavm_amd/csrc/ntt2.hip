@@ -361,36 +361,23 @@ static const u64* get_full_small(NttTables& t, int R, int inverse) {
 // per-coset ratio s_c^(2^e) for the pre-scale recurrence
 static const u64* get_coset_steps(NttTables& t, int log_n, int rate_bits, int e, u64 single_shift) {
     std::vector<u64> v;
-    if (rate_bits < 0) {
-        v.push_back(gl_pow(single_shift, (u64)1 << e));
-    } else {
-        const u64 g = gl_root_of_unity(log_n + rate_bits);
-        for (int c = 0; c < (1 << rate_bits); c++) {
-            const u64 s = gl_mul(gl_pow(g, bitrev32((u32)c, rate_bits)), GL_GENERATOR);
-            v.push_back(gl_pow(s, (u64)1 << e));
-        }
-    }
+    for (u64 s : coset_shifts(log_n, rate_bits, single_shift)) v.push_back(gl_pow(s, (u64)1 << e));
     return upload(t.ctx, v);  // small; lives in the persistent pool
 }
 
 // T-form passes of a coset transform: per coset c, (s_c^(2^lo))^m for m < 2^R -- the part of the pre-scale s^a that belongs to
 // the pass over index bits [lo, lo + R)
 static const u64* get_coset_pows(NttTables& t, int log_n, int rate_bits, int lo, int R, u64 single_shift) {
-    std::vector<u64> shifts;
-    if (rate_bits < 0) shifts.push_back(single_shift);
-    else {
-        const u64 g = gl_root_of_unity(log_n + rate_bits);
-        for (int c = 0; c < (1 << rate_bits); c++) shifts.push_back(gl_mul(gl_pow(g, bitrev32((u32)c, rate_bits)), GL_GENERATOR));
-    }
     std::vector<u64> v;
-    for (u64 sc : shifts) {
+    for (u64 sc : coset_shifts(log_n, rate_bits, single_shift)) {
         const std::vector<u64> pw = powers(gl_pow(sc, (u64)1 << lo), (size_t)1 << R);
         v.insert(v.end(), pw.begin(), pw.end());
     }
     return upload(t.ctx, v);  // small; lives in the persistent pool
 }
 
-// Same contract as ntt_run (ntt.hip) for L >= 14.  prescale: rate_bits >= 0 selects the LDE coset family
+// The transform of ntt_run (ntt.hip) for L >= 14, in passes; a natural-order result goes through `scratch` (the shape of
+// `out`).  prescale: rate_bits >= 0 selects the LDE coset family
 // (7*g^bitrev(c)) of which cosets [coset_first, coset_first + cosets) are produced, rate_bits = -1 with `shift` a single
 // coset, -2 none.
 static void ntt2_run_group(NttTables& t, const u64* in, size_t in_col_stride, u64* out, size_t out_col_stride, u64* scratch,

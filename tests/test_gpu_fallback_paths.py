@@ -118,7 +118,7 @@ def test_wide_evaluation_steps_per_workgroup_match_the_integer_reference(openeva
 def test_stepped_opening_on_poisoned_pool_blocks(oracle, log_n, tmp_path):
     """OLA_POOL_POISON=1: the stepped opening of the stress columns where every block of the pool starts as all-ones words.  The
     pool gives a call sequence the same blocks in the same roles, and the driver's fresh blocks are zero, so without the switch a
-    kernel that reads what nobody wrote reads zeros run after run.  What depends on it here: fold16_kernel writes nz / 16 outputs
+    kernel that reads what nobody wrote reads zeros run after run.  What depends on it here: fold_pairs_kernel<4> writes nz / 16 outputs
     and leaves the rest of the layer's planes to a memset (2^12 rows: the first fold; 2^16 rows: the first two); those words enter
     no word of the final polynomial, only the NEXT layer's committed values -- so the caps are compared, with the oracle's
     transform and tree over the integer reference's folded polynomials."""

@@ -4,11 +4,11 @@
    polynomial and every layer's cap against Python integers (tests/opening_reference.py's composed quotients, folded layer by layer with
    the plan's arities; the caps from the oracle's transform and tree, or tests/keccak_ref.py's tree, with leaves of 2 * arity words:
    tests/fri_plan_reference.py).  Shapes, the smallest at which a path exists (N = 8 n values in the first layer):
-     2^12 rows  the first layer is exactly 4096 non-zero coefficients: the smallest input of fold_pairs_kernel / fold16_kernel (arity 2 folds in fold_kernel), and
+     2^12 rows  the first layer is exactly 4096 non-zero coefficients: the smallest input of fold_pairs_kernel<2 | 3 | 4> (arity 2 folds in fold_kernel), and
                 4096 / 8192 / 16384 leaves for arity 8 / 4 / 2 (the staged leaf kernels need 1024); plans [3,3] [2,2,2] [1,1,1,1]
                 [3,4] [4,3] [1,4,2,3] and [] (no layer: the final polynomial is the composed quotient)
      2^11 rows  [3,3]: below the threshold, fold_kernel folds every arity
-     2^16 rows  [4,3,3]: fold16_kernel on 65536, fold_pairs_kernel<3> on exactly 4096, fold_kernel on 512; staged leaves on the first
+     2^16 rows  [4,3,3]: fold_pairs_kernel<4> on 65536, fold_pairs_kernel<3> on exactly 4096, fold_kernel on 512; staged leaves on the first
                 two layers -- also in a child process under OLA_POOL_POISON=1, where a word behind nz_out that nobody wrote is 0xFF..FF
    Challenge sets: random, beta = 1, beta = 0, beta = (p-1, p-1), and words >= p whose results must equal the run with the reduced
    words.  Columns: the stress columns of tests/opening_cases.py (all p - 1, random, ...).  Hashers: Poseidon, Blake3 and Keccak at 2^12;

@@ -9,7 +9,7 @@ Size thresholds of the launch code (olavm_amd/csrc/merkle.hip), both sides of ea
   * launch_merkle_build fuses levels (merkle_levels_bytes_kernel) while a level has more than 256 nodes: trees of 512 leaves
     (commit log_n 6) have none, of 1024 leaves (log_n 7) one fused launch of one level, of 2048 and more two levels per launch;
     levels of 256 nodes and fewer go to merkle_top_bytes_kernel.
-  * launch_leaf_hash_ext stages arity-16 leaves through LDS (leaf_bytes_ext16_kernel) from 1024 leaves: the first FRI layer of a
+  * launch_leaf_hash_ext stages arity-16 leaves through LDS (leaf_bytes_ext_tile_kernel<H, 4>) from 1024 leaves: the first FRI layer of a
     2^10-row opening has 512 leaves (direct kernel), of a 2^11-row opening 1024 (staged).
   * two FRI layers start at 2^10 rows (ConstantArityBits(4, 5), rate 3, cap height 4)."""
 import hashlib

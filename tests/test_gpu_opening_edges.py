@@ -1,11 +1,11 @@
 """The opening evaluations (eval_points_kernel, eval_points_wide_kernel, eval_reduce_kernel), the composition and division
-(compose_kernel .. finalize_kernel) and the FRI folds (fold_kernel, fold16_kernel) through the stepped ABI at opening points and
+(compose_kernel .. finalize_kernel) and the FRI folds (fold_kernel, fold_pairs_kernel<4>) through the stepped ABI at opening points and
 challenges the CALLER chooses -- base-field, (0, 1), small order, zero alpha and beta, non-canonical words -- on coefficient
 columns that sit on the edges of the kernels' limb arithmetic and index decomposition, bit for bit against Python integers
 (tests/opening_reference.py).  No transcript, proof of work or query is involved.
 
 What is compared: every opened column of every span, and every word of the final polynomial.  The final polynomial depends on the
-first n >> 4^layers words of each fold's output only; the rest of a fold's output (zero by construction: fold16_kernel leaves it
+first n >> 4^layers words of each fold's output only; the rest of a fold's output (zero by construction: fold_pairs_kernel leaves it
 to a memset) enters nothing but that layer's committed values.  So for the shapes of CAP_CHECKED the caps that next_layer returns
 are compared as well, with the oracle's transform and Merkle tree over the reference's folded polynomials -- that is the only
 assertion here that sees a fold's whole output.  Elsewhere the caps stay with the proof-byte comparisons of the other modules.
@@ -18,10 +18,10 @@ path exists:
   2^3   no FRI layer: the final polynomial is the composed quotient itself
   2^8   one chunk of eval_points_kernel
   2^11  the first fold in fold_kernel (fewer than 4096 non-zero coefficients) and its nz bookkeeping
-  2^12  the first fold in fold16_kernel with nz_out < out_len, the second in fold_kernel
+  2^12  the first fold in fold_pairs_kernel<4> with nz_out < out_len, the second in fold_kernel
   2^14  four chunks of eval_points_kernel
   2^15  the smallest launch of eval_points_wide_kernel (h = 8, one lo block)
-  2^16  fold16_kernel twice
+  2^16  fold_pairs_kernel<4> twice
   2^17  h = 9, two lo blocks: blockIdx.x % nlo_blocks and / nlo_blocks
   2^18  more than 16 chunks: eval_reduce_kernel sums on the device
 Columns (9, 5, 4) give the wide kernel the groups 4 + 4 + 1 and its surplus-column path, the narrow kernel 8 + 1, and three Zs
@@ -37,7 +37,7 @@ OLA_E_INVALID_ARG, OLA_E_ZETA_IN_SUBGROUP = -1, -6
 ALL = ("random", "base_zeta", "x_zeta", "minus_ones", "order3_zeta", "non_canonical")
 SHAPES = [(log_n, OC.MAIN_COLS, OC.MAIN_NPERM, ALL) for log_n in (3, 8, 11, 12, 14, 15, 16, 17)]
 SHAPES += [(15, (4, 1, 1), 1, ALL), (15, (1, 3, 2), 0, ALL), (18, (5, 2, 1), 1, ("random", "order3_zeta"))]
-CAP_CHECKED = {12: ALL, 16: ("random", "x_zeta")}      # fold16_kernel once / twice with a zero tail behind its outputs
+CAP_CHECKED = {12: ALL, 16: ("random", "x_zeta")}      # fold_pairs_kernel<4> once / twice with a zero tail behind its outputs
 CASES = [pytest.param(s[:3], name, id="2p%d-%s-nperm%d-%s" % (s[0], "x".join(map(str, s[1])), s[2], name)) for s in SHAPES for name in s[3]]
 
 

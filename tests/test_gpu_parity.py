@@ -95,7 +95,8 @@ def test_pow_minimal_witness(be, oracle):
 
 
 # ---------------------------------------------------------------- NTT family
-@pytest.mark.parametrize("log_n", [0, 1, 2, 3, 4, 5, 7, 8, 10, 12, 13, 14, 15, 17, 18])
+# every size of the one-tile transform (2^0 .. 2^13 points, ntt.hip), then sizes that run in passes (ntt2.hip)
+@pytest.mark.parametrize("log_n", list(range(14)) + [14, 15, 17, 18])
 def test_ntt_evaluate_interpolate(be, oracle, log_n):
     from olavm_amd.backend import OLA_NTT_EVALUATE, OLA_NTT_INTERPOLATE
     rng = np.random.default_rng(log_n)
@@ -108,7 +109,7 @@ def test_ntt_evaluate_interpolate(be, oracle, log_n):
     assert np.array_equal(back, c)
 
 
-@pytest.mark.parametrize("log_n", [0, 1, 3, 6, 9, 12, 13, 14, 16])
+@pytest.mark.parametrize("log_n", list(range(14)) + [14, 16])
 def test_coset_lde_natural_and_leaf_order(be, oracle, log_n):
     from olavm_amd.backend import OLA_NTT_COSET_LDE, OLA_NTT_COSET_LDE_LEAF_ORDER
     rng = np.random.default_rng(100 + log_n)
@@ -122,7 +123,8 @@ def test_coset_lde_natural_and_leaf_order(be, oracle, log_n):
         assert np.array_equal(leaf[b], want[rev])
 
 
-@pytest.mark.parametrize("log_n,shift", [(4, 7), (10, 7), (14, 7), (11, 49), (15, 3)])
+@pytest.mark.parametrize("log_n,shift", [(4, 7), (10, 7), (14, 7), (11, 49), (15, 3)]
+                         + [(log_n, (7, 49, 3)[log_n % 3]) for log_n in range(14) if log_n not in (4, 10, 11)])
 def test_coset_fft_and_ifft_blowup1(be, oracle, log_n, shift):
     from olavm_amd.backend import OLA_NTT_COSET_LDE, OLA_NTT_COSET_INTERPOLATE
     rng = np.random.default_rng(log_n)

@@ -1,5 +1,5 @@
 """Randomised check of round 6's opening kernels against the kernels they replace: 12-table instances with random heights of the large
-tables (2^12 .. 2^20: both sides of every size threshold of eval_points_wide_kernel / fold16_kernel / leaf_bytes_ext16_kernel), both hash
+tables (2^12 .. 2^20: both sides of every size threshold of eval_points_wide_kernel / fold_pairs_kernel<4> / leaf_bytes_ext_tile_kernel<H, 4>), both hash
 configurations.  The same instances are proven in two child processes -- one with the new kernels (default), one with OLA_EVAL_WIDE=0
 OLA_FOLD16=0 OLA_LEAF_EXT_STAGED=0 (the switches are read once per process) -- and the proofs must be the same bytes; the oracle's verifier
 accepts the first of each configuration.        usage: python tools/fuzz_openings.py [iterations] [seed]"""

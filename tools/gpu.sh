@@ -112,7 +112,7 @@ for _ in range(4):
 print(os.environ["AB_HASHER"], "wall %.1f ms, quotient kernels %.2f ms, opening evaluations %.2f ms, LDE %.2f ms, leaves %.2f ms" % best)
 PY
                  done 2>&1 | grep -v amdgpu | tee $O/quot.txt ;;
-    openings)    # round 6: eval_points_wide_kernel, fold16_kernel, leaf_bytes_ext16_kernel against the kernels they replace (environment switches, same box, alternating)
+    openings)    # round 6: eval_points_wide_kernel, fold_pairs_kernel<4>, leaf_bytes_ext_tile_kernel<H, 4> against the kernels they replace (environment switches, same box, alternating)
                  for h in blake3 poseidon; do for v in 0 1 0 1; do AB_HASHER=$h OLA_EVAL_WIDE=$v OLA_FOLD16=$v OLA_LEAF_EXT_STAGED=$v timeout 300 python - <<'PY'
 import os, sys
 sys.path.insert(0, ".")
