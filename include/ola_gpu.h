@@ -301,7 +301,7 @@ int32_t ola_table_shape(OlaCtx* ctx, const uint64_t* airset, size_t airset_words
  * the message "Tried to invert zero: table T, permutation batch B ..." (the first such batch), from this call, from
  * ola_prove_single_table and from ola_prove_with_traces alike; the context stays usable.  ola_ctl_z does not report it: it has no
  * permutation challenges and returns no permutation column.  A table without permutation arguments has no Z column here:
- * nothing is written, the call succeeds. */
+ * nothing is written, the call succeeds.  Filters are ola_ctl_z's business: this call does not look at them. */
 int32_t ola_perm_z(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, uint32_t table, uint32_t log_n,
                    const uint64_t* const* trace_cols, const uint64_t* perm_challenges, uint64_t* z_out);
 /* The table's columns of cross_table_lookup_data (cross_table_lookup.rs:224-311), looking sides before looked sides, lookups in

@@ -153,24 +153,15 @@ void check_constraints(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airse
     const bool timing = ctx->timing;
     HAirSet set = parse_airset(airset, airset_words);
     const size_t nt = set.tables.size();
-    const int nch = (int)cfg.num_challenges;
-    if (nch != 2) throw OlaError(OLA_E_INVALID_ARG, "num_challenges must be 2");
+    const int nch = two_challenges(cfg);
     // challenges: a fresh transcript that has observed nothing (include/ola_gpu.h states the order)
     OlaChallenger ch;
     challenger_init(ch, (uint32_t)ctx->hasher);
     std::vector<GpChallenge> ctl_ch;
-    for (int c = 0; c < nch; c++) {
-        const GpChallenge drawn = get_gp(ch);
-        ctl_ch.push_back(ctl_challenges ? GpChallenge{gl_canon(ctl_challenges[2 * c]), gl_canon(ctl_challenges[2 * c + 1])} : drawn);
-    }
-    std::vector<std::vector<std::vector<GpChallenge>>> perm_sets(nt);
-    for (size_t t = 0; t < nt; t++)
-        if (!set.tables[t].perm_pairs.empty())
-            for (int i = 0; i < set.tables[t].permutation_batch_size(); i++) {
-                std::vector<GpChallenge> s;
-                for (int c = 0; c < nch; c++) s.push_back(get_gp(ch));
-                perm_sets[t].push_back(s);
-            }
+    for (int c = 0; c < nch; c++) ctl_ch.push_back(get_gp(ch));
+    if (ctl_challenges) ctl_ch = read_challenges(ctl_challenges, nch);
+    std::vector<PermSets> perm_sets;
+    for (const HTable& air : set.tables) perm_sets.push_back(draw_perm_sets(air, nch, ch));
     const std::vector<std::vector<CtlJob>> jobs = ctl_jobs(set, ctl_ch);
     std::vector<size_t> poffs(nt, 0);
     { size_t p = 0; for (size_t t = 0; t < nt; t++) { poffs[t] = p; p += (size_t)set.tables[t].n_params; } }
@@ -187,7 +178,6 @@ void check_constraints(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airse
         up.add(t, traces[t], 0, dev[t].vals, (uint32_t)set.tables[t].ncols, n_t);
     }
     up.start();
-    std::vector<u64> zero_params(64, 0);
     std::vector<std::vector<u64>> z_last(nt);              // last value of each CTL Z column of a table, in ctl_jobs order
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     struct EvGuard { hipEvent_t& a; hipEvent_t& b; ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev_guard{ev0, ev1};
@@ -210,39 +200,27 @@ void check_constraints(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airse
         // ---- AIR: the table's constraint program on H ----
         const std::vector<int> kinds = emit_kinds(air);
         const size_t K = kinds.size();
-        if (!params && air.n_params > 64) throw OlaError(OLA_E_INVALID_ARG, "params required");
+        const u64* table_params = params_or_zero(params, poffs[t], air);
         unsigned long long* d_rec = (unsigned long long*)tm.alloc(2 * std::max<size_t>(1, K));
         if (timing) HIP_CHECK(hipEventRecord(ev0, ctx->stream));
-        launch_check_constraints(ctx, tm, air, dev[t].vals, n, params ? params + poffs[t] : zero_params.data(), K, d_rec);
+        launch_check_constraints(ctx, tm, air, dev[t].vals, n, table_params, K, d_rec);
         if (timing) HIP_CHECK(hipEventRecord(ev1, ctx->stream));
         HostSpan rec = tm.host(2 * std::max<size_t>(1, K));
         HIP_CHECK(hipMemcpyAsync(rec.data(), d_rec, 2 * std::max<size_t>(1, K) * 8, hipMemcpyDeviceToHost, ctx->stream));
         // ---- PERMUTATION: the running product of num / den over all rows is Z[n-1] num(n-1) / den(n-1) with Z[0] = 1 ----
-        const int nperm = air.num_permutation_batches(nch), bs = air.permutation_batch_size();
+        const PermDesc pd = build_perm_desc(air, perm_sets[t], nch);
+        const int nperm = pd.nperm();
         HostSpan perm_tot = tm.host(std::max(1, nperm));
         u64* tot = tm.alloc(pscan_tot_stride(n) * std::max<size_t>(1, jobs[t].size()));
         if (nperm) {
             u64* tmpcol = tm.alloc(n);
+            u64* d_pd = tm.upload(pd.words);
             // a row with a zero denominator gets the factor 0 (perm_factor_kernel): the batch's product is then 0, not 1, and the
             // batch is reported below like any other failing permutation argument -- the kernel's own flag is not read here
             unsigned* d_zero_den = (unsigned*)tm.alloc(1);
             HIP_CHECK(hipMemsetAsync(d_zero_den, 0xFF, 8, ctx->stream));
-            const int total = (int)air.perm_pairs.size() * nch;
-            int inst = 0;
             for (int b = 0; b < nperm; b++) {
-                std::vector<u64> pd(1, 0);
-                u64 cnt = 0;
-                for (int i = 0; i < bs && inst < total; i++, inst++, cnt++) {
-                    const auto& pair = air.perm_pairs[inst / nch];
-                    const GpChallenge c = perm_sets[t][i][inst % nch];
-                    pd.push_back(c.beta); pd.push_back(c.gamma); pd.push_back(pair.size());
-                    for (auto& pr : pair) { pd.push_back(pr.first); pd.push_back(pr.second); }
-                }
-                pd[0] = cnt;
-                u64* d_pd = tm.upload(pd);
-                hipLaunchKernelGGL(perm_factor_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, dev[t].vals, n, d_pd, tmpcol,
-                                   (unsigned)b, d_zero_den);
-                product_scan_inclusive(ctx, tmpcol, n, tot);
+                perm_z_batch(ctx, dev[t], d_pd + pd.batch_off[b], (unsigned)b, tmpcol, tot, d_zero_den);
                 HIP_CHECK(hipMemcpyAsync(&perm_tot[b], tmpcol + (n - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
             }
         }
@@ -250,28 +228,10 @@ void check_constraints(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airse
         const std::vector<CtlJob>& ctl = jobs[t];
         HostSpan zl = tm.host(std::max<size_t>(1, ctl.size()));
         if (!ctl.empty()) {
-            std::vector<u64> ctl_desc, offs;
-            for (auto& j : ctl) { offs.push_back(ctl_desc.size()); push_ctl_desc(ctl_desc, *j.twc, j.ch.beta, j.ch.gamma); }
-            std::vector<u64> pairs;
-            std::vector<char> taken(ctl.size(), 0);
-            for (size_t a = 0; a < ctl.size(); a++) {
-                if (taken[a]) continue;
-                size_t b = a;
-                for (size_t c = a + 1; c < ctl.size(); c++)
-                    if (!taken[c] && ctl[c].twc == ctl[a].twc) { b = c; break; }
-                taken[a] = taken[b] = 1;
-                pairs.push_back(a); pairs.push_back(b);
-            }
-            const size_t n_offs = offs.size();
-            offs.insert(offs.end(), pairs.begin(), pairs.end());
-            u64* d_cd = tm.upload(ctl_desc);
-            u64* d_offs = tm.upload(offs);
             unsigned* d_bad = (unsigned*)tm.alloc(1);      // a non-binary filter selects nothing here; the AIR section names the cell
             HIP_CHECK(hipMemsetAsync(d_bad, 0, 8, ctx->stream));
             u64* zc = tm.alloc(ctl.size() * n);
-            hipLaunchKernelGGL(ctl_factor_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)(pairs.size() / 2)), dim3(256), 0, ctx->stream,
-                               dev[t].vals, n, d_cd, d_offs, d_offs + n_offs, zc, d_bad);
-            product_scan_inclusive(ctx, zc, n, tot, ctl.size());
+            ctl_z_columns(ctx, tm, dev[t], build_ctl_desc(ctl), zc, tot, d_bad);
             for (size_t j = 0; j < ctl.size(); j++)
                 HIP_CHECK(hipMemcpyAsync(&zl[j], zc + j * n + (n - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
         }

@@ -1275,27 +1275,24 @@ int32_t ola_table_shape(OlaCtx* ctx, const uint64_t* airset, size_t airset_words
     OLA_CATCH
 }
 
-static int32_t ola_zs_phase(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, uint32_t table, uint32_t log_n,
-                            const uint64_t* const* trace_cols, const uint64_t* perm_ch, const uint64_t* ctl_ch, int which, uint64_t* z_out) {
+// ola_perm_z / ola_ctl_z: the same arguments, one step each (stark.hip perm_z_host, ctl_z_host)
+static int32_t ola_z_columns(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, uint32_t table, uint32_t log_n,
+                             const uint64_t* const* trace_cols, const uint64_t* challenges, uint64_t* z_out, decltype(perm_z_host)* step) {
     OLA_TRY
+    require(challenges, "null pointer");
     OLA_ON_DEVICE(ctx);
     require(ctx && airset && trace_cols && z_out, "null pointer");
     require(log_n + ctx->cfg.rate_bits <= 32, "log_n too large");
-    std::vector<u64> cols;
-    phase_zs_host(&ctx->dev, *ctx->tables, ctx->cfg, (const u64*)airset, airset_words, table, log_n, (const u64* const*)trace_cols,
-                  (const u64*)perm_ch, (const u64*)ctl_ch, which, cols);
-    if (!cols.empty()) memcpy(z_out, cols.data(), cols.size() * 8);
+    step(&ctx->dev, ctx->cfg, (const u64*)airset, airset_words, table, log_n, (const u64* const*)trace_cols, (const u64*)challenges, (u64*)z_out);
     OLA_CATCH
 }
 int32_t ola_perm_z(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, uint32_t table, uint32_t log_n,
                    const uint64_t* const* trace_cols, const uint64_t* perm_challenges, uint64_t* z_out) {
-    if (!perm_challenges) { g_last_error = "invalid argument: null pointer"; return OLA_E_INVALID_ARG; }
-    return ola_zs_phase(ctx, airset, airset_words, table, log_n, trace_cols, perm_challenges, nullptr, 0, z_out);
+    return ola_z_columns(ctx, airset, airset_words, table, log_n, trace_cols, perm_challenges, z_out, perm_z_host);
 }
 int32_t ola_ctl_z(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, uint32_t table, uint32_t log_n,
                   const uint64_t* const* trace_cols, const uint64_t* ctl_challenges, uint64_t* z_out) {
-    if (!ctl_challenges) { g_last_error = "invalid argument: null pointer"; return OLA_E_INVALID_ARG; }
-    return ola_zs_phase(ctx, airset, airset_words, table, log_n, trace_cols, nullptr, ctl_challenges, 1, z_out);
+    return ola_z_columns(ctx, airset, airset_words, table, log_n, trace_cols, ctl_challenges, z_out, ctl_z_host);
 }
 
 int32_t ola_quotient(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, uint32_t table, const OlaBatch* trace, const OlaBatch* zs,
@@ -1304,10 +1301,8 @@ int32_t ola_quotient(OlaCtx* ctx, const uint64_t* airset, size_t airset_words, u
     OLA_TRY
     OLA_ON_DEVICE(ctx);
     require(ctx && airset && trace && zs && ctl_challenges && alphas && chunks_out, "null pointer");
-    std::vector<u64> chunks;
-    phase_quotient_host(&ctx->dev, *ctx->tables, ctx->cfg, (const u64*)airset, airset_words, table, *trace, *zs, (const u64*)perm_challenges,
-                        (const u64*)ctl_challenges, (const u64*)alphas, (const u64*)params, chunks);
-    memcpy(chunks_out, chunks.data(), chunks.size() * 8);
+    quotient_host(&ctx->dev, *ctx->tables, ctx->cfg, (const u64*)airset, airset_words, table, *trace, *zs, (const u64*)perm_challenges,
+                  (const u64*)ctl_challenges, (const u64*)alphas, (const u64*)params, (u64*)chunks_out);
     OLA_CATCH
 }
 

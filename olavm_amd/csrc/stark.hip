@@ -404,18 +404,86 @@ static GpChallenge get_gp(OlaChallenger& ch) { const u64 b = challenger_get(ch);
 
 struct CtlJob { const HTwc* twc; GpChallenge ch; };
 
-// Phase-level entry points (ola_perm_z / ola_ctl_z / ola_quotient) run prove_single_table with a tap: challenges come from the
-// caller instead of the transcript, and the function hands back an intermediate result and stops.
-struct PhaseTap {
-    const u64* perm_challenges = nullptr;    // [batch_size][num_challenges][2] (beta, gamma)
-    const u64* alphas = nullptr;             // [num_challenges]
-    const OlaBatch* zs = nullptr;            // the caller's Z commitment (quotient phase: the Z columns are not recomputed)
-    bool perm_wanted = true;                 // false: perm_challenges are stand-ins, the permutation Z columns are thrown away
-    int stop_after = 0;                      // 1: after the Z columns, 2: after the quotient chunks
-    std::vector<u64>* zs_out = nullptr;      // [nz][n] column-major
-    std::vector<u64>* chunks_out = nullptr;  // [num_challenges * q][n] coefficients
-    int nperm = 0, nz = 0, q = 0;
-};
+static int two_challenges(const OlaGpuConfig& cfg) { if (cfg.num_challenges != 2) throw OlaError(OLA_E_INVALID_ARG, "num_challenges must be 2"); return 2; }
+
+// `count` pairs (beta, gamma) as a caller hands them over, [count][2] words: reduced on entry
+static std::vector<GpChallenge> read_challenges(const u64* words, size_t count) {
+    std::vector<GpChallenge> out;
+    for (size_t i = 0; i < count; i++) out.push_back({gl_canon(words[2 * i]), gl_canon(words[2 * i + 1])});
+    return out;
+}
+
+// get_n_grand_product_challenge_sets (prover.rs:360-367): [permutation_batch_size][num_challenges], none for a table without
+// permutation arguments -- from the transcript, or from a caller's words
+using PermSets = std::vector<std::vector<GpChallenge>>;
+static PermSets draw_perm_sets(const HTable& air, int nch, OlaChallenger& ch) {
+    PermSets sets(air.perm_pairs.empty() ? 0 : air.permutation_batch_size());
+    for (auto& s : sets)
+        for (int c = 0; c < nch; c++) s.push_back(get_gp(ch));
+    return sets;
+}
+static PermSets read_perm_sets(const HTable& air, int nch, const u64* words) {
+    PermSets sets(air.perm_pairs.empty() ? 0 : air.permutation_batch_size());
+    for (size_t i = 0; i < sets.size(); i++) sets[i] = read_challenges(words + i * nch * 2, nch);
+    return sets;
+}
+
+// a table's public parameters, or the zero block for a caller that has none to give
+static const u64* params_or_zero(const u64* params, size_t offset, const HTable& air) {
+    static const u64 zero_block[64] = {};
+    if (!params && air.n_params > 64) throw OlaError(OLA_E_INVALID_ARG, "params required");
+    return params ? params + offset : zero_block;
+}
+
+static HAirSet parse_airset_with_table(const u64* airset, size_t airset_words, uint32_t table) {
+    HAirSet set = parse_airset(airset, airset_words);
+    if (table >= set.tables.size()) throw OlaError(OLA_E_INVALID_ARG, "table index out of range");
+    return set;
+}
+
+// ---- descriptors of the Z columns, read by the factor kernels and, inside its own descriptor, by the quotient kernel ----
+// The permutation batches of a table: per batch [instances, then per instance beta, gamma, pairs, (lhs column, rhs column) ...];
+// batch_off[b]: where batch b starts.
+struct PermDesc { std::vector<u64> words; std::vector<size_t> batch_off; int nperm() const { return (int)batch_off.size(); } };
+static PermDesc build_perm_desc(const HTable& air, const PermSets& sets, int nch) {
+    PermDesc d;
+    const int nperm = air.num_permutation_batches(nch), bs = air.permutation_batch_size(), total = (int)air.perm_pairs.size() * nch;
+    int inst = 0;
+    for (int b = 0; b < nperm; b++) {
+        const size_t at = d.words.size();
+        d.batch_off.push_back(at);
+        d.words.push_back(0);
+        u64 cnt = 0;
+        for (int i = 0; i < bs && inst < total; i++, inst++, cnt++) {
+            const auto& pair = air.perm_pairs[inst / nch];
+            const GpChallenge c = sets[i][inst % nch];
+            d.words.push_back(c.beta); d.words.push_back(c.gamma); d.words.push_back(pair.size());
+            for (auto& pr : pair) { d.words.push_back(pr.first); d.words.push_back(pr.second); }
+        }
+        d.words[at] = cnt;
+    }
+    return d;
+}
+
+// The lookup columns of a table: the push_ctl_desc words of its jobs, and what ctl_factor_kernel indexes them by -- index[j] for
+// j < ncols: where job j starts; then the jobs in pairs (a, b).  The columns of one lookup side under the two challenges share
+// their linear combinations, so they are paired; a job without a partner is paired with itself.
+struct CtlDesc { std::vector<u64> words, index; size_t ncols = 0; size_t npairs() const { return (index.size() - ncols) / 2; } };
+static CtlDesc build_ctl_desc(const std::vector<CtlJob>& ctl) {
+    CtlDesc d;
+    d.ncols = ctl.size();
+    for (auto& j : ctl) { d.index.push_back(d.words.size()); push_ctl_desc(d.words, *j.twc, j.ch.beta, j.ch.gamma); }
+    std::vector<char> taken(ctl.size(), 0);
+    for (size_t a = 0; a < ctl.size(); a++) {
+        if (taken[a]) continue;
+        size_t b = a;
+        for (size_t c = a + 1; c < ctl.size(); c++)
+            if (!taken[c] && ctl[c].twc == ctl[a].twc) { b = c; break; }
+        taken[a] = taken[b] = 1;
+        d.index.push_back(a); d.index.push_back(b);
+    }
+    return d;
+}
 
 struct BatchHolder {
     DeviceCtx* ctx;
@@ -464,164 +532,173 @@ static bool table_is_sharded(const DeviceCtx* ctx, const OlaGpuConfig& cfg, cons
     return log_n >= ctx->shard.min_log_n && ctx->shard.log_world <= cfg.rate_bits && ctx->shard.log_world <= cfg.cap_height;
 }
 
-static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, const HTable& air, const DevTable& tv,
-                               const OlaBatch& trace_c, const std::vector<u64>& trace_cap, const std::vector<CtlJob>& ctl,
-                               const u64* params, OlaChallenger& ch, std::vector<uint8_t>& bytes, bool sharded, int table_index,
-                               PhaseTap* tap = nullptr, PowDefer* pow_defer = nullptr) {
-    DevBuf mem(ctx);
-    const int nch = (int)cfg.num_challenges;
-    if (nch != 2) throw OlaError(OLA_E_INVALID_ARG, "num_challenges must be 2");
-    const int degree_bits = (int)tv.log_n;
+// ---- steps of prove_single_table: each takes its memory from the caller's DevBuf and waits for nothing -----------------------
+// host columns -> a table on the device, reduced
+static DevTable upload_table(DeviceCtx* ctx, DevBuf& mem, const u64* const* cols, int ncols, uint32_t log_n) {
+    DevTable tv{nullptr, log_n};
     const size_t n = tv.n();
-    const int rate_bits = (int)cfg.rate_bits;
-    const size_t N = n << rate_bits;
-    const size_t len_cap = (size_t)1 << cfg.cap_height;
+    tv.vals = mem.alloc((size_t)ncols * n);
+    for (int c = 0; c < ncols; c++) HIP_CHECK(hipMemcpyAsync(tv.vals + (size_t)c * n, cols[c], n * 8, hipMemcpyHostToDevice, ctx->stream));
+    canonicalize(ctx, tv.vals, (size_t)ncols * n);
+    return tv;
+}
+
+// What the Z steps find wrong with a trace, left on the device: a non-binary CTL filter, and the first permutation batch with a zero
+// denominator (~0u: none).  The two words travel with the next read-back the host waits for anyway: fetch() after the steps,
+// check() after that wait.  The reference meets the filter first (cross_table_lookup_data runs before any prove_single_table).
+struct ZFlags {
+    unsigned* dev; HostSpan host; int table_index;
+    ZFlags(DeviceCtx* ctx, DevBuf& mem, int table) : dev((unsigned*)mem.alloc(1)), host(mem.host(1)), table_index(table) {
+        HIP_CHECK(hipMemsetAsync(dev, 0, 4, ctx->stream));
+        HIP_CHECK(hipMemsetAsync(dev + 1, 0xFF, 4, ctx->stream));
+    }
+    unsigned* bad_filter() const { return dev; }
+    unsigned* zero_den() const { return dev + 1; }
+    void fetch(DeviceCtx* ctx) const { HIP_CHECK(hipMemcpyAsync(&host[0], dev, 8, hipMemcpyDeviceToHost, ctx->stream)); }
+    void check() const {
+        if ((unsigned)host[0]) throw OlaError(OLA_E_INVALID_ARG, "Non-binary filter?");
+        const unsigned zero_batch = (unsigned)(host[0] >> 32);
+        if (zero_batch != ~0u)
+            throw OlaError(OLA_E_INVALID_ARG, "Tried to invert zero: table " + std::to_string(table_index) + ", permutation batch " +
+                                                  std::to_string(zero_batch) + " has a row whose denominator is zero");
+    }
+};
+
+// One permutation batch (permutation.rs:103-187): num / den of every row, then their running product, in `col`; the batch's Z
+// column is that product moved down one row.  tot: pscan_tot_stride(n) words.
+static void perm_z_batch(DeviceCtx* ctx, const DevTable& tv, const u64* d_batch, unsigned b, u64* col, u64* tot, unsigned* d_zero_den) {
+    const size_t n = tv.n();
+    hipLaunchKernelGGL(perm_factor_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, tv.vals, n, d_batch, col, b, d_zero_den);
+    product_scan_inclusive(ctx, col, n, tot);
+}
+
+// compute_permutation_z_polys: zcols[nperm][n]
+static void perm_z_columns(DeviceCtx* ctx, DevBuf& mem, const DevTable& tv, const PermDesc& pd, u64* zcols, u64* tot, unsigned* d_zero_den) {
+    if (!pd.nperm()) return;
+    const size_t n = tv.n();
+    u64* tmpcol = mem.alloc(n);
+    u64* d_pd = mem.upload(pd.words);
+    for (int b = 0; b < pd.nperm(); b++) {
+        perm_z_batch(ctx, tv, d_pd + pd.batch_off[b], (unsigned)b, tmpcol, tot, d_zero_den);
+        hipLaunchKernelGGL(shift_right_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, tmpcol, zcols + (size_t)b * n, n);
+    }
+}
+
+// The table's columns of cross_table_lookup_data (cross_table_lookup.rs:224-311), zcols[cd.ncols][n]: one launch per step for all
+// of them.  tot: cd.ncols * pscan_tot_stride(n) words.
+static void ctl_z_columns(DeviceCtx* ctx, DevBuf& mem, const DevTable& tv, const CtlDesc& cd, u64* zcols, u64* tot, unsigned* d_bad_filter) {
+    if (!cd.ncols) return;
+    const size_t n = tv.n();
+    u64* d_words = mem.upload(cd.words);
+    u64* d_index = mem.upload(cd.index);
+    hipLaunchKernelGGL(ctl_factor_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)cd.npairs()), dim3(256), 0, ctx->stream, tv.vals, n, d_words,
+                       d_index, d_index + cd.ncols, zcols, d_bad_filter);
+    product_scan_inclusive(ctx, zcols, n, tot, cd.ncols);
+}
+
+// ---- quotient (prover.rs:571-705) ----
+static int quotient_degree_bits(const HTable& air) { int qdb = 0; while ((1 << qdb) < air.quotient_degree_factor()) qdb++; return qdb; }
+
+// what a table's quotient is computed from
+struct QuotientIn {
+    const HTable& air; const OlaBatch &trace_c, &zs_c;
+    const PermSets& perm_sets; const PermDesc& pd; const std::vector<CtlJob>& ctl; const CtlDesc& cd;
+    const u64* params; u64 alpha[2];
+};
+
+// the descriptor quotient_kernel interprets: a header of 18 words, then the constraint program, the permutation and lookup
+// descriptors and the parameters
+static std::vector<u64> quotient_desc(const QuotientIn& in, int degree_bits, int qdb) {
+    std::vector<u64> desc(18, 0);
+    // Z_H(x)^-1 per coset (zero_poly_coset.rs:18-33): x^n = 7^n * v^i, i = natural index mod 2^qdb; coset c <-> i = bitrev
+    u64 g_pow_n = GL_GENERATOR;
+    for (int i = 0; i < degree_bits; i++) g_pow_n = gl_mul(g_pow_n, g_pow_n);
+    const u64 v = gl_root_of_unity(qdb);
+    for (int c = 0; c < (1 << qdb); c++) {
+        const u32 i = bitrev32((u32)c, qdb);
+        desc[10 + c] = gl_inv(gl_sub(gl_mul(g_pow_n, gl_pow(v, i)), 1));
+    }
+    desc[0] = in.air.ops.size() / 2;
+    desc[1] = desc.size();
+    desc.insert(desc.end(), in.air.ops.begin(), in.air.ops.end());
+    desc[2] = (u64)in.pd.nperm();
+    desc[3] = desc.size();
+    desc.insert(desc.end(), in.pd.words.begin(), in.pd.words.end());
+    desc[4] = in.ctl.size();
+    desc[5] = desc.size();
+    desc.insert(desc.end(), in.cd.words.begin(), in.cd.words.end());
+    desc[6] = (u64)in.air.n_params;
+    desc[7] = desc.size();
+    for (int i = 0; i < in.air.n_params; i++) desc.push_back(gl_canon(in.params[i]));
+    desc[8] = in.alpha[0]; desc[9] = in.alpha[1];
+    return desc;
+}
+
+// the descriptor of a specialised kernel (airq.cuh): Z_H^-1 per coset, the alpha powers of its emits, the parameters, the challenges
+// in the kernel's own order, then the limb forms of the uniform multipliers
+static std::vector<u64> spec_quotient_desc(const QuotientIn& in, const AirKernelEntry& spec, const std::vector<u64>& desc, int qdb, int nch) {
+    const int K = spec.n_emits, bs = in.air.permutation_batch_size();
+    std::vector<u64> sd(8 + 2 * (size_t)K, 0);
+    for (int c = 0; c < (1 << qdb); c++) sd[c] = desc[10 + c];
+    for (int c = 0; c < 2; c++) {
+        u64 w = 1;
+        for (int i = K - 1; i >= 0; i--) { sd[8 + (size_t)c * K + i] = w; w = gl_mul(w, in.alpha[c]); }
+    }
+    for (int i = 0; i < in.air.n_params; i++) sd.push_back(gl_canon(in.params[i]));
+    for (int b = 0; b < in.pd.nperm(); b++)
+        for (int i = 0; i < bs; i++)
+            for (int k = 0; k < 2; k++) {
+                const int inst = b * bs + i;
+                const bool live = inst < (int)in.air.perm_pairs.size() * nch;
+                sd.push_back(live ? (k ? in.perm_sets[i][inst % nch].gamma : in.perm_sets[i][inst % nch].beta) : 0);
+            }
+    for (auto& jb : in.ctl) {
+        sd.push_back(jb.ch.gamma);
+        u64 bp = 1;
+        for (size_t k = 0; k < jb.twc->columns.size(); k++) { sd.push_back(bp); bp = gl_mul(bp, jb.ch.beta); }
+    }
+    // limb forms of the uniform multipliers (airq.cuh Acc3), one slot per use in the kernel's own order
+    auto push_limbs = [&sd](u64 w) {
+        w = gl_canon(w);
+        const u64 v = gl_mul(w, (u64)1 << 32), M = 0x3FFFFF;
+        sd.push_back((w & M) | (((w >> 22) & M) << 32));
+        sd.push_back((w >> 44) | ((v & M) << 32));
+        sd.push_back(((v >> 22) & M) | ((v >> 44) << 32));
+    };
+    const size_t u64_words = sd.size();
+    sd.reserve(u64_words + 3 * (size_t)spec.n_limbs);
+    for (int sl = 0; sl < spec.n_limbs; sl++) {
+        if ((size_t)spec.limb_src[sl] >= u64_words) throw OlaError(OLA_E_INVALID_ARG, "generated kernel and descriptor disagree");
+        push_limbs(sd[(size_t)spec.limb_src[sl]]);
+    }
+    return sd;
+}
+
+// The two quotient polynomials as coefficients over the 2^qdb-coset domain; of each only the first n * q may be non-zero, which
+// the device has looked at: check() after the next wait of the host.
+struct QuotientPolys {
+    u64* coef; size_t n, size; int q;
+    HostSpan too_high; const DeviceCtx* ctx;
+    void check() const {
+#ifndef AIRQ_TIMING_ONLY_L2_LOADS      // (timing builds of airq.cuh's experiment produce garbage on purpose)
+        if ((unsigned)too_high[0] && !ctx->priming) throw OlaError(OLA_E_QUOTIENT_DEGREE, "Quotient has failed, the vanishing polynomial is not divisible by Z_H");
+#endif
+    }
+};
+
+// compute_quotient_polys: the constraints on the LDE domain -- all of it, this rank's cosets (sharded) or coset by coset (a
+// memory-lean table) --, then back to coefficients
+static QuotientPolys quotient_polys(DeviceCtx* ctx, DevBuf& mem, NttTables& tables, const OlaGpuConfig& cfg, const QuotientIn& in, bool sharded) {
+    const HTable& air = in.air;
+    const OlaBatch &trace_c = in.trace_c, &zs_c = in.zs_c;
+    const int degree_bits = (int)trace_c.log_n, rate_bits = (int)cfg.rate_bits;
+    const size_t n = (size_t)1 << degree_bits, N = n << rate_bits;
+    const bool lean = trace_c.lean;
     // this rank's part of the LDE domain (everything when not sharded)
     const uint32_t log_world = sharded ? ctx->shard.log_world : 0;
     const size_t coset_count = ((size_t)1 << rate_bits) >> log_world, coset_first = sharded ? ctx->shard.rank * coset_count : 0;
     const size_t N_loc = n * coset_count;
-
-    challenger_compact(ch);
-    // ---- permutation challenges + Z polys (prover.rs:360-377) ----
-    const int nperm = air.num_permutation_batches(nch);
-    const int bs = air.permutation_batch_size();
-    std::vector<std::vector<GpChallenge>> perm_sets;
-    if (!air.perm_pairs.empty())
-        for (int i = 0; i < bs; i++) {
-            std::vector<GpChallenge> s;
-            for (int c = 0; c < nch; c++) {
-                if (tap && tap->perm_challenges) s.push_back({gl_canon(tap->perm_challenges[(i * nch + c) * 2]), gl_canon(tap->perm_challenges[(i * nch + c) * 2 + 1])});
-                else s.push_back(get_gp(ch));
-            }
-            perm_sets.push_back(s);
-        }
-    const bool have_zs = tap && tap->zs;     // quotient phase on a caller-held Z commitment: descriptors only
-    const int nz = nperm + (int)ctl.size();
-    if (nz == 0) throw OlaError(OLA_E_INVALID_ARG, "No CTL?");
-    // OLA_TIMING scopes carry the reference's `timed!` names (prover.rs:374-544)
-    // (the reference times only the permutation Z's, and only for tables that have permutation arguments, prover.rs:371-377; its
-    // CTL Z's are computed untimed in cross_table_lookup_data, cross_table_lookup.rs:224-311 -- here both happen in this scope)
-    std::unique_ptr<PhaseTimer> ph(new PhaseTimer(ctx, nperm > 0 ? "    compute permutation Z(x) polys" : "    compute CTL Z(x) polys"));
-    u64* zvals = mem.alloc((size_t)nz * n);
-    u64* tot = mem.alloc(pscan_tot_stride(n) * std::max<size_t>(1, ctl.size()));
-    u64* tmpcol = mem.alloc(n);
-    // perm descriptors (also reused by the quotient kernel)
-    std::vector<u64> perm_desc;
-    {
-        const int total = (int)air.perm_pairs.size() * nch;
-        int inst = 0;
-        for (int b = 0; b < nperm; b++) {
-            const size_t at = perm_desc.size();
-            perm_desc.push_back(0);
-            u64 cnt = 0;
-            for (int i = 0; i < bs && inst < total; i++, inst++, cnt++) {
-                const auto& pair = air.perm_pairs[inst / nch];
-                const GpChallenge c = perm_sets[i][inst % nch];
-                perm_desc.push_back(c.beta); perm_desc.push_back(c.gamma); perm_desc.push_back(pair.size());
-                for (auto& pr : pair) { perm_desc.push_back(pr.first); perm_desc.push_back(pr.second); }
-            }
-            perm_desc[at] = cnt;
-        }
-    }
-    // two device flags: [0] a non-binary CTL filter, [1] the first permutation batch with a zero denominator (~0u: none)
-    unsigned* d_flags = (unsigned*)mem.alloc(1);
-    unsigned* d_bad_filter = d_flags;
-    HIP_CHECK(hipMemsetAsync(d_flags, 0, 4, ctx->stream));
-    HIP_CHECK(hipMemsetAsync(d_flags + 1, 0xFF, 4, ctx->stream));
-    if (nperm && !have_zs) {
-        u64* d_pd = mem.alloc(perm_desc.size());
-        HIP_CHECK(hipMemcpyAsync(d_pd, perm_desc.data(), perm_desc.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-        // offsets of each batch descriptor
-        size_t off = 0;
-        for (int b = 0; b < nperm; b++) {
-            hipLaunchKernelGGL(perm_factor_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, tv.vals, n, d_pd + off, tmpcol,
-                               (unsigned)b, d_flags + 1);
-            product_scan_inclusive(ctx, tmpcol, n, tot);
-            hipLaunchKernelGGL(shift_right_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, tmpcol, zvals + (size_t)b * n, n);
-            // advance to the next batch descriptor
-            const u64 cnt = perm_desc[off];
-            size_t p = off + 1;
-            for (u64 s = 0; s < cnt; s++) { const u64 np = perm_desc[p + 2]; p += 3 + 2 * np; }
-            off = p;
-        }
-    }
-    // ---- CTL Z polys (cross_table_lookup.rs:224-311) ----
-    std::vector<u64> ctl_desc;
-    std::vector<size_t> ctl_off;
-    for (auto& j : ctl) { ctl_off.push_back(ctl_desc.size()); push_ctl_desc(ctl_desc, *j.twc, j.ch.beta, j.ch.gamma); }
-    u64* d_cd = mem.alloc(ctl_desc.size() + 1);
-    if (!ctl_desc.empty()) HIP_CHECK(hipMemcpyAsync(d_cd, ctl_desc.data(), ctl_desc.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (!ctl.empty() && !have_zs) {   // all CTL Z columns of the table in one launch per step
-        std::vector<u64> offs(ctl_off.begin(), ctl_off.end());
-        // the columns of one lookup side under the two challenges share their linear combinations: pair them (ctl_factor_kernel)
-        std::vector<u64> pairs;
-        {
-            std::vector<char> taken(ctl.size(), 0);
-            for (size_t a = 0; a < ctl.size(); a++) {
-                if (taken[a]) continue;
-                size_t b = a;
-                for (size_t c = a + 1; c < ctl.size(); c++)
-                    if (!taken[c] && ctl[c].twc == ctl[a].twc) { b = c; break; }
-                taken[a] = taken[b] = 1;
-                pairs.push_back(a); pairs.push_back(b);
-            }
-        }
-        offs.insert(offs.end(), pairs.begin(), pairs.end());
-        u64* d_offs = mem.upload(offs);                  // staged in the scope's keep-alive list: no synchronisation for its sake
-        u64* d_pairs = d_offs + ctl_off.size();
-        u64* zc = zvals + (size_t)nperm * n;
-        hipLaunchKernelGGL(ctl_factor_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)(pairs.size() / 2)), dim3(256), 0, ctx->stream, tv.vals, n, d_cd,
-                           d_offs, d_pairs, zc, d_bad_filter);
-        product_scan_inclusive(ctx, zc, n, tot, ctl.size());
-    }
-    // the two flags travel with the next read-back the host waits for anyway (the Z commitment's cap)
-    HostSpan h_flags = mem.host(2);
-    h_flags[0] = h_flags[1] = 0;
-    const bool check_filter = !ctl.empty() && !have_zs;
-    const bool check_den = nperm && !have_zs && (!tap || tap->perm_wanted);
-    if (check_filter || check_den) HIP_CHECK(hipMemcpyAsync(&h_flags[0], d_flags, 8, hipMemcpyDeviceToHost, ctx->stream));
-    // call after the wait.  The reference meets the filter first (cross_table_lookup_data runs before any prove_single_table)
-    auto check_z_flags = [&] {
-        if (check_filter && (unsigned)h_flags[0]) throw OlaError(OLA_E_INVALID_ARG, "Non-binary filter?");
-        const unsigned zero_batch = (unsigned)(h_flags[0] >> 32);
-        if (check_den && zero_batch != ~0u)
-            throw OlaError(OLA_E_INVALID_ARG, "Tried to invert zero: table " + std::to_string(table_index) + ", permutation batch " +
-                                                  std::to_string(zero_batch) + " has a row whose denominator is zero");
-    };
-    if (tap) { tap->nperm = nperm; tap->nz = nz; tap->q = air.quotient_degree_factor(); }
-    if (tap && tap->stop_after == 1) {
-        tap->zs_out->resize((size_t)nz * n);
-        HIP_CHECK(hipMemcpyAsync(tap->zs_out->data(), zvals, (size_t)nz * n * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        check_z_flags();
-        return;
-    }
-    // ---- Zs commitment ----
-    ph.reset();
-    ph.reset(new PhaseTimer(ctx, "    compute Zs commitment"));
-    struct ZsRef { BatchHolder own; const OlaBatch* b = nullptr; explicit ZsRef(DeviceCtx* c) : own(c) {} } zs_c(ctx);
-    std::vector<u64> zs_cap;
-    const bool lean = trace_c.lean;   // the table is proven memory-lean: no LDE of its three batches is kept
-    if (lean && sharded) throw OlaError(OLA_E_INTERNAL, "a memory-lean table cannot be on the coset partition");
-    if (have_zs) {
-        if (tap->zs->ncols != (uint32_t)nz || tap->zs->log_n != (uint32_t)degree_bits || tap->zs->lean != lean || tap->zs->is_shard())
-            throw OlaError(OLA_E_INVALID_ARG, "Z commitment does not match the table");
-        zs_c.b = tap->zs;
-    } else {
-        zs_c.own.b = commit_shared(ctx, tables, zvals, (uint32_t)nz, (uint32_t)degree_bits, cfg, true, sharded, nullptr, zs_cap, lean);
-        zs_c.b = zs_c.own.b;
-        check_z_flags();                                 // commit_shared has waited for the cap
-        challenger_observe_cap(ch, zs_cap.data(), zs_cap.size() / 4);
-    }
-    const u64 alpha0 = (tap && tap->alphas) ? gl_canon(tap->alphas[0]) : challenger_get(ch);
-    const u64 alpha1 = (tap && tap->alphas) ? gl_canon(tap->alphas[1]) : challenger_get(ch);
-
-    // ---- quotient (prover.rs:571-705) ----
-    ph.reset();
-    ph.reset(new PhaseTimer(ctx, "    compute quotient polys"));
-    const int q = air.quotient_degree_factor();
-    int qdb = 0;
-    while ((1 << qdb) < q) qdb++;
+    const int q = air.quotient_degree_factor(), qdb = quotient_degree_bits(air);
     if (qdb > rate_bits) throw OlaError(OLA_E_INVALID_ARG, "Having constraints of degree higher than the rate is not supported yet.");
     const size_t size = n << qdb;
     // Lagrange first/last on the LDE domain (leaf order)
@@ -634,33 +711,8 @@ static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuCo
         WorkScope ws(ctx, rate_bits);
         if (!lean) ntt_lde_leaf_order(tables, lag_coef, lag_lde, degree_bits, rate_bits, 2, coset_first, coset_count);
     }
-    // descriptor for the kernel
-    std::vector<u64> desc(18, 0);
-    {
-        // Z_H(x)^-1 per coset (zero_poly_coset.rs:18-33): x^n = 7^n * v^i, i = natural index mod 2^qdb; coset c <-> i = bitrev
-        u64 g_pow_n = GL_GENERATOR;
-        for (int i = 0; i < degree_bits; i++) g_pow_n = gl_mul(g_pow_n, g_pow_n);
-        const u64 v = gl_root_of_unity(qdb);
-        for (int c = 0; c < (1 << qdb); c++) {
-            const u32 i = bitrev32((u32)c, qdb);
-            desc[10 + c] = gl_inv(gl_sub(gl_mul(g_pow_n, gl_pow(v, i)), 1));
-        }
-        desc[0] = air.ops.size() / 2;
-        desc[1] = desc.size();
-        desc.insert(desc.end(), air.ops.begin(), air.ops.end());
-        desc[2] = (u64)nperm;
-        desc[3] = desc.size();
-        desc.insert(desc.end(), perm_desc.begin(), perm_desc.end());
-        desc[4] = ctl.size();
-        desc[5] = desc.size();
-        desc.insert(desc.end(), ctl_desc.begin(), ctl_desc.end());
-        desc[6] = (u64)air.n_params;
-        desc[7] = desc.size();
-        for (int i = 0; i < air.n_params; i++) desc.push_back(gl_canon(params[i]));
-        desc[8] = alpha0; desc[9] = alpha1;
-    }
-    u64* d_desc = mem.alloc(desc.size());
-    HIP_CHECK(hipMemcpyAsync(d_desc, desc.data(), desc.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    const std::vector<u64> desc = quotient_desc(in, degree_bits, qdb);
+    u64* d_desc = mem.upload(desc);
     u64* qv = mem.alloc(2 * size);
     // points this rank evaluates: the whole quotient domain, or (sharded) those of its cosets that belong to the quotient
     // domain -- the first 2^qdb cosets of the leaf order; a rank that owns none of them only takes part in the exchange
@@ -670,7 +722,7 @@ static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuCo
     const size_t my_q_cosets = !sharded ? q_cosets : (coset_first >= q_cosets ? 0 : std::min(coset_count, q_cosets - coset_first));
     {
         QuotParams P = {};
-        P.trace_lde = trace_c.lde; P.zs_lde = zs_c.b->lde; P.lag_lde = lag_lde;
+        P.trace_lde = trace_c.lde; P.zs_lde = zs_c.lde; P.lag_lde = lag_lde;
         P.N = N_loc; P.n = n; P.log_n = degree_bits; P.log_N = degree_bits + rate_bits; P.qdb = qdb;
         P.coset_first = (u32)coset_first; P.out_plane = plane;
         TwoLevel gN = get_two(tables, degree_bits + rate_bits, 0);
@@ -683,7 +735,7 @@ static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuCo
         const char* mode = getenv("OLA_AIR_KERNELS");
         const bool force_interp = mode && !strcmp(mode, "interpreter"), crosscheck = mode && !strcmp(mode, "crosscheck");
         std::vector<const HTwc*> twcs;
-        for (auto& jb : ctl) twcs.push_back(jb.twc);
+        for (auto& jb : in.ctl) twcs.push_back(jb.twc);
         // the specialised kernels address rows as "workgroup base + lane": workgroups of min(AIRQ_THREADS, n) threads (airq.cuh)
         const AirKernelEntry* spec = force_interp ? nullptr : find_air_kernel(air_signature(air, twcs));
         const unsigned spec_bs = (unsigned)std::min<size_t>(AIRQ_THREADS, n);
@@ -693,55 +745,16 @@ static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuCo
         const size_t lean_cosets = lean ? ((size_t)1 << qdb) : 1;
         if (lean) {
             slice_t = mem.alloc((size_t)trace_c.ncols * n);
-            slice_z = mem.alloc((size_t)zs_c.b->ncols * n);
+            slice_z = mem.alloc((size_t)zs_c.ncols * n);
             P.trace_lde = slice_t; P.zs_lde = slice_z; P.N = n; P.npoints = n;
         }
-        u64* d_sd = nullptr;
-        int K = 0;
-        if (spec) {
-            K = spec->n_emits;
-            std::vector<u64> sd(8 + 2 * (size_t)K, 0);
-            for (int c = 0; c < (1 << qdb); c++) sd[c] = desc[10 + c];
-            const u64 al[2] = {alpha0, alpha1};
-            for (int c = 0; c < 2; c++) {
-                u64 w = 1;
-                for (int i = K - 1; i >= 0; i--) { sd[8 + (size_t)c * K + i] = w; w = gl_mul(w, al[c]); }
-            }
-            for (int i = 0; i < air.n_params; i++) sd.push_back(gl_canon(params[i]));
-            for (int b = 0; b < nperm; b++)
-                for (int i = 0; i < bs; i++)
-                    for (int k = 0; k < 2; k++) {
-                        const int inst = b * bs + i;
-                        const bool live = inst < (int)air.perm_pairs.size() * nch;
-                        sd.push_back(live ? (k ? perm_sets[i][inst % nch].gamma : perm_sets[i][inst % nch].beta) : 0);
-                    }
-            for (auto& jb : ctl) {
-                sd.push_back(jb.ch.gamma);
-                u64 bp = 1;
-                for (size_t k = 0; k < jb.twc->columns.size(); k++) { sd.push_back(bp); bp = gl_mul(bp, jb.ch.beta); }
-            }
-            // limb forms of the uniform multipliers (airq.cuh Acc3), one slot per use in the kernel's own order
-            auto push_limbs = [&sd](u64 w) {
-                w = gl_canon(w);
-                const u64 v = gl_mul(w, (u64)1 << 32), M = 0x3FFFFF;
-                sd.push_back((w & M) | (((w >> 22) & M) << 32));
-                sd.push_back((w >> 44) | ((v & M) << 32));
-                sd.push_back(((v >> 22) & M) | ((v >> 44) << 32));
-            };
-            const size_t u64_words = sd.size();
-            sd.reserve(u64_words + 3 * (size_t)spec->n_limbs);
-            for (int sl = 0; sl < spec->n_limbs; sl++) {
-                if ((size_t)spec->limb_src[sl] >= u64_words) throw OlaError(OLA_E_INVALID_ARG, "generated kernel and descriptor disagree");
-                push_limbs(sd[(size_t)spec->limb_src[sl]]);
-            }
-            d_sd = mem.upload(sd);
-        }
+        u64* d_sd = spec ? mem.upload(spec_quotient_desc(in, *spec, desc, qdb, (int)cfg.num_challenges)) : nullptr;
         u64* qv2 = (spec && crosscheck) ? mem.alloc(2 * plane) : nullptr;
         WorkScope ws(ctx, qdb);   // the quotient lives on 2^qdb cosets: that many ranks share it
         // units: LDE points evaluated; bytes a point streams -- local and next row of the trace and Z batches, two planes written
         // (quotient row streaming is priced against HBM)
         const double q_points = (double)(sharded ? my_q_cosets * n : size);
-        PhaseScope phq(ctx, PH_QUOTIENT, q_points, q_points * (8.0 * 2 * ((double)trace_c.ncols + (double)zs_c.b->ncols) + 16.0));
+        PhaseScope phq(ctx, PH_QUOTIENT, q_points, q_points * (8.0 * 2 * ((double)trace_c.ncols + (double)zs_c.ncols) + 16.0));
         if (!sharded && ctx->acct.shardable) { acct_exchange(ctx, N * 8); acct_exchange(ctx, N * 8); }   // the two planes a partitioned run gathers
         for (size_t lc = 0; lc < lean_cosets; lc++) {
             u64* out = qloc;
@@ -749,7 +762,7 @@ static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuCo
             if (sharded) { P.npoints = points; if (points == 0) break; }
             if (lean) {
                 batch_lde_slice(ctx, tables, trace_c, lc, slice_t);
-                batch_lde_slice(ctx, tables, *zs_c.b, lc, slice_z);
+                batch_lde_slice(ctx, tables, zs_c, lc, slice_z);
                 ntt_lde_leaf_order(tables, lag_coef, lag_lde, degree_bits, rate_bits, 2, lc, 1);
                 P.coset_first = (u32)lc;
                 out = qloc + lc * n;
@@ -802,45 +815,80 @@ static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuCo
     // qv is in bit-reversed order of the size-domain: un-reverse, coset iNTT (prover.rs:700-704)
     const int size_bits = degree_bits + qdb;
     u64* qnat = mem.alloc(2 * size);
-    u64* qcoef = mem.alloc(2 * size);
+    QuotientPolys qp = {mem.alloc(2 * size), n, size, q, mem.host(1), ctx};
     u64* qscratch = size_bits > 13 ? mem.alloc(2 * size) : nullptr;
     launch_bitrev_rows(ctx, qv, qnat, size_bits, 2);
-    ntt_coset_interpolate(tables, qnat, qcoef, qscratch, size_bits, 2, GL_GENERATOR);
-    // trim_to_len(n*q) (prover.rs:469-473)
+    ntt_coset_interpolate(tables, qnat, qp.coef, qscratch, size_bits, 2, GL_GENERATOR);
+    // trim_to_len(n*q) (prover.rs:469-473): nothing may be left above
+    qp.too_high[0] = 0;
     const size_t keep = n * (size_t)q;
     if (keep < size) {
         unsigned* d_flag = (unsigned*)mem.alloc(1);
         HIP_CHECK(hipMemsetAsync(d_flag, 0, 8, ctx->stream));
         for (int c = 0; c < 2; c++)
-            hipLaunchKernelGGL(any_nonzero_kernel, dim3((unsigned)((size - keep + 255) / 256)), dim3(256), 0, ctx->stream, qcoef + (size_t)c * size,
+            hipLaunchKernelGGL(any_nonzero_kernel, dim3((unsigned)((size - keep + 255) / 256)), dim3(256), 0, ctx->stream, qp.coef + (size_t)c * size,
                                keep, size, d_flag);
-        // read with the next read-back the host waits for (the quotient commitment's cap, or the tap's copy): no wait of its own
-        HIP_CHECK(hipMemcpyAsync(&h_flags[1], d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+        // read with the next read-back the host waits for (the quotient commitment's cap, or an entry point's copy): no wait of its own
+        HIP_CHECK(hipMemcpyAsync(&qp.too_high[0], d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
     }
-    auto check_degree = [&] {
-#ifndef AIRQ_TIMING_ONLY_L2_LOADS      // (timing builds of airq.cuh's experiment produce garbage on purpose)
-        if ((unsigned)h_flags[1] && !ctx->priming) throw OlaError(OLA_E_QUOTIENT_DEGREE, "Quotient has failed, the vanishing polynomial is not divisible by Z_H");
-#endif
-    };
-    // chunks of n coefficients: [challenge][k] -> column challenge*q + k
-    ph.reset();
-    ph.reset(new PhaseTimer(ctx, "    split quotient polys"));
-    u64* chunks = mem.alloc((size_t)2 * q * n);
+    return qp;
+}
+
+// chunks of n coefficients: [challenge][k] -> column challenge * q + k
+static u64* split_quotient(DeviceCtx* ctx, DevBuf& mem, const QuotientPolys& qp) {
+    const size_t keep = qp.n * (size_t)qp.q;
+    u64* chunks = mem.alloc(2 * keep);
     for (int c = 0; c < 2; c++)
-        HIP_CHECK(hipMemcpyAsync(chunks + (size_t)c * q * n, qcoef + (size_t)c * size, keep * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    if (tap && tap->stop_after == 2) {
-        tap->chunks_out->resize((size_t)2 * q * n);
-        HIP_CHECK(hipMemcpyAsync(tap->chunks_out->data(), chunks, (size_t)2 * q * n * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        check_degree();
-        return;
-    }
-    ph.reset();
-    ph.reset(new PhaseTimer(ctx, "    compute quotient commitment"));
+        HIP_CHECK(hipMemcpyAsync(chunks + (size_t)c * keep, qp.coef + (size_t)c * qp.size, keep * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    return chunks;
+}
+
+// prove_single_table (prover.rs:330-567): the transcript, and the steps above between its draws and observations
+static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, const HTable& air, const DevTable& tv,
+                               const OlaBatch& trace_c, const std::vector<u64>& trace_cap, const std::vector<CtlJob>& ctl,
+                               const u64* params, OlaChallenger& ch, std::vector<uint8_t>& bytes, bool sharded, int table_index,
+                               PowDefer* pow_defer = nullptr) {
+    DevBuf mem(ctx);
+    const int nch = two_challenges(cfg);
+    const size_t n = tv.n();
+    challenger_compact(ch);
+    // ---- permutation challenges + Z polys (prover.rs:360-377) ----
+    const PermSets perm_sets = draw_perm_sets(air, nch, ch);
+    const PermDesc pd = build_perm_desc(air, perm_sets, nch);
+    const CtlDesc cd = build_ctl_desc(ctl);
+    const int nperm = pd.nperm(), nz = nperm + (int)ctl.size();
+    if (nz == 0) throw OlaError(OLA_E_INVALID_ARG, "No CTL?");
+    // OLA_TIMING scopes carry the reference's `timed!` names (prover.rs:374-544)
+    // (the reference times only the permutation Z's, and only for tables that have permutation arguments, prover.rs:371-377; its
+    // CTL Z's are computed untimed in cross_table_lookup_data, cross_table_lookup.rs:224-311 -- here both happen in this scope)
+    std::unique_ptr<PhaseTimer> ph(new PhaseTimer(ctx, nperm > 0 ? "    compute permutation Z(x) polys" : "    compute CTL Z(x) polys"));
+    u64* zvals = mem.alloc((size_t)nz * n);
+    u64* tot = mem.alloc(pscan_tot_stride(n) * std::max<size_t>(1, ctl.size()));
+    const ZFlags zf(ctx, mem, table_index);
+    perm_z_columns(ctx, mem, tv, pd, zvals, tot, zf.zero_den());
+    ctl_z_columns(ctx, mem, tv, cd, zvals + (size_t)nperm * n, tot, zf.bad_filter());
+    zf.fetch(ctx);
+    // ---- Zs commitment ----
+    ph.reset(); ph.reset(new PhaseTimer(ctx, "    compute Zs commitment"));
+    const bool lean = trace_c.lean;   // the table is proven memory-lean: no LDE of its three batches is kept
+    if (lean && sharded) throw OlaError(OLA_E_INTERNAL, "a memory-lean table cannot be on the coset partition");
+    BatchHolder zs_c(ctx);
+    std::vector<u64> zs_cap;
+    zs_c.b = commit_shared(ctx, tables, zvals, (uint32_t)nz, tv.log_n, cfg, true, sharded, nullptr, zs_cap, lean);
+    zf.check();                                          // commit_shared has waited for the cap
+    challenger_observe_cap(ch, zs_cap.data(), zs_cap.size() / 4);
+    const u64 alpha0 = challenger_get(ch), alpha1 = challenger_get(ch);
+
+    ph.reset(); ph.reset(new PhaseTimer(ctx, "    compute quotient polys"));
+    const QuotientIn qin = {air, trace_c, *zs_c.b, perm_sets, pd, ctl, cd, params, {alpha0, alpha1}};
+    const QuotientPolys qp = quotient_polys(ctx, mem, tables, cfg, qin, sharded);
+    ph.reset(); ph.reset(new PhaseTimer(ctx, "    split quotient polys"));
+    u64* chunks = split_quotient(ctx, mem, qp);
+    ph.reset(); ph.reset(new PhaseTimer(ctx, "    compute quotient commitment"));
     BatchHolder q_c(ctx);
     std::vector<u64> q_cap;
-    q_c.b = commit_shared(ctx, tables, chunks, (uint32_t)(2 * q), (uint32_t)degree_bits, cfg, false, sharded, nullptr, q_cap, lean);
-    check_degree();                                      // commit_shared has waited for the cap
+    q_c.b = commit_shared(ctx, tables, chunks, (uint32_t)(2 * qp.q), tv.log_n, cfg, false, sharded, nullptr, q_cap, lean);
+    qp.check();                                          // commit_shared has waited for the cap
     challenger_observe_cap(ch, q_cap.data(), q_cap.size() / 4);
 
     // ---- write_proof (serialization.rs:349-358): caps, then opening set + FRI proof ----
@@ -849,8 +897,7 @@ static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuCo
     write_cap(w, zs_cap);
     write_cap(w, q_cap);
     size_t olen = 0;
-    ph.reset();
-    ph.reset(new PhaseTimer(ctx, "    compute openings proof"));
+    ph.reset(); ph.reset(new PhaseTimer(ctx, "    compute openings proof"));
     open_and_prove(ctx, tables, cfg, trace_c, *zs_c.b, *q_c.b, (uint32_t)nperm, ch, bytes, olen, pow_defer);
 }
 
@@ -870,27 +917,15 @@ static std::vector<std::vector<CtlJob>> ctl_jobs(const HAirSet& set, const std::
 void prove_single_table_host(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, const u64* airset, size_t airset_words,
                              uint32_t table, const u64* const* trace_cols, const OlaBatch& trace_c, const u64* trace_cap,
                              const u64* ctl_challenges, const u64* params, OlaChallenger& ch, std::vector<uint8_t>& bytes) {
-    HAirSet set = parse_airset(airset, airset_words);
-    if (table >= set.tables.size()) throw OlaError(OLA_E_INVALID_ARG, "table index out of range");
+    const HAirSet set = parse_airset_with_table(airset, airset_words, table);
     if (ctx->shard.world != 1) throw OlaError(OLA_E_INVALID_ARG, "per-table proving needs an unsharded context");
     const HTable& air = set.tables[table];
     if (trace_c.ncols != (uint32_t)air.ncols || trace_c.is_shard()) throw OlaError(OLA_E_INVALID_ARG, "trace commitment does not match the table");
-    std::vector<GpChallenge> ctl_ch;
-    for (uint32_t c = 0; c < cfg.num_challenges; c++) ctl_ch.push_back({gl_canon(ctl_challenges[2 * c]), gl_canon(ctl_challenges[2 * c + 1])});
-    const std::vector<std::vector<CtlJob>> jobs = ctl_jobs(set, ctl_ch);
+    const std::vector<std::vector<CtlJob>> jobs = ctl_jobs(set, read_challenges(ctl_challenges, cfg.num_challenges));
     DevBuf mem(ctx);
-    DevTable tv;
-    tv.log_n = trace_c.log_n;
-    const size_t n = tv.n();
-    tv.vals = mem.alloc((size_t)air.ncols * n);
-    for (int c = 0; c < air.ncols; c++)
-        HIP_CHECK(hipMemcpyAsync(tv.vals + (size_t)c * n, trace_cols[c], n * 8, hipMemcpyHostToDevice, ctx->stream));
-    canonicalize(ctx, tv.vals, (size_t)air.ncols * n);
-    const size_t len_cap = (size_t)1 << cfg.cap_height;
-    const std::vector<u64> cap(trace_cap, trace_cap + 4 * len_cap);
-    std::vector<u64> zero_params(64, 0);
-    if (!params && air.n_params > 64) throw OlaError(OLA_E_INVALID_ARG, "params required");
-    prove_single_table(ctx, tables, cfg, air, tv, trace_c, cap, jobs[table], params ? params : zero_params.data(), ch, bytes, false, (int)table);
+    const DevTable tv = upload_table(ctx, mem, trace_cols, air.ncols, trace_c.log_n);
+    const std::vector<u64> cap(trace_cap, trace_cap + 4 * ((size_t)1 << cfg.cap_height));
+    prove_single_table(ctx, tables, cfg, air, tv, trace_c, cap, jobs[table], params_or_zero(params, 0, air), ch, bytes, false, (int)table);
 }
 
 // Widths of a table's three batches (trace, Z, quotient chunks)
@@ -901,16 +936,14 @@ static TableWidths table_widths(const HAirSet& set, size_t t, int nch) {
     for (const HCtl& c : set.ctls) { for (const HTwc& w2 : c.looking) nctl += ((size_t)w2.table == t) ? nch : 0; nctl += ((size_t)c.looked.table == t) ? nch : 0; }
     TableWidths r;
     r.w = (size_t)air.ncols; r.wz = air.num_permutation_batches(nch) + nctl; r.wq = (size_t)nch * air.quotient_degree_factor();
-    r.qdb = 0;
-    while ((1 << r.qdb) < air.quotient_degree_factor()) r.qdb++;
+    r.qdb = quotient_degree_bits(air);
     return r;
 }
 
 // ---- phase-level entry points (one `timed!` scope of the reference at a time) --------------------------------
 // out[6] = ncols, n_params, permutation Z columns, CTL Z columns, quotient_degree_factor, permutation batch size
 void table_shape_host(const OlaGpuConfig& cfg, const u64* airset, size_t airset_words, uint32_t table, uint32_t out[6]) {
-    HAirSet set = parse_airset(airset, airset_words);
-    if (table >= set.tables.size()) throw OlaError(OLA_E_INVALID_ARG, "table index out of range");
+    const HAirSet set = parse_airset_with_table(airset, airset_words, table);
     const TableWidths tw = table_widths(set, table, (int)cfg.num_challenges);
     const HTable& air = set.tables[table];
     const uint32_t nperm = (uint32_t)air.num_permutation_batches((int)cfg.num_challenges);
@@ -918,67 +951,83 @@ void table_shape_host(const OlaGpuConfig& cfg, const u64* airset, size_t airset_
     out[4] = (uint32_t)air.quotient_degree_factor(); out[5] = (uint32_t)air.permutation_batch_size();
 }
 
-// compute_permutation_z_polys (permutation.rs:103-187) and the table's share of cross_table_lookup_data
-// (cross_table_lookup.rs:224-311): the Z columns as values over the trace domain.  which = 0: permutation columns, 1: CTL columns.
-void phase_zs_host(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, const u64* airset, size_t airset_words, uint32_t table,
-                   uint32_t log_n, const u64* const* trace_cols, const u64* perm_challenges, const u64* ctl_challenges, int which,
-                   std::vector<u64>& out_cols) {
-    HAirSet set = parse_airset(airset, airset_words);
-    if (table >= set.tables.size()) throw OlaError(OLA_E_INVALID_ARG, "table index out of range");
-    const HTable& air = set.tables[table];
-    std::vector<GpChallenge> ctl_ch;
-    for (uint32_t c = 0; c < cfg.num_challenges; c++) ctl_ch.push_back(ctl_challenges ? GpChallenge{gl_canon(ctl_challenges[2 * c]), gl_canon(ctl_challenges[2 * c + 1])} : GpChallenge{1, 1});
-    const std::vector<std::vector<CtlJob>> jobs = ctl_jobs(set, ctl_ch);
-    DevBuf mem(ctx);
-    DevTable tv;
-    tv.log_n = log_n;
-    const size_t n = tv.n();
-    tv.vals = mem.alloc((size_t)air.ncols * n);
-    for (int c = 0; c < air.ncols; c++)
-        HIP_CHECK(hipMemcpyAsync(tv.vals + (size_t)c * n, trace_cols[c], n * 8, hipMemcpyHostToDevice, ctx->stream));
-    canonicalize(ctx, tv.vals, (size_t)air.ncols * n);
-    std::vector<u64> dummy_perm((size_t)air.permutation_batch_size() * cfg.num_challenges * 2, 1);
-    PhaseTap tap;
-    tap.perm_challenges = perm_challenges ? perm_challenges : dummy_perm.data();
-    tap.perm_wanted = which == 0;     // ola_ctl_z: the (1, 1) stand-ins may well meet a zero denominator, and nobody reads those columns
-    tap.stop_after = 1;
-    std::vector<u64> zs;
-    tap.zs_out = &zs;
-    OlaBatch shape;            // only its flags are looked at before the Z columns exist
-    shape.ncols = (uint32_t)air.ncols; shape.log_n = log_n;
-    OlaChallenger ch;
-    challenger_init(ch, (uint32_t)ctx->hasher);
-    std::vector<uint8_t> bytes;
-    std::vector<u64> zero_params(64, 0), cap;
-    prove_single_table(ctx, tables, cfg, air, tv, shape, cap, jobs[table], zero_params.data(), ch, bytes, false, (int)table, &tap);
-    const size_t first = which == 0 ? 0 : (size_t)tap.nperm, count = which == 0 ? (size_t)tap.nperm : (size_t)(tap.nz - tap.nperm);
-    out_cols.assign(zs.begin() + first * n, zs.begin() + (first + count) * n);
+// after the steps of an entry point: one wait, what the device found wrong with the input, and only then the result into the
+// caller's buffer -- a refused call leaves it untouched.  Staged in the scope's host memory (pinned while the arena has room).
+template <class Finding>
+static void hand_back(DeviceCtx* ctx, DevBuf& mem, u64* out, const u64* d_result, size_t words, const Finding& finding) {
+    HostSpan staged = mem.host(words);
+    HIP_CHECK(hipMemcpyAsync(staged.data(), d_result, words * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    finding.check();
+    memcpy(out, staged.data(), words * 8);
 }
 
-// compute_quotient_polys + the split into degree-n chunks (prover.rs:441-480, 571-705): coefficients of the 2 * q chunk
-// polynomials, ready for PolynomialBatch::from_coeffs.
-void phase_quotient_host(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, const u64* airset, size_t airset_words, uint32_t table,
-                         const OlaBatch& trace_c, const OlaBatch& zs_c, const u64* perm_challenges, const u64* ctl_challenges, const u64* alphas,
-                         const u64* params, std::vector<u64>& chunks) {
-    HAirSet set = parse_airset(airset, airset_words);
-    if (table >= set.tables.size()) throw OlaError(OLA_E_INVALID_ARG, "table index out of range");
+// compute_permutation_z_polys (permutation.rs:103-187): the permutation Z columns as values over the trace domain (ola_perm_z)
+void perm_z_host(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airset, size_t airset_words, uint32_t table, uint32_t log_n,
+                 const u64* const* trace_cols, const u64* perm_challenges, u64* z_out) {
+    const HAirSet set = parse_airset_with_table(airset, airset_words, table);
+    const HTable& air = set.tables[table];
+    const int nch = two_challenges(cfg);
+    if (table_widths(set, table, nch).wz == 0) throw OlaError(OLA_E_INVALID_ARG, "No CTL?");
+    const PermDesc pd = build_perm_desc(air, read_perm_sets(air, nch, perm_challenges), nch);
+    if (!pd.nperm()) return;
+    DevBuf mem(ctx);
+    PhaseTimer ph(ctx, "    compute permutation Z(x) polys");
+    const DevTable tv = upload_table(ctx, mem, trace_cols, air.ncols, log_n);
+    u64* z = mem.alloc((size_t)pd.nperm() * tv.n());
+    const ZFlags zf(ctx, mem, (int)table);
+    perm_z_columns(ctx, mem, tv, pd, z, mem.alloc(pscan_tot_stride(tv.n())), zf.zero_den());
+    zf.fetch(ctx);
+    hand_back(ctx, mem, z_out, z, (size_t)pd.nperm() * tv.n(), zf);
+}
+
+// the table's share of cross_table_lookup_data (cross_table_lookup.rs:224-311): its CTL Z columns (ola_ctl_z)
+void ctl_z_host(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airset, size_t airset_words, uint32_t table, uint32_t log_n,
+                const u64* const* trace_cols, const u64* ctl_challenges, u64* z_out) {
+    const HAirSet set = parse_airset_with_table(airset, airset_words, table);
+    const HTable& air = set.tables[table];
+    const int nch = two_challenges(cfg);
+    if (table_widths(set, table, nch).wz == 0) throw OlaError(OLA_E_INVALID_ARG, "No CTL?");
+    const std::vector<std::vector<CtlJob>> jobs = ctl_jobs(set, read_challenges(ctl_challenges, nch));
+    const CtlDesc cd = build_ctl_desc(jobs[table]);
+    if (!cd.ncols) return;
+    DevBuf mem(ctx);
+    PhaseTimer ph(ctx, "    compute CTL Z(x) polys");
+    const DevTable tv = upload_table(ctx, mem, trace_cols, air.ncols, log_n);
+    u64* z = mem.alloc(cd.ncols * tv.n());
+    const ZFlags zf(ctx, mem, (int)table);
+    ctl_z_columns(ctx, mem, tv, cd, z, mem.alloc(cd.ncols * pscan_tot_stride(tv.n())), zf.bad_filter());
+    zf.fetch(ctx);
+    hand_back(ctx, mem, z_out, z, cd.ncols * tv.n(), zf);
+}
+
+// compute_quotient_polys + the split into degree-n chunks (prover.rs:441-480, 571-705) on the caller's two commitments:
+// coefficients of the 2 * q chunk polynomials, ready for PolynomialBatch::from_coeffs (ola_quotient)
+void quotient_host(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, const u64* airset, size_t airset_words, uint32_t table,
+                   const OlaBatch& trace_c, const OlaBatch& zs_c, const u64* perm_challenges, const u64* ctl_challenges, const u64* alphas,
+                   const u64* params, u64* chunks_out) {
+    const HAirSet set = parse_airset_with_table(airset, airset_words, table);
     if (ctx->shard.world != 1) throw OlaError(OLA_E_INVALID_ARG, "per-phase proving needs an unsharded context");
     const HTable& air = set.tables[table];
     if (trace_c.ncols != (uint32_t)air.ncols || trace_c.is_shard()) throw OlaError(OLA_E_INVALID_ARG, "trace commitment does not match the table");
     if (!air.perm_pairs.empty() && !perm_challenges) throw OlaError(OLA_E_INVALID_ARG, "the table has permutation arguments: perm_challenges required");
-    std::vector<GpChallenge> ctl_ch;
-    for (uint32_t c = 0; c < cfg.num_challenges; c++) ctl_ch.push_back({gl_canon(ctl_challenges[2 * c]), gl_canon(ctl_challenges[2 * c + 1])});
-    const std::vector<std::vector<CtlJob>> jobs = ctl_jobs(set, ctl_ch);
-    DevTable tv;
-    tv.log_n = trace_c.log_n;
-    PhaseTap tap;
-    tap.perm_challenges = perm_challenges; tap.alphas = alphas; tap.zs = &zs_c; tap.stop_after = 2; tap.chunks_out = &chunks;
-    OlaChallenger ch;
-    challenger_init(ch, (uint32_t)ctx->hasher);
-    std::vector<uint8_t> bytes;
-    std::vector<u64> zero_params(64, 0), cap;
-    if (!params && air.n_params > 64) throw OlaError(OLA_E_INVALID_ARG, "params required");
-    prove_single_table(ctx, tables, cfg, air, tv, trace_c, cap, jobs[table], params ? params : zero_params.data(), ch, bytes, false, (int)table, &tap);
+    params = params_or_zero(params, 0, air);
+    const int nch = two_challenges(cfg);
+    const std::vector<std::vector<CtlJob>> jobs = ctl_jobs(set, read_challenges(ctl_challenges, nch));
+    const std::vector<CtlJob>& ctl = jobs[table];
+    const PermSets perm_sets = read_perm_sets(air, nch, perm_challenges);
+    const PermDesc pd = build_perm_desc(air, perm_sets, nch);
+    const CtlDesc cd = build_ctl_desc(ctl);
+    const size_t nz = (size_t)pd.nperm() + ctl.size();
+    if (nz == 0) throw OlaError(OLA_E_INVALID_ARG, "No CTL?");
+    if (zs_c.ncols != nz || zs_c.log_n != trace_c.log_n || zs_c.lean != trace_c.lean || zs_c.is_shard())
+        throw OlaError(OLA_E_INVALID_ARG, "Z commitment does not match the table");
+    DevBuf mem(ctx);
+    std::unique_ptr<PhaseTimer> ph(new PhaseTimer(ctx, "    compute quotient polys"));
+    const QuotientIn qin = {air, trace_c, zs_c, perm_sets, pd, ctl, cd, params, {gl_canon(alphas[0]), gl_canon(alphas[1])}};
+    const QuotientPolys qp = quotient_polys(ctx, mem, tables, cfg, qin, false);
+    ph.reset(); ph.reset(new PhaseTimer(ctx, "    split quotient polys"));
+    hand_back(ctx, mem, chunks_out, split_quotient(ctx, mem, qp), 2 * qp.n * (size_t)qp.q, qp);
 }
 
 // Memory-lean tables (OLA_LEAN=1 forces, =0 forbids, default: when keeping every LDE resident would not fit): the LDEs of the
@@ -1018,8 +1067,6 @@ void reserve_for_proof(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airse
     const int nch = (int)cfg.num_challenges;
     const std::vector<char> lean = plan_lean_tables(ctx, cfg, set, log_n);
     std::vector<size_t> sizes;
-    size_t big = 0;
-    for (size_t t = 0; t < nt; t++) if (log_n[t] > log_n[big]) big = t;
     auto batch_blocks = [&](size_t w, size_t n, bool is_lean) {
         const size_t N = n << cfg.rate_bits;
         sizes.push_back(w * n * 8);                      // coefficients
@@ -1042,7 +1089,6 @@ void reserve_for_proof(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airse
     }
     // Z and quotient buffers go back to the pool when a table is done and are handed to the next table that asks for a size they
     // fit (alloc's rule: at most a quarter larger than wanted): reserve, in proving order, what no earlier table leaves behind
-    (void)big;
     std::vector<size_t> left_behind;
     std::sort(large.begin(), large.end());
     for (size_t t : large) {
@@ -1180,7 +1226,6 @@ void prove_with_traces(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cf
     ByteWriter w{bytes, digest_wire_bytes((uint32_t)ctx->hasher)};
     w.u32((uint32_t)nt);
     size_t poff = 0;
-    std::vector<u64> zero_params(64, 0);
     // the proof-of-work searches of the tables run on the side stream and are collected at the end (fri.hip PowDefer); the
     // slots are this scope's, allocated before any inner scope exists (the pinned arena is a stack).  OLA_POW_DEFER=0: in line.
     PowDefer pow;
@@ -1188,14 +1233,13 @@ void prove_with_traces(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cf
     if (pow_defer_on) { pow.slots = (unsigned long long*)ctx->pinned_alloc(nt * 8); pow.nslots = pow.slots ? nt : 0; }
     struct PowGuard { DeviceCtx* c; PowDefer& p; ~PowGuard() { pow_abandon(c, p); } } pow_guard{ctx, pow};
     for (size_t t = 0; t < nt; t++) {
-        const u64* pr = params ? params + poff : zero_params.data();
-        if (!params && set.tables[t].n_params > 64) throw OlaError(OLA_E_INVALID_ARG, "params required");
+        const u64* pr = params_or_zero(params, poff, set.tables[t]);
         poff += set.tables[t].n_params;
         ctx->scopes.table = (int)t;
         PhaseTimer tt(ctx, "  table " + std::to_string(t) + " prove_single_table");
         ctx->acct.shardable = log_n[t] >= ctx->shard.min_log_n;
         prove_single_table(ctx, tables, cfg, set.tables[t], dev[t], *commits[t]->b, caps[t], jobs[t], pr, ch, bytes,
-                           table_is_sharded(ctx, cfg, set.tables[t], log_n[t]), (int)t, nullptr, &pow);
+                           table_is_sharded(ctx, cfg, set.tables[t], log_n[t]), (int)t, &pow);
     }
     pow_finish(ctx, pow, bytes);
     ctx->acct.shardable = false;

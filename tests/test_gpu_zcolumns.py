@@ -202,9 +202,25 @@ def test_non_binary_filter_is_refused_and_the_context_goes_on(be):
         check_perm(be, s, 0, tr, rows, perm_shape(ZC.challenges("random", 4, 4), s.tables[0]), "after a refused filter")
 
 
-def test_ctl_z_does_not_refuse_for_its_stand_in_permutation_challenges(be):
-    """ola_ctl_z runs the permutation kernels with (beta, gamma) = (1, 1) and throws their columns away: cells of p - 1 make every
-    denominator of that run zero, which is nobody's error"""
+def test_perm_z_leaves_the_filters_to_ctl_z(be):
+    """ola_perm_z launches no lookup kernel (the reference's compute_permutation_z_polys never looks at a filter): on a trace with a
+    non-binary filter cell it returns the permutation columns of that trace, word for word; ola_ctl_z on it is still refused"""
+    from olavm_amd.backend import OlaGpuError
+    s = ZC.narrow()
+    ctl = ZC.challenges("random", 2, 3)
+    perm = perm_shape(ZC.challenges("random", 4, 4), s.tables[0])
+    for log_n, row, word in ((8, 0, 2), (12, 2048, P - 1), (12, 4095, P + 2)):
+        bad = ZC.fill(s, 0, log_n, "random", "random")
+        bad[2, row] = word
+        assert check_perm(be, s, 0, bad, R.rows(bad), perm, "non-binary filter cell at row %d of 2^%d" % (row, log_n)) is not None
+        with pytest.raises(OlaGpuError, match="Non-binary filter\\?") as e:
+            be.ctl_z(s.blob(), 0, bad, ctl)
+        assert e.value.code == OLA_E_INVALID_ARG
+
+
+def test_ctl_z_launches_no_permutation_kernel(be):
+    """ola_ctl_z runs the lookup step alone: cells of p - 1, which make every permutation denominator zero under (beta, gamma) =
+    (1, 1), are nothing it could meet -- it has no permutation challenges, stand-ins included"""
     from olavm_amd.backend import OlaGpuError
     s = ZC.narrow()
     tr = ZC.fill(s, 0, 8, "p-1", "random")
