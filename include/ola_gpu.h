@@ -80,7 +80,10 @@ typedef struct OlaGpuConfig {
     uint32_t rate_bits;         /* 3                                                                         */
     uint32_t cap_height;        /* 4                                                                         */
     uint32_t proof_of_work_bits;/* 16                                                                        */
-    uint32_t fri_arity_bits;    /* ConstantArityBits(4, 5)                                                   */
+    uint32_t fri_arity_bits;    /* ConstantArityBits(4, 5).  1..8 for proving (arities 2 to 256); the verifier supports FRI
+                                 * arities of 2 to 16: under 5..8 ola_verify_all_proof and ola_verify_opening return
+                                 * OLA_E_INVALID_ARG ("the verifier supports FRI arities of 2 to 16") and the context goes on
+                                 * proving.                                                                   */
     uint32_t fri_final_poly_bits;
     uint32_t num_query_rounds;  /* 28                                                                        */
     uint32_t num_challenges;    /* 2                                                                         */
@@ -459,7 +462,8 @@ int32_t ola_pow(OlaCtx* ctx, const uint64_t h[4], uint32_t bits, uint64_t* witne
  *   ola_pow (above)            fri_proof_of_work (prover.rs:126-148), minimal witness
  *   ola_fri_query              fri_prover_query_rounds (prover.rs:150-204) for the caller's indices (challenger output mod the LDE
  *                              size): the query round proofs in wire format (write_fri_query_rounds, serialization.rs:275-292: count, per query the three
- *                              oracles' rows and paths and every layer's leaf and path) */
+ *                              oracles' rows and paths and every layer's leaf and path); n = 0 is OLA_E_INVALID_ARG, and the
+ *                              handle goes on answering */
 typedef struct OlaFri OlaFri;
 int32_t ola_open(OlaCtx* ctx, const OlaBatch* trace, const OlaBatch* zs, const OlaBatch* quotient, uint32_t num_permutation_zs,
                  const uint64_t zeta[2], uint8_t* out, size_t cap, size_t* out_len, OlaFri** fri_out);

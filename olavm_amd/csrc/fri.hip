@@ -401,13 +401,15 @@ __global__ __launch_bounds__(256) void fold_pairs_kernel(const u64* __restrict__
     }
 }
 
-// out[q][2k], out[q][2k+1] = (a, b)[idx[q]*arity + k]
+// out[q][2k], out[q][2k+1] = (a, b)[idx[q]*arity + k]; a block per query, its threads stride over k (arities 128 and 256 are wider
+// than the 64 threads it is launched with)
 __global__ void gather_ext_leaves_kernel(const u64* __restrict__ pa, const u64* __restrict__ pb, int arity,
                                          const unsigned long long* __restrict__ idx, u64* __restrict__ out) {
-    const int q = blockIdx.x, k = threadIdx.x;
-    if (k >= arity) return;
-    out[((size_t)q * arity + k) * 2] = pa[idx[q] * arity + k];
-    out[((size_t)q * arity + k) * 2 + 1] = pb[idx[q] * arity + k];
+    const int q = blockIdx.x;
+    for (int k = threadIdx.x; k < arity; k += blockDim.x) {
+        out[((size_t)q * arity + k) * 2] = pa[idx[q] * arity + k];
+        out[((size_t)q * arity + k) * 2 + 1] = pb[idx[q] * arity + k];
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ host helpers
@@ -744,7 +746,6 @@ struct PowDefer {
     unsigned long long* slots = nullptr;   // pinned, one per table, allocated by the scope that owns the whole proof
     size_t nslots = 0;
 };
-static u64 pow_batch(u32 bits) { return std::max<u64>((u64)1 << 14, (u64)4 << bits); }
 // enqueue the first batch of the search on the side stream; false: no side stream / no slot, search synchronously
 static bool pow_enqueue(DeviceCtx* ctx, PowDefer* d, const u64 h[4], u32 bits, size_t at) {
     if (!d || !d->slots || d->jobs.size() >= d->nslots || d->jobs.size() >= DeviceCtx::kSideWords) return false;
@@ -1299,6 +1300,8 @@ size_t fri_steps_finish(OlaFri& f, const u64* beta, u64* final_poly_out, size_t 
 // fri_prover_query_rounds (fri/prover.rs:150-204) for the caller's indices: the query round proofs in wire format
 void fri_steps_query(OlaFri& f, const u64* x_index, uint32_t nq, std::vector<uint8_t>& bytes) {
     if (f.stage != 2) throw OlaError(OLA_E_INVALID_ARG, "ola_fri_query: call ola_fri_commit_finish first");
+    // no index is a grid of no block: refused before anything is launched (a configuration's num_query_rounds starts at 1 as well)
+    if (nq == 0) throw OlaError(OLA_E_INVALID_ARG, "ola_fri_query: at least one index");
     std::vector<size_t> xs(nq);
     for (uint32_t r = 0; r < nq; r++) {
         if (x_index[r] >= (u64)f.N) throw OlaError(OLA_E_INVALID_ARG, "ola_fri_query: index beyond the LDE");

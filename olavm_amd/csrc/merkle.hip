@@ -22,6 +22,7 @@
 #include "gl.cuh"
 #include "hasher.cuh"
 #include "hasher_host.h"
+#include "pow_batch.h"
 
 namespace ola {
 
@@ -412,16 +413,16 @@ void launch_poseidon_states(DeviceCtx* ctx, u64* states, size_t n, uint32_t hash
 static void launch_pow_batch(DeviceCtx* ctx, hipStream_t stream, const u64 h[4], u64 start, u64 count, u32 bits, unsigned long long* best) {
     with_perm(hasher_row((uint32_t)ctx->hasher).inner, [&](auto perm) {
         constexpr int PERM = decltype(perm)::value;
-        hipLaunchKernelGGL(pow_kernel<PERM>, dim3((unsigned)(count / 256)), dim3(256), 0, stream, h[0], h[1], h[2], h[3], start, bits, best);
+        hipLaunchKernelGGL(pow_kernel<PERM>, dim3(pow_batch_blocks(count)), dim3((unsigned)POW_BLOCK), 0, stream, h[0], h[1], h[2], h[3], start, bits, best);
+        HIP_CHECK(hipGetLastError());      // a refused launch throws: run_pow's loop would otherwise wait for a witness nobody looks for
     });
 }
-// minimal nonce with `bits` leading zeros; scans batches of 2^20 nonces in increasing order
+// minimal nonce with `bits` leading zeros; scans batches of pow_batch(bits) nonces (pow_batch.h) in increasing order
 u64 run_pow(DeviceCtx* ctx, const u64 h[4], u32 bits) {
     unsigned long long* d_best = (unsigned long long*)ctx->alloc(8);
     const unsigned long long none = ~0ull;
     unsigned long long best = none;
-    // expected witness ~2^bits: batches of 4 * 2^bits nonces find it in the first launch 98 % of the time
-    const u64 batch = std::max<u64>((u64)1 << 14, (u64)4 << bits);
+    const u64 batch = pow_batch(bits);
     for (u64 start = 0; best == none; start += batch) {
         HIP_CHECK(hipMemcpyAsync(d_best, &none, 8, hipMemcpyHostToDevice, ctx->stream));
         launch_pow_batch(ctx, ctx->stream, h, start, batch, bits, d_best);

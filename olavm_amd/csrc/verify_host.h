@@ -607,6 +607,10 @@ inline Stage all_proof_stage(const Config& cfg, const u64* airset, size_t airset
         fri_challenges(ch, cfg, p.fri, degree_bits, tc);
         // validate_proof_shape (verifier.rs:326-379)
         const int q = air.quotient_degree_factor();
+        // the three caps at the configuration's height (verifier.rs:363-365): a proof made under another cap_height stops here, as in
+        // the reference, not at whatever the wrong degree_bits breaks later
+        const size_t cap_len = (size_t)1 << cfg.cap_height;
+        if (p.trace_cap.size() != cap_len || p.zs_cap.size() != cap_len || p.quotient_cap.size() != cap_len) return fail(OLA_VERIFY_SHAPE_CAP_HEIGHT, (int)t);
         if ((int)p.op.local.size() != 2 * air.ncols || (int)p.op.next.size() != 2 * air.ncols) return fail(OLA_VERIFY_SHAPE_OPENING_WIDTH, (int)t);
         if ((int)p.op.zs.size() != 2 * (nperm + num_ctl) || (int)p.op.zs_next.size() != 2 * (nperm + num_ctl)) return fail(OLA_VERIFY_SHAPE_ZS_WIDTH, (int)t);
         if ((int)p.op.ctl_last.size() != num_ctl) return fail(OLA_VERIFY_SHAPE_CTL_ZS_LAST_WIDTH, (int)t);

@@ -488,6 +488,8 @@ static std::string verify_all_proof(const AirSet& set, const ProverConfig& cfg, 
         // validate_proof_shape
         const int nperm = air.num_permutation_batches(cfg.num_challenges);
         const int num_ctl = (int)ctl_vars[t].size();
+        const size_t cap_len = (size_t)1 << cfg.fri.cap_height;          // verifier.rs:363-365: the three caps at the configuration's height
+        if (p.trace_cap.size() != cap_len || p.zs_cap.size() != cap_len || p.quotient_cap.size() != cap_len) return tag + "cap height";
         if ((int)p.openings.local_values.size() != air.ncols || (int)p.openings.next_values.size() != air.ncols) return tag + "opening width";
         if ((int)p.openings.permutation_ctl_zs.size() != nperm + num_ctl || (int)p.openings.permutation_ctl_zs_next.size() != nperm + num_ctl) return tag + "zs width";
         if ((int)p.openings.ctl_zs_last.size() != num_ctl) return tag + "ctl_zs_last width";

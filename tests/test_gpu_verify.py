@@ -23,6 +23,7 @@ import pytest
 
 from olavm_amd.air import AirSet, miniexec as M, ola_tables as T
 from tests import tracegen
+from tests.verdicts import WORDS, agrees, oracle_says  # noqa: F401  (the oracle's words -> the report's reasons)
 
 pytestmark = pytest.mark.gpu
 
@@ -35,38 +36,9 @@ OLA_E_INVALID_ARG = -1
 STEM = {"poseidon": "wide_program", "blake3": "wide_program_blake3", "poseidon2": "wide_program_poseidon2"}
 MINI = dict(range_bits=4, limb_bits=2)
 
-# the oracle's words (oracle/stark.cpp:456-529, oracle/fri.cpp:250-323) -> the reason of the report
-WORDS = [("malformed proof bytes", "MALFORMED"), ("wrong number of table proofs", "MALFORMED"), ("empty FRI proof", "EMPTY_FRI"),
-         ("opening width", "SHAPE_OPENING_WIDTH"), ("zs width", "SHAPE_ZS_WIDTH"), ("ctl_zs_last width", "SHAPE_CTL_ZS_LAST_WIDTH"),
-         ("quotient width", "SHAPE_QUOTIENT_WIDTH"), ("Mismatch between evaluation and opening of quotient polynomial", "QUOTIENT_IDENTITY"),
-         ("cap height", "SHAPE_CAP_HEIGHT"), ("number of query rounds", "SHAPE_QUERY_ROUNDS"), ("initial proofs", "SHAPE_INITIAL_PROOFS"),
-         ("leaf len", "SHAPE_LEAF_LEN"), ("initial merkle proof len", "SHAPE_INITIAL_PATH_LEN"), ("steps", "SHAPE_STEPS"),
-         ("evals len", "SHAPE_EVALS_LEN"), ("step merkle proof len", "SHAPE_STEP_PATH_LEN"), ("final poly len", "SHAPE_FINAL_POLY_LEN"),
-         ("Invalid proof of work witness.", "POW"), ("Invalid Merkle proof (initial tree).", "MERKLE_INITIAL"),
-         ("FRI consistency check failed", "FRI_CONSISTENCY"), ("Invalid Merkle proof (commit phase).", "MERKLE_COMMIT"),
-         ("Final polynomial evaluation is invalid.", "FINAL_POLY"), ("Cross-table lookup verification failed.", "CTL")]
 # where the reference's verifier stops (the records' `reference` field) -> the reason
 REFERENCE = {"Err verifier.rs:295": ("QUOTIENT_IDENTITY",), "Err verifier.rs:52": ("POW",), "Err verifier.rs:218": ("FRI_CONSISTENCY",),
              "Err merkle_proofs.rs:71": ("MERKLE_INITIAL", "MERKLE_COMMIT")}
-
-
-def oracle_says(rc, msg):
-    """(accepted, reason, table) of an oracle verdict"""
-    if rc == 0:
-        return True, "OK", None
-    m = re.match(r"table (\d+): (.*)", msg)
-    table, words = (int(m.group(1)), m.group(2)) if m else (None, msg)
-    reason = [r for w, r in WORDS if w == words]
-    assert len(reason) == 1, msg
-    return False, reason[0], table
-
-
-def agrees(res, rc, msg):
-    """the product's result against the oracle's verdict: acceptance, reason, table, and the message starts with the oracle's words"""
-    ok, reason, table = oracle_says(rc, msg)
-    assert (bool(res), res.reason, res.table) == (ok, reason, table), (res, msg)
-    if not ok:
-        assert res.message.startswith(msg.split(": ", 1)[1] if table is not None else msg), (res.message, msg)
 
 
 def span_place(span):

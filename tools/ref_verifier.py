@@ -452,9 +452,13 @@ STARK_FIELDS = ["cpu_stark", "memory_stark", "bitwise_stark", "cmp_stark", "rang
 class RefVerifier:
     """The reference's verifier over one reference tree.  `verify(raw)` -> (True, None) or (False, "file.rs:line" of the `ensure!` that failed)."""
 
-    def __init__(self, reference="/root/reference", fast_hash=True, hasher="poseidon", reduction_strategy=None):
+    CONFIG_FIELDS = ("rate_bits", "cap_height", "proof_of_work_bits", "num_query_rounds")
+
+    def __init__(self, reference="/root/reference", fast_hash=True, hasher="poseidon", reduction_strategy=None, config_overrides=None):
         """reduction_strategy: None keeps standard_fast_config's ConstantArityBits(4, 5); ("MinSize", [None]), ("MinSize", [3]) or
-        ("Fixed", [[4, 3, 3]]) is `config.fri_config.reduction_strategy = FriReductionStrategy::<variant>(<payload>)`"""
+        ("Fixed", [[4, 3, 3]]) is `config.fri_config.reduction_strategy = FriReductionStrategy::<variant>(<payload>)`.
+        config_overrides: {"rate_bits" | "cap_height" | "proof_of_work_bits" | "num_query_rounds": n} is `config.fri_config.<field> = n`
+        on the same interpreted StarkConfig (fri/mod.rs FriConfig); None keeps standard_fast_config's 3, 4, 16 and 28"""
         sys.setrecursionlimit(max(sys.getrecursionlimit(), 20000))
         self.reference = reference
         self.hasher = hasher
@@ -463,6 +467,13 @@ class RefVerifier:
         self.config = self.it.call_assoc("StarkConfig", "standard_fast_config", [], os.path.join(self.stark_dir, "config.rs"))
         if reduction_strategy is not None:
             self.config["fri_config"]["reduction_strategy"] = Enum("FriReductionStrategy", reduction_strategy[0], list(reduction_strategy[1]))
+        for field, value in (config_overrides or {}).items():
+            if field not in self.CONFIG_FIELDS:
+                raise ValueError("config_overrides takes %s, not %r" % (", ".join(self.CONFIG_FIELDS), field))
+            old = self.config["fri_config"][field]             # the field exists in the interpreted struct, as the plain integer it is set to
+            if isinstance(old, bool) or not isinstance(old, int):
+                raise R.RustError("fri_config.%s is %r in the interpreted StarkConfig, not an integer" % (field, old))
+            self.config["fri_config"][field] = int(value)
 
     def ola_stark(self):
         """what `OlaStark::default()` (ola_stark.rs:45-64) builds, minus its init_gpu() call: twelve default table structs (compress challenges unset,
