@@ -22,7 +22,7 @@ namespace ola {
 // loaded, moved down one lane through the LDS crossbar, and the wave's last lane reads its own next cell); false reads it from
 // memory -- the same 512-byte run shifted by one word, whose lines the local load of that column has in cache.  An interpreter
 // does not know whether the local cell is in a register already, so `true` saves no load and adds the move (static count per `next`
-// op: +8 VALU, +2 ds_bpermute, +1 load instruction): `false` is what the library runs.
+// op: +10 VALU, +2 ds_bpermute, +1 load instruction): `false` is what the library runs.
 template <bool NEIGHBOUR>
 __global__ __launch_bounds__(QW) void check_constraints_kernel(const u64* __restrict__ trace, size_t n, const u64* __restrict__ D,
                                                                unsigned long long* __restrict__ rec) {
@@ -35,48 +35,31 @@ __global__ __launch_bounds__(QW) void check_constraints_kernel(const u64* __rest
     const size_t nxt = (row + 1) & (n - 1);
     const u32 n_ops = (u32)D[0], ops_off = (u32)D[1], params_off = (u32)D[2];
     u32 e = 0;
-    for (u32 k = 0; k < n_ops; k++) {
-        const u64 w0 = D[ops_off + 2 * k], w1 = D[ops_off + 2 * k + 1];
-        const int op = (int)(w0 & 0xff), kind = (int)((w0 >> 8) & 0xff);
-        const u32 dst = (u32)((w0 >> 16) & 0xffff), a = (u32)((w0 >> 32) & 0xffff), b = (u32)((w0 >> 48) & 0xffff);
-        u64 v;
-        switch (op) {
-            case AOP_LOCAL: v = gl_canon(trace[(size_t)a * n + row]); break;
-            case AOP_NEXT:
-                if (NEIGHBOUR) {
-                    const u64 loc = trace[(size_t)a * n + row];
-                    v = __shfl_down(loc, 1, QW);
-                    if (lane == QW - 1 || nxt == 0) v = trace[(size_t)a * n + nxt];
-                    v = gl_canon(v);
-                } else {
-                    v = gl_canon(trace[(size_t)a * n + nxt]);
-                }
-                break;
-            case AOP_CONST: v = w1; break;
-            case AOP_PARAM: v = D[params_off + a]; break;
-            case AOP_ADD: v = gl_add(regs[a * QW + lane], regs[b * QW + lane]); break;
-            case AOP_SUB: v = gl_sub(regs[a * QW + lane], regs[b * QW + lane]); break;
-            case AOP_MUL: v = gl_mul(regs[a * QW + lane], regs[b * QW + lane]); break;
-            case AOP_ISZERO: v = (regs[a * QW + lane] == 0) ? 1 : 0; break;
-            default: {
-                // where z_last and the Lagrange selectors are non-zero on H (constraint_consumer.rs:34-78)
-                const bool applies = kind == AK_ALL || (kind == AK_TRANSITION && row != n - 1) || (kind == AK_FIRST && row == 0) ||
-                                     (kind == AK_LAST && row == n - 1);
-                const bool fail = active && applies && gl_canon(regs[a * QW + lane]) != 0;
-                const unsigned long long m = __ballot(fail);
-                if (m) {
-                    const int first = __ffsll((long long)m) - 1;       // lanes are rows in order: the lowest failing lane is the smallest row
-                    if (lane == first) {
-                        atomicMin(&rec[2 * e], (unsigned long long)i);
-                        atomicAdd(&rec[2 * e + 1], (unsigned long long)__popcll(m));
-                    }
-                }
-                e++;
-                continue;
+    auto load = [&](u32 col, bool next) {
+        if (!next) return gl_canon(trace[(size_t)col * n + row]);
+        if (!NEIGHBOUR) return gl_canon(trace[(size_t)col * n + nxt]);
+        u64 v = __shfl_down(trace[(size_t)col * n + row], 1, QW);
+        if (lane == QW - 1 || nxt == 0) v = trace[(size_t)col * n + nxt];
+        return gl_canon(v);
+    };
+    auto emit = [&](int kind, u64 v) {
+        // where z_last and the Lagrange selectors are non-zero on H (constraint_consumer.rs:34-78).  | and & on purpose: the kind is
+        // uniform and the row tests are loop invariants, so this is a few scalar selects; && and || became branches per emit
+        // (profiles/airset_one_description_ab.txt)
+        const bool applies = (kind == AK_ALL) | ((kind == AK_TRANSITION) & (row != n - 1)) | ((kind == AK_FIRST) & (row == 0)) |
+                             ((kind == AK_LAST) & (row == n - 1));
+        const bool fail = active & applies & (gl_canon(v) != 0);
+        const unsigned long long m = __ballot(fail);
+        if (m) {
+            const int first = __ffsll((long long)m) - 1;       // lanes are rows in order: the lowest failing lane is the smallest row
+            if (lane == first) {
+                atomicMin(&rec[2 * e], (unsigned long long)i);
+                atomicAdd(&rec[2 * e + 1], (unsigned long long)__popcll(m));
             }
         }
-        regs[dst * QW + lane] = v;
-    }
+        e++;
+    };
+    air_interpret(D + ops_off, n_ops, D + params_off, regs, lane, load, emit);
 }
 
 // rows a lookup side selects: filter(row) == 1, as ctl_factor_kernel decides it (every row without a filter).  desc: push_ctl_desc.
@@ -87,7 +70,7 @@ __global__ __launch_bounds__(256) void ctl_selected_rows_kernel(const u64* __res
     const u32 ncol = (u32)desc[p++];
     for (u32 k = 0; k < ncol; k++) p += 2 * (u32)desc[p] + 2;
     bool sel = i < n;
-    if (sel && desc[p++]) sel = dev_lincol_fast(desc, p, trace, n, i) == 1;
+    if (sel && desc[p++]) sel = dev_lincol(desc, p, trace, n, i) == 1;
     const unsigned long long m = __ballot(sel);
     if (m && (threadIdx.x & 63) == 0) atomicAdd(count, (unsigned long long)__popcll(m));
 }
@@ -101,19 +84,6 @@ static bool check_neighbour_variant() {
 // the AIR section of one table whose values are on the device (canonical or not): K emits -> rec_host[2K]
 static void launch_check_constraints(DeviceCtx* ctx, DevBuf& mem, const HTable& air, const u64* vals, size_t n, const u64* params,
                                      size_t n_emits, unsigned long long* d_rec) {
-    // the kernel indexes the trace, its register file and the parameters with what the program says: hold it to the table's shape
-    for (size_t k = 0; k + 1 < air.ops.size(); k += 2) {
-        const u64 w0 = air.ops[k];
-        const int op = (int)(w0 & 0xff);
-        const u64 dst = (w0 >> 16) & 0xffff, a = (w0 >> 32) & 0xffff, b = (w0 >> 48) & 0xffff;
-        bool ok = op <= AOP_ISZERO && (int)((w0 >> 8) & 0xff) <= AK_LAST;
-        if (op != AOP_EMIT) ok = ok && dst < (u64)air.n_regs;
-        if (op == AOP_LOCAL || op == AOP_NEXT) ok = ok && a < (u64)air.ncols;
-        if (op == AOP_PARAM) ok = ok && a < (u64)air.n_params;
-        if (op == AOP_ADD || op == AOP_SUB || op == AOP_MUL) ok = ok && a < (u64)air.n_regs && b < (u64)air.n_regs;
-        if (op == AOP_EMIT || op == AOP_ISZERO) ok = ok && a < (u64)air.n_regs;
-        if (!ok) throw OlaError(OLA_E_INVALID_ARG, "AIR-set blob: constraint program refers outside its table");
-    }
     std::vector<u64> desc(3, 0);
     desc[0] = air.ops.size() / 2;
     desc[1] = desc.size();
@@ -140,8 +110,10 @@ static void launch_check_constraints(DeviceCtx* ctx, DevBuf& mem, const HTable& 
 
 static std::vector<int> emit_kinds(const HTable& air) {
     std::vector<int> k;
-    for (size_t i = 0; i + 1 < air.ops.size(); i += 2)
-        if ((int)(air.ops[i] & 0xff) == AOP_EMIT) k.push_back((int)((air.ops[i] >> 8) & 0xff));
+    for (size_t i = 0; i + 1 < air.ops.size(); i += 2) {
+        const AirOp o = air_op(air.ops[i], air.ops[i + 1]);
+        if (o.op == AOP_EMIT) k.push_back(o.kind);
+    }
     return k;
 }
 
@@ -312,7 +284,7 @@ __device__ __forceinline__ bool lk_selected(const u64* __restrict__ desc, const 
     const u32 ncol = (u32)desc[p++];
     for (u32 k = 0; k < ncol; k++) p += 2 * (u32)desc[p] + 2;
     if (!desc[p++]) return true;
-    return dev_lincol_fast(desc, p, trace, n, i) == 1;
+    return dev_lincol(desc, p, trace, n, i) == 1;
 }
 
 // selected rows of a block -> *total, and this thread's rank among them (rows in order); every thread of the block calls it
@@ -356,7 +328,7 @@ __global__ __launch_bounds__(256) void lk_extract_kernel(const u64* __restrict__
     if (pos >= N) return;
     u32 p = 2;
     const u32 ncol = (u32)desc[p++];
-    for (u32 k = 0; k < ncol; k++) planes[(size_t)k * N + pos] = dev_lincol_fast(desc, p, trace, n, i);
+    for (u32 k = 0; k < ncol; k++) planes[(size_t)k * N + pos] = dev_lincol(desc, p, trace, n, i);
     const u64 looked = blockIdx.y >= n_looking_entries ? 1 : 0;
     origin[pos] = looked << 63 | (looked ? 0 : (u64)blockIdx.y) << LK_ROW_BITS | (u64)i;
     ident[pos] = (u32)pos;
@@ -464,8 +436,7 @@ struct LookupReport {
     std::vector<OlaLookupMismatch> entries;                    // the first min(cap, totals[2])
 };
 
-// What can be said about `lookup` before a device is touched -> the tables it names (bit t = table t).  The kernels index the
-// trace with what the descriptors say: hold them to the tables' shapes.
+// What can be said about `lookup` of a parsed set before a device is touched -> the tables it names (bit t = table t)
 static uint32_t check_lookup_tables(const HAirSet& set, uint32_t lookup) {
     if (lookup >= set.ctls.size()) throw OlaError(OLA_E_INVALID_ARG, "lookup index beyond the AIR set's cross-table lookups");
     if (set.tables.size() > 32) throw OlaError(OLA_E_INVALID_ARG, "more than 32 tables");
@@ -478,11 +449,6 @@ static uint32_t check_lookup_tables(const HAirSet& set, uint32_t lookup) {
     uint32_t mask = 0;
     auto side = [&](const HTwc& s) {
         if (s.columns.size() != width) throw OlaError(OLA_E_INVALID_ARG, "AIR-set blob: the sides of a lookup differ in width");
-        const u64 ncols = (u64)set.tables[s.table].ncols;
-        auto inside = [&](const HLinCol& c) { for (auto& t : c.terms) if (t.first >= ncols) return false; return true; };
-        bool ok = !s.has_filter || inside(s.filter);
-        for (const HLinCol& c : s.columns) ok = ok && inside(c);
-        if (!ok) throw OlaError(OLA_E_INVALID_ARG, "AIR-set blob: a lookup refers outside its table");
         mask |= 1u << s.table;
     };
     for (const HTwc& s : ctl.looking) side(s);

@@ -32,6 +32,7 @@
 #include "device_ctx.h"
 #include "gl.cuh"
 #include "airset_host.h"
+#include "air_interp.cuh"
 #include "airq.cuh"
 #include "upload.h"
 
@@ -82,7 +83,8 @@ __device__ __forceinline__ u64 dev_lincol(const u64* __restrict__ d, u32& p, con
     u64 s = 0;
     for (u32 i = 0; i < nt; i++) {
         const u64 c = d[p++], f = d[p++];
-        s = gl_add(s, gl_mul(gl_canon(tab[c * cs + row]), f));
+        const u64 v = gl_canon(tab[c * cs + row]);
+        s = gl_add(s, f == 1 ? v : gl_mul(v, f));          // the coefficient is uniform: no divergence; most are 1
     }
     return gl_add(s, d[p++]);
 }
@@ -92,16 +94,6 @@ __device__ __forceinline__ u64 dev_lincol(const u64* __restrict__ d, u32& p, con
 // combinations of trace columns with different (beta, gamma).  One blockIdx.y handles such a pair: descriptors at
 // desc_all[offs[pairs[2y]]] and desc_all[offs[pairs[2y+1]]] (equal indices: an unpaired column), outputs at out_all + index*n.
 // The trace cells and the linear combinations are read / evaluated once for both.
-__device__ __forceinline__ u64 dev_lincol_fast(const u64* __restrict__ d, u32& p, const u64* __restrict__ tab, size_t cs, size_t row) {
-    const u32 nt = (u32)d[p++];
-    u64 s = 0;
-    for (u32 i = 0; i < nt; i++) {
-        const u64 c = d[p++], f = d[p++];
-        const u64 v = gl_canon(tab[c * cs + row]);
-        s = gl_add(s, f == 1 ? v : gl_mul(v, f));          // the coefficient is uniform: no divergence; most are 1
-    }
-    return gl_add(s, d[p++]);
-}
 __global__ __launch_bounds__(256) void ctl_factor_kernel(const u64* __restrict__ trace, size_t n, const u64* __restrict__ desc_all,
                                                          const u64* __restrict__ offs, const u64* __restrict__ pairs, u64* __restrict__ out_all,
                                                          unsigned* __restrict__ bad_filter) {
@@ -117,7 +109,7 @@ __global__ __launch_bounds__(256) void ctl_factor_kernel(const u64* __restrict__
     // combine = reduce_with_powers(evals, beta) + gamma = sum_k beta^k e_k + gamma
     u64 acc_a = 0, acc_b = 0, bp_a = 1, bp_b = 1;
     for (u32 k = 0; k < ncol; k++) {
-        const u64 e = dev_lincol_fast(desc, p, trace, n, i);
+        const u64 e = dev_lincol(desc, p, trace, n, i);
         acc_a = gl_add(acc_a, k == 0 ? e : gl_mul(bp_a, e));
         acc_b = gl_add(acc_b, k == 0 ? e : gl_mul(bp_b, e));
         if (k + 1 < ncol) { bp_a = gl_mul(bp_a, beta_a); bp_b = gl_mul(bp_b, beta_b); }
@@ -125,7 +117,7 @@ __global__ __launch_bounds__(256) void ctl_factor_kernel(const u64* __restrict__
     acc_a = gl_add(acc_a, gamma_a);
     acc_b = gl_add(acc_b, gamma_b);
     u64 f = 1;
-    if (desc[p++]) f = dev_lincol_fast(desc, p, trace, n, i);
+    if (desc[p++]) f = dev_lincol(desc, p, trace, n, i);
     if (f > 1) atomicOr(bad_filter, 1u);  // cross_table_lookup.rs:303-305 panics "Non-binary filter?"
     out_all[ya * n + i] = (f == 1) ? acc_a : 1;
     if (yb != ya) out_all[yb * n + i] = (f == 1) ? acc_b : 1;
@@ -266,7 +258,6 @@ __global__ __launch_bounds__(256) void any_nonzero_kernel(const u64* __restrict_
 
 // ------------------------------------------------------------------------------------------------ quotient kernel
 
-#define QW 64  // one wavefront per workgroup; register file = n_regs x 64 lanes in LDS
 __global__ __launch_bounds__(QW) void quotient_kernel(QuotParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u64* regs = reinterpret_cast<u64*>(smem_raw);
@@ -303,24 +294,8 @@ __global__ __launch_bounds__(QW) void quotient_kernel(QuotParams P) {
     const size_t N = P.N;
 
     // ---- the table's constraint program ----
-    for (u32 i = 0; i < n_ops; i++) {
-        const u64 w0 = D[ops_off + 2 * i], w1 = D[ops_off + 2 * i + 1];
-        const int op = (int)(w0 & 0xff), kind = (int)((w0 >> 8) & 0xff);
-        const u32 dst = (u32)((w0 >> 16) & 0xffff), a = (u32)((w0 >> 32) & 0xffff), b = (u32)((w0 >> 48) & 0xffff);
-        u64 v;
-        switch (op) {
-            case AOP_LOCAL: v = gl_canon(P.trace_lde[(size_t)a * N + jj]); break;
-            case AOP_NEXT: v = gl_canon(P.trace_lde[(size_t)a * N + jn]); break;
-            case AOP_CONST: v = w1; break;
-            case AOP_PARAM: v = D[params_off + a]; break;
-            case AOP_ADD: v = gl_add(regs[a * QW + lane], regs[b * QW + lane]); break;
-            case AOP_SUB: v = gl_sub(regs[a * QW + lane], regs[b * QW + lane]); break;
-            case AOP_MUL: v = gl_mul(regs[a * QW + lane], regs[b * QW + lane]); break;
-            case AOP_ISZERO: v = (regs[a * QW + lane] == 0) ? 1 : 0; break;
-            default: emit(kind, regs[a * QW + lane]); continue;
-        }
-        regs[dst * QW + lane] = v;
-    }
+    air_interpret(D + ops_off, n_ops, D + params_off, regs, lane,
+                  [&](u32 col, bool next) { return gl_canon(P.trace_lde[(size_t)col * N + (next ? jn : jj)]); }, emit);
     // ---- permutation checks (permutation.rs:302-360) ----
     {
         for (u32 i = 0; i < nperm; i++) emit(AK_FIRST, gl_sub(P.zs_lde[(size_t)i * N + jj], 1));

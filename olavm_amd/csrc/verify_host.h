@@ -445,10 +445,9 @@ struct Consumer {
 struct GpChallenge { u64 beta, gamma; };
 struct CtlVar { GpChallenge ch; const HTwc* twc; };
 
-inline Ext2 eval_lincol(const HLinCol& c, const std::vector<u64>& v, int ncols) {
+inline Ext2 eval_lincol(const HLinCol& c, const std::vector<u64>& v) {
     Ext2 s = ext_make(0, 0);
     for (const auto& t : c.terms) {
-        if (t.first >= (u64)ncols) throw OlaError(OLA_E_INVALID_ARG, "AIR-set blob: a lookup column names a column beyond its table");
         s = ext_add(s, ext_scalar_mul(ext_at(v, (size_t)t.first), gl_canon(t.second)));
     }
     return ext_add(s, ext_from(gl_canon(c.constant)));
@@ -458,33 +457,19 @@ inline Ext2 eval_lincol(const HLinCol& c, const std::vector<u64>& v, int ncols) 
 inline void eval_vanishing_poly(const HTable& air, int num_challenges, const WOpenings& op, const u64* params, const std::vector<u64>& perm_challenges,
                                 const std::vector<CtlVar>& ctl_vars, Consumer& consumer) {
     const Ext2 zero = ext_make(0, 0), one = ext_make(1, 0);
-    std::vector<Ext2> reg((size_t)std::max(air.n_regs, 0), zero);
-    const size_t nregs = reg.size(), ncols = (size_t)air.ncols;
+    std::vector<Ext2> reg((size_t)air.n_regs, zero);
     for (size_t i = 0; i + 1 < air.ops.size(); i += 2) {
-        const u64 w0 = air.ops[i], imm = air.ops[i + 1];
-        const int opc = (int)(w0 & 0xff), kind = (int)((w0 >> 8) & 0xff);
-        const size_t dst = (size_t)((w0 >> 16) & 0xffff), a = (size_t)((w0 >> 32) & 0xffff), b = (size_t)((w0 >> 48) & 0xffff);
-        auto regs_ok = [&](bool d, bool ra, bool rb) {
-            if ((d && dst >= nregs) || (ra && a >= nregs) || (rb && b >= nregs)) throw OlaError(OLA_E_INVALID_ARG, "AIR-set blob: a constraint program names a register beyond n_regs");
-        };
-        switch (opc) {
-            case AOP_LOCAL: case AOP_NEXT:
-                regs_ok(true, false, false);
-                if (a >= ncols) throw OlaError(OLA_E_INVALID_ARG, "AIR-set blob: a constraint program names a column beyond its table");
-                reg[dst] = ext_at(opc == AOP_LOCAL ? op.local : op.next, a);
-                break;
-            case AOP_CONST: regs_ok(true, false, false); reg[dst] = ext_from(gl_canon(imm)); break;
-            case AOP_PARAM:
-                regs_ok(true, false, false);
-                if (a >= (size_t)air.n_params) throw OlaError(OLA_E_INVALID_ARG, "AIR-set blob: a constraint program names a parameter beyond n_params");
-                reg[dst] = ext_from(gl_canon(params[a]));
-                break;
-            case AOP_ADD: regs_ok(true, true, true); reg[dst] = ext_add(reg[a], reg[b]); break;
-            case AOP_SUB: regs_ok(true, true, true); reg[dst] = ext_sub(reg[a], reg[b]); break;
-            case AOP_MUL: regs_ok(true, true, true); reg[dst] = ext_mul(reg[a], reg[b]); break;
-            case AOP_EMIT: regs_ok(false, true, false); consumer.emit(kind, reg[a]); break;
-            case AOP_ISZERO: regs_ok(true, true, false); reg[dst] = (reg[a].a == 0 && reg[a].b == 0) ? one : zero; break;
-            default: throw OlaError(OLA_E_INVALID_ARG, "AIR-set blob: unknown constraint operation");
+        const AirOp o = air_op(air.ops[i], air.ops[i + 1]);      // validated by parse_airset: what it names exists
+        switch (o.op) {
+            case AOP_LOCAL: reg[o.dst] = ext_at(op.local, o.a); break;
+            case AOP_NEXT: reg[o.dst] = ext_at(op.next, o.a); break;
+            case AOP_CONST: reg[o.dst] = ext_from(gl_canon(o.imm)); break;
+            case AOP_PARAM: reg[o.dst] = ext_from(gl_canon(params[o.a])); break;
+            case AOP_ADD: reg[o.dst] = ext_add(reg[o.a], reg[o.b]); break;
+            case AOP_SUB: reg[o.dst] = ext_sub(reg[o.a], reg[o.b]); break;
+            case AOP_MUL: reg[o.dst] = ext_mul(reg[o.a], reg[o.b]); break;
+            case AOP_EMIT: consumer.emit(o.kind, reg[o.a]); break;
+            case AOP_ISZERO: reg[o.dst] = (reg[o.a].a == 0 && reg[o.a].b == 0) ? one : zero; break;
         }
     }
     const int nperm = air.num_permutation_batches(num_challenges);
@@ -500,7 +485,6 @@ inline void eval_vanishing_poly(const HTable& air, int num_challenges, const WOp
                 const u64* ch = perm_challenges.data() + 2 * ((size_t)i * num_challenges + (size_t)(inst % num_challenges));
                 Ext2 l = zero, r = zero;
                 for (size_t k = pair.size(); k-- > 0;) {
-                    if (pair[k].first >= ncols || pair[k].second >= ncols) throw OlaError(OLA_E_INVALID_ARG, "AIR-set blob: a permutation pair names a column beyond its table");
                     l = ext_add(ext_scalar_mul(l, ch[0]), ext_at(op.local, (size_t)pair[k].first));
                     r = ext_add(ext_scalar_mul(r, ch[0]), ext_at(op.local, (size_t)pair[k].second));
                 }
@@ -515,10 +499,10 @@ inline void eval_vanishing_poly(const HTable& air, int num_challenges, const WOp
         const HTwc& twc = *ctl_vars[i].twc;
         auto combine = [&](const std::vector<u64>& v) {
             Ext2 acc = zero;
-            for (size_t k = twc.columns.size(); k-- > 0;) acc = ext_add(ext_scalar_mul(acc, ch.beta), eval_lincol(twc.columns[k], v, air.ncols));
+            for (size_t k = twc.columns.size(); k-- > 0;) acc = ext_add(ext_scalar_mul(acc, ch.beta), eval_lincol(twc.columns[k], v));
             return ext_add(acc, ext_from(ch.gamma));
         };
-        auto filter = [&](const std::vector<u64>& v) { return twc.has_filter ? eval_lincol(twc.filter, v, air.ncols) : one; };
+        auto filter = [&](const std::vector<u64>& v) { return twc.has_filter ? eval_lincol(twc.filter, v) : one; };
         auto select = [&](Ext2 f, Ext2 x) { return ext_sub(ext_add(ext_mul(f, x), one), f); };
         const Ext2 lz = ext_at(op.zs, (size_t)nperm + i), nz = ext_at(op.zs_next, (size_t)nperm + i);
         consumer.emit(AK_FIRST, ext_sub(lz, select(filter(op.local), combine(op.local))));

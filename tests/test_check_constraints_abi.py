@@ -97,6 +97,31 @@ def test_table_mask_beyond_the_set_is_refused(lib, instance):
         assert rc == OLA_E_INVALID_ARG and b"table_mask" in lib.ola_gpu_last_error()
 
 
+def test_a_program_that_names_a_register_beyond_n_regs_is_refused_before_a_device_is_looked_for(lib, instance):
+    """the parser every entry point shares holds the constraint programs to their tables: the caller's error, device or not"""
+    from olavm_amd.air import ola_tables as T
+    from olavm_amd.backend import U64P
+    traces, params = instance
+    a = _args(traces)
+    table = T.ola_stark(range_bits=4, limb_bits=2).tables[0]
+    ops, n_regs = table.compile()
+    at = 4 + len(table.words()) - 2 * len(ops)                # the first op of table 0
+    bad = a["blob"].copy()
+    w0 = int(ops[0][0])
+    assert int(bad[at]) == w0 and w0 & 0xff != 7             # not an emit: it writes dst
+    bad[at] = (w0 & ~(0xffff << 16)) | (int(n_regs) << 16)
+    p = bad.ctypes.data_as(U64P)
+
+    def call(blob_p):
+        return lib.ola_check_constraints(None, blob_p, bad.size, a["ptrs"], a["logs"], params.ctypes.data_as(U64P), None, a["mask"], a["out"], 8,
+                                         C.byref(a["n_out"]))
+    assert call(p) == OLA_E_INVALID_ARG and b"AIR-set blob" in lib.ola_gpu_last_error()
+    flags = (C.c_uint8 * 12)()
+    assert lib.ola_air_kernels_available(p, bad.size, flags, 12) == OLA_E_INVALID_ARG and b"AIR-set blob" in lib.ola_gpu_last_error()
+    assert lib.ola_air_kernels_available(a["blob"].ctypes.data_as(U64P), bad.size, flags, 12) == 0
+    assert a["n_out"].value == 77 and all(f.rows_failing == 0 for f in a["out"])
+
+
 def test_no_cpu_fallback_without_device(lib, instance):
     """A context cannot be created without a device (ola_gpu_init answers OLA_E_NO_DEVICE): a well-formed call then reports the
     same instead of evaluating anything on the host, and writes nothing."""

@@ -133,6 +133,25 @@ def test_arguments_are_checked_before_a_device_is_looked_for(lib, call):
     assert s["n_out"].value == 77 and s["width"].value == 99 and list(s["totals"]) == [5, 5, 5, 5]
 
 
+def test_a_column_beyond_its_table_in_another_lookup_is_refused_before_a_device_is_looked_for(lib, call):
+    """the parser every entry point shares holds every lookup to its tables, not only the one asked about"""
+    from olavm_amd.air import ola_tables as T
+    from olavm_amd.backend import U64P
+    airset = T.ola_stark(range_bits=4, limb_bits=2)
+    blob = np.ascontiguousarray(airset.blob(), dtype=np.uint64)
+    side = airset.ctls[0].looking_tables[0]
+    assert side.columns[0].terms
+    at = 4 + sum(len(t.words()) for t in airset.tables) + 1 + 2 + 1     # lookup 0: count of looking sides | table, columns | terms | column
+    assert int(blob[at]) == side.columns[0].terms[0][0]
+    blob[at] = airset.tables[side.table].ncols
+    p = blob.ctypes.data_as(U64P)
+    assert call(airset=p, lookup=16) == OLA_E_INVALID_ARG and b"AIR-set blob" in lib.ola_gpu_last_error()
+    flags = (C.c_uint8 * 12)()
+    assert lib.ola_air_kernels_available(p, blob.size, flags, 12) == OLA_E_INVALID_ARG and b"AIR-set blob" in lib.ola_gpu_last_error()
+    s = call.state
+    assert s["n_out"].value == 77 and s["width"].value == 99 and list(s["totals"]) == [5, 5, 5, 5]
+
+
 def test_a_lookup_wider_than_the_struct_is_refused(lib, call):
     from olavm_amd.air.dsl import AirSet, AirTable, Col, CrossTableLookup, TableWithColumns
     from olavm_amd.backend import OLA_LOOKUP_MAX_VALUES, U64P
