@@ -1,6 +1,7 @@
 """The whole-proof entry point from the reference's own trace type -- per table a list of columns, every column its own allocation
 (circuits/src/stark/prover.rs:79-83, plonky2/field/src/polynomial/mod.rs:24-26) -- through ola_prove_with_traces_cols, the three
-upload paths of olavm_amd/csrc/upload.h, and the `timed!` scopes handed back for the caller's TimingTree (ola_gpu_scope_times)."""
+upload paths of olavm_amd/csrc/upload.h, and the `timed!` scopes handed back for the caller's TimingTree (ola_gpu_scope_times).
+The exact `link_bytes` of a staged run: tests/noncanonical_cases.link_bytes_model(), held to upload_stats() by tests/test_gpu_noncanonical_traces.py."""
 import numpy as np
 import pytest
 
