@@ -183,7 +183,7 @@ void check_constraints(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airse
         const PermDesc pd = build_perm_desc(air, perm_sets[t], nch);
         const int nperm = pd.nperm();
         HostSpan perm_tot = tm.host(std::max(1, nperm));
-        u64* tot = tm.alloc(pscan_tot_stride(n) * std::max<size_t>(1, jobs[t].size()));
+        u64* tot = tm.alloc(scan_tot_stride(n) * std::max<size_t>(1, jobs[t].size()));
         if (nperm) {
             u64* tmpcol = tm.alloc(n);
             u64* d_pd = tm.upload(pd.words);
@@ -519,11 +519,8 @@ void check_lookup(DeviceCtx* ctx, const u64* airset, size_t airset_words, const 
     const dim3 grid((unsigned)widest, (unsigned)sides.size());
     hipLaunchKernelGGL(lk_count_kernel, grid, dim3(256), 0, ctx->stream, d_ent, d_desc, d_counts);
     launches++;
-    {
-        const size_t bytes = exclusive_sum_tmp_bytes(n_blocks + 1);
-        exclusive_sum_dev(ctx->stream, mem.alloc_bytes(bytes), bytes, d_counts, d_offs, n_blocks + 1);
-        library_calls++;
-    }
+    ExclusiveSumU32(mem, n_blocks + 1).run(ctx->stream, d_counts, d_offs, n_blocks + 1);
+    library_calls++;
     HostSpan h = mem.host(2);
     HIP_CHECK(hipMemcpyAsync(h.data(), d_offs + looked_block0, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_CHECK(hipMemcpyAsync(h.data() + 1, d_offs + n_blocks, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -546,8 +543,7 @@ void check_lookup(DeviceCtx* ctx, const u64* airset, size_t airset_words, const 
     {
         u64* keys = mem.alloc(N);
         u64* keys_sorted = mem.alloc(N);
-        const size_t bytes = sort_pairs_tmp_bytes(N);
-        void* tmp = mem.alloc_bytes(bytes);
+        SortPairsU64 sort(mem, N);
         for (u32 w = width; w-- > 0;) {
             const u64* in = planes + (size_t)w * N;
             if (w + 1 != width) {
@@ -555,7 +551,7 @@ void check_lookup(DeviceCtx* ctx, const u64* airset, size_t airset_words, const 
                 launches++;
                 in = keys;
             }
-            sort_pairs_dev(ctx->stream, tmp, bytes, in, keys_sorted, idx_a, idx_b, N);
+            sort.run(ctx->stream, in, keys_sorted, idx_a, idx_b);
             library_calls++;
             std::swap(idx_a, idx_b);
         }
@@ -569,13 +565,12 @@ void check_lookup(DeviceCtx* ctx, const u64* airset, size_t airset_words, const 
     u32* mpos = (u32*)mem.alloc_bytes(((size_t)N + 1) * 4);
     unsigned long long* d_totals = (unsigned long long*)mem.alloc(4);
     HIP_CHECK(hipMemsetAsync(d_totals, 0, 32, ctx->stream));
-    const size_t scan_bytes = exclusive_sum_tmp_bytes(2 * ((size_t)N + 1));
-    void* scan_tmp = mem.alloc_bytes(scan_bytes);
+    ExclusiveSumU32 scan(mem, 2 * ((size_t)N + 1));                // both scans below, the second over half as many words
     hipLaunchKernelGGL(lk_boundary_kernel, dim3(nb1), dim3(256), 0, ctx->stream, planes, idx, N, width, n_looking, flags);
-    exclusive_sum_dev(ctx->stream, scan_tmp, scan_bytes, flags, sc, 2 * ((size_t)N + 1));
+    scan.run(ctx->stream, flags, sc, 2 * ((size_t)N + 1));
     hipLaunchKernelGGL(lk_run_start_kernel, dim3(nb), dim3(256), 0, ctx->stream, flags, sc, N, run_start);
     hipLaunchKernelGGL(lk_mismatch_kernel, dim3(nb1), dim3(256), 0, ctx->stream, sc, run_start, N, mism, d_totals);
-    exclusive_sum_dev(ctx->stream, scan_tmp, scan_bytes, mism, mpos, (size_t)N + 1);
+    scan.run(ctx->stream, mism, mpos, (size_t)N + 1);
     // ---- 4. the report
     const u32 cap_dev = std::min(cap, N);
     u64* d_out = mem.alloc(std::max<size_t>(1, (size_t)cap_dev * LK_REC_WORDS));

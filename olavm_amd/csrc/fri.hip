@@ -19,13 +19,14 @@
 
 #include <algorithm>
 #include <cstring>
-#include <deque>
 #include <vector>
 
 #include "../../include/ola_gpu.h"
+#include "dev_buf.h"
 #include "device_ctx.h"
 #include "eval_plan.h"
 #include "gl.cuh"
+#include "scan.cuh"
 #include "poseidon_host.h"
 #include "poseidon2_host.h"
 #include "blake3.cuh"
@@ -260,75 +261,6 @@ __global__ __launch_bounds__(256) void weight_kernel(u64* __restrict__ pa, u64* 
     pb[k] = d.b;
 }
 
-// Additive suffix scan over one plane of base elements, 3 phases; blocks of SCAN_B elements.
-#define SCAN_B 2048
-__global__ __launch_bounds__(256) void scan_local_kernel(u64* __restrict__ d, size_t n, u64* __restrict__ block_tot) {
-    __shared__ u64 sh[256];
-    const size_t b0 = (size_t)blockIdx.x * SCAN_B;
-    const int t = threadIdx.x;
-    // thread t owns elements [b0 + 8t, b0 + 8t + 8); suffix order: later indices first
-    u64 v[8];
-    u64 run = 0;
-#pragma unroll
-    for (int i = 7; i >= 0; i--) {
-        const size_t k = b0 + (size_t)t * 8 + i;
-        run = gl_add(run, k < n ? d[k] : 0);
-        v[i] = run;
-    }
-    sh[t] = run;
-    __syncthreads();
-    // exclusive suffix scan of the thread totals (Hillis-Steele over 256 entries)
-    u64 incl = run;
-    for (int s = 1; s < 256; s <<= 1) {
-        const u64 other = (t + s < 256) ? sh[t + s] : 0;
-        __syncthreads();
-        incl = gl_add(incl, other);
-        sh[t] = incl;
-        __syncthreads();
-    }
-    const u64 excl = gl_sub(incl, run);
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const size_t k = b0 + (size_t)t * 8 + i;
-        if (k < n) d[k] = gl_add(v[i], excl);
-    }
-    if (t == 0) block_tot[blockIdx.x] = incl;
-}
-// single block: exclusive suffix scan of nblocks totals in place
-__global__ __launch_bounds__(256) void scan_totals_kernel(u64* __restrict__ tot, size_t nblocks) {
-    // exclusive suffix sum of the block totals, one workgroup: thread t owns a contiguous chunk (chunks in reverse order)
-    __shared__ u64 sh[256];
-    const int t = threadIdx.x;
-    const size_t per = (nblocks + 255) / 256;
-    // chunk of thread t counted from the END: indices [nblocks - hi_off, nblocks - lo_off)
-    const size_t lo_off = (size_t)t * per < nblocks ? (size_t)t * per : nblocks;
-    const size_t hi_off = lo_off + per < nblocks ? lo_off + per : nblocks;
-    u64 run = 0;
-    for (size_t o = lo_off; o < hi_off; o++) run = gl_add(run, tot[nblocks - 1 - o]);
-    sh[t] = run;
-    __syncthreads();
-    u64 incl = run;
-    for (int s = 1; s < 256; s <<= 1) {
-        const u64 other = (t >= s) ? sh[t - s] : 0;
-        __syncthreads();
-        incl = gl_add(incl, other);
-        sh[t] = incl;
-        __syncthreads();
-    }
-    u64 acc = (t > 0) ? sh[t - 1] : 0;
-    for (size_t o = lo_off; o < hi_off; o++) {
-        const size_t i = nblocks - 1 - o;
-        const u64 v = tot[i];
-        tot[i] = acc;
-        acc = gl_add(acc, v);
-    }
-}
-__global__ __launch_bounds__(256) void scan_add_kernel(u64* __restrict__ d, size_t n, const u64* __restrict__ tot) {
-    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    d[k] = gl_add(d[k], tot[k / SCAN_B]);
-}
-
 // final[k] = sum_b w_b * S_b[k] * z_b^-k  (k >= 1), final[0] = 0.  S planes as produced by compose/weight/scan.
 // fa/fb have length N >= n and are zero beyond n.
 __global__ __launch_bounds__(256) void finalize_kernel(const u64* __restrict__ S, size_t n, ExtPow zi0, ExtPow zi1, ExtPow zi2,
@@ -413,74 +345,6 @@ __global__ void gather_ext_leaves_kernel(const u64* __restrict__ pa, const u64* 
 }
 
 // ------------------------------------------------------------------------------------------------ host helpers
-// host memory that outlives the asynchronous copies issued from / into it: pinned when the context's arena has room
-struct HostSpan {
-    u64* p = nullptr; size_t n = 0;
-    u64& operator[](size_t i) const { return p[i]; }
-    u64* data() const { return p; }
-    size_t size() const { return n; }
-    u64* begin() const { return p; }
-    u64* end() const { return p + n; }
-};
-struct DevBuf {
-    DeviceCtx* ctx;
-    std::vector<void*> ptrs;
-    // Host staging of asynchronous copies (descriptors, power tables, index lists, read-backs): lives as long as the scope, whose
-    // destructor drains the stream first -- so an upload needs no synchronisation of its own (each one stalled the host's
-    // run-ahead: 14 of the 22 synchronisations per table were of this kind; the small tables are bound by exactly that latency).
-    // Pinned (the context's arena, DeviceCtx::pinned_alloc) while it has room, pageable otherwise.
-    std::deque<std::vector<u64>> hosts;
-    size_t pinned_mark;
-    struct Pending { void* dst; const u64* src; size_t bytes; };
-    std::vector<Pending> pending;      // read-backs that landed in pinned memory and still have to reach the caller's buffer
-    const bool use_pinned;             // false: a scope that outlives its call (OlaFri) -- the arena is a stack and is left to the calls
-    HostSpan host(size_t elems) {
-        if (use_pinned)
-            if (void* p = ctx->pinned_alloc(std::max<size_t>(1, elems) * 8)) return {(u64*)p, elems};
-        hosts.emplace_back(std::max<size_t>(1, elems));
-        return {hosts.back().data(), elems};
-    }
-    u64* upload(const std::vector<u64>& v) {
-        HostSpan h = host(v.size());
-        std::copy(v.begin(), v.end(), h.begin());
-        u64* d = alloc(std::max<size_t>(1, v.size()));
-        if (!v.empty()) HIP_CHECK(hipMemcpyAsync(d, h.data(), v.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-        return d;
-    }
-    // device -> the caller's (pageable) buffer, complete after the next synchronisation + collect(): through pinned memory, so
-    // that the copy is really asynchronous
-    void readback(void* dst, const void* src_dev, size_t bytes) {
-        if (!bytes) return;
-        if (void* p = use_pinned ? ctx->pinned_alloc(bytes) : nullptr) {
-            HIP_CHECK(hipMemcpyAsync(p, src_dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
-            pending.push_back({dst, (const u64*)p, bytes});
-        } else {
-            HIP_CHECK(hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        }
-    }
-    // after a synchronisation of the context's stream
-    void collect() {
-        for (const Pending& r : pending) memcpy(r.dst, r.src, r.bytes);
-        pending.clear();
-    }
-    void sync_collect() {
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        collect();
-    }
-    explicit DevBuf(DeviceCtx* c, bool pinned = true) : ctx(c), pinned_mark(c->pinned_top), use_pinned(pinned) {}
-    u64* alloc(size_t elems) { return (u64*)alloc_bytes(elems * 8); }
-    void* alloc_bytes(size_t bytes) {
-        void* p = ctx->alloc(bytes);
-        ptrs.push_back(p);
-        return p;
-    }
-    ~DevBuf() {
-        (void)hipStreamSynchronize(ctx->stream);
-        for (void* p : ptrs) ctx->free(p);
-        if (use_pinned) ctx->pinned_top = pinned_mark;      // (a scope that never took from the arena does not rewind it either)
-    }
-};
-
 // two-level power tables of `count` extension points, one host buffer, one upload (a table's opening phase needs six: zeta,
 // g zeta, g^-1 and their inverses -- six copies of a few hundred bytes each before round 6).  The first `nlimb` of them also get
 // the limb form of their hi table (eval_points_wide_kernel).
@@ -693,16 +557,6 @@ static void eval_batch_collect_sharded(const EvalJob& job, const u64* recv, size
     }
 }
 
-static void scan_plane(DevBuf& mem, u64* plane, size_t n, u64* tot) {
-    DeviceCtx* ctx = mem.ctx;
-    const size_t nblocks = (n + SCAN_B - 1) / SCAN_B;
-    hipLaunchKernelGGL(scan_local_kernel, dim3((unsigned)nblocks), dim3(256), 0, ctx->stream, plane, n, tot);
-    if (nblocks > 1) {
-        hipLaunchKernelGGL(scan_totals_kernel, dim3(1), dim3(256), 0, ctx->stream, tot, nblocks);
-        hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, plane, n, tot);
-    }
-}
-
 struct ByteWriter {
     std::vector<uint8_t>& b;
     int bytes_hash = 0;        // digest_wire_bytes: Blake3 digests are 32 bytes, Keccak digests 25 (BytesHash::to_bytes), written as they are; 0: a HashOut is 4 canonical words
@@ -888,14 +742,11 @@ static u64* final_poly_coeffs(DevBuf& keep, DevBuf& tmp, const FriOracles& o, co
                        o.quot->coeffs, Q, (int)o.nperm, n, d_apow, napow, S);
     const int l1 = W + Z, l2 = Z - (int)o.nperm;
     const bool use2 = l2 > 0;
-    u64* tot = tmp.alloc((n + SCAN_B - 1) / SCAN_B + 1);
-    for (int b = 0; b < 3; b++) {
-        if (b == 2 && !use2) continue;
+    const int live = use2 ? 3 : 2;                                          // batches whose planes of S are used: adjacent, from 0
+    for (int b = 0; b < live; b++)
         hipLaunchKernelGGL(weight_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, S + 2 * b * n, S + (2 * b + 1) * n,
                            n, pts.zpow[b]);
-        scan_plane(tmp, S + 2 * b * n, n, tot);
-        scan_plane(tmp, S + (2 * b + 1) * n, n, tot);
-    }
+    scan_inclusive<ScanSum, true>(ctx->stream, S, n, 2 * (size_t)live, tmp.alloc(2 * (size_t)live * scan_tot_stride(n)));
     // weights: ((q0 * alpha^l1) + q1) * alpha^l2 + q2   (oracle.rs:212-213)
     const Ext2 w2 = ext_make(1, 0);
     const Ext2 w1 = use2 ? ext_pow(alpha, (u64)l2) : ext_make(1, 0);

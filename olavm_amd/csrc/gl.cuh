@@ -15,7 +15,7 @@
 
 namespace ola {
 
-typedef unsigned long long u64;
+typedef unsigned long long u64;   // dev_buf.h (host only, includes nothing of the kernels) repeats this typedef: change both
 typedef unsigned int u32;
 
 static const u64 GL_P = 0xFFFFFFFF00000001ull;

@@ -4,6 +4,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "dev_buf.h"
 #include "device_ctx.h"
 #include "gl.cuh"
 
@@ -25,13 +26,21 @@ struct PermutedPair {
 };
 void permuted_cols_batch_dev(DeviceCtx* ctx, size_t n, const u64* const* tables, size_t n_tables, const PermutedPair* pairs, size_t n_pairs);
 
-// The radix sort and the prefix sum of this unit for a caller outside it (ola_check_lookup, check.hip): one stable sort pass of
-// (64-bit key, 32-bit payload) pairs over all 64 key bits, and the exclusive sum of n 32-bit words.  The caller owns the
-// temporary storage (*_tmp_bytes says how much; never 0); everything is enqueued on `stream`, nothing synchronises.  n >= 1.
-size_t sort_pairs_tmp_bytes(size_t n);
-void sort_pairs_dev(hipStream_t stream, void* tmp, size_t tmp_bytes, const u64* keys_in, u64* keys_out, const u32* payload_in,
-                    u32* payload_out, size_t n);
-size_t exclusive_sum_tmp_bytes(size_t n);
-void exclusive_sum_dev(hipStream_t stream, void* tmp, size_t tmp_bytes, const u32* in, u32* out, size_t n);
+// The radix sort and the prefix sum of this unit for a caller outside it (ola_check_lookup, check.hip), in the shape of
+// rocprim_ops.h: sized once, temporary storage from the caller's DevBuf, any number of runs, everything enqueued on `stream` and
+// nothing synchronises.  SortPairsU64: one stable pass over n (64-bit key, 32-bit payload) pairs over all 64 key bits.
+// ExclusiveSumU32: the exclusive sum of n <= max_n 32-bit words.  n >= 1.
+struct SortPairsU64 {
+    size_t n, bytes = 0;
+    void* tmp = nullptr;
+    SortPairsU64(DevBuf& mem, size_t n);
+    void run(hipStream_t stream, const u64* keys_in, u64* keys_out, const u32* payload_in, u32* payload_out);
+};
+struct ExclusiveSumU32 {
+    size_t bytes = 0;
+    void* tmp = nullptr;
+    ExclusiveSumU32(DevBuf& mem, size_t max_n);
+    void run(hipStream_t stream, const u32* in, u32* out, size_t n);
+};
 
 }  // namespace ola

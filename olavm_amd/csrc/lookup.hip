@@ -1,7 +1,7 @@
 // Device-side `permuted_cols`: the permuted input / permuted table columns of the Halo2-style lookup
 // argument that the range-check, bitwise and program tables carry (reference: circuits/src/stark/lookup.rs:68-132, called
 // from generation/builtin.rs:121-200 and generation/prog.rs).  Own translation unit: rocPRIM (radix sort, scans) is needed
-// here and in tablegen.hip only; what the two share of it is rocprim_scratch.h.
+// here and in tablegen.hip only; what the two share of it is rocprim_ops.h.
 //
 // The reference walks the two SORTED columns with one sequential merge loop that keeps a stack of "unused" table values:
 //   table value not wanted by any input  -> push;   repeated input (its table entry is already taken) -> pop, or, with
@@ -24,7 +24,7 @@
 #include <cstring>
 
 #include "lookup.h"
-#include "rocprim_scratch.h"
+#include "rocprim_ops.h"
 
 namespace ola {
 
@@ -214,13 +214,13 @@ __global__ __launch_bounds__(256) void fill_kernel(PairArgs a, u32 n, u32 count,
 
 // One batch of at most kMaxBatch pairs of n rows.  tables[k]: the distinct table columns (any words), sorted once each;
 // table_of[p]: which of them pair p looks into.  Enqueued on the context's stream; `mem` is released by the caller.
-void permuted_batch(DeviceCtx* ctx, Scratch& mem, u32 n, const u64* const* tables, u32 n_tables, const PermutedPair* pairs_in,
+void permuted_batch(DeviceCtx* ctx, DevBuf& mem, u32 n, const u64* const* tables, u32 n_tables, const PermutedPair* pairs_in,
                     const u32* table_of, u32 pairs) {
     hipStream_t stream = ctx->stream;
     // ---- 1. canonical, sorted: every distinct table once, every pair's inputs into its permuted_inputs
     u64* canon = mem.alloc<u64>((size_t)std::max(pairs, n_tables) * n);
     u64* st = mem.alloc<u64>((size_t)n_tables * n);
-    SortU64 sort(mem, stream, n);
+    SortU64 sort(mem, n);
     CanonArgs ca = {};
     for (u32 k = 0; k < n_tables; k++) ca.src[k] = tables[k];
     hipLaunchKernelGGL(canon_kernel, dim3(blocks(n), n_tables), dim3(256), 0, stream, ca, canon, n);
@@ -242,7 +242,7 @@ void permuted_batch(DeviceCtx* ctx, Scratch& mem, u32 n, const u64* const* table
     u32* other_tab = mem.alloc<u32>((size_t)pairs * n);
     u32* ev_base = mem.alloc<u32>(kMaxBatch + 1);
     hipLaunchKernelGGL(classify_kernel, dim3(blocks(2 * (size_t)n), pairs), dim3(256), 0, stream, a, pairs, n, flags, other_in, other_tab);
-    scan_exclusive(mem, stream, flags, sc, 0u, n_flags, rocprim::plus<u32>());
+    ExclusiveSum<u32>(mem, n_flags).run(stream, flags, sc, n_flags);
     hipLaunchKernelGGL(event_base_kernel, dim3(1), dim3(64), 0, stream, sc, pairs, n, ev_base);
     u32 base_host[kMaxBatch + 1];
     HIP_CHECK(hipMemcpyAsync(base_host, ev_base, (pairs + 1) * sizeof(u32), hipMemcpyDeviceToHost, stream));
@@ -267,20 +267,16 @@ void permuted_batch(DeviceCtx* ctx, Scratch& mem, u32 n, const u64* const* table
     u32* ev_sc = mem.alloc<u32>(2 * ((size_t)count + 1));
     hipLaunchKernelGGL(place_events_kernel, dim3(blocks(2 * (size_t)n), pairs), dim3(256), 0, stream, pairs, n, flags, sc, other_in, other_tab,
                        ev_base, delta, src, ev_pair);
-    scan_inclusive_by_key(mem, stream, ev_pair, delta, s, count, rocprim::plus<int>());
+    ScanInclusiveByKey<int> scan_events(mem, count);
+    scan_events.run(stream, ev_pair, delta, s, rocprim::plus<int>());
     hipLaunchKernelGGL(clamp_min_kernel, dim3(blocks(count)), dim3(256), 0, stream, s, count, clamped);
-    scan_inclusive_by_key(mem, stream, ev_pair, clamped, runmin, count, rocprim::minimum<int>());
+    scan_events.run(stream, ev_pair, clamped, runmin, rocprim::minimum<int>());
     hipLaunchKernelGGL(level_kernel, dim3(blocks((size_t)count + 1)), dim3(256), 0, stream, delta, s, runmin, ev_pair, ev_base, count, level_bits,
                        key, ident, ev_flags);
-    {
-        size_t bytes = 0;
-        HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, key, key_sorted, ident, ev_sorted, count, 0, level_bits + pair_bits, stream));
-        void* tmp = mem.alloc<unsigned char>(bytes);
-        HIP_CHECK(rocprim::radix_sort_pairs(tmp, bytes, key, key_sorted, ident, ev_sorted, count, 0, level_bits + pair_bits, stream));
-    }
+    SortPairs<u32>(mem, count, level_bits + pair_bits).run(stream, key, key_sorted, ident, ev_sorted, level_bits + pair_bits);
     hipLaunchKernelGGL(pair_kernel, dim3(blocks((size_t)count + 1)), dim3(256), 0, stream, a, key_sorted, ev_sorted, count, level_bits, delta, src,
                        ev_flags + count + 1);
-    scan_exclusive(mem, stream, ev_flags, ev_sc, 0u, 2 * ((size_t)count + 1), rocprim::plus<u32>());
+    ExclusiveSum<u32>(mem, 2 * ((size_t)count + 1)).run(stream, ev_flags, ev_sc, 2 * ((size_t)count + 1));
     // ---- 4. leftovers
     u32* slots = mem.alloc<u32>((size_t)pairs * n);
     u64* values = mem.alloc<u64>((size_t)pairs * n);
@@ -315,7 +311,7 @@ void permuted_cols_batch_dev(DeviceCtx* ctx, size_t n_, const u64* const* tables
             if (k == n_tabs) tabs[n_tabs++] = t;
             table_of[p] = k;
         }
-        Scratch mem(ctx);
+        DevBuf mem(ctx);
         permuted_batch(ctx, mem, n, tabs, n_tabs, pairs + first, table_of, count);
         HIP_CHECK(hipGetLastError());
     }
@@ -327,23 +323,20 @@ void permuted_cols_dev(DeviceCtx* ctx, const u64* inputs, const u64* table, size
 }
 
 // ------------------------------------------------------------------------------------------------ sort / scan for check.hip
-// the key + payload variant of SortU64 (rocPRIM's radix sort is stable: equal keys keep the order of their payloads)
-size_t sort_pairs_tmp_bytes(size_t n) {
-    size_t bytes = 0;
-    HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, (const u64*)nullptr, (u64*)nullptr, (const u32*)nullptr, (u32*)nullptr, n, 0, 64, (hipStream_t) nullptr));
-    return std::max<size_t>(bytes, 8);
+// the shape of rocprim_ops.h with external linkage: the pair sort over all 64 key bits, the 32-bit exclusive sum
+SortPairsU64::SortPairsU64(DevBuf& mem, size_t n_) : n(n_) {
+    HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, (const u64*)nullptr, (u64*)nullptr, (const u32*)nullptr, (u32*)nullptr, n, 0, 64, mem.ctx->stream));
+    tmp = mem.alloc_bytes(bytes);
 }
-void sort_pairs_dev(hipStream_t stream, void* tmp, size_t tmp_bytes, const u64* keys_in, u64* keys_out, const u32* payload_in, u32* payload_out,
-                    size_t n) {
-    HIP_CHECK(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys_in, keys_out, payload_in, payload_out, n, 0, 64, stream));
+void SortPairsU64::run(hipStream_t stream, const u64* keys_in, u64* keys_out, const u32* payload_in, u32* payload_out) {
+    HIP_CHECK(rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, payload_in, payload_out, n, 0, 64, stream));
 }
-size_t exclusive_sum_tmp_bytes(size_t n) {
-    size_t bytes = 0;
-    HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, (const u32*)nullptr, (u32*)nullptr, 0u, n, rocprim::plus<u32>(), (hipStream_t) nullptr));
-    return std::max<size_t>(bytes, 8);
+ExclusiveSumU32::ExclusiveSumU32(DevBuf& mem, size_t max_n) {
+    HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, (const u32*)nullptr, (u32*)nullptr, 0u, max_n, rocprim::plus<u32>(), mem.ctx->stream));
+    tmp = mem.alloc_bytes(bytes);
 }
-void exclusive_sum_dev(hipStream_t stream, void* tmp, size_t tmp_bytes, const u32* in, u32* out, size_t n) {
-    HIP_CHECK(rocprim::exclusive_scan(tmp, tmp_bytes, in, out, 0u, n, rocprim::plus<u32>(), stream));
+void ExclusiveSumU32::run(hipStream_t stream, const u32* in, u32* out, size_t n) {
+    HIP_CHECK(rocprim::exclusive_scan(tmp, bytes, in, out, 0u, n, rocprim::plus<u32>(), stream));
 }
 
 }  // namespace ola

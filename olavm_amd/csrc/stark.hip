@@ -34,6 +34,8 @@
 #include "airset_host.h"
 #include "air_interp.cuh"
 #include "airq.cuh"
+#include "dev_buf.h"
+#include "scan.cuh"
 #include "upload.h"
 
 namespace ola {
@@ -152,92 +154,11 @@ __global__ __launch_bounds__(256) void perm_factor_kernel(const u64* __restrict_
     out[i] = gl_mul(num, gl_inv(den));
 }
 
-// multiplicative inclusive prefix scan, 3 phases, blocks of 2048
-#define PSCAN_B 2048
-// (the scan kernels take one column per blockIdx.y: data at d + y*n, block totals at block_tot + y*tot_stride)
-__global__ __launch_bounds__(256) void pscan_local_kernel(u64* __restrict__ d_all, size_t n, u64* __restrict__ tot_all, size_t tot_stride) {
-    __shared__ u64 sh[256];
-    u64* __restrict__ d = d_all + (size_t)blockIdx.y * n;
-    u64* __restrict__ block_tot = tot_all + (size_t)blockIdx.y * tot_stride;
-    const size_t b0 = (size_t)blockIdx.x * PSCAN_B;
-    const int t = threadIdx.x;
-    u64 v[8];
-    u64 run = 1;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const size_t k = b0 + (size_t)t * 8 + i;
-        run = gl_mul(run, k < n ? d[k] : 1);
-        v[i] = run;
-    }
-    sh[t] = run;
-    __syncthreads();
-    u64 incl = run;
-    for (int s = 1; s < 256; s <<= 1) {
-        const u64 other = (t >= s) ? sh[t - s] : 1;
-        __syncthreads();
-        incl = gl_mul(incl, other);
-        sh[t] = incl;
-        __syncthreads();
-    }
-    const u64 excl = (t > 0) ? sh[t - 1] : 1;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const size_t k = b0 + (size_t)t * 8 + i;
-        if (k < n) d[k] = gl_mul(v[i], excl);
-    }
-    if (t == 255) block_tot[blockIdx.x] = incl;
-}
-// exclusive running product of the block totals, one workgroup: each thread owns a contiguous chunk, chunk totals
-// are combined with a Hillis-Steele scan in LDS
-__global__ __launch_bounds__(256) void pscan_totals_kernel(u64* __restrict__ tot_all, size_t nblocks, size_t tot_stride) {
-    __shared__ u64 sh[256];
-    u64* __restrict__ tot = tot_all + (size_t)blockIdx.y * tot_stride;
-    const int t = threadIdx.x;
-    const size_t per = (nblocks + 255) / 256;
-    const size_t lo = (size_t)t * per, hi = lo + per < nblocks ? lo + per : nblocks;
-    u64 run = 1;
-    for (size_t i = lo; i < hi; i++) run = gl_mul(run, tot[i]);
-    sh[t] = run;
-    __syncthreads();
-    u64 incl = run;
-    for (int s = 1; s < 256; s <<= 1) {
-        const u64 other = (t >= s) ? sh[t - s] : 1;
-        __syncthreads();
-        incl = gl_mul(incl, other);
-        sh[t] = incl;
-        __syncthreads();
-    }
-    u64 acc = (t > 0) ? sh[t - 1] : 1;
-    for (size_t i = lo; i < hi; i++) {
-        const u64 v = tot[i];
-        tot[i] = acc;
-        acc = gl_mul(acc, v);
-    }
-}
-__global__ __launch_bounds__(256) void pscan_apply_kernel(u64* __restrict__ d_all, size_t n, const u64* __restrict__ tot_all, size_t tot_stride) {
-    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    u64* __restrict__ d = d_all + (size_t)blockIdx.y * n;
-    const u64* __restrict__ tot = tot_all + (size_t)blockIdx.y * tot_stride;
-    d[k] = gl_mul(d[k], tot[k / PSCAN_B]);
-}
 // exclusive form: out[0] = 1, out[i] = incl[i-1]
 __global__ __launch_bounds__(256) void shift_right_kernel(const u64* __restrict__ incl, u64* __restrict__ out, size_t n) {
     const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     out[k] = k ? incl[k - 1] : 1;
-}
-
-// running products of `ncols` adjacent columns (n each) in place; tot: scratch of ncols * pscan_tot_stride(n) words
-static size_t pscan_tot_stride(size_t n) { return (n + PSCAN_B - 1) / PSCAN_B + 1; }
-static void product_scan_inclusive(DeviceCtx* ctx, u64* cols, size_t n, u64* tot, size_t ncols = 1) {
-    if (ncols == 0) return;
-    const size_t nblocks = (n + PSCAN_B - 1) / PSCAN_B, ts = pscan_tot_stride(n);
-    hipLaunchKernelGGL(pscan_local_kernel, dim3((unsigned)nblocks, (unsigned)ncols), dim3(256), 0, ctx->stream, cols, n, tot, ts);
-    if (nblocks > 1) {
-        hipLaunchKernelGGL(pscan_totals_kernel, dim3(1, (unsigned)ncols), dim3(256), 0, ctx->stream, tot, nblocks, ts);
-        hipLaunchKernelGGL(pscan_apply_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)ncols), dim3(256), 0, ctx->stream, cols, n, tot, ts);
-    }
 }
 
 // Lagrange selector polynomials in coefficient form: L_0 = (1/n) sum X^k ; L_{n-1} = (1/n) sum g^k X^k
@@ -540,11 +461,11 @@ struct ZFlags {
 };
 
 // One permutation batch (permutation.rs:103-187): num / den of every row, then their running product, in `col`; the batch's Z
-// column is that product moved down one row.  tot: pscan_tot_stride(n) words.
+// column is that product moved down one row.  tot: scan_tot_stride(n) words.
 static void perm_z_batch(DeviceCtx* ctx, const DevTable& tv, const u64* d_batch, unsigned b, u64* col, u64* tot, unsigned* d_zero_den) {
     const size_t n = tv.n();
     hipLaunchKernelGGL(perm_factor_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, tv.vals, n, d_batch, col, b, d_zero_den);
-    product_scan_inclusive(ctx, col, n, tot);
+    scan_inclusive<ScanProduct, false>(ctx->stream, col, n, 1, tot);
 }
 
 // compute_permutation_z_polys: zcols[nperm][n]
@@ -560,7 +481,7 @@ static void perm_z_columns(DeviceCtx* ctx, DevBuf& mem, const DevTable& tv, cons
 }
 
 // The table's columns of cross_table_lookup_data (cross_table_lookup.rs:224-311), zcols[cd.ncols][n]: one launch per step for all
-// of them.  tot: cd.ncols * pscan_tot_stride(n) words.
+// of them.  tot: cd.ncols * scan_tot_stride(n) words.
 static void ctl_z_columns(DeviceCtx* ctx, DevBuf& mem, const DevTable& tv, const CtlDesc& cd, u64* zcols, u64* tot, unsigned* d_bad_filter) {
     if (!cd.ncols) return;
     const size_t n = tv.n();
@@ -568,7 +489,7 @@ static void ctl_z_columns(DeviceCtx* ctx, DevBuf& mem, const DevTable& tv, const
     u64* d_index = mem.upload(cd.index);
     hipLaunchKernelGGL(ctl_factor_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)cd.npairs()), dim3(256), 0, ctx->stream, tv.vals, n, d_words,
                        d_index, d_index + cd.ncols, zcols, d_bad_filter);
-    product_scan_inclusive(ctx, zcols, n, tot, cd.ncols);
+    scan_inclusive<ScanProduct, false>(ctx->stream, zcols, n, cd.ncols, tot);
 }
 
 // ---- quotient (prover.rs:571-705) ----
@@ -838,7 +759,7 @@ static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuCo
     // CTL Z's are computed untimed in cross_table_lookup_data, cross_table_lookup.rs:224-311 -- here both happen in this scope)
     std::unique_ptr<PhaseTimer> ph(new PhaseTimer(ctx, nperm > 0 ? "    compute permutation Z(x) polys" : "    compute CTL Z(x) polys"));
     u64* zvals = mem.alloc((size_t)nz * n);
-    u64* tot = mem.alloc(pscan_tot_stride(n) * std::max<size_t>(1, ctl.size()));
+    u64* tot = mem.alloc(scan_tot_stride(n) * std::max<size_t>(1, ctl.size()));
     const ZFlags zf(ctx, mem, table_index);
     perm_z_columns(ctx, mem, tv, pd, zvals, tot, zf.zero_den());
     ctl_z_columns(ctx, mem, tv, cd, zvals + (size_t)nperm * n, tot, zf.bad_filter());
@@ -951,7 +872,7 @@ void perm_z_host(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airset, siz
     const DevTable tv = upload_table(ctx, mem, trace_cols, air.ncols, log_n);
     u64* z = mem.alloc((size_t)pd.nperm() * tv.n());
     const ZFlags zf(ctx, mem, (int)table);
-    perm_z_columns(ctx, mem, tv, pd, z, mem.alloc(pscan_tot_stride(tv.n())), zf.zero_den());
+    perm_z_columns(ctx, mem, tv, pd, z, mem.alloc(scan_tot_stride(tv.n())), zf.zero_den());
     zf.fetch(ctx);
     hand_back(ctx, mem, z_out, z, (size_t)pd.nperm() * tv.n(), zf);
 }
@@ -971,7 +892,7 @@ void ctl_z_host(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airset, size
     const DevTable tv = upload_table(ctx, mem, trace_cols, air.ncols, log_n);
     u64* z = mem.alloc(cd.ncols * tv.n());
     const ZFlags zf(ctx, mem, (int)table);
-    ctl_z_columns(ctx, mem, tv, cd, z, mem.alloc(cd.ncols * pscan_tot_stride(tv.n())), zf.bad_filter());
+    ctl_z_columns(ctx, mem, tv, cd, z, mem.alloc(cd.ncols * scan_tot_stride(tv.n())), zf.bad_filter());
     zf.fetch(ctx);
     hand_back(ctx, mem, z_out, z, cd.ncols * tv.n(), zf);
 }

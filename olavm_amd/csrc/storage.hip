@@ -1,6 +1,6 @@
 // The account-storage tree and the storage-access table on the device (ola_generate_storage_trace), and the Poseidon table at its
 // padded height (ola_generate_poseidon_table).  Part of ola_gpu.hip's translation unit, behind merkle.hip (the permutation and its
-// constants) and fri.hip (DevBuf); tablegen_api.hip, further down in that unit, holds the two entry points with the other generators'.
+// constants) and dev_buf.h (DevBuf); tablegen_api.hip, further down in that unit, holds the two entry points with the other generators'.
 //
 // The tree is the one of builtins/storage/storage_access_stark.rs:110-334: 256 levels, the key's bits (four limbs, most significant
 // first) choose the child, an inner node is Poseidon(left || right || 0,0,0,0)[0..4], the lowest level hashes the two 4-word values

@@ -41,7 +41,7 @@ void generate_cmp_trace_dev(DeviceCtx* ctx, const u64* ops, size_t n_ops, u64* o
 // are device memory, every table is 2^small_trace_log_n(rows) high with rows = n_cells, the sum of 1 + len / 8 over the calls (the
 // caller's validation pass computed it, and checked every psdn_row + len / 8 against the Poseidon table's height), n_chunks.  psdn is the
 // resident Poseidon table, 134 x 2^psdn_log_n; n_chunks <= 2^psdn_log_n.  The tape table waits for the stream once (the address bits
-// that size the sort) and once more, like the Poseidon-chunk table with calls, before its work space goes back to the pool (Scratch's
+// that size the sort) and once more, like the Poseidon-chunk table with calls, before its work space goes back to the pool (DevBuf's
 // destructor); the program-chunk table only enqueues.
 u32 small_trace_log_n(u64 rows);
 void generate_tape_trace_dev(DeviceCtx* ctx, const u64* cells, size_t n_cells, u64* out);

@@ -1,5 +1,5 @@
 // Device-side table generators (tablegen.h): kernels and launchers of nine tables.  Own translation unit, the second that pulls in
-// rocPRIM (sorts and scans, rocprim_scratch.h); the entry points that call it are tablegen_api.hip.
+// rocPRIM (sorts and scans, rocprim_ops.h); the entry points that call it are tablegen_api.hip.
 //
 // The range-check, bitwise and program tables from their primary columns (generation/builtin.rs:35-206, 249-316,
 // generation/prog.rs:18-156): one fill kernel per table writes every column that is not a permuted one -- thread = row, so
@@ -8,7 +8,7 @@
 #include <algorithm>
 
 #include "lookup.h"
-#include "rocprim_scratch.h"
+#include "rocprim_ops.h"
 #include "tablegen.h"
 #include "tablegen_columns.h"
 #include "tablegen_cpu_columns.h"
@@ -597,7 +597,7 @@ bool generate_prog_trace_steps_dev(DeviceCtx* ctx, const u64* steps, size_t n_st
                                    u64* out, u64* exec_rows) {
     const u32 n = 1u << log_n, n_steps = (u32)n_steps_;
     hipStream_t stream = ctx->stream;
-    Scratch mem(ctx);
+    DevBuf mem(ctx);
     u32 total = 0;
     u32* at = nullptr;
     if (n_steps) {
@@ -605,7 +605,7 @@ bool generate_prog_trace_steps_dev(DeviceCtx* ctx, const u64* steps, size_t n_st
         at = mem.alloc<u32>((size_t)n_steps + 1);
         hipLaunchKernelGGL(exec_count_kernel, dim3(blocks((size_t)n_steps + 1)), dim3(256), 0, stream, steps, n_steps, counts);
         HIP_CHECK(hipGetLastError());
-        scan_exclusive(mem, stream, counts, at, 0u, (size_t)n_steps + 1, rocprim::plus<u32>());
+        ExclusiveSum<u32>(mem, (size_t)n_steps + 1).run(stream, counts, at, (size_t)n_steps + 1);
         HIP_CHECK(hipMemcpyAsync(&total, at + n_steps, sizeof(u32), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
     }
@@ -633,7 +633,7 @@ void generate_memory_trace_dev(DeviceCtx* ctx, const u64* cells, size_t n_cells_
         HIP_CHECK(hipGetLastError());
         return;
     }
-    Scratch mem(ctx);
+    DevBuf mem(ctx);
     u64* canon = mem.alloc<u64>((size_t)tm::MEM_CELL_WORDS * n_cells);
     u64* keys = mem.alloc<u64>(2 * (size_t)n_cells);                       // a pass's keys, and where the sort leaves them
     u32* idx[2] = {mem.alloc<u32>(n_cells), mem.alloc<u32>(n_cells)};
@@ -646,23 +646,17 @@ void generate_memory_trace_dev(DeviceCtx* ctx, const u64* cells, size_t n_cells_
     HIP_CHECK(hipStreamSynchronize(stream));
     // least significant key first; rocPRIM's radix sort is stable, so each pass keeps the order of the ones before it
     const u32 order[tm::MEM_CELL_WORDS] = {CELL_IS_WRITE, CELL_VALUE, CELL_OP, CELL_CLK, CELL_ADDR};
-    // one temporary buffer for every pass: the largest any of their bit ranges asks for
-    u32 bits[tm::MEM_CELL_WORDS];
-    size_t tmp_bytes = 8;
-    for (u32 field : order) {
-        bits[field] = bit_length(host_stats[field]);
-        size_t bytes = 0;
-        if (bits[field]) HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, keys, keys + n_cells, idx[0], idx[1], n_cells, 0, bits[field], stream));
-        tmp_bytes = std::max(tmp_bytes, bytes);
-    }
-    void* tmp = mem.alloc<unsigned char>(tmp_bytes);
+    // one sort for every pass, sized for the widest of their bit ranges (rocPRIM's temporary storage grows with the number of digit
+    // places, ceil(bits / radix bits), so the widest range asks for the most)
+    u32 bits[tm::MEM_CELL_WORDS], widest = 0;
+    for (u32 field : order) widest = std::max(widest, bits[field] = bit_length(host_stats[field]));
+    SortPairs<u64> sort(mem, n_cells, std::max(widest, 1u));
     u32 cur = 0;
     for (u32 field : order) {
         if (bits[field] == 0) continue;                                     // every key of this field is 0
         hipLaunchKernelGGL(mem_pass_key_kernel, dim3(blocks(n_cells)), dim3(256), 0, stream, canon, n_cells, idx[cur], field, keys);
         HIP_CHECK(hipGetLastError());
-        size_t bytes = tmp_bytes;
-        HIP_CHECK(rocprim::radix_sort_pairs(tmp, bytes, keys, keys + n_cells, idx[cur], idx[cur ^ 1], n_cells, 0, bits[field], stream));
+        sort.run(stream, keys, keys + n_cells, idx[cur], idx[cur ^ 1], bits[field]);
         cur ^= 1;
     }
     const u32 first_heap = (u32)host_stats[MS_BELOW_HEAP];
@@ -690,7 +684,7 @@ void generate_tape_trace_dev(DeviceCtx* ctx, const u64* cells, size_t n_cells_, 
         HIP_CHECK(hipGetLastError());
         return;
     }
-    Scratch mem(ctx);
+    DevBuf mem(ctx);
     u64* keys = mem.alloc<u64>(2 * (size_t)n_cells);
     u32* idx = mem.alloc<u32>(2 * (size_t)n_cells);
     unsigned long long* stats = mem.alloc<unsigned long long>(1);
@@ -703,10 +697,7 @@ void generate_tape_trace_dev(DeviceCtx* ctx, const u64* cells, size_t n_cells_, 
     const u32 bits = bit_length(host_stats);
     const u32* order = nullptr;
     if (bits) {
-        size_t bytes = 0;
-        HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, keys, keys + n_cells, idx, idx + n_cells, n_cells, 0, bits, stream));
-        void* tmp = mem.alloc<unsigned char>(std::max<size_t>(bytes, 8));
-        HIP_CHECK(rocprim::radix_sort_pairs(tmp, bytes, keys, keys + n_cells, idx, idx + n_cells, n_cells, 0, bits, stream));
+        SortPairs<u64>(mem, n_cells, bits).run(stream, keys, keys + n_cells, idx, idx + n_cells, bits);
         order = idx + n_cells;
     }
     hipLaunchKernelGGL(tape_fill_kernel, dim3(blocks(n)), dim3(256), 0, stream, cells, order, n_cells, n, out);
@@ -718,14 +709,14 @@ void generate_tape_trace_dev(DeviceCtx* ctx, const u64* cells, size_t n_cells_, 
 void generate_poseidon_chunk_trace_dev(DeviceCtx* ctx, const u64* calls, size_t n_calls_, u64 rows, const u64* psdn, u32 psdn_log_n, u64* out) {
     const u32 n = 1u << small_trace_log_n(rows), n_calls = (u32)n_calls_;
     hipStream_t stream = ctx->stream;
-    Scratch mem(ctx);
+    DevBuf mem(ctx);
     u32* at = nullptr;
     if (n_calls) {
         u32* counts = mem.alloc<u32>((size_t)n_calls + 1);
         at = mem.alloc<u32>((size_t)n_calls + 1);
         hipLaunchKernelGGL(pchunk_count_kernel, dim3(blocks((size_t)n_calls + 1)), dim3(256), 0, stream, calls, n_calls, counts);
         HIP_CHECK(hipGetLastError());
-        scan_exclusive(mem, stream, counts, at, 0u, (size_t)n_calls + 1, rocprim::plus<u32>());
+        ExclusiveSum<u32>(mem, (size_t)n_calls + 1).run(stream, counts, at, (size_t)n_calls + 1);
     }
     hipLaunchKernelGGL(pchunk_fill_kernel, dim3(blocks(n)), dim3(256), 0, stream, calls, n_calls, at, (u32)rows, psdn, 1u << psdn_log_n, n, out);
     HIP_CHECK(hipGetLastError());

@@ -1,15 +1,15 @@
 """The Z-column kernels of olavm_amd/csrc/stark.hip -- perm_factor_kernel, ctl_factor_kernel, the three-phase product scan
-(pscan_local_kernel, pscan_totals_kernel, pscan_apply_kernel) and shift_right_kernel -- through ola_perm_z / ola_ctl_z at
-challenges the CALLER chooses, on tables no execution produces: every word of every Z column equals Python integers
+(scan.cuh: field_scan_tile_kernel, field_scan_totals_kernel, field_scan_apply_kernel over gl_mul) and shift_right_kernel --
+through ola_perm_z / ola_ctl_z at challenges the CALLER chooses, on tables no execution produces: every word of every Z column equals Python integers
 (tests/zcolumn_reference.py, pinned to the oracle prover by tests/test_zcolumn_reference.py).  No transcript is involved.
 
 Sizes, each the smallest at which a path exists (PSCAN_B = 2048 rows per scan block, 256 threads of eight rows):
   2^1   fewer rows than one thread's eight elements
   2^8   part of one scan block; one workgroup of the factor kernels
   2^11  exactly one full block; no totals pass
-  2^12  two blocks: totals and apply, two live threads of pscan_totals_kernel
+  2^12  two blocks: totals and apply, two live threads of field_scan_totals_kernel
   2^19  256 block totals, one per thread
-  2^20  512 block totals, two per thread: the only size at which pscan_totals_kernel loops
+  2^20  512 block totals, two per thread: the only size at which field_scan_totals_kernel loops
 `narrow` (tests/zcolumn_cases.py) runs at every size -- at 2^19 and 2^20 with one lookup, of which it is the filtered looking side
 (one pair of Z columns), and its one permutation batch --, `wide` at 2^8, 2^11 and 2^12, the twelve tables of an executed program at the sizes they have.  Up to 2^12
 every trace filler meets every challenge set; at 2^19 and 2^20 a random trace meets `random` and `zero_factor` with the zero in

@@ -6,7 +6,7 @@ import numpy as np
 from olavm_amd.air.dsl import AirSet, AirTable, Col, CrossTableLookup, TableWithColumns
 from tests.zcolumn_reference import P, ctl_sides, zero_factor_gamma
 
-PSCAN_B = 2048                                   # rows per block of the product scan (stark.hip)
+PSCAN_B = 2048                                   # rows per block of the product scan (kScanTile, scan.cuh)
 MAXW = 0xFFFFFFFFFFFFFFFF
 
 
