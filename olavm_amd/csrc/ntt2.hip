@@ -294,12 +294,40 @@ static bool ntt2_tform() {
     static const bool v = [] { const char* e = getenv("OLA_NTT2_TFORM"); return !(e && atoi(e) == 0); }();
     return v;
 }
+// OLA_NTT2_CLOSE6 (read once): 0 keeps the even split at every size (the A/B switch of the 6-bit closing pass), 2 also
+// gives 2^14 the 6-bit closing pass; anything else is the default below.
+static int ntt2_close6() {
+    static const int v = [] { const char* e = getenv("OLA_NTT2_CLOSE6"); return e ? atoi(e) : 1; }();
+    return v;
+}
+// Pass widths of the T-form path, first pass first.  The closing pass is the issue-bound one and its 6-bit form has no
+// multiplication between its rounds (ntt2t.cuh), so it gets 6 bits wherever the other L - 6 split evenly into the strided passes
+// with every width in 4..8 and every tile group addressable (lo - 4 >= 8 - R): 2^17 - 2^22 (2^20: 7+7+6, 2^22: 8+8+6) and
+// 2^25 - 2^28.  Every other size keeps the even split with the widest pass last.  So does 2^14, where 8+6 fits as well: two
+// launches of four workgroups per column are over before the widths matter, and 7+7 is the plan the transform matrix of the
+// suite pins at that size; OLA_NTT2_CLOSE6=2 runs it as 8+6.
+static std::vector<int> ntt2t_widths(int L) {
+    const int P = (L + 7) / 8;
+    std::vector<int> even = split_even(L, P);
+    std::reverse(even.begin(), even.end());
+    if (ntt2_close6() == 0 || (P < 3 && ntt2_close6() != 2)) return even;
+    std::vector<int> v = split_even(L - 6, P - 1);
+    std::reverse(v.begin(), v.end());
+    int lo = L;
+    for (int R : v) {
+        lo -= R;
+        if (R < 4 || R > 8 || lo - 4 < 8 - R) return even;
+    }
+    v.push_back(6);
+    return v;
+}
 template <int R, int MODE, bool INV, int LM>
 static void ntt2t_launch(const Ntt2Params& p0, size_t cols, size_t cosets, hipStream_t stream) {
     constexpr int CB = NTT2_STRIDED_COLS;   // every pass has sixteen load multipliers per thread to amortise
     Ntt2Params p = p0;
     p.ncols = cols;
-    const size_t lds_bytes = (size_t)ntt2_lds_elems<R, MODE>() * 8 + (R > 4 ? ((size_t)sizeof(TfTw) << R) : 0) + (LM == 1 ? ((size_t)8 << R) : 0);
+    constexpr bool tw1 = R > 4 && !(R == 6 && MODE != N2_STRIDED);   // a 6-bit closing pass shifts instead (no round-twiddle table)
+    const size_t lds_bytes = (size_t)ntt2_lds_elems<R, MODE>() * 8 + (tw1 ? ((size_t)sizeof(TfTw) << R) : 0) + (LM == 1 ? ((size_t)8 << R) : 0);
     dim3 grid((unsigned)(((size_t)1 << p.log_n) >> 12), (unsigned)((cols + CB - 1) / CB), (unsigned)cosets);
     hipLaunchKernelGGL((ntt2t_pass_kernel<R, MODE, INV, CB, LM>), grid, dim3(256), lds_bytes, stream, p);
 }
@@ -399,6 +427,7 @@ static void ntt2_run_group(NttTables& t, const u64* in, size_t in_col_stride, u6
         // T-form passes (ntt2t.cuh): pass i multiplies what it LOADS by w_{2^(L-lo)}^(a_i * K) -- the inter-pass twiddles in the
         // factorisation that depends on the pass's own index a_i only -- and, in a coset transform, by (s^(2^lo))^a_i; the closing
         // pass also takes the final scale and writes canonical words
+        Rs = ntt2t_widths(L);
         for (int i = 0; i < P; i++) {
             const int R = Rs[i];
             lo -= R;

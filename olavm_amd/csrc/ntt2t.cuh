@@ -72,6 +72,14 @@ constexpr int ntt2_lds_elems() {
     return (1 << (8 - R)) * 16 * ((1 << R) + 1);
 }
 
+// 6-bit closing pass, one wave's m_low = ML: round twiddle (a shift, tf_round6_pair) and exchange write of limbs 2h, 2h + 1 of the
+// thread's sixteen elements m = ML + 4j; dst points at the row's word ML
+template <int ML, bool INV>
+__device__ __forceinline__ void ntt2t_close6_put(const T4* x, int h, u64* dst) {
+    if (h == 0) tf_round6_pair<ML, INV, 0>(x, dst, 4);
+    else tf_round6_pair<ML, INV, 1>(x, dst, 4);
+}
+
 // ------------------------------------------------------------------------------------------------ the pass
 // LM: how an element is multiplied as it is loaded (see the header): 0 not at all (first pass of a plain transform), 1 by a
 // 2^R-entry table in LDS (strided passes), 2 by sixteen per-thread registers (closing passes; times the transform's final scale).
@@ -84,6 +92,10 @@ __device__ __forceinline__ void ntt2t_pass_body(const Ntt2Params& p) {
     constexpr int D = 8 - R;      // log2(tiles per workgroup)
     constexpr int G2 = 1 << K2;   // values per second-round group
     constexpr int ROW = (1 << R) + 1;
+    // A 6-bit closing pass gives each WAVE one m_low: its round twiddles w_64^(m_low * q1) are then compile-time powers of two
+    // (tf_round6_pair) instead of fifteen general multiplications per thread.  Lanes that share m_low sit in 64 different rows, so
+    // the tile is loaded a 512-byte row per wave instruction and passed through the exchange buffer once to reach this map.
+    constexpr bool CLOSE6 = (R == 6 && MODE != N2_STRIDED);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u64* lds = reinterpret_cast<u64*>(smem_raw);
     TfTw* tw1 = reinterpret_cast<TfTw*>(lds + ntt2_lds_elems<R, MODE>());
@@ -94,7 +106,7 @@ __device__ __forceinline__ void ntt2t_pass_body(const Ntt2Params& p) {
     const size_t col0 = (size_t)blockIdx.y * CB, coset = blockIdx.z;
     const int L = p.log_n, lo = p.lo;
 
-    if (R > 4) {
+    if (R > 4 && !CLOSE6) {
         if (tid < (1 << R)) tw1[tid] = tf_split_u64(p.tw_r[tid]);   // [q1][m_low]: w_{2^R}^(m_low*q1)
     }
 
@@ -107,6 +119,10 @@ __device__ __forceinline__ void ntt2t_pass_body(const Ntt2Params& p) {
         const int rest = tid >> 4;
         m_low = rest & ((1 << K2) - 1);
         tA = rest >> K2;
+    } else if (CLOSE6) {
+        m_low = __builtin_amdgcn_readfirstlane(tid >> 6);   // the wave's: a scalar
+        uA = tid & 15;
+        tA = (tid >> 4) & 3;
     } else {
         m_low = tid & ((1 << K2) - 1);
         uA = (tid >> K2) & 15;
@@ -166,7 +182,7 @@ __device__ __forceinline__ void ntt2t_pass_body(const Ntt2Params& p) {
         }
     }
 
-    if (LM == 1 || R > 4) __syncthreads();   // tw1 / lmtab visible
+    if (LM == 1 || (R > 4 && !CLOSE6)) __syncthreads();   // tw1 / lmtab visible
 
 #pragma unroll 1
     for (int cc = 0; cc < CB; cc++) {
@@ -188,6 +204,24 @@ __device__ __forceinline__ void ntt2t_pass_body(const Ntt2Params& p) {
                     const u32 off = (a0_lane + zlane) * 8u;
 #pragma unroll
                     for (int j = 0; j < 16; j++) raw[j] = *reinterpret_cast<const u64*>(base + j * jstride * 8 + off);
+                } else if (CLOSE6) {
+                    // wave w loads rows (tile w, u = k), k < 16, whole: uniform row base + the lane's word; raw words go through the
+                    // exchange buffer (row stride 65 words: the lanes of a wave, one row each, hit distinct bank pairs)
+                    const u32 wv = (u32)m_low, ln = (u32)tid & 63u;
+                    const u32 ntile = (blk << D) + wv;
+                    const u32 off = (ln + zlane) * 8u;
+#pragma unroll
+                    for (int k = 0; k < 16; k++) {
+                        size_t row;
+                        if (MODE == N2_BITREV_LAST) row = ((size_t)ntile << 4) + k;
+                        else row = ((size_t)rev_bits_c(k, 4) << (L - R - 4)) + bitrev32(ntile, L - R - 4);
+                        raw[k] = *reinterpret_cast<const u64*>(reinterpret_cast<const char*>(in + (row << R)) + off);
+                    }
+#pragma unroll
+                    for (int k = 0; k < 16; k++) lds[((wv << 4) + k) * ROW + ln] = raw[k];
+                    __syncthreads();
+#pragma unroll
+                    for (int j = 0; j < 16; j++) raw[j] = lds[((tA << 4) + uA) * ROW + (j << K2) + m_low];
                 } else {
 #pragma unroll
                     for (int j = 0; j < 16; j++) raw[j] = in[a0 + j * jstride];
@@ -204,7 +238,11 @@ __device__ __forceinline__ void ntt2t_pass_body(const Ntt2Params& p) {
                 }
             }
             tf_dft<4, INV>(x);
-            if (R > 4) {
+            if (CLOSE6) {
+#pragma unroll
+                for (int j = 0; j < 16; j++) tf_pin(x[j]);
+            }
+            if (R > 4 && !CLOSE6) {
 #pragma unroll
                 for (int j = 0; j < 16; j++) {
                     const int q1 = rev_bits_c(j, 4);
@@ -215,9 +253,19 @@ __device__ __forceinline__ void ntt2t_pass_body(const Ntt2Params& p) {
             // ------------------------------------------------------------ exchange, two limbs at a time (the buffer of ntt2_pass_body)
 #pragma unroll
             for (int h = 0; h < 2; h++) {
-                if (h == 1) __syncthreads();
+                if (h == 1 || CLOSE6) __syncthreads();   // (CLOSE6, h = 0: every thread has read its staged words back)
+                if (CLOSE6) {
+                    // the round twiddles are shifts by the wave's constants: one scalar branch per half, the products go straight to LDS
+                    u64* dst = lds + ((tA << 4) + uA) * ROW + m_low;
+                    switch (m_low) {
+                        case 0: ntt2t_close6_put<0, INV>(x, h, dst); break;
+                        case 1: ntt2t_close6_put<1, INV>(x, h, dst); break;
+                        case 2: ntt2t_close6_put<2, INV>(x, h, dst); break;
+                        default: ntt2t_close6_put<3, INV>(x, h, dst); break;
+                    }
+                }
 #pragma unroll
-                for (int j = 0; j < 16; j++) {
+                for (int j = 0; j < 16 && !CLOSE6; j++) {
                     const int m = (j << K2) + m_low;
                     const u64 v = (u64)(u32)x[j].v[2 * h] | ((u64)(u32)x[j].v[2 * h + 1] << 32);
                     if (MODE == N2_STRIDED) lds[pad1((((tA << R) + m) << 4) + uA)] = v;

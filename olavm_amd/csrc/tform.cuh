@@ -25,8 +25,17 @@ GL_HD u32 tf_alignbit(u32 hi, u32 lo, int s) {   // bits [s, s + 32) of hi:lo
 #endif
 }
 
+// A limb is an i32.  tests/host_tform_pow2_check.cpp defines OLA_TF_LIMB to a range-checked class (wide arithmetic that fails
+// when a limb leaves the signed 32-bit bound of tf_to_u64) and runs the same functions on it; that is why limbs convert to
+// integers by explicit casts only.
+#if defined(OLA_TF_LIMB)
+typedef OLA_TF_LIMB tf_limb;
+#else
+typedef i32 tf_limb;
+#endif
+
 struct T4 {
-    i32 v[4];
+    tf_limb v[4];
 };
 struct TfTw {   // a twiddle as its 24 / 24 / 16-bit pieces
     i32 w0, w1, w2, pad;
@@ -181,13 +190,42 @@ GL_HD T4 tf_sub_mul_pow2(const T4& a, const T4& b) {
     return o;
 }
 
+// x * 2^S for a compile-time S in [0, 192): what tf_sub_mul_pow2<S>(x, 0) computes.  S = 24q + r: r = 0 is a renaming of limbs (a
+// wrapped limb changes sign), r != 0 one shift-and-carry step that also re-normalises.  Needs |x_i| < 2^31; returns
+// |y_i| < 2^24 + |x|/2^(24-r)  (r != 0)  or |x| (r = 0).  Every limb of the result is a function of two limbs of x, so a caller
+// that wants only some of them (tf_round6_pair) pays for those: tf_mul_pow2_limb<S, T> is limb T.
+template <int S, int T>
+GL_HD tf_limb tf_mul_pow2_limb(const T4& x) {
+    static_assert(S >= 0 && S < 192 && T >= 0 && T < 4, "shift or limb out of range");
+    constexpr int q8 = S / 24, r = S % 24, q = q8 & 3;
+    constexpr int i = (T - q) & 3;   // the limb of x that lands in limb T
+    constexpr bool flip = (q8 >= 4) != (i + q >= 4);
+    tf_limb y = x.v[i];
+    if (r != 0) {
+        constexpr int k = 24 - r;
+        const i32 mask = (i32)((1 << k) - 1);
+        const tf_limb lo = (x.v[i] & mask) << r, hi = x.v[(i + 3) & 3] >> k;
+        y = (i == 0) ? lo - hi : lo + hi;
+    }
+    return flip ? -y : y;
+}
+template <int S>
+GL_HD T4 tf_mul_pow2(const T4& x) {
+    T4 o;
+    o.v[0] = tf_mul_pow2_limb<S, 0>(x);
+    o.v[1] = tf_mul_pow2_limb<S, 1>(x);
+    o.v[2] = tf_mul_pow2_limb<S, 2>(x);
+    o.v[3] = tf_mul_pow2_limb<S, 3>(x);
+    return o;
+}
+
 // x * w for a twiddle given as its pieces.  Needs |x_i| < 2^31 (the four 64-bit sums stay below 2^57); returns
 // |y_i| < 2^24 + 2^24 + 2^9.
 GL_HD T4 tf_mul(const T4& x_in, const TfTw& w) {
     T4 x = x_in;
     tf_pin(x);
     const i32 w0 = w.w0, w1 = w.w1, w2 = w.w2;
-    const i32 n2 = -x.v[2], n3 = -x.v[3];
+    const tf_limb n2 = -x.v[2], n3 = -x.v[3];
     // z_k = sum_{i+j=k} x_i w_j - sum_{i+j=k+4} x_i w_j
     i64 z[4];
     z[0] = (i64)x.v[0] * w0 + (i64)n3 * w1 + (i64)n2 * w2;
@@ -219,6 +257,38 @@ GL_HD constexpr int tf_root_exp(int k, bool inv) {
     int e = 39;
     for (int i = k; i < 6; i++) e = (2 * e) % 192;
     return inv ? (192 - e) % 192 : e;
+}
+
+// Round twiddles of a 64-point block split 16 x 4, for the elements m = ML + 4j (j < 16) of one row: after tf_dft<4> slot j
+// holds the first-round frequency q1 = bitrev_4(j), which is multiplied by w_64^(ML * q1) = 2^(tf_root_exp(6) * ML * q1 mod 192)
+// -- a compile-time power of two once ML is one (ntt2t.cuh gives each wave one ML and branches on it).  tf_round6_pair returns
+// limbs 2H and 2H + 1 of the sixteen products as the words the pass exchanges, out[j * stride] = limb 2H | limb 2H+1 << 32,
+// each stored as soon as it is made: products that leave the branches of a switch in registers cost copies (30 64-bit moves
+// and 38 more registers), and sixteen of them collected before their stores cost 26 registers.  Limb bounds: the slots arrive from tf_dft<4> on limbs below 2^24, so
+// below 2^28; a shift that is a multiple of 24 leaves them there (a renaming) and any other brings them below 2^24 + 2^27, so
+// the tf_dft<2> that follows returns limbs below 2^30 < 2^31 - 2^8 (tf_to_u64) with no tf_norm in any case;
+// tests/host_tform_pow2_check.cpp runs every exponent of both directions on range-checked limbs.  The pins are where tf_mul has
+// them (see tf_pin): the caller pins x before it branches (a pin inside a branch makes x a value that leaves it), the
+// products are pinned here.
+GL_HD void tf_pin2(tf_limb& a, tf_limb& b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(a), "+v"(b));
+#else
+    (void)a;
+    (void)b;
+#endif
+}
+template <int ML, bool INV, int H, int J = 0>
+GL_HD void tf_round6_pair(const T4* x, u64* out, int stride) {
+    static_assert(ML >= 0 && ML < 4 && (H == 0 || H == 1), "second-round index of a 6-bit pass, half of the limbs");
+    if constexpr (J < 16) {
+        constexpr int q1 = ((J & 1) << 3) | ((J & 2) << 1) | ((J & 4) >> 1) | ((J & 8) >> 3);
+        constexpr int S = (tf_root_exp(6, INV) * ML * q1) % 192;
+        tf_limb a = tf_mul_pow2_limb<S, 2 * H>(x[J]), b = tf_mul_pow2_limb<S, 2 * H + 1>(x[J]);
+        tf_pin2(a, b);
+        out[J * stride] = (u64)(u32)a | ((u64)(u32)b << 32);
+        tf_round6_pair<ML, INV, H, J + 1>(x, out, stride);
+    }
 }
 
 // In-register decimation-in-frequency transform of 2^K values, all twiddles powers of two; output index j holds X[bitrev_K(j)].

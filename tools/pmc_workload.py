@@ -12,7 +12,7 @@ torch.cuda.synchronize()      # the library runs on a stream of its own
 for _ in range(3):
     be.ntt_dev(OLA_NTT_EVALUATE, data.data_ptr(), out.data_ptr(), 22, 94, scratch_ptr=scratch.data_ptr())
 torch.cuda.synchronize()
-b = be.commit_dev(data.data_ptr(), 94, 19)      # 2^19: its pass kernels (6 + 6 + 7 bits) are not the 2^22 transform's (7 + 7 + 8)
+b = be.commit_dev(data.data_ptr(), 94, 19)      # 2^19: its pass kernels (6 + 7 + 6 bits, inverse and leaf order) are not the 2^22 transform's (8 + 8 + 6, natural order)
 torch.cuda.synchronize()
 b.free()
 be.close()
