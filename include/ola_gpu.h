@@ -59,8 +59,10 @@ extern "C" {
  * the reason of a refusal); so were the hasher OLA_HASH_KECCAK (KeccakGoldilocksConfig: Keccak-256 trees and challenger, 25-byte
  * digests) and the host entry points ola_keccak_hash_elements and ola_challenger_init_keccak; so were the OLA_FRI_* strategies and
  * the entry points ola_gpu_set_fri_reduction and ola_fri_reduction_arity_bits (FriReductionStrategy::Fixed and MinSize: an arity
- * per FRI layer, in the prover and in the verifier). */
+ * per FRI layer, in the prover and in the verifier); so were OlaGpuConfig.num_challenges 1..OLA_MAX_CHALLENGES (it had to be 2) and
+ * the host entry point ola_air_kernels_available_cfg (the generated kernels of a configuration's challenge count). */
 #define OLA_GPU_ABI_VERSION 7
+#define OLA_MAX_CHALLENGES 8 /* OlaGpuConfig.num_challenges: 1..8, the range the verifier reads */
 #define OLA_OK 0
 #define OLA_E_INVALID_ARG (-1)
 #define OLA_E_NO_DEVICE (-2)
@@ -86,7 +88,12 @@ typedef struct OlaGpuConfig {
                                  * proving.                                                                   */
     uint32_t fri_final_poly_bits;
     uint32_t num_query_rounds;  /* 28                                                                        */
-    uint32_t num_challenges;    /* 2                                                                         */
+    uint32_t num_challenges;    /* 2.  1..OLA_MAX_CHALLENGES (0 and 9 up: OLA_E_INVALID_ARG): the number of grand-product
+                                 * challenge sets, of CTL challenges and of alphas (prover.rs:360-367,425,
+                                 * cross_table_lookup.rs:182-188, permutation.rs:265-280), hence of Z columns per lookup side
+                                 * and of quotient polynomials.  Every entry point runs at the context's value; 2 and 3 have
+                                 * generated quotient kernels for the default table sets, the other counts run the
+                                 * interpreter kernel (ola_air_kernels_available_cfg).                          */
     uint32_t hasher;            /* GenericConfig::Hasher of the Merkle trees and the challenger (plonk/config.rs:112-161):
                                  * OLA_HASH_POSEIDON = PoseidonGoldilocksConfig (0, the default),
                                  * OLA_HASH_BLAKE3 = Blake3GoldilocksConfig.  InnerHasher (proof of work) is Poseidon in both.
@@ -550,7 +557,7 @@ typedef struct OlaConstraintFailure {
     uint32_t table;
     uint32_t section;           /* OLA_CHECK_AIR | OLA_CHECK_PERMUTATION | OLA_CHECK_LOOKUP                                   */
     uint32_t index;             /* AIR: emit ordinal; PERMUTATION: batch; LOOKUP: lookup index                                */
-    uint32_t kind;              /* AIR: OLA_CONSTRAINT_*; LOOKUP: challenge index                                             */
+    uint32_t kind;              /* AIR: OLA_CONSTRAINT_*; LOOKUP: challenge index, 0 .. num_challenges - 1                    */
     uint64_t first_row;         /* LOOKUP: selected rows on the looking side                                                  */
     uint64_t rows_failing;      /* LOOKUP: selected rows on the looked side                                                   */
 } OlaConstraintFailure;
@@ -1051,6 +1058,10 @@ int32_t ola_gpu_get_stream(OlaCtx* ctx, void** stream_out);
  * The environment variable OLA_AIR_KERNELS=interpreter disables the specialised kernels, =crosscheck runs both and fails
  * with OLA_E_INTERNAL if they disagree (test hooks). */
 int32_t ola_air_kernels_available(const uint64_t* airset, size_t airset_words, uint8_t* has_kernel, size_t ntables);
+/* The same for a context created with `cfg` (NULL: the defaults, i.e. ola_air_kernels_available): a kernel is generated for one
+ * num_challenges, so the answer depends on it.  Host only; OLA_E_INVALID_ARG for a configuration ola_gpu_init would refuse. */
+int32_t ola_air_kernels_available_cfg(const OlaGpuConfig* cfg, const uint64_t* airset, size_t airset_words, uint8_t* has_kernel,
+                                      size_t ntables);
 
 #ifdef __cplusplus
 }

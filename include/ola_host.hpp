@@ -88,6 +88,19 @@ struct StarkConfig {
     static StarkConfig standard_fast_config() { return StarkConfig{}; }
 };
 
+// Which tables of the AIR set have a generated quotient kernel under `c` (ola_air_kernels_available_cfg: host only; the
+// configuration's num_challenges decides -- a table without one runs the interpreter kernel, same bytes).
+inline std::vector<bool> air_kernels_available(const std::vector<uint64_t>& airset, size_t ntables,
+                                               const StarkConfig& c = StarkConfig::standard_fast_config()) {
+    OlaGpuConfig g{};
+    g.device = -1; g.stream = nullptr; g.rate_bits = c.rate_bits; g.cap_height = c.cap_height;
+    g.proof_of_work_bits = c.proof_of_work_bits; g.fri_arity_bits = c.fri_arity_bits; g.fri_final_poly_bits = c.fri_final_poly_bits;
+    g.num_query_rounds = c.num_query_rounds; g.num_challenges = c.num_challenges; g.hasher = c.hasher;
+    std::vector<uint8_t> flags(ntables, 0);
+    check(ola_air_kernels_available_cfg(&g, airset.data(), airset.size(), flags.data(), ntables));
+    return std::vector<bool>(flags.begin(), flags.end());
+}
+
 // One device context (replaces the reference's process-wide init_gpu()/GPU_LOCK, cfft/ntt/mod.rs:21-50).
 class Gpu {
 public:

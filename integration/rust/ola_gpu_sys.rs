@@ -12,6 +12,7 @@
 use std::os::raw::{c_char, c_void};
 
 pub const OLA_GPU_ABI_VERSION: i32 = 7;
+pub const OLA_MAX_CHALLENGES: u32 = 8;
 pub const OLA_OK: i32 = 0;
 pub const OLA_E_INVALID_ARG: i32 = -1;
 pub const OLA_E_NO_DEVICE: i32 = -2;
@@ -397,6 +398,8 @@ extern "C" {
     pub fn ola_set_shard_options(ctx: *mut OlaCtx, flags: u32) -> i32;
     pub fn ola_gpu_get_stream(ctx: *mut OlaCtx, stream_out: *mut *mut c_void) -> i32;
     pub fn ola_air_kernels_available(airset: *const u64, airset_words: usize, has_kernel: *mut u8, ntables: usize) -> i32;
+    pub fn ola_air_kernels_available_cfg(cfg: *const OlaGpuConfig, airset: *const u64, airset_words: usize, has_kernel: *mut u8,
+        ntables: usize) -> i32;
 }
 
 /// Non-zero status -> `anyhow::Error` carrying the library's message (the reference's `Result` / `ensure!` sites).

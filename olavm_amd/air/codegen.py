@@ -21,7 +21,7 @@ from .dsl import (OP_LOCAL, OP_NEXT, OP_CONST, OP_PARAM, OP_ADD, OP_SUB, OP_MUL,
                   KIND_ALL, KIND_TRANSITION, KIND_FIRST, KIND_LAST, P)
 
 D_ZH = 0          # D[0..8): 1/Z_H per coset
-D_W = 8           # D[8 .. 8+2K): alpha weights, challenge-major
+D_W = 8           # D[8 .. 8+CK): alpha weights, challenge-major (C challenges)
 
 
 def _lit(v):
@@ -71,8 +71,8 @@ ACC_REFOLD_EVERY = 480   # multiply-accumulates into one lazy sum before it is f
 
 
 class _Emitter:
-    def __init__(self, K):
-        self.lines, self.K, self.idx = [], K, 0
+    def __init__(self, K, nch=2):
+        self.lines, self.K, self.idx, self.nch = [], K, 0, nch
         self.n_all = self.n_trans = 0
         self.limb_src = []      # per limb slot (three descriptor words each, in the order the kernel uses them): the u64 word it is the limb form of
 
@@ -86,11 +86,11 @@ class _Emitter:
         if trans:
             self.n_trans += 1
             if self.n_trans % ACC_REFOLD_EVERY == 0:
-                self.add("AIRQ_REFOLD_TRANS;")
+                self.add("AIRQ_REFOLD_TRANS;" if self.nch == 2 else "AIRQ_REFOLD_N(T);")
         else:
             self.n_all += 1
             if self.n_all % ACC_REFOLD_EVERY == 0:
-                self.add("AIRQ_REFOLD_ALL;")
+                self.add("AIRQ_REFOLD_ALL;" if self.nch == 2 else "AIRQ_REFOLD_N(A);")
 
     def add(self, s):
         self.lines.append("    " + s)
@@ -102,9 +102,17 @@ class _Emitter:
             self.idx += 1
         else:
             i = index
-        sl = self.slot(D_W + i, D_W + self.K + i)     # the two challenges' weights, side by side in the limb area
-        self.add("AIRQ_W(%d); AIRQ_W(%d); %s" % (sl, sl + 1, W_MARK))
-        if kind == KIND_ALL:
+        sl = self.slot(*[D_W + c * self.K + i for c in range(self.nch)])     # the challenges' weights, side by side in the limb area
+        self.add(" ".join("AIRQ_W(%d);" % (sl + c) for c in range(self.nch)) + " " + W_MARK)
+        if self.nch != 2:
+            # the n-ary interface (airq.cuh): the value once, one multiply-accumulate per challenge
+            S = "T" if kind == KIND_TRANSITION else "A"
+            if kind == KIND_FIRST:
+                expr = "gl_mul(%s, lag_first)" % expr
+            elif kind == KIND_LAST:
+                expr = "gl_mul(%s, lag_last)" % expr
+            self.add("AIRQ_EMIT_N(%s, %s); %s" % (" ".join("AIRQ_TO(%s, %d, %d, %d)" % (S, c, i, sl + c) for c in range(self.nch)), expr, USE_MARK))
+        elif kind == KIND_ALL:
             self.add("AIRQ_EMIT_ALL(%d, %d, %d, %s); %s" % (i, sl, sl + 1, expr, USE_MARK))
         elif kind == KIND_TRANSITION:
             self.add("AIRQ_EMIT_TRANS(%d, %d, %d, %s); %s" % (i, sl, sl + 1, expr, USE_MARK))
@@ -149,6 +157,10 @@ CTL_REG_CELLS = int(os.environ.get("OLA_AIRQ_CTL_REG_CELLS", "12"))   # cells mo
 CTL_REG_MIN_USES = 6
 LDS_SLOTS = int(os.environ.get("OLA_AIRQ_LDS_SLOTS", "20"))       # lane-private LDS slots per thread (20 x 2 KB per workgroup: four workgroups per CU still fit in 160 KB)
 MIN_WAVES = int(os.environ.get("OLA_AIRQ_MIN_WAVES", "4"))        # waves per SIMD the kernels are compiled for (__launch_bounds__: 4 -> 128 VGPRs, 3 -> 168)
+# More than two challenges: six lazy sums and more (36 VGPRs at three, against 24) do not fit the 128 registers of four waves next to
+# the CPU, Poseidon and chunk tables' programs -- their kernels spilled 12 to 160 bytes of scratch per thread --, so those kernels
+# are compiled for three waves (168 VGPRs; three workgroups' LDS slots still fit).
+MIN_WAVES_WIDE = int(os.environ.get("OLA_AIRQ_MIN_WAVES_WIDE", "3"))
 ORDER_WINDOWS = (0, 2, 3, 5, 8)   # candidate evaluation orders of the constraint program: 0 = the reference's, W = greedy with a window of W constraints
 
 
@@ -332,16 +344,16 @@ def _table_kernel(airset, t, name, num_challenges=2, uses=None, ctl_regs=(), pla
     nperm = tab.num_permutation_batches(num_challenges)
     bs = tab.quotient_degree_factor
     K = num_emits(airset, t, num_challenges)
-    d_params = D_W + 2 * K
+    d_params = D_W + num_challenges * K
     d_perm = d_params + tab.n_params
     d_ctl = d_perm + 2 * nperm * bs
-    e = _Emitter(K)
-    e.add("AIRQ_PROLOGUE(%d)" % K)
+    e = _Emitter(K, num_challenges)
+    e.add("AIRQ_PROLOGUE(%d)" % K if num_challenges == 2 else "AIRQ_PROLOGUE_N(%d, %d)" % (K, num_challenges))
     nodes = tab.nodes
     LEAF = (OP_LOCAL, OP_NEXT, OP_CONST, OP_PARAM)
     use_lds = plan is not None and any(plan[0]) or plan is not None and any(plan[1])
     section = {"name": "program"}
-    BARRIER = "AIRQ_SEGMENT_BARRIER_C;" if use_lds else "AIRQ_SEGMENT_BARRIER;"
+    BARRIER = ("AIRQ_SEGMENT_BARRIER_C" if use_lds else "AIRQ_SEGMENT_BARRIER") + ("" if num_challenges == 2 else "N" if use_lds else "_N") + ";"
     state = {"seg": 0, "ops": 0, "local": {}, "cells": {}}      # seg: running index over ALL segments (program, permutation, lookups)
     if uses is not None:
         uses["segs"].append(set())
@@ -535,32 +547,36 @@ def _table_kernel(airset, t, name, num_challenges=2, uses=None, ctl_regs=(), pla
     assert e.idx == K, (e.idx, K)
     if plan is not None:
         check_plan(plan, seen)
-    e.add("AIRQ_EPILOGUE")
-    head = "// table %d (%s): %d columns, %d constraints, %d permutation Zs, %d CTL Zs, K = %d\n" % (
-        t, tab.name, tab.ncols, len(tab.emits), nperm, len(jobs), K)
-    src = head + "__global__ __launch_bounds__(AIRQ_THREADS, %d) void %s(QuotParams P) {\n%s\n}\n" % (MIN_WAVES, name, "\n".join(hoist_limb_loads(e.lines)))
+    e.add("AIRQ_EPILOGUE" if num_challenges == 2 else "AIRQ_EPILOGUE_N")
+    head = "// table %d (%s): %d columns, %d constraints, %d permutation Zs, %d CTL Zs, K = %d%s\n" % (
+        t, tab.name, tab.ncols, len(tab.emits), nperm, len(jobs), K, "" if num_challenges == 2 else ", %d challenges" % num_challenges)
+    src = head + "__global__ __launch_bounds__(AIRQ_THREADS, %d) void %s(QuotParams P) {\n%s\n}\n" % (
+        MIN_WAVES if num_challenges == 2 else MIN_WAVES_WIDE, name, "\n".join(hoist_limb_loads(e.lines)))
     src += "// limb slot -> the descriptor word it is the limb form of (the host appends the limb area in this order: the kernel reads it front to back)\n"
     src += "static const int %s_limb_src[%d] = {%s};\n" % (name, max(1, len(e.limb_src)), ", ".join(str(x) for x in e.limb_src) or "0")
     return src, K, len(e.limb_src)
 
 
-def generate(airsets):
-    """-> {file name: source}: one translation unit per distinct table signature of the given AirSets (compiled in
-    parallel by build()) plus air_registry.inc, the list stark.hip searches."""
+CHALLENGE_COUNTS = (2, 3)     # StarkConfig::num_challenges the default table sets get kernels for; other counts run the interpreter kernel
+
+
+def generate(airsets, challenge_counts=(2,)):
+    """-> {file name: source}: one translation unit per distinct (table signature, challenge count) of the given AirSets
+    (compiled in parallel by build()) plus air_registry.inc, the list stark.hip searches."""
     files, entries = {}, []
-    for s in airsets:
+    for nch, s in [(c, a) for c in challenge_counts for a in airsets]:
         for t in range(len(s.tables)):
-            sig = s.signature(t)
+            sig = s.signature(t, nch)
             name = "airq_%016x" % sig
             if name + ".hip" in files:
                 continue
-            src, K, nl = table_kernel(s, t, name, with_limbs=True)
+            src, K, nl = table_kernel(s, t, name, nch, with_limbs=True)
             tab = s.tables[t]
             files[name + ".hip"] = (
                 "// GENERATED by olavm_amd/air/codegen.py -- do not edit; regenerated by __graft_entry__.build().\n"
                 "#define AIRQ_GENERATED_TU 1\n#include \"../airq.cuh\"\nnamespace ola {\n" + src +
                 "extern const AirKernelEntry %s_entry;\nconst AirKernelEntry %s_entry = {0x%016Xull, %s, %d, %d, %d, \"%s\", %s_limb_src, %d};\n}  // namespace ola\n"
-                % (name, name, sig, name, K, tab.n_params, tab.num_permutation_batches(), tab.name, name, nl))
+                % (name, name, sig, name, K, tab.n_params, tab.num_permutation_batches(nch), tab.name, name, nl))
             entries.append(name)
     reg = "// GENERATED by olavm_amd/air/codegen.py -- do not edit.\n"
     reg += "".join("extern const AirKernelEntry %s_entry;\n" % n for n in entries)
@@ -578,7 +594,7 @@ def default_airsets():
 def write_default(gen_dir):
     """Writes the generated sources into gen_dir (only files whose content changed are touched, stale ones are removed);
     returns the sorted list of .hip translation units."""
-    files = generate(default_airsets())
+    files = generate(default_airsets(), CHALLENGE_COUNTS)
     os.makedirs(gen_dir, exist_ok=True)
     for f in os.listdir(gen_dir):
         if f not in files and not f.endswith(".o"):

@@ -310,19 +310,21 @@ class AirSet:
                 jobs += [t for t in c.looking_tables + [c.looked_table] if t.table == table]
         return jobs
 
-    def signature_words(self, table):
+    def signature_words(self, table, num_challenges=2):
         """What a specialised quotient kernel depends on: the table's description and the static part of its CTL jobs.
-        Hashed (FNV-1a over the little-endian bytes) on both sides of the C ABI to pair a blob with a generated kernel."""
-        w = list(self.tables[table].words())
-        jobs = self.ctl_jobs(table)
+        Hashed (FNV-1a over the little-endian bytes) on both sides of the C ABI to pair a blob with a generated kernel.
+        A challenge count other than two goes in front (a table without lookups and permutation pairs has the same words at
+        every count); two, the reference's standard configuration, keeps the words it has always had."""
+        w = ([] if num_challenges == 2 else [num_challenges]) + list(self.tables[table].words())
+        jobs = self.ctl_jobs(table, num_challenges)
         w.append(len(jobs))
         for j in jobs:
             w += j.words()[1:]          # without the table index
         return w
 
-    def signature(self, table):
+    def signature(self, table, num_challenges=2):
         h = 0xCBF29CE484222325
-        for x in self.signature_words(table):
+        for x in self.signature_words(table, num_challenges):
             for k in range(8):
                 h = ((h ^ ((int(x) >> (8 * k)) & 0xFF)) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
         return h

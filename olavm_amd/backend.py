@@ -294,6 +294,8 @@ def load_library():
     L.ola_gpu_selftest.argtypes = [C.c_void_p, C.c_uint64, U64P]
     L.ola_gpu_reserve.argtypes = [C.c_void_p, U64P, C.c_size_t, C.POINTER(C.c_uint32)]
     L.ola_air_kernels_available.argtypes = [U64P, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t]
+    L.ola_air_kernels_available_cfg.argtypes = [C.POINTER(OlaGpuConfig), U64P, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t]
+    L.ola_air_kernels_available_cfg.restype = C.c_int32
     L.ola_check_constraints.argtypes = [C.c_void_p, U64P, C.c_size_t, C.POINTER(C.POINTER(U64P)), C.POINTER(C.c_uint32), U64P, U64P, C.c_uint32,
                                         C.POINTER(OlaConstraintFailure), C.c_uint32, C.POINTER(C.c_uint32)]
     L.ola_check_constraints.restype = C.c_int32
@@ -334,6 +336,7 @@ EXPORTS = [
     "ola_open", "ola_fri_plan", "ola_fri_commit_begin", "ola_fri_commit_next_layer", "ola_fri_commit_finish", "ola_fri_query", "ola_fri_free",
     "ola_verify_all_proof", "ola_verify_opening",
     "ola_gpu_set_fri_reduction", "ola_fri_reduction_arity_bits",
+    "ola_air_kernels_available_cfg",
 ]
 
 # FriReductionStrategy (include/ola_gpu.h OLA_FRI_*)
@@ -375,6 +378,21 @@ def fri_reduction_arity_bits(reduction, degree_bits, **cfg):
     if code != 0:
         raise OlaGpuError(code, L.ola_gpu_last_error().decode())
     return [int(out[i]) for i in range(n_out.value)]
+
+
+def air_kernels_available(airset_blob, ntables, **cfg):
+    """ola_air_kernels_available_cfg: which tables of the AIR set have a generated quotient kernel for a context created with `cfg`
+    (the configuration's num_challenges decides).  Host only: needs no device."""
+    L = load_library()
+    c = OlaGpuConfig(-1, None, cfg.get("rate_bits", 3), cfg.get("cap_height", 4), cfg.get("proof_of_work_bits", 16),
+                     cfg.get("fri_arity_bits", 4), cfg.get("fri_final_poly_bits", 5), cfg.get("num_query_rounds", 28),
+                     cfg.get("num_challenges", 2), HASHERS[cfg.get("hasher", "poseidon")])
+    blob = np.ascontiguousarray(airset_blob, dtype=np.uint64)
+    flags = (C.c_uint8 * ntables)()
+    code = L.ola_air_kernels_available_cfg(C.byref(c), _p(blob), blob.size, flags, ntables)
+    if code != 0:
+        raise OlaGpuError(code, L.ola_gpu_last_error().decode())
+    return [bool(x) for x in flags]
 
 
 def describe_column(col):
@@ -631,6 +649,8 @@ class Backend:
         self.hasher = int(c.hasher)
         self.cap_height = c.cap_height
         self.rate_bits = c.rate_bits
+        self.num_challenges = int(c.num_challenges)
+        self._cfg = c
         self.ctx = C.c_void_p()
         if devices is not None:
             dv = (C.c_int32 * len(devices))(*[int(d) for d in devices])
@@ -1231,14 +1251,14 @@ class Backend:
         return self._zs_phase(self.lib.ola_ctl_z, airset_blob, table, trace, ctl_challenges, self.table_shape(airset_blob, table)["ctl_zs"])
 
     def quotient(self, airset_blob, table, trace_batch, zs_batch, perm_challenges, ctl_challenges, alphas, params, n):
-        """Coefficients of the 2 * quotient_degree_factor quotient chunk polynomials, [chunks][n]."""
+        """Coefficients of the num_challenges * quotient_degree_factor quotient chunk polynomials, [chunks][n]."""
         blob = np.ascontiguousarray(airset_blob, dtype=np.uint64)
         q = self.table_shape(airset_blob, table)["quotient_degree_factor"]
         pc = None if perm_challenges is None else np.ascontiguousarray(np.array(perm_challenges, dtype=np.uint64).reshape(-1))
         cc = np.ascontiguousarray(np.array(ctl_challenges, dtype=np.uint64).reshape(-1))
         al = np.ascontiguousarray(alphas, dtype=np.uint64)
         pr = None if params is None or len(params) == 0 else np.ascontiguousarray(params, dtype=np.uint64)
-        out = np.zeros((2 * q, n), dtype=np.uint64)
+        out = np.zeros((self.num_challenges * q, n), dtype=np.uint64)
         self._chk(self.lib.ola_quotient(self.ctx, _p(blob), blob.size, table, trace_batch.h, zs_batch.h, None if pc is None else _p(pc), _p(cc), _p(al),
                                         None if pr is None else _p(pr), _p(out)))
         return out
@@ -1529,10 +1549,11 @@ class Backend:
             return bytes(buf.raw[:need.value])
 
     def air_kernels_available(self, airset_blob, ntables):
-        """-> list of bool: which tables of the AIR set have a specialised quotient kernel in this build."""
+        """-> list of bool: which tables of the AIR set have a specialised quotient kernel in this build, at this context's
+        num_challenges (ola_air_kernels_available_cfg)."""
         blob = np.ascontiguousarray(airset_blob, dtype=np.uint64)
         flags = (C.c_uint8 * ntables)()
-        self._chk(self.lib.ola_air_kernels_available(_p(blob), blob.size, flags, ntables))
+        self._chk(self.lib.ola_air_kernels_available_cfg(C.byref(self._cfg), _p(blob), blob.size, flags, ntables))
         return [bool(x) for x in flags]
 
     def open(self, trace, zs, quot, num_permutation_zs, zeta):

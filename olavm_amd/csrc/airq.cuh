@@ -15,7 +15,7 @@ struct QuotParams {
     const u64* gN_lo; const u64* gN_hi; int gN_h;   // two-level powers of the order-N root
     const u64* desc;                                // per-proof descriptor (layout in build_quot_desc)
     u64 g_inv;                                      // last = g^-1 (prover.rs:617)
-    u64* out;                                       // [num_challenges][size]
+    u64* out;                                       // [num_challenges][out_plane]
     int n_regs;
     // a rank's share (coset partition): the buffers hold cosets [coset_first, ...), N is their column stride, `out` holds
     // `out_plane` values per challenge, and leaf j of the buffers is global leaf j + coset_first * n
@@ -27,7 +27,7 @@ struct QuotParams {
 };
 
 // Straight-line kernels printed by olavm_amd/air/codegen.py, one per table signature.  Descriptor D (u64 words):
-//   [0,8) 1/Z_H per coset | [8, 8+2K) alpha weights alpha_c^(K-1-i), challenge-major | params | permutation (beta,gamma)
+//   [0,8) 1/Z_H per coset | [8, 8+CK) alpha weights alpha_c^(K-1-i), challenge-major (C challenges) | params | permutation (beta,gamma)
 //   per batch slot | per CTL Z column: gamma, beta^0 .. beta^(ncol-1) | limb forms (three words each) of the alpha weights and
 //   beta powers in the order the kernel uses them (AirKernelEntry::limb_src).
 struct Acc160 { u64 lo, hi; u32 top; };   // sum of < 2^32 products of two u64
@@ -100,7 +100,7 @@ typedef const u64 __attribute__((address_space(4)))* airq_cptr;
 // bs_-aligned runs -- so every load is "uniform base + small lane offset" and its address lives in SGPRs (global_load ... v_off,
 // s[base]) instead of one VGPR pair per column and row.  Tables of fewer than 256 rows run one workgroup per coset (round 6:
 // they went to the interpreter kernel before -- 37 to 320 us per 8-row table, 1.5 ms for the Poseidon table's program).
-#define AIRQ_PROLOGUE(K_)                                                                                                  \
+#define AIRQ_PROLOGUE_HEAD(K_)                                                                                             \
     const u32 lane_ = threadIdx.x;                                                                                         \
     const u32 bs_ = blockDim.x;                                                                                            \
     const size_t jb_ = (size_t)blockIdx.x * bs_;                                                                           \
@@ -119,8 +119,16 @@ typedef const u64 __attribute__((address_space(4)))* airq_cptr;
     airq_cptr D = (airq_cptr)P.desc;                                                                                       \
     airq_gptr T_ = (airq_gptr)P.trace_lde;                                                                                 \
     airq_gptr Z_ = (airq_gptr)P.zs_lde;                                                                                    \
-    constexpr int AIRQ_K = (K_);                                                                                           \
+    constexpr int AIRQ_K = (K_);
+// Two challenges (the reference's standard configuration) keep the named accumulators their kernels were printed with; any
+// other count C is printed against the n-ary interface below: accA_[C] / accT_[C], indexed by constants only -- registers.
+#define AIRQ_PROLOGUE(K_)                                                                                                  \
+    AIRQ_PROLOGUE_HEAD(K_)                                                                                                 \
     AIRQ_ACC accA0 = {0, 0, 0}, accA1 = {0, 0, 0}, accT0 = {0, 0, 0}, accT1 = {0, 0, 0};
+#define AIRQ_PROLOGUE_N(K_, C_)                                                                                            \
+    AIRQ_PROLOGUE_HEAD(K_)                                                                                                 \
+    constexpr int AIRQ_NCH = (C_);                                                                                         \
+    AIRQ_ACC accA_[AIRQ_NCH] = {}, accT_[AIRQ_NCH] = {};
 // LDE values are canonical (the NTT writes canonical words)
 #ifdef AIRQ_TIMING_ONLY_L2_LOADS
 // Timing experiment (wrong results): every workgroup reads the first 2048 points of each column, so all cell loads hit L2 --
@@ -148,6 +156,7 @@ typedef const u64 __attribute__((address_space(4)))* airq_cptr;
 #define AIRQ_ACC_REDUCE(a) acc_reduce(a)
 #define AIRQ_REFOLD_ALL
 #define AIRQ_REFOLD_TRANS
+#define AIRQ_REFOLD_N(S)
 #define AIRQ_ACC_FIRST(a) (a).lo
 #else
 #define AIRQ_ACC Acc3
@@ -157,11 +166,16 @@ typedef const u64 __attribute__((address_space(4)))* airq_cptr;
 #define AIRQ_ACC_REDUCE(a) acc3_reduce(a)
 #define AIRQ_REFOLD_ALL { accA0 = acc3_init(acc3_reduce(accA0)); accA1 = acc3_init(acc3_reduce(accA1)); }
 #define AIRQ_REFOLD_TRANS { accT0 = acc3_init(acc3_reduce(accT0)); accT1 = acc3_init(acc3_reduce(accT1)); }
+#define AIRQ_REFOLD_N(S) { _Pragma("unroll") for (int c2_ = 0; c2_ < AIRQ_NCH; c2_++) acc##S##_[c2_] = acc3_init(acc3_reduce(acc##S##_[c2_])); }
 #define AIRQ_ACC_FIRST(a) (a).c0
 #endif
 // constraint i (its alpha power), limb slots s0 and s1 (the two challenges)
 #define AIRQ_EMIT_ALL(i, s0, s1, v) { const u64 v_ = (v); AIRQ_MAD(accA0, v_, 8 + (i), s0); AIRQ_MAD(accA1, v_, 8 + AIRQ_K + (i), s1); }
 #define AIRQ_EMIT_TRANS(i, s0, s1, v) { const u64 v_ = (v); AIRQ_MAD(accT0, v_, 8 + (i), s0); AIRQ_MAD(accT1, v_, 8 + AIRQ_K + (i), s1); }
+// n-ary form: AIRQ_EMIT_N(AIRQ_TO(S, c, i, s) ..., v) adds v times the weight of constraint i under challenge c (limb slot s) to the
+// sum S (A: all rows, T: transition) of every challenge named; v is evaluated once.
+#define AIRQ_TO(S, c, i, s) AIRQ_MAD(acc##S##_[c], v_, 8 + (c) * AIRQ_K + (i), s);
+#define AIRQ_EMIT_N(mads, ...) { const u64 v_ = (__VA_ARGS__); mads }
 // Segment boundary: the base pointers and the running accumulators pass through one opaque (empty) volatile asm.  The
 // compiler can then neither merge a re-load of a trace cell with the load of an earlier segment, nor start the loads of
 // this segment before the emits of the previous one are done -- the live ranges of re-loaded cells stay inside their
@@ -179,6 +193,15 @@ typedef const u64 __attribute__((address_space(4)))* airq_cptr;
 #define AIRQ_CACHE_PUT(s, v) (*(u64*)((char*)cache_ + coff_ + (s) * (AIRQ_THREADS * 8)) = (v))
 #define CL(s) (*(const u64*)((const char*)cache_ + coff_ + (s) * (AIRQ_THREADS * 8)))
 #define AIRQ_SEGMENT_BARRIER_C asm volatile("" : "+s"(T_), "+s"(Z_), "+s"(D), "+v"(AIRQ_ACC_FIRST(accA0)), "+v"(AIRQ_ACC_FIRST(accT0)), "+v"(coff_))
+#define AIRQ_SEGMENT_BARRIER_N asm volatile("" : "+s"(T_), "+s"(Z_), "+s"(D), "+v"(AIRQ_ACC_FIRST(accA_[0])), "+v"(AIRQ_ACC_FIRST(accT_[0])))
+#define AIRQ_SEGMENT_BARRIER_CN asm volatile("" : "+s"(T_), "+s"(Z_), "+s"(D), "+v"(AIRQ_ACC_FIRST(accA_[0])), "+v"(AIRQ_ACC_FIRST(accT_[0])), "+v"(coff_))
+#define AIRQ_EPILOGUE_N                                                                                                    \
+    {                                                                                                                      \
+        const u64 zh_inv = D[c_];                                                                                          \
+        _Pragma("unroll") for (int c2_ = 0; c2_ < AIRQ_NCH; c2_++)                                                         \
+            P.out[(size_t)c2_ * P.out_plane + j] =                                                                         \
+                gl_mul(gl_add(AIRQ_ACC_REDUCE(accA_[c2_]), gl_mul(z_last, AIRQ_ACC_REDUCE(accT_[c2_]))), zh_inv);          \
+    }
 #define AIRQ_EPILOGUE                                                                                                      \
     {                                                                                                                      \
         const u64 zh_inv = D[c_];                                                                                          \

@@ -125,7 +125,7 @@ void check_constraints(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airse
     const bool timing = ctx->timing;
     HAirSet set = parse_airset(airset, airset_words);
     const size_t nt = set.tables.size();
-    const int nch = two_challenges(cfg);
+    const int nch = (int)cfg.num_challenges;
     // challenges: a fresh transcript that has observed nothing (include/ola_gpu.h states the order)
     OlaChallenger ch;
     challenger_init(ch, (uint32_t)ctx->hasher);
@@ -203,7 +203,7 @@ void check_constraints(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airse
             unsigned* d_bad = (unsigned*)tm.alloc(1);      // a non-binary filter selects nothing here; the AIR section names the cell
             HIP_CHECK(hipMemsetAsync(d_bad, 0, 8, ctx->stream));
             u64* zc = tm.alloc(ctl.size() * n);
-            ctl_z_columns(ctx, tm, dev[t], build_ctl_desc(ctl), zc, tot, d_bad);
+            ctl_z_columns(ctx, tm, dev[t], build_ctl_desc(ctl, nch), zc, tot, d_bad);
             for (size_t j = 0; j < ctl.size(); j++)
                 HIP_CHECK(hipMemcpyAsync(&zl[j], zc + j * n + (n - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
         }

@@ -157,7 +157,7 @@ static OlaGpuConfig resolve_config(const OlaGpuConfig* cfg) {
     require(c.fri_arity_bits >= 1 && c.fri_arity_bits <= 8, "fri_arity_bits must be in 1..8");
     require(c.fri_final_poly_bits <= 16, "fri_final_poly_bits must be at most 16");
     require(c.num_query_rounds >= 1 && c.num_query_rounds <= 1024, "num_query_rounds must be in 1..1024");
-    require(c.num_challenges == 2, "num_challenges must be 2 (circuits/src/stark/config.rs)");
+    require(c.num_challenges >= 1 && c.num_challenges <= OLA_MAX_CHALLENGES, "num_challenges must be in 1..8");
     require(known_hasher(c.hasher), "hasher must be OLA_HASH_POSEIDON, OLA_HASH_BLAKE3, OLA_HASH_POSEIDON2, OLA_HASH_POSEIDON2_POW_POSEIDON or OLA_HASH_KECCAK");
     return c;
 }
@@ -1520,7 +1520,15 @@ int32_t ola_set_shard(OlaCtx* ctx, uint32_t rank, uint32_t world, ola_all_gather
 int32_t ola_air_kernels_available(const uint64_t* airset, size_t airset_words, uint8_t* has_kernel, size_t ntables) {
     OLA_TRY
     require(airset && has_kernel, "null pointer");
-    air_kernels_available((const u64*)airset, airset_words, has_kernel, ntables);
+    air_kernels_available((const u64*)airset, airset_words, has_kernel, ntables, 2);
+    OLA_CATCH
+}
+
+int32_t ola_air_kernels_available_cfg(const OlaGpuConfig* cfg, const uint64_t* airset, size_t airset_words, uint8_t* has_kernel, size_t ntables) {
+    OLA_TRY
+    require(airset && has_kernel, "null pointer");
+    const OlaGpuConfig c = resolve_config(cfg);
+    air_kernels_available((const u64*)airset, airset_words, has_kernel, ntables, (int)c.num_challenges);
     OLA_CATCH
 }
 

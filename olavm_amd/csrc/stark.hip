@@ -61,8 +61,11 @@ struct SigHasher {
     void word(u64 x) { for (int k = 0; k < 8; k++) { h ^= (x >> (8 * k)) & 0xFF; h *= 0x100000001B3ull; } }
     void lincol(const HLinCol& c) { word(c.terms.size()); for (auto& t : c.terms) { word(t.first); word(t.second); } word(c.constant); }
 };
-static u64 air_signature(const HTable& a, const std::vector<const HTwc*>& jobs) {
+// nch: the challenge count the kernel is printed for.  Two is the reference's standard configuration and leaves the hash what it
+// was; any other count is hashed in front (a table without lookups and permutation pairs has the same words at every count).
+static u64 air_signature(const HTable& a, const std::vector<const HTwc*>& jobs, int nch) {
     SigHasher s;
+    if (nch != 2) s.word((u64)nch);
     s.word((u64)a.ncols); s.word((u64)a.constraint_degree); s.word((u64)a.n_regs); s.word((u64)a.n_params);
     s.word(a.perm_pairs.size());
     for (auto& pr : a.perm_pairs) { s.word(pr.size()); for (auto& lr : pr) { s.word(lr.first); s.word(lr.second); } }
@@ -93,36 +96,40 @@ __device__ __forceinline__ u64 dev_lincol(const u64* __restrict__ d, u32& p, con
 
 // CTL factor columns: out[i] = filter(i) ? combine(i) : 1   (cross_table_lookup.rs:284-311)
 // A table carries one Z column per (lookup side, challenge); the num_challenges columns of one side combine the SAME linear
-// combinations of trace columns with different (beta, gamma).  One blockIdx.y handles such a pair: descriptors at
-// desc_all[offs[pairs[2y]]] and desc_all[offs[pairs[2y+1]]] (equal indices: an unpaired column), outputs at out_all + index*n.
-// The trace cells and the linear combinations are read / evaluated once for both.
+// combinations of trace columns with different (beta, gamma).  One blockIdx.y handles such a group of G columns: descriptors at
+// desc_all[offs[groups[G y + c]]], outputs at out_all + index*n.  The trace cells, the linear combinations and the filter are
+// read / evaluated once for the whole group.
+template <int G>
 __global__ __launch_bounds__(256) void ctl_factor_kernel(const u64* __restrict__ trace, size_t n, const u64* __restrict__ desc_all,
-                                                         const u64* __restrict__ offs, const u64* __restrict__ pairs, u64* __restrict__ out_all,
+                                                         const u64* __restrict__ offs, const u64* __restrict__ groups, u64* __restrict__ out_all,
                                                          unsigned* __restrict__ bad_filter) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const u64 ya = pairs[2 * blockIdx.y], yb = pairs[2 * blockIdx.y + 1];
-    const u64* __restrict__ desc = desc_all + offs[ya];
-    const u64* __restrict__ descb = desc_all + offs[yb];
-    u32 p = 0;
-    const u64 beta_a = desc[0], gamma_a = desc[1], beta_b = descb[0], gamma_b = descb[1];
-    p = 2;
+    u64 col[G], beta[G], acc[G], bp[G];
+#pragma unroll
+    for (int c = 0; c < G; c++) {
+        col[c] = groups[(size_t)G * blockIdx.y + c];
+        beta[c] = desc_all[offs[col[c]]];
+        acc[c] = 0;
+        bp[c] = 1;
+    }
+    const u64* __restrict__ desc = desc_all + offs[col[0]];      // the linear combinations: the same words in every member
+    u32 p = 2;
     const u32 ncol = (u32)desc[p++];
     // combine = reduce_with_powers(evals, beta) + gamma = sum_k beta^k e_k + gamma
-    u64 acc_a = 0, acc_b = 0, bp_a = 1, bp_b = 1;
     for (u32 k = 0; k < ncol; k++) {
         const u64 e = dev_lincol(desc, p, trace, n, i);
-        acc_a = gl_add(acc_a, k == 0 ? e : gl_mul(bp_a, e));
-        acc_b = gl_add(acc_b, k == 0 ? e : gl_mul(bp_b, e));
-        if (k + 1 < ncol) { bp_a = gl_mul(bp_a, beta_a); bp_b = gl_mul(bp_b, beta_b); }
+#pragma unroll
+        for (int c = 0; c < G; c++) {
+            acc[c] = gl_add(acc[c], k == 0 ? e : gl_mul(bp[c], e));
+            if (k + 1 < ncol) bp[c] = gl_mul(bp[c], beta[c]);
+        }
     }
-    acc_a = gl_add(acc_a, gamma_a);
-    acc_b = gl_add(acc_b, gamma_b);
     u64 f = 1;
     if (desc[p++]) f = dev_lincol(desc, p, trace, n, i);
     if (f > 1) atomicOr(bad_filter, 1u);  // cross_table_lookup.rs:303-305 panics "Non-binary filter?"
-    out_all[ya * n + i] = (f == 1) ? acc_a : 1;
-    if (yb != ya) out_all[yb * n + i] = (f == 1) ? acc_b : 1;
+#pragma unroll
+    for (int c = 0; c < G; c++) out_all[col[c] * n + i] = (f == 1) ? gl_add(acc[c], desc_all[offs[col[c]] + 1]) : 1;
 }
 
 // permutation quotient column: out[i] = prod_inst (gamma + sum beta^k lhs_k) / prod_inst (gamma + sum beta^k rhs_k)
@@ -179,6 +186,10 @@ __global__ __launch_bounds__(256) void any_nonzero_kernel(const u64* __restrict_
 
 // ------------------------------------------------------------------------------------------------ quotient kernel
 
+// descriptor header (quotient_desc): 8 words of counts and offsets, the alphas, 1/Z_H per coset
+constexpr int QD_ALPHA = 8, QD_ZH = QD_ALPHA + OLA_MAX_CHALLENGES, QD_HEAD = QD_ZH + 8;
+
+template <int NCH>
 __global__ __launch_bounds__(QW) void quotient_kernel(QuotParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u64* regs = reinterpret_cast<u64*>(smem_raw);
@@ -202,15 +213,16 @@ __global__ __launch_bounds__(QW) void quotient_kernel(QuotParams P) {
     const u64* __restrict__ D = P.desc;
     const u32 n_ops = (u32)D[0], ops_off = (u32)D[1], nperm = (u32)D[2], perm_off = (u32)D[3], nctl = (u32)D[4], ctl_off = (u32)D[5];
     const u32 params_off = (u32)D[7];
-    const u64 alpha0 = D[8], alpha1 = D[9];
-    const u64 zh_inv = D[10 + c];
-    u64 acc0 = 0, acc1 = 0;
+    const u64 zh_inv = D[QD_ZH + c];
+    u64 alpha[NCH], acc[NCH];       // in registers: every loop over them is unrolled
+#pragma unroll
+    for (int a = 0; a < NCH; a++) { alpha[a] = D[QD_ALPHA + a]; acc[a] = 0; }
     auto emit = [&](int kind, u64 v) {
         if (kind == AK_TRANSITION) v = gl_mul(v, z_last);
         else if (kind == AK_FIRST) v = gl_mul(v, lag_first);
         else if (kind == AK_LAST) v = gl_mul(v, lag_last);
-        acc0 = gl_add(gl_mul(acc0, alpha0), v);
-        acc1 = gl_add(gl_mul(acc1, alpha1), v);
+#pragma unroll
+        for (int a = 0; a < NCH; a++) acc[a] = gl_add(gl_mul(acc[a], alpha[a]), v);
     };
     const size_t N = P.N;
 
@@ -272,8 +284,8 @@ __global__ __launch_bounds__(QW) void quotient_kernel(QuotParams P) {
         }
     }
     if (active) {
-        P.out[j] = gl_mul(acc0, zh_inv);
-        P.out[P.out_plane + j] = gl_mul(acc1, zh_inv);
+#pragma unroll
+        for (int a = 0; a < NCH; a++) P.out[(size_t)a * P.out_plane + j] = gl_mul(acc[a], zh_inv);
     }
 }
 
@@ -300,7 +312,13 @@ static GpChallenge get_gp(OlaChallenger& ch) { const u64 b = challenger_get(ch);
 
 struct CtlJob { const HTwc* twc; GpChallenge ch; };
 
-static int two_challenges(const OlaGpuConfig& cfg) { if (cfg.num_challenges != 2) throw OlaError(OLA_E_INVALID_ARG, "num_challenges must be 2"); return 2; }
+// the instantiation of a kernel template for a challenge count (ola_gpu.hip resolve_config admits 1..OLA_MAX_CHALLENGES)
+#define OLA_FOR_NCH(nch, F)                                                                       \
+    switch (nch) {                                                                                \
+        case 1: F(1); break; case 2: F(2); break; case 3: F(3); break; case 4: F(4); break;       \
+        case 5: F(5); break; case 6: F(6); break; case 7: F(7); break; case 8: F(8); break;       \
+        default: throw OlaError(OLA_E_INTERNAL, "challenge count out of range");                  \
+    }
 
 // `count` pairs (beta, gamma) as a caller hands them over, [count][2] words: reduced on entry
 static std::vector<GpChallenge> read_challenges(const u64* words, size_t count) {
@@ -362,21 +380,21 @@ static PermDesc build_perm_desc(const HTable& air, const PermSets& sets, int nch
 }
 
 // The lookup columns of a table: the push_ctl_desc words of its jobs, and what ctl_factor_kernel indexes them by -- index[j] for
-// j < ncols: where job j starts; then the jobs in pairs (a, b).  The columns of one lookup side under the two challenges share
-// their linear combinations, so they are paired; a job without a partner is paired with itself.
-struct CtlDesc { std::vector<u64> words, index; size_t ncols = 0; size_t npairs() const { return (index.size() - ncols) / 2; } };
-static CtlDesc build_ctl_desc(const std::vector<CtlJob>& ctl) {
+// j < ncols: where job j starts; then the jobs in groups of `group`.  The columns of one lookup side under the challenges share
+// their linear combinations, so they form a group: num_challenges columns each (ctl_jobs).
+struct CtlDesc { std::vector<u64> words, index; size_t ncols = 0; int group = 1; size_t ngroups() const { return (index.size() - ncols) / (size_t)group; } };
+static CtlDesc build_ctl_desc(const std::vector<CtlJob>& ctl, int nch) {
     CtlDesc d;
     d.ncols = ctl.size();
+    d.group = nch;
     for (auto& j : ctl) { d.index.push_back(d.words.size()); push_ctl_desc(d.words, *j.twc, j.ch.beta, j.ch.gamma); }
     std::vector<char> taken(ctl.size(), 0);
     for (size_t a = 0; a < ctl.size(); a++) {
         if (taken[a]) continue;
-        size_t b = a;
-        for (size_t c = a + 1; c < ctl.size(); c++)
-            if (!taken[c] && ctl[c].twc == ctl[a].twc) { b = c; break; }
-        taken[a] = taken[b] = 1;
-        d.index.push_back(a); d.index.push_back(b);
+        int members = 0;
+        for (size_t c = a; c < ctl.size(); c++)
+            if (!taken[c] && ctl[c].twc == ctl[a].twc) { taken[c] = 1; d.index.push_back(c); members++; }
+        if (members != nch) throw OlaError(OLA_E_INTERNAL, "a lookup side does not carry one Z column per challenge");
     }
     return d;
 }
@@ -487,8 +505,11 @@ static void ctl_z_columns(DeviceCtx* ctx, DevBuf& mem, const DevTable& tv, const
     const size_t n = tv.n();
     u64* d_words = mem.upload(cd.words);
     u64* d_index = mem.upload(cd.index);
-    hipLaunchKernelGGL(ctl_factor_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)cd.npairs()), dim3(256), 0, ctx->stream, tv.vals, n, d_words,
-                       d_index, d_index + cd.ncols, zcols, d_bad_filter);
+#define OLA_CTL_FACTOR(G)                                                                                                                      \
+    hipLaunchKernelGGL(ctl_factor_kernel<G>, dim3((unsigned)((n + 255) / 256), (unsigned)cd.ngroups()), dim3(256), 0, ctx->stream, tv.vals, n, \
+                       d_words, d_index, d_index + cd.ncols, zcols, d_bad_filter)
+    OLA_FOR_NCH(cd.group, OLA_CTL_FACTOR)
+#undef OLA_CTL_FACTOR
     scan_inclusive<ScanProduct, false>(ctx->stream, zcols, n, cd.ncols, tot);
 }
 
@@ -499,20 +520,20 @@ static int quotient_degree_bits(const HTable& air) { int qdb = 0; while ((1 << q
 struct QuotientIn {
     const HTable& air; const OlaBatch &trace_c, &zs_c;
     const PermSets& perm_sets; const PermDesc& pd; const std::vector<CtlJob>& ctl; const CtlDesc& cd;
-    const u64* params; u64 alpha[2];
+    const u64* params; std::vector<u64> alpha;      // one alpha per challenge
 };
 
-// the descriptor quotient_kernel interprets: a header of 18 words, then the constraint program, the permutation and lookup
+// the descriptor quotient_kernel interprets: a header of QD_HEAD words, then the constraint program, the permutation and lookup
 // descriptors and the parameters
 static std::vector<u64> quotient_desc(const QuotientIn& in, int degree_bits, int qdb) {
-    std::vector<u64> desc(18, 0);
+    std::vector<u64> desc(QD_HEAD, 0);
     // Z_H(x)^-1 per coset (zero_poly_coset.rs:18-33): x^n = 7^n * v^i, i = natural index mod 2^qdb; coset c <-> i = bitrev
     u64 g_pow_n = GL_GENERATOR;
     for (int i = 0; i < degree_bits; i++) g_pow_n = gl_mul(g_pow_n, g_pow_n);
     const u64 v = gl_root_of_unity(qdb);
     for (int c = 0; c < (1 << qdb); c++) {
         const u32 i = bitrev32((u32)c, qdb);
-        desc[10 + c] = gl_inv(gl_sub(gl_mul(g_pow_n, gl_pow(v, i)), 1));
+        desc[QD_ZH + c] = gl_inv(gl_sub(gl_mul(g_pow_n, gl_pow(v, i)), 1));
     }
     desc[0] = in.air.ops.size() / 2;
     desc[1] = desc.size();
@@ -526,7 +547,7 @@ static std::vector<u64> quotient_desc(const QuotientIn& in, int degree_bits, int
     desc[6] = (u64)in.air.n_params;
     desc[7] = desc.size();
     for (int i = 0; i < in.air.n_params; i++) desc.push_back(gl_canon(in.params[i]));
-    desc[8] = in.alpha[0]; desc[9] = in.alpha[1];
+    for (size_t a = 0; a < in.alpha.size(); a++) desc[QD_ALPHA + a] = in.alpha[a];
     return desc;
 }
 
@@ -534,9 +555,9 @@ static std::vector<u64> quotient_desc(const QuotientIn& in, int degree_bits, int
 // in the kernel's own order, then the limb forms of the uniform multipliers
 static std::vector<u64> spec_quotient_desc(const QuotientIn& in, const AirKernelEntry& spec, const std::vector<u64>& desc, int qdb, int nch) {
     const int K = spec.n_emits, bs = in.air.permutation_batch_size();
-    std::vector<u64> sd(8 + 2 * (size_t)K, 0);
-    for (int c = 0; c < (1 << qdb); c++) sd[c] = desc[10 + c];
-    for (int c = 0; c < 2; c++) {
+    std::vector<u64> sd(8 + (size_t)nch * K, 0);
+    for (int c = 0; c < (1 << qdb); c++) sd[c] = desc[QD_ZH + c];
+    for (int c = 0; c < nch; c++) {
         u64 w = 1;
         for (int i = K - 1; i >= 0; i--) { sd[8 + (size_t)c * K + i] = w; w = gl_mul(w, in.alpha[c]); }
     }
@@ -570,10 +591,10 @@ static std::vector<u64> spec_quotient_desc(const QuotientIn& in, const AirKernel
     return sd;
 }
 
-// The two quotient polynomials as coefficients over the 2^qdb-coset domain; of each only the first n * q may be non-zero, which
+// The quotient polynomials (one per challenge) as coefficients over the 2^qdb-coset domain; of each only the first n * q may be non-zero, which
 // the device has looked at: check() after the next wait of the host.
 struct QuotientPolys {
-    u64* coef; size_t n, size; int q;
+    u64* coef; size_t n, size; int q, nch;
     HostSpan too_high; const DeviceCtx* ctx;
     void check() const {
 #ifndef AIRQ_TIMING_ONLY_L2_LOADS      // (timing builds of airq.cuh's experiment produce garbage on purpose)
@@ -597,6 +618,7 @@ static QuotientPolys quotient_polys(DeviceCtx* ctx, DevBuf& mem, NttTables& tabl
     const int q = air.quotient_degree_factor(), qdb = quotient_degree_bits(air);
     if (qdb > rate_bits) throw OlaError(OLA_E_INVALID_ARG, "Having constraints of degree higher than the rate is not supported yet.");
     const size_t size = n << qdb;
+    const int nch = (int)cfg.num_challenges;
     // Lagrange first/last on the LDE domain (leaf order)
     u64* lag_coef = mem.alloc(2 * n);
     u64* lag_lde = mem.alloc(2 * (lean ? n : N_loc));
@@ -609,11 +631,11 @@ static QuotientPolys quotient_polys(DeviceCtx* ctx, DevBuf& mem, NttTables& tabl
     }
     const std::vector<u64> desc = quotient_desc(in, degree_bits, qdb);
     u64* d_desc = mem.upload(desc);
-    u64* qv = mem.alloc(2 * size);
+    u64* qv = mem.alloc((size_t)nch * size);
     // points this rank evaluates: the whole quotient domain, or (sharded) those of its cosets that belong to the quotient
     // domain -- the first 2^qdb cosets of the leaf order; a rank that owns none of them only takes part in the exchange
     const size_t plane = sharded ? N_loc : size;
-    u64* qloc = sharded ? mem.alloc(2 * plane) : qv;
+    u64* qloc = sharded ? mem.alloc((size_t)nch * plane) : qv;
     const size_t q_cosets = (size_t)1 << qdb;
     const size_t my_q_cosets = !sharded ? q_cosets : (coset_first >= q_cosets ? 0 : std::min(coset_count, q_cosets - coset_first));
     {
@@ -633,7 +655,7 @@ static QuotientPolys quotient_polys(DeviceCtx* ctx, DevBuf& mem, NttTables& tabl
         std::vector<const HTwc*> twcs;
         for (auto& jb : in.ctl) twcs.push_back(jb.twc);
         // the specialised kernels address rows as "workgroup base + lane": workgroups of min(AIRQ_THREADS, n) threads (airq.cuh)
-        const AirKernelEntry* spec = force_interp ? nullptr : find_air_kernel(air_signature(air, twcs));
+        const AirKernelEntry* spec = force_interp ? nullptr : find_air_kernel(air_signature(air, twcs, nch));
         const unsigned spec_bs = (unsigned)std::min<size_t>(AIRQ_THREADS, n);
         // memory-lean: the trace and Z values of one coset at a time, re-derived from the coefficients; the quotient of a table
         // with 2^qdb < 2^rate_bits cosets lives on the first 2^qdb cosets of the leaf order
@@ -644,14 +666,14 @@ static QuotientPolys quotient_polys(DeviceCtx* ctx, DevBuf& mem, NttTables& tabl
             slice_z = mem.alloc((size_t)zs_c.ncols * n);
             P.trace_lde = slice_t; P.zs_lde = slice_z; P.N = n; P.npoints = n;
         }
-        u64* d_sd = spec ? mem.upload(spec_quotient_desc(in, *spec, desc, qdb, (int)cfg.num_challenges)) : nullptr;
-        u64* qv2 = (spec && crosscheck) ? mem.alloc(2 * plane) : nullptr;
+        u64* d_sd = spec ? mem.upload(spec_quotient_desc(in, *spec, desc, qdb, nch)) : nullptr;
+        u64* qv2 = (spec && crosscheck) ? mem.alloc((size_t)nch * plane) : nullptr;
         WorkScope ws(ctx, qdb);   // the quotient lives on 2^qdb cosets: that many ranks share it
-        // units: LDE points evaluated; bytes a point streams -- local and next row of the trace and Z batches, two planes written
+        // units: LDE points evaluated; bytes a point streams -- local and next row of the trace and Z batches, one plane per challenge written
         // (quotient row streaming is priced against HBM)
         const double q_points = (double)(sharded ? my_q_cosets * n : size);
-        PhaseScope phq(ctx, PH_QUOTIENT, q_points, q_points * (8.0 * 2 * ((double)trace_c.ncols + (double)zs_c.ncols) + 16.0));
-        if (!sharded && ctx->acct.shardable) { acct_exchange(ctx, N * 8); acct_exchange(ctx, N * 8); }   // the two planes a partitioned run gathers
+        PhaseScope phq(ctx, PH_QUOTIENT, q_points, q_points * (8.0 * 2 * ((double)trace_c.ncols + (double)zs_c.ncols) + 8.0 * nch));
+        if (!sharded && ctx->acct.shardable) for (int c = 0; c < nch; c++) acct_exchange(ctx, N * 8);   // the planes a partitioned run gathers
         for (size_t lc = 0; lc < lean_cosets; lc++) {
             u64* out = qloc;
             size_t points = sharded ? my_q_cosets * n : plane;
@@ -668,9 +690,12 @@ static QuotientPolys quotient_polys(DeviceCtx* ctx, DevBuf& mem, NttTables& tabl
                 P.out = o;
                 const size_t lds = (size_t)air.n_regs * QW * 8;
                 if (lds > 160 * 1024) throw OlaError(OLA_E_INVALID_ARG, "constraint program needs too many registers");
-                if (lds > 48 * 1024)
-                    HIP_CHECK(hipFuncSetAttribute((const void*)quotient_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(quotient_kernel, dim3((unsigned)((points + QW - 1) / QW)), dim3(QW), lds, ctx->stream, P);
+#define OLA_QUOTIENT_INTERP(NCH)                                                                                                          \
+    if (lds > 48 * 1024)                                                                                                                  \
+        HIP_CHECK(hipFuncSetAttribute((const void*)quotient_kernel<NCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));         \
+    hipLaunchKernelGGL(quotient_kernel<NCH>, dim3((unsigned)((points + QW - 1) / QW)), dim3(QW), lds, ctx->stream, P)
+                OLA_FOR_NCH(nch, OLA_QUOTIENT_INTERP)
+#undef OLA_QUOTIENT_INTERP
             };
             if (!spec) {
                 run_interp_on(out);
@@ -686,7 +711,7 @@ static QuotientPolys quotient_polys(DeviceCtx* ctx, DevBuf& mem, NttTables& tabl
             unsigned* d_flag = (unsigned*)mem.alloc(1);
             HIP_CHECK(hipMemsetAsync(d_flag, 0, 8, ctx->stream));
             const size_t evaluated = sharded ? my_q_cosets * n : plane;       // per plane
-            for (int c = 0; c < 2 && evaluated; c++)
+            for (int c = 0; c < nch && evaluated; c++)
                 hipLaunchKernelGGL(any_diff_kernel, dim3((unsigned)((evaluated + 255) / 256)), dim3(256), 0, ctx->stream, qloc + (size_t)c * plane,
                                    qv2 + (size_t)c * plane, evaluated, d_flag);
             unsigned flag = 0;
@@ -699,10 +724,10 @@ static QuotientPolys quotient_polys(DeviceCtx* ctx, DevBuf& mem, NttTables& tabl
         // every rank needs the whole quotient for the inverse transform: gather the ranks' planes (rank order = leaf order) and
         // keep the first n * 2^qdb values of each
         if (N == size) {
-            for (int c = 0; c < 2; c++) shard_all_gather(ctx, qloc + (size_t)c * plane, qv + (size_t)c * size, plane * 8);
+            for (int c = 0; c < nch; c++) shard_all_gather(ctx, qloc + (size_t)c * plane, qv + (size_t)c * size, plane * 8);
         } else {
             u64* gath = mem.alloc(N);
-            for (int c = 0; c < 2; c++) {
+            for (int c = 0; c < nch; c++) {
                 shard_all_gather(ctx, qloc + (size_t)c * plane, gath, plane * 8);
                 HIP_CHECK(hipMemcpyAsync(qv + (size_t)c * size, gath, size * 8, hipMemcpyDeviceToDevice, ctx->stream));
             }
@@ -710,18 +735,18 @@ static QuotientPolys quotient_polys(DeviceCtx* ctx, DevBuf& mem, NttTables& tabl
     }
     // qv is in bit-reversed order of the size-domain: un-reverse, coset iNTT (prover.rs:700-704)
     const int size_bits = degree_bits + qdb;
-    u64* qnat = mem.alloc(2 * size);
-    QuotientPolys qp = {mem.alloc(2 * size), n, size, q, mem.host(1), ctx};
-    u64* qscratch = size_bits > 13 ? mem.alloc(2 * size) : nullptr;
-    launch_bitrev_rows(ctx, qv, qnat, size_bits, 2);
-    ntt_coset_interpolate(tables, qnat, qp.coef, qscratch, size_bits, 2, GL_GENERATOR);
+    u64* qnat = mem.alloc((size_t)nch * size);
+    QuotientPolys qp = {mem.alloc((size_t)nch * size), n, size, q, nch, mem.host(1), ctx};
+    u64* qscratch = size_bits > 13 ? mem.alloc((size_t)nch * size) : nullptr;
+    launch_bitrev_rows(ctx, qv, qnat, size_bits, nch);
+    ntt_coset_interpolate(tables, qnat, qp.coef, qscratch, size_bits, nch, GL_GENERATOR);
     // trim_to_len(n*q) (prover.rs:469-473): nothing may be left above
     qp.too_high[0] = 0;
     const size_t keep = n * (size_t)q;
     if (keep < size) {
         unsigned* d_flag = (unsigned*)mem.alloc(1);
         HIP_CHECK(hipMemsetAsync(d_flag, 0, 8, ctx->stream));
-        for (int c = 0; c < 2; c++)
+        for (int c = 0; c < nch; c++)
             hipLaunchKernelGGL(any_nonzero_kernel, dim3((unsigned)((size - keep + 255) / 256)), dim3(256), 0, ctx->stream, qp.coef + (size_t)c * size,
                                keep, size, d_flag);
         // read with the next read-back the host waits for (the quotient commitment's cap, or an entry point's copy): no wait of its own
@@ -733,8 +758,8 @@ static QuotientPolys quotient_polys(DeviceCtx* ctx, DevBuf& mem, NttTables& tabl
 // chunks of n coefficients: [challenge][k] -> column challenge * q + k
 static u64* split_quotient(DeviceCtx* ctx, DevBuf& mem, const QuotientPolys& qp) {
     const size_t keep = qp.n * (size_t)qp.q;
-    u64* chunks = mem.alloc(2 * keep);
-    for (int c = 0; c < 2; c++)
+    u64* chunks = mem.alloc((size_t)qp.nch * keep);
+    for (int c = 0; c < qp.nch; c++)
         HIP_CHECK(hipMemcpyAsync(chunks + (size_t)c * keep, qp.coef + (size_t)c * qp.size, keep * 8, hipMemcpyDeviceToDevice, ctx->stream));
     return chunks;
 }
@@ -745,13 +770,13 @@ static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuCo
                                const u64* params, OlaChallenger& ch, std::vector<uint8_t>& bytes, bool sharded, int table_index,
                                PowDefer* pow_defer = nullptr) {
     DevBuf mem(ctx);
-    const int nch = two_challenges(cfg);
+    const int nch = (int)cfg.num_challenges;
     const size_t n = tv.n();
     challenger_compact(ch);
     // ---- permutation challenges + Z polys (prover.rs:360-377) ----
     const PermSets perm_sets = draw_perm_sets(air, nch, ch);
     const PermDesc pd = build_perm_desc(air, perm_sets, nch);
-    const CtlDesc cd = build_ctl_desc(ctl);
+    const CtlDesc cd = build_ctl_desc(ctl, nch);
     const int nperm = pd.nperm(), nz = nperm + (int)ctl.size();
     if (nz == 0) throw OlaError(OLA_E_INVALID_ARG, "No CTL?");
     // OLA_TIMING scopes carry the reference's `timed!` names (prover.rs:374-544)
@@ -773,17 +798,18 @@ static void prove_single_table(DeviceCtx* ctx, NttTables& tables, const OlaGpuCo
     zs_c.b = commit_shared(ctx, tables, zvals, (uint32_t)nz, tv.log_n, cfg, true, sharded, nullptr, zs_cap, lean);
     zf.check();                                          // commit_shared has waited for the cap
     challenger_observe_cap(ch, zs_cap.data(), zs_cap.size() / 4);
-    const u64 alpha0 = challenger_get(ch), alpha1 = challenger_get(ch);
+    std::vector<u64> alphas;                             // challenger.get_n_challenges (prover.rs:425)
+    for (int c = 0; c < nch; c++) alphas.push_back(challenger_get(ch));
 
     ph.reset(); ph.reset(new PhaseTimer(ctx, "    compute quotient polys"));
-    const QuotientIn qin = {air, trace_c, *zs_c.b, perm_sets, pd, ctl, cd, params, {alpha0, alpha1}};
+    const QuotientIn qin = {air, trace_c, *zs_c.b, perm_sets, pd, ctl, cd, params, alphas};
     const QuotientPolys qp = quotient_polys(ctx, mem, tables, cfg, qin, sharded);
     ph.reset(); ph.reset(new PhaseTimer(ctx, "    split quotient polys"));
     u64* chunks = split_quotient(ctx, mem, qp);
     ph.reset(); ph.reset(new PhaseTimer(ctx, "    compute quotient commitment"));
     BatchHolder q_c(ctx);
     std::vector<u64> q_cap;
-    q_c.b = commit_shared(ctx, tables, chunks, (uint32_t)(2 * qp.q), tv.log_n, cfg, false, sharded, nullptr, q_cap, lean);
+    q_c.b = commit_shared(ctx, tables, chunks, (uint32_t)(nch * qp.q), tv.log_n, cfg, false, sharded, nullptr, q_cap, lean);
     qp.check();                                          // commit_shared has waited for the cap
     challenger_observe_cap(ch, q_cap.data(), q_cap.size() / 4);
 
@@ -863,7 +889,7 @@ void perm_z_host(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airset, siz
                  const u64* const* trace_cols, const u64* perm_challenges, u64* z_out) {
     const HAirSet set = parse_airset_with_table(airset, airset_words, table);
     const HTable& air = set.tables[table];
-    const int nch = two_challenges(cfg);
+    const int nch = (int)cfg.num_challenges;
     if (table_widths(set, table, nch).wz == 0) throw OlaError(OLA_E_INVALID_ARG, "No CTL?");
     const PermDesc pd = build_perm_desc(air, read_perm_sets(air, nch, perm_challenges), nch);
     if (!pd.nperm()) return;
@@ -882,10 +908,10 @@ void ctl_z_host(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airset, size
                 const u64* const* trace_cols, const u64* ctl_challenges, u64* z_out) {
     const HAirSet set = parse_airset_with_table(airset, airset_words, table);
     const HTable& air = set.tables[table];
-    const int nch = two_challenges(cfg);
+    const int nch = (int)cfg.num_challenges;
     if (table_widths(set, table, nch).wz == 0) throw OlaError(OLA_E_INVALID_ARG, "No CTL?");
     const std::vector<std::vector<CtlJob>> jobs = ctl_jobs(set, read_challenges(ctl_challenges, nch));
-    const CtlDesc cd = build_ctl_desc(jobs[table]);
+    const CtlDesc cd = build_ctl_desc(jobs[table], nch);
     if (!cd.ncols) return;
     DevBuf mem(ctx);
     PhaseTimer ph(ctx, "    compute CTL Z(x) polys");
@@ -898,7 +924,7 @@ void ctl_z_host(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airset, size
 }
 
 // compute_quotient_polys + the split into degree-n chunks (prover.rs:441-480, 571-705) on the caller's two commitments:
-// coefficients of the 2 * q chunk polynomials, ready for PolynomialBatch::from_coeffs (ola_quotient)
+// coefficients of the num_challenges * q chunk polynomials, ready for PolynomialBatch::from_coeffs (ola_quotient)
 void quotient_host(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, const u64* airset, size_t airset_words, uint32_t table,
                    const OlaBatch& trace_c, const OlaBatch& zs_c, const u64* perm_challenges, const u64* ctl_challenges, const u64* alphas,
                    const u64* params, u64* chunks_out) {
@@ -908,22 +934,24 @@ void quotient_host(DeviceCtx* ctx, NttTables& tables, const OlaGpuConfig& cfg, c
     if (trace_c.ncols != (uint32_t)air.ncols || trace_c.is_shard()) throw OlaError(OLA_E_INVALID_ARG, "trace commitment does not match the table");
     if (!air.perm_pairs.empty() && !perm_challenges) throw OlaError(OLA_E_INVALID_ARG, "the table has permutation arguments: perm_challenges required");
     params = params_or_zero(params, 0, air);
-    const int nch = two_challenges(cfg);
+    const int nch = (int)cfg.num_challenges;
     const std::vector<std::vector<CtlJob>> jobs = ctl_jobs(set, read_challenges(ctl_challenges, nch));
     const std::vector<CtlJob>& ctl = jobs[table];
     const PermSets perm_sets = read_perm_sets(air, nch, perm_challenges);
     const PermDesc pd = build_perm_desc(air, perm_sets, nch);
-    const CtlDesc cd = build_ctl_desc(ctl);
+    const CtlDesc cd = build_ctl_desc(ctl, nch);
     const size_t nz = (size_t)pd.nperm() + ctl.size();
     if (nz == 0) throw OlaError(OLA_E_INVALID_ARG, "No CTL?");
     if (zs_c.ncols != nz || zs_c.log_n != trace_c.log_n || zs_c.lean != trace_c.lean || zs_c.is_shard())
         throw OlaError(OLA_E_INVALID_ARG, "Z commitment does not match the table");
     DevBuf mem(ctx);
     std::unique_ptr<PhaseTimer> ph(new PhaseTimer(ctx, "    compute quotient polys"));
-    const QuotientIn qin = {air, trace_c, zs_c, perm_sets, pd, ctl, cd, params, {gl_canon(alphas[0]), gl_canon(alphas[1])}};
+    std::vector<u64> alpha;
+    for (int c = 0; c < nch; c++) alpha.push_back(gl_canon(alphas[c]));
+    const QuotientIn qin = {air, trace_c, zs_c, perm_sets, pd, ctl, cd, params, alpha};
     const QuotientPolys qp = quotient_polys(ctx, mem, tables, cfg, qin, false);
     ph.reset(); ph.reset(new PhaseTimer(ctx, "    split quotient polys"));
-    hand_back(ctx, mem, chunks_out, split_quotient(ctx, mem, qp), 2 * qp.n * (size_t)qp.q, qp);
+    hand_back(ctx, mem, chunks_out, split_quotient(ctx, mem, qp), (size_t)nch * qp.n * (size_t)qp.q, qp);
 }
 
 // Memory-lean tables (OLA_LEAN=1 forces, =0 forbids, default: when keeping every LDE resident would not fit): the LDEs of the
@@ -994,7 +1022,7 @@ void reserve_for_proof(DeviceCtx* ctx, const OlaGpuConfig& cfg, const u64* airse
         { std::vector<size_t> keep; keep.swap(sizes);
           sizes.push_back(tw.wz * n * 8);              // Z values
           batch_blocks(tw.wz, n, lean[t] != 0);
-          for (int i = 0; i < 4; i++) sizes.push_back(2 * size * 8);   // quotient values, natural order, coefficients, scratch
+          for (int i = 0; i < 4; i++) sizes.push_back((size_t)nch * size * 8);   // quotient values, natural order, coefficients, scratch
           sizes.push_back(tw.wq * n * 8);              // chunks
           batch_blocks(tw.wq, n, lean[t] != 0);
           if (lean[t]) { sizes.push_back(tw.w * n * 8); sizes.push_back(tw.wz * n * 8); }
@@ -1156,17 +1184,17 @@ std::vector<size_t> airset_widths(const u64* airset, size_t airset_words) {
     return w;
 }
 
-// ola_air_kernels_available
-void air_kernels_available(const u64* airset, size_t airset_words, uint8_t* has_kernel, size_t ntables) {
+// ola_air_kernels_available / ola_air_kernels_available_cfg: nch challenges
+void air_kernels_available(const u64* airset, size_t airset_words, uint8_t* has_kernel, size_t ntables, int nch) {
     HAirSet set = parse_airset(airset, airset_words);
     if (ntables != set.tables.size()) throw OlaError(OLA_E_INVALID_ARG, "ntables does not match the AIR set");
     std::vector<std::vector<const HTwc*>> jobs(set.tables.size());
     for (const HCtl& ctl : set.ctls)
-        for (int c = 0; c < 2; c++) {
+        for (int c = 0; c < nch; c++) {
             for (const HTwc& twc : ctl.looking) jobs[twc.table].push_back(&twc);
             jobs[ctl.looked.table].push_back(&ctl.looked);
         }
-    for (size_t t = 0; t < set.tables.size(); t++) has_kernel[t] = find_air_kernel(air_signature(set.tables[t], jobs[t])) ? 1 : 0;
+    for (size_t t = 0; t < set.tables.size(); t++) has_kernel[t] = find_air_kernel(air_signature(set.tables[t], jobs[t], nch)) ? 1 : 0;
 }
 
 }  // namespace ola

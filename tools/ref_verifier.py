@@ -454,11 +454,14 @@ class RefVerifier:
 
     CONFIG_FIELDS = ("rate_bits", "cap_height", "proof_of_work_bits", "num_query_rounds")
 
-    def __init__(self, reference="/root/reference", fast_hash=True, hasher="poseidon", reduction_strategy=None, config_overrides=None):
+    def __init__(self, reference="/root/reference", fast_hash=True, hasher="poseidon", reduction_strategy=None, config_overrides=None,
+                 num_challenges=None):
         """reduction_strategy: None keeps standard_fast_config's ConstantArityBits(4, 5); ("MinSize", [None]), ("MinSize", [3]) or
         ("Fixed", [[4, 3, 3]]) is `config.fri_config.reduction_strategy = FriReductionStrategy::<variant>(<payload>)`.
         config_overrides: {"rate_bits" | "cap_height" | "proof_of_work_bits" | "num_query_rounds": n} is `config.fri_config.<field> = n`
-        on the same interpreted StarkConfig (fri/mod.rs FriConfig); None keeps standard_fast_config's 3, 4, 16 and 28"""
+        on the same interpreted StarkConfig (fri/mod.rs FriConfig); None keeps standard_fast_config's 3, 4, 16 and 28.
+        num_challenges: n is `config.num_challenges = n` (config.rs:9: a field of StarkConfig itself, not of its FriConfig, which is why
+        config_overrides does not take it); None keeps standard_fast_config's 2"""
         sys.setrecursionlimit(max(sys.getrecursionlimit(), 20000))
         self.reference = reference
         self.hasher = hasher
@@ -474,6 +477,11 @@ class RefVerifier:
             if isinstance(old, bool) or not isinstance(old, int):
                 raise R.RustError("fri_config.%s is %r in the interpreted StarkConfig, not an integer" % (field, old))
             self.config["fri_config"][field] = int(value)
+        if num_challenges is not None:
+            old = self.config["num_challenges"]
+            if isinstance(old, bool) or not isinstance(old, int):
+                raise R.RustError("num_challenges is %r in the interpreted StarkConfig, not an integer" % (old,))
+            self.config["num_challenges"] = int(num_challenges)
 
     def ola_stark(self):
         """what `OlaStark::default()` (ola_stark.rs:45-64) builds, minus its init_gpu() call: twelve default table structs (compress challenges unset,
@@ -568,8 +576,8 @@ class RefProver(RefVerifier):
     provers take: packing width 1 (`<F as Packable>::Packing` is a SIMD width, not a value) and the SMALLEST proof-of-work witness
     (`find_any` over 0..p may return any)."""
 
-    def __init__(self, reference="/root/reference", hasher="poseidon"):
-        super().__init__(reference, True, hasher)
+    def __init__(self, reference="/root/reference", hasher="poseidon", num_challenges=None):
+        super().__init__(reference, True, hasher, num_challenges=num_challenges)
         it, ref = self.it, reference
         cf = os.path.join(ref, "plonky2", "field", "src")
         pl = os.path.join(ref, "plonky2", "plonky2", "src")
